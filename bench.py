@@ -2,17 +2,25 @@
 """bench.py — vectorised env.step()/s at batch = 1 048 576 boards per MI355X (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--boards B | --total-boards N]
-                    [--mode replay|gym|policy|random|random-fused] [--no-legs]
+                    [--mode replay|gym|policy|random|random-fused] [--dump-outputs DIR] [--full [--no-legs]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one launch of the fused qttt_step kernel over the whole batch of B boards of this
 rank (Env.step for every board, auto-reset throughput mode).  Actions are pre-recorded (an
-untimed pass of policy kernel + step kernel), the boards are reset, and a timed region replays
+untimed pass of the fused policy + step kernel on a second environment), and a timed region replays
 K recorded steps, so it contains env.step and nothing else, with inputs resident in HBM.
 
-Clock.  A region of K launches is short (K = 20 -> 0.16 ms), so the region (W untimed warm-up
-steps + K timed steps, bracketed by barrier + torch.cuda.synchronize() on both sides) is repeated
-R times (R chosen so that the timed parts add up to >= ~50 ms) and the MEDIAN region is reported.
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps once, the outputs
+(--dump-outputs DIR: what the last timed step computed, DIR/<name>.npy in float32, at most 64 MB, a fixed sample of
+boards beyond that) and the JSON line.  Before its region it replays the first recorded steps, untimed, WARM_PASSES
+times (the regions a --full run discards or puts ahead of its median).  The recorded stream is held to RECORD_BYTES_CAP:
+a longer run records and replays it chunk by chunk (the recording outside the HIP events), so memory does not grow
+with K.
+
+Clock.  A region = W untimed warm-up steps + K timed steps, bracketed by barrier + torch.cuda.synchronize() on both
+sides.  A plain run times one region (--regions R: R of them, the median).  With --full, a region of K launches being
+short (K = 20 -> 0.16 ms), a pilot region is run and the region repeated R times (R chosen so that the timed parts add
+up to >= ~50 ms) and the MEDIAN region is reported.
 Each region is timed twice: by HIP events recorded on the launch stream right around the K timed
 launches (`value`, `ms_per_step` and `roofline` all come from this one clock) and by the host's
 perf_counter over the whole bracket (`host_wall_ms_per_step` = bracket time / (W + K) launches,
@@ -29,7 +37,7 @@ of ones over the process group; the line is refused unless n_gpus == ranks_seen.
 `--total-boards 2097152 --gpus 8` is BASELINE config 4 as stated (2 097 152 boards sharded over 8 GPUs with
 dist.shard_range: STRONG scaling, the JSON says so); `--boards B` is per GPU (weak scaling, the default).
 
-Legs.  At N = 1 the same JSON object carries `legs`: the other BASELINE configurations and modes measured
+Legs (--full only).  At N = 1 the same JSON object carries `legs` and `cpu_baseline`: the other BASELINE configurations and modes measured
 in the same process on the same clock (HIP events, median region) — env.step replay at 4 096 / 262 144 /
 16 777 216 boards (the last cannot live in the 256 MB Infinity Cache), `gym` and `random` at 1 M, the fused
 random-policy multi-step kernel (qttt_step_random_many) at 4 096 / 262 144 / 1 M, BASELINE config 5's
@@ -45,6 +53,8 @@ BASELINE config 4 as stated (2 097 152 boards over 8 GPUs, STRONG scaling: 262 1
 occupancy round per launch, predicted 3.9 - 4.1x launch-per-step and 5.4 - 5.7x fused, DESIGN.md §8 — the >= 7x claim
 does NOT apply to it):
     python bench.py --gpus 8 --total-boards 2097152 --mode random-fused
+Everything else this file measures (legs, CPU baseline, repeated regions):
+    python bench.py --full
 QTTT_BENCH_NO_GATHER=1 skips the optional returns gather (the only collective that moves per-board data).
 Prints ONE JSON line on rank 0.
 """
@@ -71,6 +81,10 @@ HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_ACHIEVABLE_GBS = 6290.0   # same guide: what a float4 copy kernel reaches on this part
 PMC_SUMMARY = os.path.join("profiles", "pmc_traffic.json")
 TARGET_TIMED_S = 0.05     # the repeated regions add up to at least this much device time
+# a plain run's untimed warm-up before its one region: the first recorded steps (at most one chunk) replayed from reset
+# this many times — what the pilot region and the first regions ahead of the median are in --full.  The first regions of
+# a process read 2 - 7 % slower per step than the later ones.
+WARM_PASSES = 3
 MAX_REGIONS = 400
 
 
@@ -83,11 +97,18 @@ def parse_args(argv=None):
     ap.add_argument("--total-boards", type=int, default=0,
                     help="boards over ALL GPUs, sharded with dist.shard_range (strong scaling; "
                          "2097152 with --gpus 8 = BASELINE config 4); overrides --boards")
-    ap.add_argument("--no-legs", action="store_true", help="skip the extra legs (other configs / modes) at N = 1")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the extra legs (other configs / modes) and the CPU baseline at "
+                         "N = 1, and the headline as the median of repeated regions; off by default (a plain run times "
+                         "exactly --steps steps once)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the extra legs (other configs / modes) at N = 1")
     ap.add_argument("--fused-steps", type=int, default=64, help="steps per launch of --mode random-fused (<= 64)")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--regions", type=int, default=0, help="repeat count of the K-step timed region (0 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--regions", type=int, default=0,
+                    help="repeat count of the K-step timed region (0 = one region, or auto with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU work for cpu_baseline")
     ap.add_argument("--mode", choices=["replay", "gym", "gym-default", "policy", "random", "random-fused"], default="replay",
                     help="replay: timed region is env.step only (default, the metric); "
@@ -364,15 +385,31 @@ WHAT = {"replay": "recorded actions replayed (env.step only in the timed region)
                         "action / reward / terminated kept"}
 
 
+# The recorded stream is held to this size: the whole stream's actions (2 B per board-step) when they fit, recorded once;
+# else one chunk's (action 2 B + reward 4 B + terminated 1 B + 1 B of scratch per board-step), recorded and replayed
+# chunk after chunk inside every region, so that device memory does not grow with --steps.
+# QTTT_BENCH_RECORD_BYTES sets another cap (tests/test_bench_contract_gpu.py: the chunked path on a small batch).
+RECORD_BYTES_CAP = int(os.environ.get("QTTT_BENCH_RECORD_BYTES", 8 << 30))
+
+
+def torch_ne_sum(torch, x, scratch):
+    """(x != 0).sum() through a preallocated bool buffer: no allocation inside a region"""
+    torch.ne(x, 0, out=scratch)
+    return scratch.sum()
+
+
 class Workload:
-    """B boards on one device, uniform-legal policy, auto-reset: records the action stream (untimed), then
-    times regions of W warm-up + EXACTLY K steps with HIP events on the launch stream."""
+    """B boards on one device, uniform-legal policy, auto-reset: records the action stream (untimed) on a second
+    environment, then times regions of W warm-up + EXACTLY K steps with HIP events on the launch stream.  When the
+    stream of K + W steps does not fit in RECORD_BYTES_CAP it is recorded and replayed in chunks inside each region
+    (the recording between two chunks is outside the HIP events)."""
 
     def __init__(self, torch, dev, B, K, W, seed, board_offset, mode, fused_T):
         from qtttgym_amd import VecEnv, _native
         self.torch, self.dev, self.B, self.K, self.W, self.mode, self.fused_T = torch, dev, B, K, W, mode, fused_T
         T = K + W
         self.env = env = VecEnv(B, device=dev, seed=seed, auto_reset=True, board_offset=board_offset)
+        self.rec = VecEnv(B, device=dev, seed=seed, auto_reset=True, board_offset=board_offset)
         self.state_bytes = int(_native.lib().qttt_state_bytes(64)) // 64
         gym = mode in ("gym", "gym-default")
         # algorithmic bytes per board-step: state r+w, action, reward f32, terminated (+ the 30-byte
@@ -382,54 +419,118 @@ class Workload:
         if mode == "random-fused":
             self.algo_bytes = 7.0 + 2.0 * self.state_bytes / fused_T
         self.shape = _native.step_launch_shape(B, 0, gym)
-        # ---- untimed: record the action stream of the uniform-legal policy
-        self.actions = actions = torch.empty((T, B, 2), dtype=torch.uint8, device=dev)
         self.term_count = torch.zeros((), dtype=torch.int64, device=dev)
         self.win_count = torch.zeros((), dtype=torch.int64, device=dev)
-        for t in range(T):
-            env.sample_actions(out=actions[t])
-            r, tm = env.step_raw(actions[t])
-            if t >= W:
-                self.term_count += tm.sum()
-                self.win_count += (r != 0).sum()
-        torch.cuda.synchronize(dev)
-        self.final_state = env.state.clone()
+        self.counted = False
+        self.recorded_once = 2 * T * B <= RECORD_BYTES_CAP
+        if self.recorded_once:
+            # ---- untimed: the whole stream once (actions only), replayed by every region
+            self.chunk = T
+            self.actions = actions = torch.empty((T, B, 2), dtype=torch.uint8, device=dev)
+            rec = self.rec
+            for t in range(T):
+                rec.sample_actions(out=actions[t])
+                r, tm = rec.step_raw(actions[t])
+                if t >= W:
+                    self.term_count += tm.sum()
+                    self.win_count += (r != 0).sum()
+            self.counted = True
+            torch.cuda.synchronize(dev)
+        else:
+            # ---- recorded again chunk by chunk inside every region (record()), all buffers allocated here
+            self.chunk = C = max(1, min(T, RECORD_BYTES_CAP // (8 * max(B, 1))))
+            self.actions = torch.empty((C, B, 2), dtype=torch.uint8, device=dev)
+            self.rec_reward = torch.empty((C, B), dtype=torch.float32, device=dev)
+            self.rec_term = torch.empty((C, B), dtype=torch.bool, device=dev)
+            self.rec_nonzero = torch.empty((C, B), dtype=torch.bool, device=dev)
         if mode == "random-fused":
             Tf = min(fused_T, K)
             self.f_act = torch.empty((Tf, B, 2), dtype=torch.uint8, device=dev)
             self.f_rew = torch.empty((Tf, B), dtype=torch.float32, device=dev)
             self.f_term = torch.empty((Tf, B), dtype=torch.bool, device=dev)
-        self.ev0 = torch.cuda.Event(enable_timing=True)
-        self.ev1 = torch.cuda.Event(enable_timing=True)
+        self.last = None
 
-    def preroll(self):
-        """back to the recorded state after W steps (the contract's W untimed warm-up steps)"""
-        self.env.reset_raw()
-        if self.W:
-            self.env.step_many(self.actions[:self.W])
+    def record(self, t0, c, count=True):
+        """steps t0 .. t0+c of the uniform-legal policy on the recording environment (step_random_many == sample_actions
+        + step_raw per step), their actions kept in self.actions[:c]; the episode counters over the timed steps once."""
+        self.rec.step_random_many(c, actions_out=self.actions[:c], reward=self.rec_reward[:c], terminated=self.rec_term[:c])
+        lo = max(0, self.W - t0)
+        if count and not self.counted and lo < c:
+            self.term_count += self.rec_term[lo:c].sum()
+            self.win_count += torch_ne_sum(self.torch, self.rec_reward[lo:c], self.rec_nonzero[lo:c])
 
-    def timed_steps(self):
-        env, K, W, mode = self.env, self.K, self.W, self.mode
+    def warm(self, passes):
+        """untimed: the first recorded steps (at most one chunk) replayed from reset `passes` times"""
+        n = min(self.chunk, self.K + self.W)
+        if not self.recorded_once:
+            self.rec.reset_raw()
+            self.record(0, n, count=False)
+        for _ in range(passes):
+            self.env.reset_raw()
+            self.env.step_many(self.actions[:n])
+            self.torch.cuda.synchronize(self.dev)
+
+    def first_actions(self, n):
+        """the first n (<= chunk) recorded steps' actions, on the host"""
+        if not self.recorded_once:
+            self.rec.reset_raw()
+            self.record(0, n)
+        return self.actions[:n].cpu().numpy()
+
+    def timed_steps(self, acts):
+        env, mode = self.env, self.mode
+        k = int(acts.shape[0])
         if mode == "replay":
-            env.step_many(self.actions[W:])
+            r, tm = env.step_many(acts)
+            last = {"reward": r, "terminated": tm}
         elif mode == "gym":
-            for t in range(K):
-                env.step_observe_raw(self.actions[W + t])
+            for t in range(k):
+                o, r, tm = env.step_observe_raw(acts[t])
+            last = dict(o, reward=r, terminated=tm)
         elif mode == "gym-default":
-            for t in range(K):                                    # a gym loop: the names are rebound every step
-                obs, reward, terminated, truncated, info = env.step(self.actions[W + t])
+            for t in range(k):                                    # a gym loop: the names are rebound every step
+                obs, reward, terminated, truncated, info = env.step(acts[t])
+            last = dict(obs, reward=reward, terminated=terminated, truncated=truncated)
         elif mode == "policy":
-            for t in range(K):
-                env.step_raw(env.sample_actions())
+            for t in range(k):
+                r, tm = env.step_raw(env.sample_actions())
+            last = {"reward": r, "terminated": tm}
         elif mode == "random":
-            for t in range(K):
-                env.step_random()
-        else:                                                     # random-fused: exactly K steps, <= fused_T per launch
+            for t in range(k):
+                r, tm = env.step_random()
+            last = {"reward": r, "terminated": tm}
+        else:                                                     # random-fused: exactly k steps, <= fused_T per launch
             done = 0
-            while done < K:
-                t = min(self.fused_T, K - done)
+            while done < k:
+                t = min(self.fused_T, k - done)
                 env.step_random_many(t, actions_out=self.f_act[:t], reward=self.f_rew[:t], terminated=self.f_term[:t])
                 done += t
+            last = {"actions": self.f_act[t - 1], "reward": self.f_rew[t - 1], "terminated": self.f_term[t - 1]}
+        self.last = last
+
+    def run_pass(self):
+        """reset, the W warm-up steps and the K timed steps, chunk by chunk; returns the (start, end) HIP events of the
+        timed launches.  The warm-up launches are enqueued right in front of the timed ones."""
+        torch, env, T, C, W = self.torch, self.env, self.K + self.W, self.chunk, self.W
+        env.reset_raw()
+        if not self.recorded_once:
+            self.rec.reset_raw()
+        events = []
+        for c0 in range(0, T, C):
+            c = min(C, T - c0)
+            if not self.recorded_once:
+                self.record(c0, c)
+            w = min(max(W - c0, 0), c)
+            if w:
+                env.step_many(self.actions[:w])
+            if w < c:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                self.timed_steps(self.actions[w:c])
+                e1.record()
+                events.append((e0, e1))
+        self.counted = True
+        return events
 
     def region(self, barrier):
         """One bracket = barrier + synchronize, W untimed steps, EXACTLY K timed steps, synchronize +
@@ -442,29 +543,62 @@ class Workload:
         torch.cuda.synchronize(self.dev)
         barrier()
         t0 = time.perf_counter()
-        self.preroll()
-        self.ev0.record()
-        self.timed_steps()
-        self.ev1.record()
+        events = self.run_pass()
         torch.cuda.synchronize(self.dev)
         t1 = time.perf_counter()
         barrier()
-        return self.ev0.elapsed_time(self.ev1) * 1e-3, (t1 - t0) * self.K / float(self.K + self.W)
+        return sum(e0.elapsed_time(e1) for e0, e1 in events) * 1e-3, (t1 - t0) * self.K / float(self.K + self.W)
 
-    def measure(self, barrier, all_max, regions=0, target_s=TARGET_TIMED_S, min_regions=5, max_regions=MAX_REGIONS):
-        pilot_ev, _ = self.region(barrier)                        # also the first-touch / clock ramp pass
-        pilot_ev = all_max(pilot_ev)
-        R = regions if regions > 0 else int(min(max_regions, max(min_regions, math.ceil(target_s / max(pilot_ev, 1e-6)))))
+    def measure(self, barrier, all_max, regions=0, target_s=TARGET_TIMED_S, min_regions=5, max_regions=MAX_REGIONS,
+                pilot=True):
+        """pilot=False: WARM_PASSES untimed warm-up passes, then exactly `regions` regions (at least one)."""
+        if pilot:
+            pilot_ev, _ = self.region(barrier)                    # also the first-touch / clock ramp pass
+            pilot_ev = all_max(pilot_ev)
+            R = regions if regions > 0 else int(min(max_regions, max(min_regions, math.ceil(target_s / max(pilot_ev, 1e-6)))))
+        else:
+            self.warm(WARM_PASSES)
+            R = max(1, regions)
         ev_s, wall_s = [], []
         for _ in range(R):
             e, w = self.region(barrier)
             ev_s.append(e)
             wall_s.append(w)
-        self.replay_ok = bool(self.torch.equal(self.env.state, self.final_state))
+        self.replay_ok = bool(self.torch.equal(self.env.state, self.rec.state))
         # this rank's own numbers (reported per rank in the N > 1 line) ...
         self.rank_median_s, self.rank_best_s, self.rank_wall_s = median(ev_s), min(ev_s), median(wall_s)
         # ... and the MAX over ranks of each rank's median region: what `value` is made from
         return all_max(self.rank_median_s), all_max(self.rank_best_s), all_max(self.rank_wall_s), R
+
+    def dump(self, out_dir, outputs_budget=40 * 10 ** 6, board_sample=65536):
+        """What the last timed step computed as out_dir/<name>.npy in float32 (every field is an integer below 2**24 or
+        already float32): the arrays its caller receives (reward, terminated, ...), for every board while they fit in
+        `outputs_budget` bytes, else for a fixed seeded sample of boards (sample_index.npy); and the boards after it
+        (export_boards, board_*.npy) for a fixed seeded sample of at most `board_sample` boards (board_index.npy).
+        Under 64 MB in all."""
+        import numpy as np
+        torch, B = self.torch, self.B
+
+        def sample(n, seed):
+            if n >= B:
+                return None
+            return np.sort(np.random.default_rng(seed).choice(B, size=n, replace=False))
+
+        def save(arrays, idx, index_name):
+            if idx is not None:
+                np.save(os.path.join(out_dir, index_name + ".npy"), idx.astype(np.float64))
+                idx = torch.from_numpy(idx).to(self.dev)
+            for k, v in arrays.items():
+                v = v.reshape(B, -1) if v.dim() != 1 else v
+                if idx is not None:
+                    v = v.index_select(0, idx)
+                np.save(os.path.join(out_dir, k + ".npy"), v.to(torch.float32).cpu().numpy())
+
+        os.makedirs(out_dir, exist_ok=True)
+        outputs = {k: v for k, v in self.last.items() if torch.is_tensor(v)}
+        per_board = sum(4 * (v.numel() // B) for v in outputs.values())
+        save(outputs, sample(max(1, outputs_budget // (per_board + 8)), 12345), "sample_index")
+        save({"board_" + k: v for k, v in self.env.export_boards().items()}, sample(board_sample, 54321), "board_index")
 
 
 def run_legs(torch, dev, args):
@@ -519,6 +653,7 @@ def gym_default_leg(torch, dev, args, n=1 << 20, K=100, W=10):
     timed Python calls: the slower of host and device), the same calls captured in a hipGraph and replayed
     (device-paced: the kernel's own rate), and K eager calls onto an idle stream."""
     w = Workload(torch, dev, n, K, W, args.seed, 0, "gym-default", 64)
+    assert w.recorded_once                                      # w.actions holds all K + W steps
     ev, ev_min, _, R = w.measure(lambda: None, float, target_s=0.02, max_regions=100)
     us = ev / K * 1e6
     env, a = w.env, w.actions[W]
@@ -778,7 +913,11 @@ def run(args):
         torch.cuda.set_stream(torch.cuda.Stream(device=dev))
     wl = Workload(torch, dev, B, K, W, args.seed, offset, args.mode, args.fused_steps)
     env, state_bytes, algo_bytes = wl.env, wl.state_bytes, wl.algo_bytes
-    ev_med, ev_min, wall_med, R = wl.measure(barrier, all_max, regions=args.regions)
+    # a plain run times exactly K steps once (--regions R: R regions, the median); --full: a pilot region, then regions
+    # until their timed parts add up to TARGET_TIMED_S
+    ev_med, ev_min, wall_med, R = wl.measure(barrier, all_max, regions=args.regions, pilot=args.full)
+    if args.dump_outputs and rank == 0:
+        wl.dump(args.dump_outputs)
     replay_ok = wl.replay_ok
     term_count, win_count = wl.term_count, wl.win_count
     from qtttgym_amd.dist import gather_rank_values, agree
@@ -935,9 +1074,12 @@ def run(args):
                              "beyond_cache_frac_of_achievable": None,
                              "beyond_cache": None},
             }
-            actions = wl.actions
+            cpu_actions = None
+            if args.full and not args.no_cpu_baseline and world == 1:
+                # bounded sample: the first <=256 recorded steps of every board of rank 0
+                cpu_actions = wl.first_actions(min(K + W, 256, wl.chunk))
             del wl
-            if world == 1 and not args.no_legs:
+            if args.full and world == 1 and not args.no_legs:
                 out["legs"] = run_legs(torch, dev, args)
                 big = [l for l in out["legs"] if l["name"].startswith("beyond_infinity_cache")]
                 if big:
@@ -948,10 +1090,8 @@ def run(args):
                     out["roofline"].update(beyond_cache_boards=big[0]["boards"], beyond_cache_launch_us=big[0]["us_per_step"],
                                            beyond_cache_frac=big[0]["frac"],
                                            beyond_cache_frac_of_achievable=big[0]["achieved_GBps"] / HBM_ACHIEVABLE_GBS)
-            if not args.no_cpu_baseline and world == 1:                 # rank 0 at N = 1 only
-                # bounded sample: the first <=256 recorded steps of every board of rank 0, ~14 s of CPU in all
-                t_cpu = min(K + W, 256)
-                out["cpu_baseline"] = cpu_baseline(actions[:t_cpu].cpu().numpy(), args.seed, args.cpu_budget)
+            if cpu_actions is not None:                                 # rank 0 at N = 1 only, ~14 s of CPU in all
+                out["cpu_baseline"] = cpu_baseline(cpu_actions, args.seed, args.cpu_budget)
             if "legs" in out:
                 # LAST in the object, so that a stored tail of the line still carries them: BASELINE configs 2 / 3 / 5 and
                 # the beyond-cache fraction as plain scalars ("report both")

@@ -25,7 +25,7 @@ def run_bench(*args, env=None):
 
 
 def test_bench_json_contract_small_batch():
-    d = run_bench("--boards", "65536", "--steps", "40", "--warmup", "5", "--cpu-budget", "2", "--no-legs")
+    d = run_bench("--boards", "65536", "--steps", "40", "--warmup", "5", "--cpu-budget", "2", "--no-legs", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "ranks_seen", "steps", "warmup", "ms_per_step",
               "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline",
               "cpu_baseline", "clock", "regions", "host_wall_ms_per_step"):
@@ -93,11 +93,11 @@ def test_bench_gpus_2_starts_its_own_two_ranks():
 
 
 def test_bench_default_line_carries_the_legs():
-    """the driver-run line itself carries the other BASELINE configurations and modes, measured
+    """the --full line carries the other BASELINE configurations and modes, measured
     in the same process on the same clock, and the whole run stays short."""
     import time
     t0 = time.time()
-    d = run_bench("--steps", "20", "--warmup", "5", "--cpu-budget", "2")
+    d = run_bench("--steps", "20", "--warmup", "5", "--cpu-budget", "2", "--full")
     assert time.time() - t0 < 120
     assert d["config"]["boards_per_gpu"] == 1 << 20 and d["config"]["mode"] == "replay"
     legs = {l["name"]: l for l in d["legs"]}
@@ -256,3 +256,37 @@ def test_bench_two_ranks_on_rccl_when_two_gpus_are_visible():
     assert s["scaling"] == "strong" and s["config"]["boards_per_gpu"] == 262144 and s["ranks_seen"] == 2
     one = run_bench("--boards", "524288", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-legs")
     assert one["config"]["episodes_finished"] == d["config"]["episodes_finished"]      # the same 524 288 boards, sharded or not
+
+
+def test_plain_run_times_exactly_the_steps_asked_and_nothing_else():
+    """A plain run: one region of exactly --steps timed steps, no legs, no CPU baseline, the headline fields."""
+    d = run_bench("--boards", "65536", "--steps", "30", "--warmup", "3")
+    assert d["steps"] == 30 and d["warmup"] == 3 and d["regions"] == 1
+    assert "legs" not in d and "cpu_baseline" not in d and "configs" not in d
+    assert d["metric"] == "env_steps_per_sec" and d["unit"] == "steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "u64" and d["ms_per_step"] > 0
+    assert abs(d["value"] - 65536 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-9
+    assert d["config"]["replay_matches_recording"] is True
+
+
+def test_dump_outputs_are_reproducible_and_chunking_does_not_change_them(tmp_path):
+    """--dump-outputs: the last timed step's reward / terminated and the boards after it, float32, identical from run
+    to run; a recording cap of 16 steps (the stream recorded and replayed in chunks) computes the same."""
+    import numpy as np
+    common = ("--boards", "65536", "--steps", "100", "--warmup", "7")
+    a = run_bench(*common, "--dump-outputs", str(tmp_path / "a"))
+    b = run_bench(*common, "--dump-outputs", str(tmp_path / "b"))
+    c = run_bench(*common, "--dump-outputs", str(tmp_path / "c"), env={"QTTT_BENCH_RECORD_BYTES": str(8 * 65536 * 16)})
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert "reward.npy" in names and "terminated.npy" in names and "board_board.npy" in names
+    assert sorted(os.listdir(tmp_path / "b")) == names == sorted(os.listdir(tmp_path / "c"))
+    total = 0
+    for n in names:
+        x = np.load(tmp_path / "a" / n)
+        total += x.nbytes
+        assert x.dtype == np.float32 and x.shape[0] == 65536, n
+        assert np.array_equal(x, np.load(tmp_path / "b" / n)) and np.array_equal(x, np.load(tmp_path / "c" / n)), n
+    assert total <= 64 << 20
+    for d in (a, b, c):
+        assert d["config"]["replay_matches_recording"] is True and d["steps"] == 100
+    assert a["config"]["episodes_finished"] == c["config"]["episodes_finished"] > 0

@@ -83,7 +83,7 @@ def test_one_rank_failing_to_prepare_the_gather_does_not_hang_the_others():
 def test_the_tail_of_the_default_line_carries_the_baseline_configs():
     """a driver that stores only the tail of the (14 KB) line, or only scalar fields of `roofline`, still
     sees BASELINE configs 2 / 3 / 5 and the beyond-cache fraction."""
-    out, lines = bench("--cpu-budget", "2")
+    out, lines = bench("--cpu-budget", "2", "--full")
     line = lines[0]
     tail = line[-800:]
     for k in ("config2_us", "config3_us", "config3_frac", "config5_us", "beyond_cache_frac", "gym_default_us", "gym_default_eager_us"):

@@ -4,7 +4,7 @@
 # Passes (each its own process; counters never share a run with --kernel-trace/--stats):
 #   kt        --kernel-trace --stats over the driver-shaped command (bench.py --steps 20 --warmup 5), no legs: the
 #             timed region's dispatches, their gaps and periods (tools/trace_summary.py)
-#   kt_full   the same over the DEFAULT command with its legs (what the driver runs), --stats table only
+#   kt_full   the same over bench.py --full (the legs included), --stats table only
 #   kt16      16 777 216 boards per launch (a 105 us kernel: the profiler's per-dispatch cost no longer shows)
 #   kt_gym    --mode gym;  kt_fused  --mode random-fused at 262 144 boards (BASELINE config 3 / config 4's shard)
 #   kt_rows   tools/bench_rows.py: the kernels beside the step (observe, export, import, node_info, expand, rollout, ...)
@@ -21,7 +21,7 @@ SQ="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYC
 run() { name=$1; shift; echo "== $name: $*"; "$@" > "$out/$name.log" 2>&1; echo "rc=$?" >> "$out/$name.log"; tail -2 "$out/$name.log"; }
 N="--no-cpu-baseline --no-legs"
 run kt       rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt"       -- python3 "$B" --steps 20 --warmup 5 $N "$@"
-run kt_full  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt_full"  -- python3 "$B" --no-cpu-baseline "$@"
+run kt_full  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt_full"  -- python3 "$B" --full --no-cpu-baseline "$@"
 run kt16     rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt16"     -- python3 "$B" --boards 16777216 --steps 10 --warmup 2 --regions 4 $N "$@"
 run kt_gym   rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt_gym"   -- python3 "$B" --steps 20 --warmup 5 $N --mode gym "$@"
 QTTT_ROWS_MIN_S=0 run kt_rows  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt_rows"  -- python3 "$R/tools/bench_rows.py"
