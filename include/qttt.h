@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define QTTT_ABI_VERSION 5
+#define QTTT_ABI_VERSION 6
 
 #define QTTT_ERR_NULL   (-1)
 #define QTTT_ERR_SIZE   (-2)
@@ -326,4 +326,8 @@ uint64_t qttt_hash(uint64_t seed, uint64_t board_id, uint32_t step_idx);
 #ifdef __cplusplus
 }
 #endif
+
+/* The policy/value network entry points (ABI 6) are declared in qttt_nn.h, included here so that this one
+ * header gives a C caller the whole library. */
+#include "qttt_nn.h"
 #endif

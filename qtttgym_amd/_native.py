@@ -7,13 +7,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # QTTT_LIB_PATH: load another build of the same ABI (A/B diagnostics); default = the in-tree build
 LIB_PATH = os.environ.get("QTTT_LIB_PATH") or os.path.join(_HERE, "libqttt_hip.so")
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 FLAG_AUTO_RESET = 1
 FLAG_FUSED = 2
 BOARD_RECORD_BYTES = 64
 SIM_STRIDE = 16
 EXPAND_ROLLOUT_MAX_SIMS = 128
 OP_MAKE_MOVE, OP_UPDATE_QSTRUCTS, OP_CHECK_WIN = 0, 1, 2
+NN_F32, NN_BF16 = 0, 1
 
 class EnvRecord(ctypes.Structure):
     """include/qttt.h: struct qttt_env."""
@@ -62,6 +63,11 @@ SIGNATURES = {
     "qttt_counter_add": (_i32, [_vp, _u32, _vp]),
     "qttt_step_random": (_i32, [_vp, _u64, _u32, _i64, _u32, _vp, _vp, _vp, _i64, _vp]),
     "qttt_hash": (_u64, [_u64, _u64, _u32]),
+}
+# every symbol include/qttt_nn.h declares (the policy/value network, ABI 6; qttt.h includes it)
+NN_SIGNATURES = {
+    "qttt_nn_weights_bytes": (_i64, [_i32]),
+    "qttt_evaluate": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None
@@ -124,7 +130,7 @@ def lib():
                 "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(NN_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -46,7 +46,7 @@
 //
 // Files: qttt_state.h (layout, loads/stores, shared tables) -> qttt_step_core.h (the step) ->
 // qttt_observation.h -> qttt_step_kernels.h; qttt_board_forms.h (unpacked views, winner, legal mask,
-// tuple hash) -> qttt_aux_kernels.h, qttt_mcts_kernels.h; this file: launch logic + the C ABI.
+// tuple hash) -> qttt_aux_kernels.h, qttt_mcts_kernels.h, qttt_nn_kernels.h (the policy/value network); this file: launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -54,6 +54,7 @@
 #include "qttt_step_kernels.h"
 #include "qttt_aux_kernels.h"
 #include "qttt_mcts_kernels.h"
+#include "qttt_nn_kernels.h"
 
 namespace {
 
@@ -913,6 +914,29 @@ int qttt_encode(const void *state, float *vec, uint8_t *mask, int64_t n, void *s
     if (((uintptr_t)vec & 15u) || ((uintptr_t)mask & 3u)) return QTTT_ERR_ACTION;   // vector stores
     hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((n + QTTT_ENC_BOARDS - 1) / QTTT_ENC_BOARDS)),
                        dim3(QTTT_ENC_BLOCK), 0, (hipStream_t)stream, p.P, p.Q, vec, mask, n);
+    return launch_status();
+}
+
+int64_t qttt_nn_weights_bytes(int precision) {
+    if (precision == QTTT_NN_F32) return NNBlob<0>::BYTES;
+    if (precision == QTTT_NN_BF16) return NNBlob<1>::BYTES;
+    return -1;
+}
+
+int qttt_evaluate(const void *state, const void *weights, int precision, float *value, float *logits, float *probs,
+                  int64_t n, void *stream) {
+    if (n < 0 || (precision != QTTT_NN_F32 && precision != QTTT_NN_BF16)) return QTTT_ERR_SIZE;
+    if (n == 0) return 0;
+    if (!state || !weights || (!value && !logits && !probs)) return QTTT_ERR_NULL;
+    if (((uintptr_t)weights & 15u) || ((uintptr_t)value & 3u) || ((uintptr_t)logits & 3u) || ((uintptr_t)probs & 3u))
+        return QTTT_ERR_ACTION;                                  // 16-byte fragment loads / f32 stores
+    Planes p = planes(const_cast<void *>(state), n);
+    if (precision == QTTT_NN_F32)
+        hipLaunchKernelGGL(evaluate_kernel<0>, dim3((unsigned)((n + NNCfg<0>::M - 1) / NNCfg<0>::M)), dim3(QTTT_NN_BLOCK),
+                           0, (hipStream_t)stream, p.P, p.Q, weights, value, logits, probs, n);
+    else
+        hipLaunchKernelGGL(evaluate_kernel<1>, dim3((unsigned)((n + NNCfg<1>::M - 1) / NNCfg<1>::M)), dim3(QTTT_NN_BLOCK),
+                           0, (hipStream_t)stream, p.P, p.Q, weights, value, logits, probs, n);
     return launch_status();
 }
 

@@ -829,6 +829,33 @@ class VecEnv:
         _native.check(rc, "qttt_encode")
         return (vec, mask) if with_mask else vec
 
+    _EVAL_ROWS = {"value": (), "logits": (36,), "probs": (36,)}
+
+    def evaluate(self, net, rows=("value", "logits"), out=None):
+        """nn.Model.forward(GameState.to_vector()) (nn.py:7-72, alphazero.py:294-300) for every board in ONE kernel
+        (include/qttt_nn.h qttt_evaluate): a dict of the requested rows among value f32[N], logits f32[N,36] (-inf at
+        illegal actions) and probs f32[N,36] (= Categorical(logits).probs; NaN rows where every action is masked).
+        `net` = a PolicyValueNet on this device.  `out` = the dict of an earlier call: its tensors are overwritten and
+        its keys decide which rows are computed (`rows` is then ignored).  Runs on the current stream."""
+        n, dev = self.num_envs, self.state.device
+        if getattr(net, "device", None) != dev or not hasattr(net, "blob"):
+            raise ValueError("net must be a PolicyValueNet on %s" % (dev,))
+        if out is None:
+            rows = (rows,) if isinstance(rows, str) else tuple(rows)
+            if not rows or any(r not in self._EVAL_ROWS for r in rows):
+                raise ValueError("rows must be a non-empty subset of %s" % (tuple(self._EVAL_ROWS),))
+            with torch.cuda.device(dev):
+                out = {r: torch.empty((n,) + self._EVAL_ROWS[r], dtype=torch.float32, device=dev) for r in rows}
+        else:
+            if not out or any(r not in self._EVAL_ROWS for r in out):
+                raise ValueError("out must be a dict returned by evaluate()")
+            for r, t in out.items():
+                _check_out(t, torch.float32, (n,) + self._EVAL_ROWS[r], dev, "out[%r]" % r)
+        rc = self._launch(self._lib.qttt_evaluate, self.state.data_ptr(), net.blob.data_ptr(), net.precision,
+                          _ptr(out.get("value")), _ptr(out.get("logits")), _ptr(out.get("probs")), n, self._stream())
+        _native.check(rc, "qttt_evaluate")
+        return out
+
     # ------------------------------------------------------------------ hipGraph of T step launches
     def capture(self, n_steps, mode="random", actions=None, bits=None, actions_out=None, reward=None, terminated=None):
         """Captures n_steps step LAUNCHES into one hipGraph and returns it (`.replay()`): for loops on small
