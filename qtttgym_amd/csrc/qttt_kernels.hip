@@ -51,6 +51,7 @@
 #include <chrono>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include "qttt_step_kernels.h"
 #include "qttt_aux_kernels.h"
 #include "qttt_mcts_kernels.h"
@@ -119,6 +120,47 @@ inline int blocks_for(int64_t n_groups, int block) { return (int)((n_groups + bl
 inline int launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
+}
+
+// Kernel selection: f(std::integral_constant<bool, b>...) for the runtime flags b..., and f(std::integral_constant<int,
+// V>) for the V of Vs that equals v (the last one when none does).  Every combination is one instantiation of f, reached
+// through a tree of plain branches, so a launch inside f is a direct launch of one kernel instance.
+template <typename F>
+inline void with_bools(F &&f) { f(); }
+template <typename F, typename... B>
+inline void with_bools(F &&f, bool b, B... rest) {
+    if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+template <int V, int... Vs, typename F>
+inline void with_int(int v, F &&f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>{});
+    else if (v == V) f(std::integral_constant<int, V>{});
+    else with_int<Vs...>(v, f);
+}
+
+// The observation buffers (qttt_observe's outputs) of a batch of n boards: all given when n > 0, q_p1 2-byte and q_p2
+// 8-byte aligned (the kernels store whole rows from LDS, 2 / 8 bytes at a time).
+inline bool obs_missing(const ObsOut &o) {
+    return !o.classical || !o.q_p1 || !o.q_p1_len || !o.q_p2 || !o.q_p2_len || !o.turn;
+}
+inline int obs_check(const ObsOut &o, int64_t n) {
+    if (n > 0 && obs_missing(o)) return QTTT_ERR_NULL;
+    return (((uintptr_t)o.q_p1 & 1u) || ((uintptr_t)o.q_p2 & 7u)) ? QTTT_ERR_ACTION : 0;
+}
+
+// Runs of at most FUSED_MAX_PLIES plies from step_idx0 on, one launch each (the plies' launch keys travel as a kernel
+// argument): launch(done, plies, keys) for every run, in order; stops at the first launch that fails.
+template <typename F>
+inline int fused_runs(uint64_t seed, uint32_t step_idx0, int32_t n_steps, F &&launch) {
+    for (int64_t done = 0; done < n_steps; done += FUSED_MAX_PLIES) {
+        const int32_t plies = (int32_t)(n_steps - done < FUSED_MAX_PLIES ? n_steps - done : FUSED_MAX_PLIES);
+        FusedKeys keys;
+        for (int32_t t = 0; t < FUSED_MAX_PLIES; ++t) keys.k[t] = launch_key(seed, step_idx0 + (u32)done + (u32)(t < plies ? t : 0));
+        launch(done, plies, keys);
+        if (const int rc = launch_status()) return rc;
+    }
+    return 0;
 }
 
 // A hint: the single-record mailbox wave (board_mailbox, below) MAY be resident.  It holds one wave slot of one CU, so a
@@ -226,7 +268,8 @@ int qttt_reset_observe(void *state, int8_t *classical, uint8_t *q_p1, uint8_t *q
                        uint8_t *q_p2_len, uint8_t *turn, int64_t n, void *stream) {
     if (n < 0) return QTTT_ERR_SIZE;
     if (n == 0) return 0;
-    if (!state || !classical || !q_p1 || !q_p1_len || !q_p2 || !q_p2_len || !turn) return QTTT_ERR_NULL;
+    const ObsOut o = {classical, q_p1, q_p1_len, q_p2, q_p2_len, turn};
+    if (!state || obs_missing(o)) return QTTT_ERR_NULL;
     FillSegs f;
     const int64_t sb = plane_stride(n) * QTTT_STATE_BYTES;
     uint8_t *ptrs[7] = {static_cast<uint8_t *>(state), reinterpret_cast<uint8_t *>(classical), q_p1, q_p1_len, q_p2, q_p2_len, turn};
@@ -244,81 +287,71 @@ int qttt_reset_observe(void *state, int8_t *classical, uint8_t *q_p1, uint8_t *q
     return launch_status();
 }
 
+// reset_kernel rather than hipMemsetAsync: measured with bench.py, alternating on one box (profiles/r05/bench_reset_ab.txt)
 int qttt_reset(void *state, int64_t n, void *stream) {
     if (n < 0) return QTTT_ERR_SIZE;
     if (n == 0) return 0;
     if (!state) return QTTT_ERR_NULL;
-#ifdef QTTT_RESET_MEMSET                      // (A/B builds only: hipMemsetAsync, as up to round 4)
-    hipError_t e = hipMemsetAsync(state, 0, (size_t)(plane_stride(n) * QTTT_STATE_BYTES), (hipStream_t)stream);
-    return e == hipSuccess ? 0 : (int)e;
-#else
     const int64_t n16 = plane_stride(n) * QTTT_STATE_BYTES / 16;
     hipLaunchKernelGGL(reset_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        static_cast<u32x4 *>(state), n16);
     return launch_status();
-#endif
 }
 
-static int launch_step(void *state, uint8_t *actions, const uint8_t *bits, uint64_t seed,
-                       uint32_t step_idx, int64_t board_offset, uint32_t flags, float *reward,
-                       uint8_t *terminated, int64_t n, void *stream, bool sample, const ObsOut *obs,
-                       const uint32_t *step_ctr = nullptr) {
+// One step of the record's boards: qttt_env_step's modes STEP, STEP_OBSERVE (obs) and STEP_RANDOM (sample: the policy
+// draws the actions, and writes them to `actions` when that is not null).
+static int launch_step(const qttt_env &e, uint8_t *actions, const uint8_t *bits, uint32_t step_idx, void *stream,
+                       bool sample, const ObsOut *obs) {
+    const int64_t n = e.n, board_offset = e.board_offset;
     if (n < 0 || board_offset < 0) return QTTT_ERR_SIZE;
     if (n == 0) return 0;
-    if (!state || !reward || !terminated || (!sample && !actions)) return QTTT_ERR_NULL;
+    if (!e.state || !e.reward || !e.terminated || (!sample && !actions)) return QTTT_ERR_NULL;
     if ((uintptr_t)actions & 1u) return QTTT_ERR_ACTION;   // actions are accessed as u16 pairs
     retire_mailbox_for(n, stream);
-    Planes p = planes(state, n);
+    const Planes p = planes(e.state, n);
+    const uint32_t *step_ctr = e.step_counter;
     // with a device-side step counter the kernel makes the key itself: it gets the offset and the id fold
-    const u64 key = step_ctr ? ((u64)step_idx << 32) : launch_key(seed, step_idx);
+    const u64 key = step_ctr ? ((u64)step_idx << 32) : launch_key(e.seed, step_idx);
     const u32 key_lo = (u32)key, key_hi = (u32)(key >> 32);
     hipStream_t s = (hipStream_t)stream;
     uint16_t *a16 = reinterpret_cast<uint16_t *>(actions);
-    u32 *rb = reinterpret_cast<u32 *>(reward);
-    const bool ar = (flags & QTTT_FLAG_AUTO_RESET) != 0;
+    u32 *rb = reinterpret_cast<u32 *>(e.reward);
     int bpl_max, blk_sel;
-    resolve_shape(n, flags, obs != nullptr, bpl_max, blk_sel);
+    resolve_shape(n, e.flags, obs != nullptr, bpl_max, blk_sel);
     // widest boards-per-lane the caller's pointers are aligned for (the planes always are)
     auto aligned = [&](int k) {
-        return ((uintptr_t)actions % (2u * k)) == 0 && ((uintptr_t)reward % (4u * k)) == 0 &&
-               ((uintptr_t)terminated % (unsigned)k) == 0 && (!bits || ((uintptr_t)bits % (unsigned)k) == 0);
+        return ((uintptr_t)actions % (2u * k)) == 0 && ((uintptr_t)e.reward % (4u * k)) == 0 &&
+               ((uintptr_t)e.terminated % (unsigned)k) == 0 && (!bits || ((uintptr_t)bits % (unsigned)k) == 0);
     };
     while (bpl_max > 1 && !aligned(bpl_max)) bpl_max >>= 1;
     const ObsOut oo = obs ? *obs : ObsOut{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-#define QTTT_LAUNCH_B(BLK, BPL, HB, AR, SM, OB, I0, NG, KF, IDB)                                        \
-    hipLaunchKernelGGL((step_kernel<BLK, BPL, HB, AR, SM, OB>), dim3(blocks_for(NG, BLK)), dim3(BLK), 0, s, \
-                       p.P, p.Q, a16, bits, (u32)(KF), key_hi, (u32)(IDB), rb, terminated, oo,         \
-                       (int64_t)(I0), (u32)((NG) - (int64_t)(blocks_for(NG, BLK) - 1) * (BLK)), StepKeySource<false>{})
-    // workgroup size as chosen above; four boards per lane exists with 512 threads only
-#define QTTT_LAUNCH(BPL, HB, AR, SM, OB, I0, NG, KF, IDB)                                              \
-    do {                                                                                              \
-        if ((BPL) == 4 || blk_sel == QTTT_BLOCK) QTTT_LAUNCH_B(QTTT_BLOCK, BPL, HB, AR, SM, OB, I0, NG, KF, IDB); \
-        else if (blk_sel == 1024) QTTT_LAUNCH_B(1024, ((BPL) == 4 ? 2 : (BPL)), HB, AR, SM, OB, I0, NG, KF, IDB); \
-        else QTTT_LAUNCH_B(256, ((BPL) == 4 ? 2 : (BPL)), HB, AR, SM, OB, I0, NG, KF, IDB);             \
-    } while (0)
-#define QTTT_DISPATCH(BPL, I0, NG, KF, IDB)                                                           \
-    do {                                                                                              \
-        if (obs) {                                                                                    \
-            if (bits) { if (ar) QTTT_LAUNCH(BPL, true, true, false, true, I0, NG, KF, IDB); else QTTT_LAUNCH(BPL, true, false, false, true, I0, NG, KF, IDB); } \
-            else { if (ar) QTTT_LAUNCH(BPL, false, true, false, true, I0, NG, KF, IDB); else QTTT_LAUNCH(BPL, false, false, false, true, I0, NG, KF, IDB); } \
-        }                                                                                             \
-        else if (sample) { if (ar) QTTT_LAUNCH(BPL, false, true, true, false, I0, NG, KF, IDB); else QTTT_LAUNCH(BPL, false, false, true, false, I0, NG, KF, IDB); } \
-        else if (bits) { if (ar) QTTT_LAUNCH(BPL, true, true, false, false, I0, NG, KF, IDB); else QTTT_LAUNCH(BPL, true, false, false, false, I0, NG, KF, IDB); } \
-        else { if (ar) QTTT_LAUNCH(BPL, false, true, false, false, I0, NG, KF, IDB); else QTTT_LAUNCH(BPL, false, false, false, false, I0, NG, KF, IDB); } \
-    } while (0)
-    // Device-side step counter (graph capture: small, launch-bound batches): one launch shape — one board per
-    // lane, 256-thread workgroups — and the kernels that make the launch key themselves.
-    const StepKeySource<true> sk = {step_ctr, (u64)seed};
-#define QTTT_LAUNCH_DEV(AR, SM, OB, I0, NG, KF, IDB)                                                    \
-    hipLaunchKernelGGL((step_kernel<256, 1, false, AR, SM, OB, true>), dim3(blocks_for(NG, 256)), dim3(256), 0, s, \
-                       p.P, p.Q, a16, bits, (u32)(KF), key_hi, (u32)(IDB), rb, terminated, oo,         \
-                       (int64_t)(I0), (u32)((NG) - (int64_t)(blocks_for(NG, 256) - 1) * 256), sk)
-#define QTTT_DISPATCH_DEV(I0, NG, KF, IDB)                                                            \
-    do {                                                                                              \
-        if (obs) { if (ar) QTTT_LAUNCH_DEV(true, false, true, I0, NG, KF, IDB); else QTTT_LAUNCH_DEV(false, false, true, I0, NG, KF, IDB); } \
-        else if (sample) { if (ar) QTTT_LAUNCH_DEV(true, true, false, I0, NG, KF, IDB); else QTTT_LAUNCH_DEV(false, true, false, I0, NG, KF, IDB); } \
-        else { if (ar) QTTT_LAUNCH_DEV(true, false, false, I0, NG, KF, IDB); else QTTT_LAUNCH_DEV(false, false, false, I0, NG, KF, IDB); } \
-    } while (0)
+    // Device-side step counter (graph capture: small, launch-bound batches): one launch shape — one board per lane,
+    // 256-thread workgroups — and the kernels that make the launch key themselves.  Explicit bits need no key: the
+    // ordinary kernels take them.
+    const bool devstep = step_ctr && !bits;
+    const StepKeySource<true> sk = {step_ctr, (u64)e.seed};
+    const bool ob = obs != nullptr, sm = sample && !ob, hb = bits && !sm;
+    // `groups` lane-groups of bpl boards from board i0, in blk-thread workgroups (four boards per lane come with
+    // QTTT_BLOCK threads: resolve_shape)
+    auto launch = [&](int bpl, int blk, int64_t i0, int64_t groups, u32 key_fold, u32 id_base) {
+        with_bools([&](auto DEV, auto HB, auto AR, auto SM, auto OB) {
+            with_int<4, 2, 1>(bpl, [&](auto BPL) {
+                with_int<QTTT_BLOCK, 1024, 256>(blk, [&](auto BLK) {
+                    // the instances that exist: the policy draws its own bits and writes no observation, the
+                    // observation tiles take at most two boards per lane, four boards per lane come with QTTT_BLOCK
+                    // threads, and the device-side counter has its one shape
+                    if constexpr (!(SM && (HB || OB)) && !(OB && BPL == 4) && (BPL != 4 || BLK == QTTT_BLOCK) &&
+                                  (!DEV || (BLK == 256 && BPL == 1 && !HB))) {
+                        const int grid = blocks_for(groups, BLK);
+                        const auto key_source = [&] { if constexpr (DEV) return sk; else return StepKeySource<false>{}; };
+                        hipLaunchKernelGGL((step_kernel<BLK, BPL, HB, AR, SM, OB, DEV>), dim3(grid), dim3(BLK), 0, s,
+                                           p.P, p.Q, a16, bits, key_fold, key_hi, id_base, rb, e.terminated, oo, i0,
+                                           (u32)(groups - (int64_t)(grid - 1) * BLK), key_source());
+                    }
+                });
+            });
+        }, devstep, hb, (e.flags & QTTT_FLAG_AUTO_RESET) != 0, sm, ob);
+    };
     // The hash folds the global board id as lo32 ^ hi32*C (fold_id).  hi32 is uniform over a
     // range of boards unless the range crosses a multiple of 2^32; the batch is cut there (at most
     // once), so the kernel only ever adds a lane index to a 32-bit base.
@@ -329,81 +362,85 @@ static int launch_step(void *state, uint8_t *actions, const uint8_t *bits, uint6
         const int64_t seg_n = (int64_t)((u64)(n - seg_begin) < to_boundary ? (u64)(n - seg_begin) : to_boundary);
         const u32 key_fold = key_lo ^ ((u32)(first >> 32) * 0x9E3779B9u);
         const u32 id_base = (u32)first;
-        if (step_ctr && !bits) {                                 // (explicit bits need no key: the ordinary kernels do)
-            QTTT_DISPATCH_DEV(seg_begin, seg_n, key_fold, id_base);
+        if (devstep) {
+            launch(1, 256, seg_begin, seg_n, key_fold, id_base);
             seg_begin += seg_n;
             continue;
         }
         int bpl = bpl_max;
         while (bpl > 1 && (seg_begin % bpl) != 0) bpl >>= 1;     // vector accesses need an aligned start
         const int64_t n_groups = seg_n / bpl, n_main = n_groups * bpl;
-        if (n_groups > 0) {
-            if (bpl == 4) QTTT_DISPATCH(4, seg_begin, n_groups, key_fold, id_base);
-            else if (bpl == 2) QTTT_DISPATCH(2, seg_begin, n_groups, key_fold, id_base);
-            else QTTT_DISPATCH(1, seg_begin, n_groups, key_fold, id_base);
-        }
+        if (n_groups > 0) launch(bpl, blk_sel, seg_begin, n_groups, key_fold, id_base);
         if (n_main < seg_n)                                      // ragged tail, one board per lane
-            QTTT_DISPATCH(1, seg_begin + n_main, seg_n - n_main, key_fold, id_base + (u32)n_main);
+            launch(1, blk_sel, seg_begin + n_main, seg_n - n_main, key_fold, id_base + (u32)n_main);
         seg_begin += seg_n;
     }
-#undef QTTT_DISPATCH_DEV
-#undef QTTT_LAUNCH_DEV
-#undef QTTT_DISPATCH
-#undef QTTT_LAUNCH
-#undef QTTT_LAUNCH_B
     return launch_status();
+}
+
+static int launch_sample(const qttt_env &e, uint8_t *actions, uint32_t step_idx, void *stream) {
+    const int64_t n = e.n;
+    if (n < 0 || e.board_offset < 0) return QTTT_ERR_SIZE;
+    if (n == 0) return 0;
+    if (!e.state || !actions) return QTTT_ERR_NULL;
+    if ((uintptr_t)actions & 1u) return QTTT_ERR_ACTION;   // written as u16 pairs
+    const Planes p = planes(e.state, n);
+    const u64 key = e.step_counter ? ((u64)step_idx << 32) : launch_key(e.seed, step_idx);
+    hipLaunchKernelGGL(sample_actions_kernel, dim3(grid_for((n + 1) / 2)), dim3(QTTT_BLOCK), 0,
+                       (hipStream_t)stream, p.P, (u32)key, (u32)(key >> 32), (u64)e.board_offset,
+                       (u32)((e.flags & QTTT_FLAG_AUTO_RESET) != 0), reinterpret_cast<uint16_t *>(actions), n,
+                       e.step_counter, (u64)e.seed);
+    return launch_status();
+}
+
+// The flat step entries are this call on a record of their arguments.
+int qttt_env_step(const qttt_env *e, uint8_t *actions, const uint8_t *bits, uint32_t step_idx, int mode,
+                  void *stream) {
+    if (!e) return QTTT_ERR_NULL;
+    switch (mode) {
+    case QTTT_ENV_STEP:
+        return launch_step(*e, actions, bits, step_idx, stream, false, nullptr);
+    case QTTT_ENV_STEP_OBSERVE: {
+        const ObsOut o = {e->classical, e->q_p1, e->q_p1_len, e->q_p2, e->q_p2_len, e->turn};
+        if (const int rc = obs_check(o, e->n)) return rc;
+        return launch_step(*e, actions, bits, step_idx, stream, false, &o);
+    }
+    case QTTT_ENV_STEP_RANDOM:
+        return launch_step(*e, actions, nullptr, step_idx, stream, true, nullptr);
+    case QTTT_ENV_SAMPLE:
+        return launch_sample(*e, actions, step_idx, stream);
+    default:
+        return QTTT_ERR_SIZE;
+    }
 }
 
 int qttt_step(void *state, const uint8_t *actions, const uint8_t *bits, uint64_t seed,
               uint32_t step_idx, int64_t board_offset, uint32_t flags, float *reward,
               uint8_t *terminated, int64_t n, void *stream) {
-    return launch_step(state, const_cast<uint8_t *>(actions), bits, seed, step_idx, board_offset, flags,
-                       reward, terminated, n, stream, false, nullptr);
+    const qttt_env e = {state, n, board_offset, seed, flags, 0u, reward, terminated};
+    return qttt_env_step(&e, const_cast<uint8_t *>(actions), bits, step_idx, QTTT_ENV_STEP, stream);
 }
 
 int qttt_step_observe(void *state, const uint8_t *actions, const uint8_t *bits, uint64_t seed,
                       uint32_t step_idx, int64_t board_offset, uint32_t flags, float *reward,
                       uint8_t *terminated, int8_t *classical, uint8_t *q_p1, uint8_t *q_p1_len,
                       uint8_t *q_p2, uint8_t *q_p2_len, uint8_t *turn, int64_t n, void *stream) {
-    if (n > 0 && (!classical || !q_p1 || !q_p1_len || !q_p2 || !q_p2_len || !turn)) return QTTT_ERR_NULL;
-    if (((uintptr_t)q_p1 & 1u) || ((uintptr_t)q_p2 & 7u)) return QTTT_ERR_ACTION;   // 2- / 8-byte LDS row stores
-    const ObsOut o = {classical, q_p1, q_p1_len, q_p2, q_p2_len, turn};
-    return launch_step(state, const_cast<uint8_t *>(actions), bits, seed, step_idx, board_offset, flags,
-                       reward, terminated, n, stream, false, &o);
+    const qttt_env e = {state, n, board_offset, seed, flags, 0u, reward, terminated, classical, q_p1, q_p1_len, q_p2,
+                        q_p2_len, turn};
+    return qttt_env_step(&e, const_cast<uint8_t *>(actions), bits, step_idx, QTTT_ENV_STEP_OBSERVE, stream);
 }
 
 int qttt_step_random(void *state, uint64_t seed, uint32_t step_idx, int64_t board_offset,
                      uint32_t flags, uint8_t *actions_out, float *reward, uint8_t *terminated,
                      int64_t n, void *stream) {
-    return launch_step(state, actions_out, nullptr, seed, step_idx, board_offset, flags, reward,
-                       terminated, n, stream, true, nullptr);
+    const qttt_env e = {state, n, board_offset, seed, flags, 0u, reward, terminated};
+    return qttt_env_step(&e, actions_out, nullptr, step_idx, QTTT_ENV_STEP_RANDOM, stream);
 }
 
-static int launch_sample(const void *state, uint64_t seed, uint32_t step_idx, int64_t board_offset,
-                         uint32_t flags, uint8_t *actions, int64_t n, void *stream, const uint32_t *step_ctr);
-
-int qttt_env_step(const qttt_env *e, uint8_t *actions, const uint8_t *bits, uint32_t step_idx, int mode,
-                  void *stream) {
-    if (!e) return QTTT_ERR_NULL;
-    switch (mode) {
-    case QTTT_ENV_STEP:
-        return launch_step(e->state, actions, bits, e->seed, step_idx, e->board_offset, e->flags, e->reward,
-                           e->terminated, e->n, stream, false, nullptr, e->step_counter);
-    case QTTT_ENV_STEP_OBSERVE: {
-        if (e->n > 0 && (!e->classical || !e->q_p1 || !e->q_p1_len || !e->q_p2 || !e->q_p2_len || !e->turn)) return QTTT_ERR_NULL;
-        if (((uintptr_t)e->q_p1 & 1u) || ((uintptr_t)e->q_p2 & 7u)) return QTTT_ERR_ACTION;
-        const ObsOut o = {e->classical, e->q_p1, e->q_p1_len, e->q_p2, e->q_p2_len, e->turn};
-        return launch_step(e->state, actions, bits, e->seed, step_idx, e->board_offset, e->flags, e->reward,
-                           e->terminated, e->n, stream, false, &o, e->step_counter);
-    }
-    case QTTT_ENV_STEP_RANDOM:
-        return launch_step(e->state, actions, nullptr, e->seed, step_idx, e->board_offset, e->flags, e->reward,
-                           e->terminated, e->n, stream, true, nullptr, e->step_counter);
-    case QTTT_ENV_SAMPLE:
-        return launch_sample(e->state, e->seed, step_idx, e->board_offset, e->flags, actions, e->n, stream, e->step_counter);
-    default:
-        return QTTT_ERR_SIZE;
-    }
+int qttt_sample_actions(const void *state, uint64_t seed, uint32_t step_idx, int64_t board_offset,
+                        uint32_t flags, uint8_t *actions, int64_t n, void *stream) {
+    const qttt_env e = {const_cast<void *>(state), n, board_offset, seed, flags};
+    return qttt_env_step(&e, actions, nullptr, step_idx, QTTT_ENV_SAMPLE, stream);
 }
 
 int qttt_counter_add(uint32_t *counter, uint32_t by, void *stream) {
@@ -424,30 +461,18 @@ int qttt_step_many(void *state, const uint8_t *actions, const uint8_t *bits, uin
         if (!state || !actions || !reward || !terminated) return QTTT_ERR_NULL;
         if ((uintptr_t)actions & 1u) return QTTT_ERR_ACTION;
         retire_mailbox_for(n, stream);
-        Planes p = planes(state, n);
-        const bool ar = (flags & QTTT_FLAG_AUTO_RESET) != 0;
+        const Planes p = planes(state, n);
         const u32 hi_fold = (u32)(first >> 32) * 0x9E3779B9u;
-        dim3 g(grid_for(n)), b(QTTT_BLOCK);
-        hipStream_t s = (hipStream_t)stream;
         const uint16_t *a16 = reinterpret_cast<const uint16_t *>(actions);
         u32 *rb = reinterpret_cast<u32 *>(reward);
-        // at most FUSED_MAX_PLIES plies per launch (their keys travel as a kernel argument): a longer run is that many
-        // launches.  With out_stride == 0 every launch writes its last ply's outputs to the same place; the run's last wins.
-#define QTTT_FUSED(HB, AR)                                                                                    \
-    hipLaunchKernelGGL((step_fused_kernel<HB, AR>), g, b, 0, s, p.P, p.Q, a16 + (int64_t)done * n,            \
-                       bits ? bits + (int64_t)done * n : nullptr, keys, hi_fold, (u32)first,                   \
-                       rb + (int64_t)done * out_stride, terminated + (int64_t)done * out_stride, out_stride, n, plies)
-        for (int64_t done = 0; done < n_steps; done += FUSED_MAX_PLIES) {
-            const int32_t plies = (int32_t)(n_steps - done < FUSED_MAX_PLIES ? n_steps - done : FUSED_MAX_PLIES);
-            FusedKeys keys;
-            for (int32_t t = 0; t < FUSED_MAX_PLIES; ++t) keys.k[t] = launch_key(seed, step_idx0 + (u32)done + (u32)(t < plies ? t : 0));
-            if (bits) { if (ar) QTTT_FUSED(true, true); else QTTT_FUSED(true, false); }
-            else      { if (ar) QTTT_FUSED(false, true); else QTTT_FUSED(false, false); }
-            const int rc = launch_status();
-            if (rc) return rc;
-        }
-#undef QTTT_FUSED
-        return 0;
+        // With out_stride == 0 every launch writes its last ply's outputs to the same place; the run's last wins.
+        return fused_runs(seed, step_idx0, n_steps, [&](int64_t done, int32_t plies, const FusedKeys &keys) {
+            with_bools([&](auto HB, auto AR) {
+                hipLaunchKernelGGL((step_fused_kernel<HB, AR>), dim3(grid_for(n)), dim3(QTTT_BLOCK), 0, (hipStream_t)stream,
+                                   p.P, p.Q, a16 + done * n, bits ? bits + done * n : nullptr, keys, hi_fold, (u32)first,
+                                   rb + done * out_stride, terminated + done * out_stride, out_stride, n, plies);
+            }, bits != nullptr, (flags & QTTT_FLAG_AUTO_RESET) != 0);
+        });
     }
     for (int32_t t = 0; t < n_steps; ++t) {
         int rc = qttt_step(state, actions + (int64_t)t * 2 * n, bits ? bits + (int64_t)t * n : nullptr,
@@ -467,60 +492,46 @@ int qttt_step_random_many(void *state, uint64_t seed, uint32_t step_idx0, int64_
     if (!state || (reward == nullptr) != (terminated == nullptr)) return QTTT_ERR_NULL;
     if (((uintptr_t)actions_out & 1u) || ((uintptr_t)reward & 3u) || ((uintptr_t)returns & 3u)) return QTTT_ERR_ACTION;
     retire_mailbox_for(n, stream);
-    Planes p = planes(state, n);
-    hipStream_t s = (hipStream_t)stream;
+    const Planes p = planes(state, n);
     uint16_t *a16 = reinterpret_cast<uint16_t *>(actions_out);
     u32 *rb = reinterpret_cast<u32 *>(reward);
-    const bool ar = (flags & QTTT_FLAG_AUTO_RESET) != 0;
     // 256-thread workgroups: the finest spread of a small batch over the 256 CUs (4 096 boards = 16 CUs
     // with 512 threads, 16 with 256 — but 262 144 boards = 1 024 workgroups, four per CU, instead of two)
-    // at most FUSED_MAX_PLIES plies per launch (their keys travel as a kernel argument); a longer run is that many launches,
-    // the boards going through HBM in between (32 bytes per board and 64 plies).  With out_stride == 0 only the LAST ply's
-    // outputs are kept, so the earlier launches of such a run write none.
-#define QTTT_RFK(AR, RT, KP) hipLaunchKernelGGL((step_random_fused_kernel<256, AR, RT, KP>), dim3(blocks_for(n, 256)), dim3(256), 0, s, \
-                                               p.P, p.Q, keys, (u64)board_offset, a_c, r_c, t_c, out_stride, n, plies, returns)
-    // the instantiation without the per-ply "what is kept" tests, where it pays: one or two waves per SIMD are bound by a wave's
-    // own in-order stream (65 536 boards 0.59 -> 0.56 us per ply, 4 096: 0.58 -> 0.55), from four waves up the test-free loop
-    // is no faster and at 1 M boards 2 % slower (profiles/r05/fused_keep_instantiation_ab.txt, same box, alternating)
+    // The boards go through HBM between the launches of a longer run (32 bytes per board and 64 plies).  With
+    // out_stride == 0 only the LAST ply's outputs are kept, so the earlier launches of such a run write none.
+    // The instantiation without the per-ply "what is kept" tests, where it pays: one or two waves per SIMD are bound by a
+    // wave's own in-order stream (65 536 boards 0.59 -> 0.56 us per ply, 4 096: 0.58 -> 0.55), from four waves up the
+    // test-free loop is no faster and at 1 M boards 2 % slower (profiles/r05/fused_keep_instantiation_ab.txt, same box,
+    // alternating)
     const bool keep_all = out_stride != 0 && a16 && rb && n < 262144;
-#define QTTT_RF(AR, RT) do { if (keep_all) QTTT_RFK(AR, RT, true); else QTTT_RFK(AR, RT, false); } while (0)
-    for (int64_t done = 0; done < n_steps; done += FUSED_MAX_PLIES) {
-        const int32_t plies = (int32_t)(n_steps - done < FUSED_MAX_PLIES ? n_steps - done : FUSED_MAX_PLIES);
-        const bool last = done + plies == n_steps;
-        FusedKeys keys;
-        for (int32_t t = 0; t < FUSED_MAX_PLIES; ++t) keys.k[t] = launch_key(seed, step_idx0 + (u32)done + (u32)(t < plies ? t : 0));
-        const bool writes = out_stride != 0 || last;
-        uint16_t *a_c = (a16 && writes) ? a16 + (int64_t)done * out_stride : nullptr;
-        u32 *r_c = (rb && writes) ? rb + (int64_t)done * out_stride : nullptr;
-        uint8_t *t_c = (terminated && writes) ? terminated + (int64_t)done * out_stride : nullptr;
-        if (returns) { if (ar) QTTT_RF(true, true); else QTTT_RF(false, true); }
-        else         { if (ar) QTTT_RF(true, false); else QTTT_RF(false, false); }
-        const int rc = launch_status();
-        if (rc) return rc;
-    }
-#undef QTTT_RF
-#undef QTTT_RFK
-    return 0;
+    return fused_runs(seed, step_idx0, n_steps, [&](int64_t done, int32_t plies, const FusedKeys &keys) {
+        const bool writes = out_stride != 0 || done + plies == n_steps;
+        uint16_t *a_c = (a16 && writes) ? a16 + done * out_stride : nullptr;
+        u32 *r_c = (rb && writes) ? rb + done * out_stride : nullptr;
+        uint8_t *t_c = (terminated && writes) ? terminated + done * out_stride : nullptr;
+        with_bools([&](auto AR, auto RT, auto KP) {
+            hipLaunchKernelGGL((step_random_fused_kernel<256, AR, RT, KP>), dim3(blocks_for(n, 256)), dim3(256), 0,
+                               (hipStream_t)stream, p.P, p.Q, keys, (u64)board_offset, a_c, r_c, t_c, out_stride, n, plies,
+                               returns);
+        }, (flags & QTTT_FLAG_AUTO_RESET) != 0, returns != nullptr, keep_all);
+    });
 }
 
 int qttt_observe(const void *state, int8_t *classical, uint8_t *q_p1, uint8_t *q_p1_len,
                  uint8_t *q_p2, uint8_t *q_p2_len, uint8_t *turn, int64_t n, void *stream) {
     if (n < 0) return QTTT_ERR_SIZE;
     if (n == 0) return 0;
-    if (!state || !classical || !q_p1 || !q_p1_len || !q_p2 || !q_p2_len || !turn) return QTTT_ERR_NULL;
-    if (((uintptr_t)q_p1 & 1u) || ((uintptr_t)q_p2 & 7u)) return QTTT_ERR_ACTION;   // 2- / 8-byte LDS row stores
-    Planes p = planes(const_cast<void *>(state), n);
+    if (!state) return QTTT_ERR_NULL;
     const ObsOut o = {classical, q_p1, q_p1_len, q_p2, q_p2_len, turn};
+    if (const int rc = obs_check(o, n)) return rc;
+    const Planes p = planes(const_cast<void *>(state), n);
     // 256-thread workgroups: best or tied at every batch size for this write-heavy kernel (tools/rowbench, us per
     // launch, 256 / 512 / 1024 threads: 65 536 boards 3.7 / 4.1 / 5.2, 1 M: 8.7 / 8.7 / 8.6)
     const int blk_default = tuning_word().load(std::memory_order_relaxed) >> 8;
-    const int blk = blk_default ? blk_default : 256;
-#define QTTT_OBSERVE(BLK) hipLaunchKernelGGL((observe_kernel<BLK>), dim3((unsigned)((n + 2 * (BLK) - 1) / (2 * (BLK)))), \
-                                             dim3(BLK), 0, (hipStream_t)stream, p.P, p.Q, o, n)
-    if (blk == 1024) QTTT_OBSERVE(1024);
-    else if (blk == 256) QTTT_OBSERVE(256);
-    else QTTT_OBSERVE(QTTT_BLOCK);
-#undef QTTT_OBSERVE
+    with_int<1024, 256, QTTT_BLOCK>(blk_default ? blk_default : 256, [&](auto BLK) {
+        hipLaunchKernelGGL((observe_kernel<BLK>), dim3((unsigned)((n + 2 * BLK - 1) / (2 * BLK))), dim3(BLK), 0,
+                           (hipStream_t)stream, p.P, p.Q, o, n);
+    });
     return launch_status();
 }
 
@@ -546,12 +557,10 @@ int qttt_export(const void *state, uint8_t *moves, uint8_t *n_moves, int8_t *boa
     // tools/rowbench (profiles/r03/rowbench_*.txt), us per launch, boards per lane x workgroup size:
     //   1 M boards: 1 x 256 / 512 / 1024 = 13.7 / 14.1 / 12.7, 2 x 256 / 512 / 1024 = 9.2 / 9.4 / 9.4 (one occupancy round)
     //   64 K boards: 1 x 256 = 3.3, 2 x 256 = 3.8 (latency-bound: more waves in flight win)
-    if (n >= 384 * 1024)
-        hipLaunchKernelGGL((export_kernel<QTTT_COLD_BLOCK, 2>), dim3(cold_grid_for((n + 1) / 2)), dim3(QTTT_COLD_BLOCK), 0,
-                           (hipStream_t)stream, p.P, p.Q, o, n);
-    else
-        hipLaunchKernelGGL((export_kernel<QTTT_COLD_BLOCK, 1>), dim3(cold_grid_for(n)), dim3(QTTT_COLD_BLOCK), 0,
-                           (hipStream_t)stream, p.P, p.Q, o, n);
+    with_int<2, 1>(n >= 384 * 1024 ? 2 : 1, [&](auto BPL) {
+        hipLaunchKernelGGL((export_kernel<QTTT_COLD_BLOCK, BPL>), dim3(cold_grid_for((n + BPL - 1) / BPL)),
+                           dim3(QTTT_COLD_BLOCK), 0, (hipStream_t)stream, p.P, p.Q, o, n);
+    });
     return launch_status();
 }
 
@@ -766,26 +775,6 @@ int qttt_board_op_host(const void *records_in, void *records_out, int64_t n, voi
     return e == hipSuccess ? 0 : (int)e;
 }
 
-static int launch_sample(const void *state, uint64_t seed, uint32_t step_idx, int64_t board_offset,
-                         uint32_t flags, uint8_t *actions, int64_t n, void *stream, const uint32_t *step_ctr) {
-    if (n < 0 || board_offset < 0) return QTTT_ERR_SIZE;
-    if (n == 0) return 0;
-    if (!state || !actions) return QTTT_ERR_NULL;
-    if ((uintptr_t)actions & 1u) return QTTT_ERR_ACTION;   // written as u16 pairs
-    Planes p = planes(const_cast<void *>(state), n);
-    const u64 key = step_ctr ? ((u64)step_idx << 32) : launch_key(seed, step_idx);
-    hipLaunchKernelGGL(sample_actions_kernel, dim3(grid_for((n + 1) / 2)), dim3(QTTT_BLOCK), 0,
-                       (hipStream_t)stream, p.P, (u32)key, (u32)(key >> 32), (u64)board_offset,
-                       (u32)((flags & QTTT_FLAG_AUTO_RESET) != 0), reinterpret_cast<uint16_t *>(actions), n,
-                       step_ctr, (u64)seed);
-    return launch_status();
-}
-
-int qttt_sample_actions(const void *state, uint64_t seed, uint32_t step_idx, int64_t board_offset,
-                        uint32_t flags, uint8_t *actions, int64_t n, void *stream) {
-    return launch_sample(state, seed, step_idx, board_offset, flags, actions, n, stream, nullptr);
-}
-
 int qttt_node_info(const void *state, int8_t *winner, uint8_t *terminal, uint64_t *legal,
                    int64_t *key, uint64_t *state_key, int64_t n, void *stream) {
     if (n < 0) return QTTT_ERR_SIZE;
@@ -797,11 +786,12 @@ int qttt_node_info(const void *state, int8_t *winner, uint8_t *terminal, uint64_
     // the 12 KB of tables are filled once per workgroup; 64 K boards 4.6 / 4.7 / 5.8 — latency-bound).  Measured and not
     // adopted: a 1 000-entry table of the accumulator after the first three board elements (three multiply steps
     // less per board): 10.2 us with 1024 threads, but every smaller shape and expand lose as much to the 8 KB fill.
-#define QTTT_NI(BLK, PK) hipLaunchKernelGGL((node_info_kernel<BLK, PK>), dim3(blocks_for((n + 1) / 2, BLK)), dim3(BLK), 0, \
-                                            (hipStream_t)stream, p.P, p.Q, winner, terminal, (u64 *)legal, key, (u64 *)state_key, n)
-    if (n >= 384 * 1024) { if (key) QTTT_NI(1024, true); else QTTT_NI(1024, false); }
-    else                 { if (key) QTTT_NI(256, true);  else QTTT_NI(256, false); }
-#undef QTTT_NI
+    with_int<1024, 256>(n >= 384 * 1024 ? 1024 : 256, [&](auto BLK) {
+        with_bools([&](auto PK) {
+            hipLaunchKernelGGL((node_info_kernel<BLK, PK>), dim3(blocks_for((n + 1) / 2, BLK)), dim3(BLK), 0,
+                               (hipStream_t)stream, p.P, p.Q, winner, terminal, (u64 *)legal, key, (u64 *)state_key, n);
+        }, key != nullptr);
+    });
     return launch_status();
 }
 
@@ -825,11 +815,12 @@ int qttt_expand(const void *state, const uint8_t *action36, void *child0, void *
     const ExpandOut o = {n_children, winner, terminal, (u64 *)legal, key, (u64 *)state_key};
     // workgroup size by batch (tools/rowbench, us per launch, 256 / 512 / 1024 threads: 1 M pairs with native keys 18.3 /
     // 18.2 / 17.5, with the CPython keys 28.3 / 26.8 / 25.0; 64 K pairs 4.5 / 4.4 / 4.7 and 5.8 / 6.1 / 7.7)
-#define QTTT_EX(BLK, PK) hipLaunchKernelGGL((expand_kernel<BLK, PK>), dim3(blocks_for(n, BLK)), dim3(BLK), 0, (hipStream_t)stream, \
-                                            p.P, p.Q, action36, c0.P, c0.Q, c1.P, c1.Q, o, n)
-    if (n >= 384 * 1024) { if (key) QTTT_EX(1024, true); else QTTT_EX(1024, false); }
-    else                 { if (key) QTTT_EX(256, true);  else QTTT_EX(256, false); }
-#undef QTTT_EX
+    with_int<1024, 256>(n >= 384 * 1024 ? 1024 : 256, [&](auto BLK) {
+        with_bools([&](auto PK) {
+            hipLaunchKernelGGL((expand_kernel<BLK, PK>), dim3(blocks_for(n, BLK)), dim3(BLK), 0, (hipStream_t)stream,
+                               p.P, p.Q, action36, c0.P, c0.Q, c1.P, c1.Q, o, n);
+        }, key != nullptr);
+    });
     return launch_status();
 }
 
@@ -864,20 +855,20 @@ int qttt_expand_rollout(const void *state, const uint8_t *action36, void *child0
         while (P * 2 <= XR_MAX_PAIRS && P * 2 * 1024 <= n) P *= 2;
         const u32 ppb = (u32)P;
         const unsigned grid = (unsigned)((n + ppb - 1) / ppb);
-#define QTTT_XJ(PK) hipLaunchKernelGGL((expand_rollout_jobs_kernel<BLK, PK>), dim3(grid), dim3(BLK), 0, (hipStream_t)stream,  \
-                                       p.P, p.Q, action36, c0.P, c0.Q, c1.P, c1.Q, o, (u64)seed, step_idx0,                 \
-                                       (u64)board_offset, (u32)n_sims, ppb, value_sum, result, n)
-        if (key) QTTT_XJ(true); else QTTT_XJ(false);
-#undef QTTT_XJ
+        with_bools([&](auto PK) {
+            hipLaunchKernelGGL((expand_rollout_jobs_kernel<BLK, PK>), dim3(grid), dim3(BLK), 0, (hipStream_t)stream,
+                               p.P, p.Q, action36, c0.P, c0.Q, c1.P, c1.Q, o, (u64)seed, step_idx0, (u64)board_offset,
+                               (u32)n_sims, ppb, value_sum, result, n);
+        }, key != nullptr);
         return launch_status();
     }
     const u32 ppb = (u32)(BLK / (2 * n_sims));                    // whole pairs per workgroup
     const unsigned grid = (unsigned)((n + ppb - 1) / ppb);
-#define QTTT_XR(PK) hipLaunchKernelGGL((expand_rollout_kernel<BLK, PK>), dim3(grid), dim3(BLK), 0, (hipStream_t)stream,     \
-                                       p.P, p.Q, action36, c0.P, c0.Q, c1.P, c1.Q, o, (u64)seed, step_idx0,               \
-                                       (u64)board_offset, (u32)n_sims, ppb, value_sum, result, n)
-    if (key) QTTT_XR(true); else QTTT_XR(false);
-#undef QTTT_XR
+    with_bools([&](auto PK) {
+        hipLaunchKernelGGL((expand_rollout_kernel<BLK, PK>), dim3(grid), dim3(BLK), 0, (hipStream_t)stream,
+                           p.P, p.Q, action36, c0.P, c0.Q, c1.P, c1.Q, o, (u64)seed, step_idx0, (u64)board_offset,
+                           (u32)n_sims, ppb, value_sum, result, n);
+    }, key != nullptr);
     return launch_status();
 }
 
@@ -931,12 +922,11 @@ int qttt_evaluate(const void *state, const void *weights, int precision, float *
     if (((uintptr_t)weights & 15u) || ((uintptr_t)value & 3u) || ((uintptr_t)logits & 3u) || ((uintptr_t)probs & 3u))
         return QTTT_ERR_ACTION;                                  // 16-byte fragment loads / f32 stores
     Planes p = planes(const_cast<void *>(state), n);
-    if (precision == QTTT_NN_F32)
-        hipLaunchKernelGGL(evaluate_kernel<0>, dim3((unsigned)((n + NNCfg<0>::M - 1) / NNCfg<0>::M)), dim3(QTTT_NN_BLOCK),
-                           0, (hipStream_t)stream, p.P, p.Q, weights, value, logits, probs, n);
-    else
-        hipLaunchKernelGGL(evaluate_kernel<1>, dim3((unsigned)((n + NNCfg<1>::M - 1) / NNCfg<1>::M)), dim3(QTTT_NN_BLOCK),
-                           0, (hipStream_t)stream, p.P, p.Q, weights, value, logits, probs, n);
+    with_int<QTTT_NN_F32, QTTT_NN_BF16>(precision, [&](auto P) {
+        constexpr int M = NNCfg<P>::M;
+        hipLaunchKernelGGL((evaluate_kernel<P>), dim3((unsigned)((n + M - 1) / M)), dim3(QTTT_NN_BLOCK), 0,
+                           (hipStream_t)stream, p.P, p.Q, weights, value, logits, probs, n);
+    });
     return launch_status();
 }
 

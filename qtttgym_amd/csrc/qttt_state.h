@@ -64,11 +64,7 @@ template <> struct RawOf<32> { typedef u32x8 type; };
 template <typename V>
 __device__ __forceinline__ V load_stream(const V *p) {
     typedef typename RawOf<sizeof(V)>::type R;
-#ifdef QTTT_PLAIN_LOADS                       // (A/B builds only: the loads without the non-temporal hint)
-    R r = *reinterpret_cast<const R *>(p);
-#else
     R r = __builtin_nontemporal_load(reinterpret_cast<const R *>(p));
-#endif
     V v;
     __builtin_memcpy(&v, &r, sizeof(V));
     return v;
@@ -87,10 +83,6 @@ __device__ __forceinline__ void store_stream(V *p, const V &v) {
 template <typename V>
 __device__ __forceinline__ void store_stream_sbase(void *block_base, u32 byte_offset, const V &v) {
     static_assert(sizeof(V) == 8 || sizeof(V) == 16 || sizeof(V) == 32, "plane vectors only");
-#ifdef QTTT_NO_SBASE_STORES                    // (A/B builds only: the compiler's own addressing)
-    store_stream(reinterpret_cast<V *>(static_cast<uint8_t *>(block_base) + byte_offset), v);
-    return;
-#endif
     if constexpr (sizeof(V) == 8) {
         u32x2 r;
         __builtin_memcpy(&r, &v, 8);
@@ -114,12 +106,6 @@ __device__ __forceinline__ void store_stream_sbase(void *block_base, u32 byte_of
 template <int BYTES>
 __device__ __forceinline__ void store_stream_sbase_word(void *block_base, u32 byte_offset, u32 value) {
     static_assert(BYTES == 1 || BYTES == 2 || BYTES == 4, "one register");
-#ifdef QTTT_NO_SBASE_STORES
-    if constexpr (BYTES == 1) store_stream(static_cast<uint8_t *>(block_base) + byte_offset, (uint8_t)value);
-    else if constexpr (BYTES == 2) store_stream(reinterpret_cast<uint16_t *>(static_cast<uint8_t *>(block_base) + byte_offset), (uint16_t)value);
-    else store_stream(reinterpret_cast<u32 *>(static_cast<uint8_t *>(block_base) + byte_offset), value);
-    return;
-#endif
     if constexpr (BYTES == 1) asm volatile("global_store_byte %0, %1, %2 nt" : : "v"(byte_offset), "v"(value), "s"(block_base) : "memory");
     else if constexpr (BYTES == 2) asm volatile("global_store_short %0, %1, %2 nt" : : "v"(byte_offset), "v"(value), "s"(block_base) : "memory");
     else asm volatile("global_store_dword %0, %1, %2 nt" : : "v"(byte_offset), "v"(value), "s"(block_base) : "memory");
@@ -179,11 +165,7 @@ __device__ inline void fill_line_lut_nosync(uint8_t *lut) {
     // the latency-bound batches, where the scalar load's own latency sits in front of the barrier — the entry is computed
     // (tools/stepbench, 262 144 boards: 3.52 against 3.74 us best, 3.83 / 3.89 median; 1 M boards, policy in the step
     // kernel: 7.31 with the scalar piece against 7.50 computed).
-#ifdef QTTT_LUT_COMPUTED                       // (A/B builds only: always computed, as up to round 4)
-    constexpr bool SCALAR_PIECE = false;
-#else
     constexpr bool SCALAR_PIECE = SCALAR == 1 || BLOCK >= 512;
-#endif
     for (u32 w = threadIdx.x; w < 512u; w += BLOCK) {
         if constexpr (SCALAR_PIECE) {
             const u64 piece = g_line_bits.w[__builtin_amdgcn_readfirstlane(w >> 6)];  // wave-uniform: s_load_dwordx2

@@ -115,14 +115,10 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(
             const u32 h1 = lowbias32((id0 + (u32)k) ^ key_fold);
             hpol[k] = lowbias32(h1 ^ key_hi);
             hbit[k] = h1 >> 31;
-#ifndef QTTT_NO_HASH_HOIST                  // (A/B builds only: without the pin the compiler sinks the hash behind the loads' wait)
             asm volatile("" : "+v"(hbit[k]), "+v"(hpol[k]));
-#endif
         } else if (!HAS_BITS) {
             hbit[k] = collapse_bit_of((id0 + (u32)k) ^ key_fold);
-#ifndef QTTT_NO_HASH_HOIST
             asm volatile("" : "+v"(hbit[k]));
-#endif
         }
     }
 //@isa pack

@@ -71,6 +71,81 @@ def test_env_record_call_validates_before_touching_the_device():
     assert L.qttt_state_key(0, 0) == 0 and L.qttt_state_key(1 << 40, 0) != 0
     assert L.qttt_state_key(1 << 40, 5) == L.qttt_state_key((1 << 40) | (1 << 63) | (0xF << 44), 5 | (0x1FF << 32))
     assert L.qttt_export(None, None, None, None, None, None, 0, None) == 0
+    # every entry of include/qttt.h and include/qttt_nn.h that takes a batch: the code for null required pointers
+    # with n > 0, for n < 0 and other bad sizes, and for n == 0.  Only null pointers and non-positive sizes are
+    # passed, so no call here can reach a kernel with a usable address.
+    for name, call, expect in _argument_table(L, _native):
+        assert call() == expect, name
+
+
+def _argument_table(L, _native):
+    N = None
+    FUSED = 2
+    rows = []
+
+    def row(fn, expect, *args):
+        rows.append(("%s%r" % (fn, args), lambda: getattr(L, fn)(*args), expect))
+
+    def batch(fn, make, null=-1, neg=-2, zero=0):
+        for n, expect in ((8, null), (-1, neg), (0, zero)):
+            if expect is not None:
+                row(fn, expect, *make(n))
+
+    batch("qttt_reset", lambda n: (N, n, N))
+    batch("qttt_reset_observe", lambda n: (N,) * 7 + (n, N))
+    batch("qttt_step", lambda n: (N, N, N, 0, 0, 0, 0, N, N, n, N))
+    row("qttt_step", -2, N, N, N, 0, 0, -1, 0, N, N, 8, N)                   # board_offset < 0
+    row("qttt_step", -2, N, N, N, 0, 0, -1, 0, N, N, 0, N)
+    batch("qttt_step_observe", lambda n: (N, N, N, 0, 0, 0, 0) + (N,) * 8 + (n, N))
+    row("qttt_step_observe", -1, *((N, N, N, 0, 0, -1, 0) + (N,) * 8 + (8, N)))   # buffers first
+    row("qttt_step_observe", -2, *((N, N, N, 0, 0, -1, 0) + (N,) * 8 + (0, N)))
+    batch("qttt_step_random", lambda n: (N, 0, 0, 0, 0, N, N, N, n, N))
+    row("qttt_step_random", -2, N, 0, 0, -1, 0, N, N, N, 8, N)
+    for flags in (0, FUSED):
+        batch("qttt_step_many", lambda n, f=flags: (N, N, N, 0, 0, 0, f, N, N, 0, n, 1, N))
+        row("qttt_step_many", 0, N, N, N, 0, 0, 0, flags, N, N, 0, 8, 0, N)     # no steps
+        row("qttt_step_many", 0, N, N, N, 0, 0, 0, flags, N, N, 0, -1, 0, N)
+        row("qttt_step_many", -2, N, N, N, 0, 0, 0, flags, N, N, 0, 8, -1, N)   # n_steps < 0
+        row("qttt_step_many", -2, N, N, N, 0, 0, 0, flags, N, N, -1, 8, 1, N)   # out_stride < 0
+        row("qttt_step_many", -2, N, N, N, 0, 0, -1, flags, N, N, 0, 8, 1, N)   # board_offset < 0
+    batch("qttt_step_random_many", lambda n: (N, 0, 0, 0, 0, N, N, N, 0, N, n, 4, N))
+    row("qttt_step_random_many", 0, N, 0, 0, 0, 0, N, N, N, 0, N, 8, 0, N)
+    row("qttt_step_random_many", -2, N, 0, 0, 0, 0, N, N, N, 0, N, 8, -1, N)
+    row("qttt_step_random_many", -2, N, 0, 0, 0, 0, N, N, N, -1, N, 8, 4, N)
+    row("qttt_step_random_many", -2, N, 0, 0, -1, 0, N, N, N, 0, N, 8, 4, N)
+    batch("qttt_observe", lambda n: (N,) * 7 + (n, N))
+    batch("qttt_check_win", lambda n: (N, N, N, n, N))
+    batch("qttt_export", lambda n: (N,) * 6 + (n, N))
+    batch("qttt_import", lambda n: (N,) * 6 + (n, N))
+    batch("qttt_board_op", lambda n: (N, N, n, N))
+    batch("qttt_board_op_sync", lambda n: (N, N, n, N), zero=None)          # (n == 0 synchronises the stream)
+    batch("qttt_board_op_host", lambda n: (N, N, n, N))
+    batch("qttt_sample_actions", lambda n: (N, 0, 0, 0, 0, N, n, N))
+    row("qttt_sample_actions", -2, N, 0, 0, -1, 0, N, 8, N)
+    batch("qttt_node_info", lambda n: (N,) * 6 + (n, N))
+    batch("qttt_expand", lambda n: (N,) * 10 + (n, N))
+    batch("qttt_expand_rollout", lambda n: (N,) * 10 + (0, 0, 0, 1, N, N, n, N))
+    for n_sims in (0, 129):
+        row("qttt_expand_rollout", -2, *((N,) * 10 + (0, 0, 0, n_sims, N, N, 0, N)))
+    row("qttt_expand_rollout", -2, *((N,) * 10 + (0, 0, -1, 1, N, N, 8, N)))
+    batch("qttt_rollout", lambda n: (N, 0, 0, 0, N, N, N, n, N))
+    row("qttt_rollout", -2, N, 0, 0, -1, N, N, N, 8, N)
+    batch("qttt_rollout_many", lambda n: (N, 0, 0, 0, 1, N, N, n, N))
+    row("qttt_rollout_many", 0, N, 0, 0, 0, 0, N, N, 8, N)            # no simulations
+    row("qttt_rollout_many", -2, N, 0, 0, 0, -1, N, N, 8, N)
+    row("qttt_rollout_many", -2, N, 0, 0, -1, 1, N, N, 8, N)
+    batch("qttt_encode", lambda n: (N, N, N, n, N))
+    for precision in (0, 1):
+        batch("qttt_evaluate", lambda n, p=precision: (N, N, p, N, N, N, n, N))
+    row("qttt_evaluate", -2, N, N, 2, N, N, N, 0, N)                      # unknown precision
+    row("qttt_evaluate", -2, N, N, -1, N, N, N, 8, N)
+    recs = []
+    for mode in (_native.ENV_STEP, _native.ENV_STEP_OBSERVE, _native.ENV_STEP_RANDOM, _native.ENV_SAMPLE):
+        for n, board_offset, expect in ((8, 0, -1), (-1, 0, -2), (0, 0, 0), (0, -1, -2),
+                                        (8, -1, -1 if mode == _native.ENV_STEP_OBSERVE else -2)):
+            recs.append(_native.EnvRecord(n=n, board_offset=board_offset))
+            row("qttt_env_step", expect, ctypes.byref(recs[-1]), N, N, 0, mode, N)
+    return rows
 
 
 def test_header_is_plain_c_and_the_env_record_layout_matches_the_binding(tmp_path):
