@@ -15,6 +15,7 @@ SIM_STRIDE = 16
 EXPAND_ROLLOUT_MAX_SIMS = 128
 OP_MAKE_MOVE, OP_UPDATE_QSTRUCTS, OP_CHECK_WIN = 0, 1, 2
 NN_F32, NN_BF16 = 0, 1
+POLICY_ROLLOUT_MAX_SIMS = 128
 
 class EnvRecord(ctypes.Structure):
     """include/qttt.h: struct qttt_env."""
@@ -68,6 +69,10 @@ SIGNATURES = {
 NN_SIGNATURES = {
     "qttt_nn_weights_bytes": (_i64, [_i32]),
     "qttt_evaluate": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+}
+# every symbol include/qttt_policy_rollout.h declares (network-guided playouts; qttt.h includes it)
+POLICY_ROLLOUT_SIGNATURES = {
+    "qttt_rollout_policy": (_i32, [_vp, _vp, _i32, _u64, _u32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None
@@ -130,8 +135,12 @@ def lib():
                 "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(NN_SIGNATURES.items()):
-            fn = getattr(L, name)
+        for name, (res, args) in (list(SIGNATURES.items()) + list(NN_SIGNATURES.items())
+                                  + list(POLICY_ROLLOUT_SIGNATURES.items())):
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                raise QtttNativeError("%s does not export %s (stale build?)" % (LIB_PATH, name)) from None
             fn.restype = res
             fn.argtypes = args
         if L.qttt_abi_version() != ABI_VERSION:

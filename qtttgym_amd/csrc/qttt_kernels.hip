@@ -46,7 +46,8 @@
 //
 // Files: qttt_state.h (layout, loads/stores, shared tables) -> qttt_step_core.h (the step) ->
 // qttt_observation.h -> qttt_step_kernels.h; qttt_board_forms.h (unpacked views, winner, legal mask,
-// tuple hash) -> qttt_aux_kernels.h, qttt_mcts_kernels.h, qttt_nn_kernels.h (the policy/value network); this file: launch logic + the C ABI.
+// tuple hash) -> qttt_aux_kernels.h, qttt_mcts_kernels.h, qttt_nn_kernels.h (the policy/value network) -> qttt_policy_rollout_kernels.h (network-guided
+// playouts); this file: launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -56,6 +57,7 @@
 #include "qttt_aux_kernels.h"
 #include "qttt_mcts_kernels.h"
 #include "qttt_nn_kernels.h"
+#include "qttt_policy_rollout_kernels.h"
 
 namespace {
 
@@ -926,6 +928,27 @@ int qttt_evaluate(const void *state, const void *weights, int precision, float *
         constexpr int M = NNCfg<P>::M;
         hipLaunchKernelGGL((evaluate_kernel<P>), dim3((unsigned)((n + M - 1) / M)), dim3(QTTT_NN_BLOCK), 0,
                            (hipStream_t)stream, p.P, p.Q, weights, value, logits, probs, n);
+    });
+    return launch_status();
+}
+
+int qttt_rollout_policy(const void *state, const void *weights, int precision, uint64_t seed, uint32_t step_idx0,
+                        int64_t board_offset, int n_sims, int8_t *result, uint8_t *plies, uint8_t *trace,
+                        float *leaf_value, float *leaf_probs, int64_t n, void *stream) {
+    if (n < 0 || board_offset < 0 || (precision != QTTT_NN_F32 && precision != QTTT_NN_BF16) || n_sims < 1 ||
+        n_sims > QTTT_POLICY_ROLLOUT_MAX_SIMS)
+        return QTTT_ERR_SIZE;
+    if (n == 0) return 0;
+    if (!state || !weights || !result) return QTTT_ERR_NULL;
+    if (((uintptr_t)weights & 15u) || ((uintptr_t)leaf_value & 3u) || ((uintptr_t)leaf_probs & 3u))
+        return QTTT_ERR_ACTION;                                  // 16-byte fragment loads / f32 stores
+    Planes p = planes(const_cast<void *>(state), n);
+    const int64_t lanes = n * (int64_t)n_sims;
+    with_int<QTTT_NN_F32, QTTT_NN_BF16>(precision, [&](auto P) {
+        constexpr int M = NNCfg<P>::M;
+        hipLaunchKernelGGL((rollout_policy_kernel<P>), dim3((unsigned)((lanes + M - 1) / M)), dim3(QTTT_NN_BLOCK), 0,
+                           (hipStream_t)stream, p.P, p.Q, weights, (u64)seed, step_idx0, (u64)board_offset, (u32)n_sims,
+                           result, plies, trace, leaf_value, leaf_probs, lanes);
     });
     return launch_status();
 }

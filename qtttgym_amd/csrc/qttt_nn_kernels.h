@@ -150,6 +150,56 @@ __device__ __forceinline__ void nn_head(const typename NNCfg<PREC>::T *__restric
     __syncthreads();
 }
 
+// Row b of the to_vector encoding (mcts.py:67-85, as encode_kernel) at x, the quarter `part` of it (four threads per row),
+// and legal[b], the row's legal mask (GameState.actions of the autofilled board, nn.py:44-61's mask).  A row that is not
+// `live` gets zeros and an empty mask; the board P[base + b] / Q[base + b] (global memory or LDS) is read only for a live
+// row.  Shared by evaluate_kernel
+// and rollout_policy_kernel.
+template <int PREC>
+__device__ __forceinline__ void nn_encode_row(typename NNCfg<PREC>::T *x, u64 *legal, u32 b, bool live, const u64 *P,
+                                              const u64 *Q, int64_t base, u32 part) {
+    typedef NNCfg<PREC> C;
+    typedef typename C::T T;
+    if (live) {
+        Cold s;
+        cold_unpack(P[base + b], Q[base + b], s);
+        const u32 qsets = s.comp(0) | s.comp(1) | s.comp(2) | s.comp(3);
+        for (u32 v = part; v < 9u; v += 4u) {
+            const u32 col = (s.cl >> v & 1u) ? s.sqv(v) : 9u;        // board -1 indexes column 9
+            u32 touched = 0;
+            for (u32 t = 0; t < s.n; ++t)
+                if ((s.mv(t) & 0xFu) == v || (s.mv(t) >> 4) == v) touched |= 1u << t;
+            for (u32 c = 0; c < 10u; ++c) {
+                x[v * 10u + c] = (T)(c == col ? 1.0f : 0.0f);
+                float q = (touched >> c & 1u) ? (1.0f / 3.0f) : 0.0f;   // 1/math.sqrt(9)
+                if (c == 9u && !(qsets >> v & 1u)) q = 1.0f;            // square in no qstruct
+                x[90u + v * 10u + c] = (T)q;
+            }
+        }
+        if (part == 3u) legal[b] = fast_legal_mask(s.cl);
+    } else {                                                             // tail rows: zeros, outputs not written
+        for (u32 k = part; k < 180u; k += 4u) x[k] = (T)0.0f;
+        if (part == 3u) legal[b] = 0;
+    }
+    for (u32 k = 180u + part; k < (u32)C::K1; k += 4u) x[k] = (T)0.0f;  // K padding (bf16)
+}
+
+// The mask and softmax of one head row o[0..35] (nn.py:44-61: action (i,j) -> -inf iff square i or j is classical;
+// torch.softmax / Categorical(logits).probs): the max and the exp-sum over the legal actions, in ascending action
+// order, and a probability from them.  A row with every action masked gives NaN probabilities, like torch.
+__device__ __forceinline__ void nn_softmax_stats(const float *o, u64 lm, float &mx_out, float &sum_out) {
+    float mx = -INFINITY, sum = 0.f;
+    for (u32 a = 0; a < 36u; ++a)
+        if (lm >> a & 1ull) mx = fmaxf(mx, o[a]);
+    for (u32 a = 0; a < 36u; ++a)
+        if (lm >> a & 1ull) sum += expf(o[a] - mx);
+    mx_out = mx;
+    sum_out = sum;
+}
+__device__ __forceinline__ float nn_prob(float lg, bool ok, u64 lm, float mx, float sum) {
+    return ok ? expf(lg - mx) / sum : (lm ? 0.f : __builtin_nanf(""));
+}
+
 template <int PREC>
 __global__ __launch_bounds__(QTTT_NN_BLOCK) void evaluate_kernel(const u64 *pP, const u64 *pQ, const void *weights,
                                                                  float *value, float *logits, float *probs, int64_t n) {
@@ -169,29 +219,7 @@ __global__ __launch_bounds__(QTTT_NN_BLOCK) void evaluate_kernel(const u64 *pP, 
     // ---- the to_vector encoding (mcts.py:67-85, as encode_kernel) of the tile's boards: four threads per board
     for (u32 b = tid >> 2; b < (u32)C::M; b += QTTT_NN_BLOCK / 4) {
         const u32 part = tid & 3u;
-        T *x = H + b * C::LD;
-        if (b < valid) {
-            Cold s;
-            cold_unpack(pP[base + b], pQ[base + b], s);
-            const u32 qsets = s.comp(0) | s.comp(1) | s.comp(2) | s.comp(3);
-            for (u32 v = part; v < 9u; v += 4u) {
-                const u32 col = (s.cl >> v & 1u) ? s.sqv(v) : 9u;        // board -1 indexes column 9
-                u32 touched = 0;
-                for (u32 t = 0; t < s.n; ++t)
-                    if ((s.mv(t) & 0xFu) == v || (s.mv(t) >> 4) == v) touched |= 1u << t;
-                for (u32 c = 0; c < 10u; ++c) {
-                    x[v * 10u + c] = (T)(c == col ? 1.0f : 0.0f);
-                    float q = (touched >> c & 1u) ? (1.0f / 3.0f) : 0.0f;   // 1/math.sqrt(9)
-                    if (c == 9u && !(qsets >> v & 1u)) q = 1.0f;            // square in no qstruct
-                    x[90u + v * 10u + c] = (T)q;
-                }
-            }
-            if (part == 3u) legal[b] = fast_legal_mask(s.cl);
-        } else {                                                             // tail rows: zeros, outputs not written
-            for (u32 k = part; k < 180u; k += 4u) x[k] = (T)0.0f;
-            if (part == 3u) legal[b] = 0;
-        }
-        for (u32 k = 180u + part; k < (u32)C::K1; k += 4u) x[k] = (T)0.0f;  // K padding (bf16)
+        nn_encode_row<PREC>(H + b * C::LD, legal, b, b < valid, pP, pQ, base, part);
     }
     __syncthreads();
 
@@ -202,18 +230,9 @@ __global__ __launch_bounds__(QTTT_NN_BLOCK) void evaluate_kernel(const u64 *pP, 
     float *O = reinterpret_cast<float *>(H);
     nn_head<PREC>(W + L::WH, bias + 3 * QTTT_NN_HIDDEN, H, O, wave, lane);
 
-    // ---- mask (nn.py:44-61: action (i,j) -> -inf iff square i or j is classical) and softmax (torch.softmax /
-    // Categorical(logits).probs): a row with every action masked gives NaN probabilities, like torch
+    // ---- mask and softmax (nn_softmax_stats, nn_prob)
     if (probs && tid < valid) {
-        const u64 lm = legal[tid];
-        const float *o = O + tid * QTTT_NN_OUT_LD;
-        float mx = -INFINITY, sum = 0.f;
-        for (u32 a = 0; a < 36u; ++a)
-            if (lm >> a & 1ull) mx = fmaxf(mx, o[a]);
-        for (u32 a = 0; a < 36u; ++a)
-            if (lm >> a & 1ull) sum += expf(o[a] - mx);
-        rmax[tid] = mx;
-        rsum[tid] = sum;
+        nn_softmax_stats(O + tid * QTTT_NN_OUT_LD, legal[tid], rmax[tid], rsum[tid]);
     }
     __syncthreads();
     if (value)
@@ -226,7 +245,7 @@ __global__ __launch_bounds__(QTTT_NN_BLOCK) void evaluate_kernel(const u64 *pP, 
             const bool ok = lm >> a & 1ull;
             const float lg = O[b * QTTT_NN_OUT_LD + a];
             if (logits) logits[base * 36 + k] = ok ? lg : -INFINITY;
-            if (probs) probs[base * 36 + k] = ok ? expf(lg - rmax[b]) / rsum[b] : (lm ? 0.f : __builtin_nanf(""));
+            if (probs) probs[base * 36 + k] = nn_prob(lg, ok, lm, rmax[b], rsum[b]);
         }
     }
 }

@@ -856,6 +856,45 @@ class VecEnv:
         _native.check(rc, "qttt_evaluate")
         return out
 
+    _LEAF_ROWS = {"value": (), "probs": (36,)}
+
+    def rollout_policy(self, net, n_sims=1, step_idx0=None, with_plies=False, with_trace=False, leaf=(), out=None):
+        """AlphaZero._rollout's simulations (alphazero.py:173-180) with _simulate (:192-205) under the policy/value
+        network, n_sims per board in ONE launch (include/qttt_policy_rollout.h qttt_rollout_policy): every ply evaluates
+        `net` on the board, samples an action from Categorical(logits) and a collapse branch, until the game ends.
+        Returns a dict: result int8[N, n_sims] (AlphaZero._reward), and on request plies uint8[N, n_sims], trace
+        uint8[N, n_sims, 9] (action36 | bit << 6 per ply, 0xFF after the last) and the leaf's network outputs `leaf` =
+        a subset of ("value", "probs"): value f32[N] and probs f32[N, 36], equal to evaluate()'s.  Column s equals the
+        one-simulation call with step_idx0 + 16 * s.  `out` = the dict of an earlier call: its tensors are overwritten
+        and its keys decide what is written.  The boards and step_idx do not change; runs on the current stream."""
+        n, S, dev = self.num_envs, int(n_sims), self.state.device
+        if getattr(net, "device", None) != dev or not hasattr(net, "blob"):
+            raise ValueError("net must be a PolicyValueNet on %s" % (dev,))
+        if not 1 <= S <= _native.POLICY_ROLLOUT_MAX_SIMS:
+            raise ValueError("n_sims must be in 1..%d" % _native.POLICY_ROLLOUT_MAX_SIMS)
+        if step_idx0 is None:
+            step_idx0 = self.step_idx
+        shapes = {"result": (torch.int8, (n, S)), "plies": (torch.uint8, (n, S)), "trace": (torch.uint8, (n, S, 9)),
+                  "value": (torch.float32, (n,)), "probs": (torch.float32, (n, 36))}
+        if out is None:
+            leaf = (leaf,) if isinstance(leaf, str) else tuple(leaf)
+            if any(r not in self._LEAF_ROWS for r in leaf):
+                raise ValueError("leaf must be a subset of %s" % (tuple(self._LEAF_ROWS),))
+            keys = ["result"] + (["plies"] if with_plies else []) + (["trace"] if with_trace else []) + list(leaf)
+            with torch.cuda.device(dev):
+                out = {k: torch.empty(shapes[k][1], dtype=shapes[k][0], device=dev) for k in keys}
+        else:
+            if "result" not in out or any(k not in shapes for k in out):
+                raise ValueError("out must be a dict returned by rollout_policy()")
+            for k, t in out.items():
+                _check_out(t, shapes[k][0], shapes[k][1], dev, "out[%r]" % k)
+        rc = self._launch(self._lib.qttt_rollout_policy, self.state.data_ptr(), net.blob.data_ptr(), net.precision,
+                          self.seed, int(step_idx0), self.board_offset, S, out["result"].data_ptr(),
+                          _ptr(out.get("plies")), _ptr(out.get("trace")), _ptr(out.get("value")), _ptr(out.get("probs")),
+                          n, self._stream())
+        _native.check(rc, "qttt_rollout_policy")
+        return out
+
     # ------------------------------------------------------------------ hipGraph of T step launches
     def capture(self, n_steps, mode="random", actions=None, bits=None, actions_out=None, reward=None, terminated=None):
         """Captures n_steps step LAUNCHES into one hipGraph and returns it (`.replay()`): for loops on small

@@ -1,0 +1,197 @@
+"""qttt_rollout_policy / VecEnv.rollout_policy without a device: the header, the binding table, the order of the argument
+checks, the Python-side validation, and the draw rule (hash -> u, collapse bit, inverse CDF) restated in float64."""
+import ctypes
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "qttt_policy_rollout.h")
+
+
+def _lib():
+    from qtttgym_amd import _native
+    return _native.lib()
+
+
+def _declared():
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(qttt_[a-z0-9_]+)\s*\(", text)))
+
+
+# ---------------------------------------------------------------- the draw rule (include/qttt_policy_rollout.h)
+def draw(h64):
+    """(collapse bit, u) of one ply from qttt_hash's 64 bits."""
+    h1, h2 = h64 & 0xFFFFFFFF, h64 >> 32
+    return h1 >> 31, (h2 >> 8) * 2.0 ** -24
+
+
+def pick(logits, legal, u):
+    """The smallest legal a whose running sum of exp(logit - max) exceeds u * S, in float64; the largest legal a if none."""
+    idx = [a for a in range(36) if legal >> a & 1]
+    mx = max(logits[a] for a in idx)
+    e = [math.exp(logits[a] - mx) for a in idx]
+    target, c = u * sum(e), 0.0
+    for a, ea in zip(idx, e):
+        c += ea
+        if c > target:
+            return a
+    return idx[-1]
+
+
+def cdf_interval(logits, legal, a):
+    """[lo, hi) of u that picks action a (float64)."""
+    idx = [b for b in range(36) if legal >> b & 1]
+    mx = max(logits[b] for b in idx)
+    e = np.array([math.exp(logits[b] - mx) for b in idx])
+    c = np.cumsum(e) / e.sum()
+    k = idx.index(a)
+    return (c[k - 1] if k else 0.0), c[k]
+
+
+def test_header_is_plain_c_and_included_by_qttt_h(tmp_path):
+    from qtttgym_amd import _native
+    src = tmp_path / "probe.c"
+    src.write_text('#include <stdio.h>\n#include "qttt.h"\n'
+                   'int main(void) {\n'
+                   '  int (*f)(const void *, const void *, int, uint64_t, uint32_t, int64_t, int, int8_t *, uint8_t *,\n'
+                   '           uint8_t *, float *, float *, int64_t, void *) = qttt_rollout_policy;\n'
+                   '  printf("%d %d %u", QTTT_POLICY_ROLLOUT_MAX_SIMS, f != NULL, QTTT_SIM_STRIDE);\n  return 0;\n}\n')
+    exe = tmp_path / "probe"
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-Wno-address",
+                           "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe),
+                           "-L" + os.path.dirname(_native.LIB_PATH), "-l:libqttt_hip.so",
+                           "-Wl,-rpath," + os.path.dirname(_native.LIB_PATH)])
+    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    assert out == [_native.POLICY_ROLLOUT_MAX_SIMS, 1, _native.SIM_STRIDE]
+    assert '#include "qttt_policy_rollout.h"' in open(os.path.join(ROOT, "include", "qttt.h")).read()
+
+
+def test_binding_table_equals_the_header_and_the_library_exports_it():
+    from qtttgym_amd import _native
+    declared = _declared()
+    assert declared == ["qttt_rollout_policy"]
+    assert sorted(_native.POLICY_ROLLOUT_SIGNATURES) == declared
+    assert not set(declared) & (set(_native.SIGNATURES) | set(_native.NN_SIGNATURES))
+    L = ctypes.CDLL(_native.LIB_PATH)
+    assert all(hasattr(L, name) for name in declared)
+    assert L.qttt_abi_version() == _native.ABI_VERSION == 6
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    assert all("`%s`" % name in doc for name in declared)
+
+
+def test_a_library_without_the_symbol_is_reported_as_stale(tmp_path, monkeypatch):
+    """An older build of the same ABI lacks qttt_rollout_policy: loading it names the symbol, not an AttributeError."""
+    from qtttgym_amd import _native
+    src = tmp_path / "old.c"
+    src.write_text("int qttt_abi_version(void) { return 6; }\n")
+    so = tmp_path / "libold.so"
+    subprocess.check_call(["gcc", "-shared", "-fPIC", str(src), "-o", str(so)])
+    monkeypatch.setattr(_native, "LIB_PATH", str(so))
+    monkeypatch.setattr(_native, "_lib", None)
+    monkeypatch.setattr(_native, "SIGNATURES", {"qttt_abi_version": _native.SIGNATURES["qttt_abi_version"]})
+    monkeypatch.setattr(_native, "NN_SIGNATURES", {})
+    with pytest.raises(_native.QtttNativeError, match="qttt_rollout_policy.*stale build"):
+        _native.lib()
+
+
+def test_return_codes_in_the_documented_order():
+    """Null pointers and non-positive sizes only (the device is never reached)."""
+    L = _lib()
+    N = None
+    st, w, res = ctypes.c_void_p(0x10000), ctypes.c_void_p(0x20000), ctypes.c_void_p(0x30000)
+    f = ctypes.c_void_p(0x40000)
+    R = L.qttt_rollout_policy
+
+    def call(state=st, weights=w, prec=0, off=0, sims=1, result=res, value=N, probs=N, n=4):
+        return R(state, weights, prec, 0, 0, off, sims, result, N, N, value, probs, n, N)
+
+    table = [
+        (dict(n=-1), -2), (dict(n=-1, state=N), -2),                       # sizes before anything else
+        (dict(off=-1), -2), (dict(off=-1, n=0), -2),
+        (dict(prec=2), -2), (dict(prec=-1, n=0), -2),
+        (dict(sims=0), -2), (dict(sims=-3), -2), (dict(sims=129), -2), (dict(sims=0, n=0), -2),
+        (dict(n=0), 0), (dict(n=0, state=N, weights=N, result=N), 0),       # nothing to do
+        (dict(n=0, sims=128, prec=1), 0),
+        (dict(state=N), -1), (dict(weights=N), -1), (dict(result=N), -1),
+        (dict(result=N, weights=ctypes.c_void_p(0x20008)), -1),            # null before alignment
+        (dict(weights=ctypes.c_void_p(0x20008)), -3),                      # weights not 16-byte aligned
+        (dict(weights=ctypes.c_void_p(0x20004), prec=1), -3),
+        (dict(value=ctypes.c_void_p(0x40002)), -3),                        # float outputs not 4-byte aligned
+        (dict(probs=ctypes.c_void_p(0x40001)), -3),
+    ]
+    for kw, expect in table:
+        assert call(**kw) == expect, (kw, expect)
+    assert call(value=f, probs=N, n=0) == 0
+
+
+def test_rollout_policy_validates_its_arguments_without_a_device():
+    """The Python checks that come before any device work: the net, n_sims, leaf rows and `out`."""
+    import torch
+    from qtttgym_amd import VecEnv
+
+    class FakeEnv:                       # the method reads only these attributes before the launch
+        num_envs = 4
+        state = torch.zeros(64, dtype=torch.uint8)
+        step_idx = 0
+        _LEAF_ROWS = VecEnv._LEAF_ROWS
+    env = FakeEnv()
+
+    class Net:
+        device = torch.device("cpu")
+        blob = torch.zeros(16, dtype=torch.uint8)
+    fn = VecEnv.rollout_policy
+    with pytest.raises(ValueError, match="PolicyValueNet"):
+        fn(env, object())
+    for bad in (0, -1, 129):
+        with pytest.raises(ValueError, match="n_sims"):
+            fn(env, Net(), n_sims=bad)
+    with pytest.raises(ValueError, match="leaf"):
+        fn(env, Net(), leaf=("logits",))
+    with pytest.raises(ValueError, match="leaf"):
+        fn(env, Net(), leaf="policy")
+    with pytest.raises(ValueError, match="out"):
+        fn(env, Net(), out={"plies": torch.zeros((4, 1), dtype=torch.uint8)})
+    with pytest.raises(ValueError, match="out"):
+        fn(env, Net(), out={"result": torch.zeros((4, 1), dtype=torch.int8), "logits": torch.zeros((4, 36))})
+    with pytest.raises(ValueError, match="out"):
+        fn(env, Net(), n_sims=2, out={"result": torch.zeros((4, 1), dtype=torch.int8)})
+
+
+def test_draw_rule_by_hand():
+    # the bit is the top bit of the low word, u the top 24 bits of the high word
+    assert draw(0x00000000_7FFFFFFF) == (0, 0.0)
+    assert draw(0x00000000_80000000) == (1, 0.0)
+    assert draw(0xFFFFFFFF_00000000) == (0, (2 ** 24 - 1) / 2 ** 24)
+    assert draw(0x80000000_00000000) == (0, 0.5)
+    assert draw(0x000001FF_00000000) == (0, 1 / 2 ** 24)              # the low 8 bits of h2 are not used
+    # three legal actions (1, 4, 35) with equal logits: thirds of [0, 1)
+    legal = (1 << 1) | (1 << 4) | (1 << 35)
+    lg = [0.0] * 36
+    assert [pick(lg, legal, u) for u in (0.0, 0.33, 1 / 3 + 1e-9, 0.66, 0.67, 1 - 2 ** -24)] == [1, 1, 4, 4, 35, 35]
+    # illegal logits never matter, and the max is taken over the legal ones only
+    lg2 = [100.0] * 36
+    lg2[1], lg2[4], lg2[35] = math.log(1.0), math.log(3.0), math.log(4.0)    # probabilities 1/8, 3/8, 4/8
+    assert [pick(lg2, legal, u) for u in (0.124, 0.126, 0.49, 0.51, 0.999)] == [1, 4, 4, 35, 35]
+    assert cdf_interval(lg2, legal, 4) == pytest.approx((0.125, 0.5))
+    # one legal action takes every u; "exceeds" is strict: u = exactly the first boundary goes to the next action
+    assert pick([5.0] * 36, 1 << 7, 0.999) == 7
+    assert pick([0.0] * 36, (1 << 0) | (1 << 1), 0.5) == 1
+
+
+def test_draw_rule_uses_the_counter_hash_of_the_simulation():
+    """Ply p of simulation s of board i draws from qttt_hash(seed, board_offset + i, step_idx0 + 16 s + p)."""
+    import oracle
+    L = _lib()
+    seed, off, i, t0 = 12345, 7, 3, 100
+    for s in range(3):
+        for p in range(9):
+            h = L.qttt_hash(seed, off + i, t0 + 16 * s + p)
+            assert h == oracle.hash64(seed, off + i, t0 + 16 * s + p)
+            bit, u = draw(h)
+            assert bit == oracle.collapse_bit(seed, off + i, t0 + 16 * s + p)
+            assert 0.0 <= u < 1.0
