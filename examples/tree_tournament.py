@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""The reference's strat_eval.eval_strats (strat_eval.py:34-95) batched over G games, with real search trees on the
+device (qtttgym_amd.TreeSearch).  Player 1 moves first in the first half of the games and second in the other half.
+Each side keeps its own tree per half, contemplates `rollouts` times before each of its moves, chooses, and every tree
+syncs after every move (strat_eval.play_game).  Finished games are frozen: their later moves are noops.
+
+    python examples/tree_tournament.py --p1 az:300 --p2 mcts:3000 [--games 1024] [--sims 10] [--dtype f32|bf16]
+                                       [--weights tests/golden/model_eval.npz | --model model.pt]
+
+A player is mcts:R (uniform playouts and priors, MCTS(R)), az:R (the network's playouts and priors, AlphaZero(R)) or
+random (the uniform-legal policy).  Prints player 1's win, loss and draw counts and rates.
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+from qtttgym_amd import PolicyValueNet, TreeSearch, VecEnv  # noqa: E402
+from qtttgym_amd import recommended_env  # noqa: E402
+from qtttgym_amd.actions import action36_to_pairs  # noqa: E402
+from qtttgym_amd.policy_value import SHAPES  # noqa: E402
+recommended_env(apply=True)
+
+
+def parse_player(spec):
+    kind, _, n = spec.partition(":")
+    if kind == "random":
+        return ("random", 0)
+    if kind not in ("mcts", "az") or not n.isdigit() or int(n) < 1:
+        raise SystemExit("a player is mcts:R, az:R or random, not %r" % spec)
+    return (kind, int(n))
+
+
+def load_state_dict(args):
+    if args.model:
+        return torch.load(args.model, map_location="cpu")
+    with np.load(args.weights) as d:
+        return {k: torch.from_numpy(d[k.replace(".", "_")]) for k in SHAPES}
+
+
+def play(players, G, sims, net, seed):
+    """One half: players[0] moves first.  Returns winner i8[G] (1 = the first mover, 0 = the second, -1 = none)."""
+    env = VecEnv(G, seed=seed)
+    trees = []
+    for i, (kind, R) in enumerate(players):
+        if kind == "random":
+            trees.append(None)
+            continue
+        own_moves = 5 if i == 0 else 4
+        t = TreeSearch(G, capacity=1 + 2 * R * own_moves + 9, num_simulations=sims, net=net if kind == "az" else None,
+                       seed=seed * 2 + 1 + i, device=env.device)
+        t.reset(env)
+        trees.append(t)
+    finished = torch.zeros(G, dtype=torch.bool, device=env.device)
+    for ply in range(9):
+        mover = ply % 2
+        kind, R = players[mover]
+        if trees[mover] is None:
+            actions = env.sample_actions()
+        else:
+            trees[mover].contemplate(R)
+            actions = action36_to_pairs(trees[mover].choose())
+        actions = torch.where(finished[:, None], torch.full_like(actions, 255), actions).contiguous()
+        _, term = env.step_raw(actions)
+        finished |= term
+        for t in trees:
+            if t is not None:
+                t.sync(env)
+    return env.node_info(python_key=False)["winner"]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--p1", default="az:300")
+    ap.add_argument("--p2", default="mcts:3000")
+    ap.add_argument("--games", type=int, default=1024)
+    ap.add_argument("--sims", type=int, default=10)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--model", default=None, help="state dict with nn.Model's keys (torch.load)")
+    ap.add_argument("--weights", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                      "tests", "golden", "model_eval.npz"))
+    ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32")
+    args = ap.parse_args()
+    p1, p2 = parse_player(args.p1), parse_player(args.p2)
+    half = args.games // 2
+    if half < 1:
+        raise SystemExit("--games must be at least 2")
+    net = None
+    if "az" in (p1[0], p2[0]):
+        net = PolicyValueNet(load_state_dict(args), device="cuda",
+                             dtype=torch.float32 if args.dtype == "f32" else torch.bfloat16)
+    w_a = play((p1, p2), half, args.sims, net, args.seed)                  # player 1 moves first
+    w_b = play((p2, p1), half, args.sims, net, args.seed + 1)              # player 2 moves first
+    wins = int((w_a == 1).sum()) + int((w_b == 0).sum())
+    losses = int((w_a == 0).sum()) + int((w_b == 1).sum())
+    draws = int((w_a == -1).sum()) + int((w_b == -1).sum())
+    n = 2 * half
+    first = int((w_a == 1).sum())
+    print("%s vs %s, %d games, %d simulations: wins %d, losses %d, draws %d; rates %.3f, %.3f, %.3f; "
+          "moving first %d of %d wins (%.3f)"
+          % (args.p1, args.p2, n, args.sims, wins, losses, draws, wins / n, losses / n, draws / n, first, half,
+             first / half))
+    return wins, losses, draws
+
+
+if __name__ == "__main__":
+    main()

@@ -1,7 +1,8 @@
 """qtttgym_amd — MI355X-native vectorised Quantum Tic-Tac-Toe environment.
 
 Exports the reference package's four names (qtttgym/__init__.py:1-4) plus `VecEnv`, `PolicyValueNet` (the
-reference's nn.py network, evaluated on the GPU) and the 36-action
+reference's nn.py network, evaluated on the GPU), `TreeSearch` (batched
+MCTS / AlphaZero search trees on the device) and the 36-action
 indexing L3 callers share (mcts.py:339-350)."""
 from .vec_env import VecEnv
 from .board import Board, QEvalClassic, displayBoard
@@ -9,6 +10,7 @@ from .env import Env
 from .actions import ind2move, move2ind
 from ._native import recommended_env, retire_mailbox
 from .policy_value import PolicyValueNet
+from .tree import TreeSearch
 
-__all__ = ["Board", "QEvalClassic", "displayBoard", "Env", "VecEnv", "PolicyValueNet", "ind2move", "move2ind", "recommended_env",
+__all__ = ["Board", "QEvalClassic", "displayBoard", "Env", "VecEnv", "PolicyValueNet", "TreeSearch", "ind2move", "move2ind", "recommended_env",
            "retire_mailbox"]

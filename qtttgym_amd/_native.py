@@ -16,6 +16,12 @@ EXPAND_ROLLOUT_MAX_SIMS = 128
 OP_MAKE_MOVE, OP_UPDATE_QSTRUCTS, OP_CHECK_WIN = 0, 1, 2
 NN_F32, NN_BF16 = 0, 1
 POLICY_ROLLOUT_MAX_SIMS = 128
+TREE_GAME_BYTES, TREE_NODE_BYTES, TREE_PRIOR_BYTES = 128, 608, 144
+TREE_MAX_DEPTH = 10
+TREE_MAX_CAPACITY = 1 << 30
+TREE_MAX_SIMS = 128
+TREE_MAX_ROLLOUTS = 1 << 24
+TREE_SELECT_BASE = 1 << 31
 
 class EnvRecord(ctypes.Structure):
     """include/qttt.h: struct qttt_env."""
@@ -73,6 +79,18 @@ NN_SIGNATURES = {
 # every symbol include/qttt_policy_rollout.h declares (network-guided playouts; qttt.h includes it)
 POLICY_ROLLOUT_SIGNATURES = {
     "qttt_rollout_policy": (_i32, [_vp, _vp, _i32, _u64, _u32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+}
+
+# every symbol include/qttt_tree.h declares (the batched search trees; qttt.h includes it)
+_f64 = ctypes.c_double
+TREE_SIGNATURES = {
+    "qttt_tree_bytes": (_i64, [_i64, _i64]),
+    "qttt_tree_reset": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    "qttt_tree_select": (_i32, [_vp, _i64, _i64, _u64, _u32, _i64, _f64, _vp, _vp]),
+    "qttt_tree_backup": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _vp]),
+    "qttt_tree_sync": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    "qttt_tree_root": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qttt_tree_sqrt": (_i32, [_u32, _i64, _vp, _vp]),
 }
 
 _lib = None
@@ -136,7 +154,7 @@ def lib():
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(NN_SIGNATURES.items())
-                                  + list(POLICY_ROLLOUT_SIGNATURES.items())):
+                                  + list(POLICY_ROLLOUT_SIGNATURES.items()) + list(TREE_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -47,7 +47,7 @@
 // Files: qttt_state.h (layout, loads/stores, shared tables) -> qttt_step_core.h (the step) ->
 // qttt_observation.h -> qttt_step_kernels.h; qttt_board_forms.h (unpacked views, winner, legal mask,
 // tuple hash) -> qttt_aux_kernels.h, qttt_mcts_kernels.h, qttt_nn_kernels.h (the policy/value network) -> qttt_policy_rollout_kernels.h (network-guided
-// playouts); this file: launch logic + the C ABI.
+// playouts); qttt_tree_kernels.h (the batched search trees); this file: launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -58,6 +58,7 @@
 #include "qttt_mcts_kernels.h"
 #include "qttt_nn_kernels.h"
 #include "qttt_policy_rollout_kernels.h"
+#include "qttt_tree_kernels.h"
 
 namespace {
 
@@ -950,6 +951,87 @@ int qttt_rollout_policy(const void *state, const void *weights, int precision, u
                            (hipStream_t)stream, p.P, p.Q, weights, (u64)seed, step_idx0, (u64)board_offset, (u32)n_sims,
                            result, plies, trace, leaf_value, leaf_probs, lanes);
     });
+    return launch_status();
+}
+
+// ---------------------------------------------------------------- search trees (include/qttt_tree.h)
+static bool tree_size_bad(int64_t games, int64_t capacity) {
+    return games < 0 || capacity < 1 || capacity > QTTT_TREE_MAX_CAPACITY;
+}
+static unsigned tree_grid(int64_t games) { return (unsigned)((games + TREE_GAMES_PER_BLOCK - 1) / TREE_GAMES_PER_BLOCK); }
+
+int64_t qttt_tree_bytes(int64_t games, int64_t capacity) {
+    if (tree_size_bad(games, capacity)) return QTTT_ERR_SIZE;
+    const int64_t per_game = QTTT_TREE_GAME_BYTES + capacity * (int64_t)(QTTT_TREE_NODE_BYTES + QTTT_TREE_PRIOR_BYTES);
+    if (games > 0 && per_game > INT64_MAX / games) return QTTT_ERR_SIZE;
+    return games * per_game;
+}
+
+int qttt_tree_reset(void *tree, int64_t games, int64_t capacity, const void *state, void *stream) {
+    if (tree_size_bad(games, capacity)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (!tree || !state) return QTTT_ERR_NULL;
+    if ((uintptr_t)tree & 15u) return QTTT_ERR_ACTION;
+    Planes p = planes(const_cast<void *>(state), games);
+    hipLaunchKernelGGL(tree_reset_kernel, dim3(tree_grid(games)), dim3(TREE_BLOCK), 0, (hipStream_t)stream, tree, games,
+                       capacity, p.P, p.Q);
+    return launch_status();
+}
+
+int qttt_tree_select(void *tree, int64_t games, int64_t capacity, uint64_t seed, uint32_t rollout_idx,
+                     int64_t board_offset, double c_puct, void *leaf_state, void *stream) {
+    if (tree_size_bad(games, capacity) || board_offset < 0 || rollout_idx >= QTTT_TREE_MAX_ROLLOUTS) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (!tree || !leaf_state) return QTTT_ERR_NULL;
+    if ((uintptr_t)tree & 15u) return QTTT_ERR_ACTION;
+    Planes l = planes(leaf_state, games);
+    hipLaunchKernelGGL(tree_select_kernel, dim3(tree_grid(games)), dim3(TREE_BLOCK), 0, (hipStream_t)stream, tree, games,
+                       capacity, (u64)seed, rollout_idx, (u64)board_offset, c_puct, l.P, l.Q);
+    return launch_status();
+}
+
+int qttt_tree_backup(void *tree, int64_t games, int64_t capacity, const int8_t *result, int n_sims,
+                     const float *leaf_probs, void *stream) {
+    if (tree_size_bad(games, capacity) || n_sims < 1 || n_sims > QTTT_TREE_MAX_SIMS) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (!tree || !result) return QTTT_ERR_NULL;
+    if (((uintptr_t)tree & 15u) || ((uintptr_t)leaf_probs & 3u)) return QTTT_ERR_ACTION;
+    hipLaunchKernelGGL(tree_backup_kernel, dim3(tree_grid(games)), dim3(TREE_BLOCK), 0, (hipStream_t)stream, tree, games,
+                       capacity, result, (u32)n_sims, leaf_probs);
+    return launch_status();
+}
+
+int qttt_tree_sync(void *tree, int64_t games, int64_t capacity, const void *state, void *stream) {
+    if (tree_size_bad(games, capacity)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (!tree || !state) return QTTT_ERR_NULL;
+    if ((uintptr_t)tree & 15u) return QTTT_ERR_ACTION;
+    Planes p = planes(const_cast<void *>(state), games);
+    hipLaunchKernelGGL(tree_sync_kernel, dim3(tree_grid(games)), dim3(TREE_BLOCK), 0, (hipStream_t)stream, tree, games,
+                       capacity, p.P, p.Q);
+    return launch_status();
+}
+
+int qttt_tree_root(const void *tree, int64_t games, int64_t capacity, int32_t *N, double *W, double *Q, double *P,
+                   int32_t *Ntot, uint8_t *choose, int32_t *nodes_used, uint8_t *overflow, void *stream) {
+    if (tree_size_bad(games, capacity)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (!tree) return QTTT_ERR_NULL;
+    if (((uintptr_t)tree & 15u) || ((uintptr_t)N & 3u) || ((uintptr_t)Ntot & 3u) || ((uintptr_t)nodes_used & 3u) ||
+        ((uintptr_t)W & 7u) || ((uintptr_t)Q & 7u) || ((uintptr_t)P & 7u))
+        return QTTT_ERR_ACTION;
+    const TreeRootOut o = {N, W, Q, P, Ntot, choose, nodes_used, overflow};
+    hipLaunchKernelGGL(tree_root_kernel, dim3(tree_grid(games)), dim3(TREE_BLOCK), 0, (hipStream_t)stream, tree, games,
+                       capacity, o);
+    return launch_status();
+}
+
+int qttt_tree_sqrt(uint32_t first, int64_t n, double *out, void *stream) {
+    if (n < 0) return QTTT_ERR_SIZE;
+    if (n == 0) return 0;
+    if (!out) return QTTT_ERR_NULL;
+    if ((uintptr_t)out & 7u) return QTTT_ERR_ACTION;
+    hipLaunchKernelGGL(tree_sqrt_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, first, n, out);
     return launch_status();
 }
 

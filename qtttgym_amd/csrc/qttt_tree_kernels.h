@@ -1,0 +1,356 @@
+// qttt_tree_kernels.h — batched MCTS / AlphaZero search trees on the device (include/qttt_tree.h).
+//
+// Mapping: ONE WAVEFRONT PER GAME, lane a = action a (lanes 36..63 idle).  A tree level is one node: its 36 action
+// slots are read as one coalesced 576-byte load (16 B per lane), every lane scores its action in f64, and a butterfly
+// over the wave picks the argmax.  The one-lane-per-board mapping of the step kernels fits a state that
+// lives in registers; a tree node is 36-wide and lives in HBM, so here a lane per action is the natural unit.
+// A wave owns its game: node allocation needs no atomics, and no kernel re-reads what it wrote itself (a freshly
+// expanded child has no priors, so select ends on it; the child's header is still in registers).
+// Buffer layout: include/qttt_tree.h.
+#ifndef QTTT_TREE_KERNELS_H
+#define QTTT_TREE_KERNELS_H
+#include "qttt_step_core.h"
+#include "qttt_board_forms.h"
+#include "qttt_mcts_kernels.h"
+#include "qttt_tree.h"
+
+namespace {
+
+constexpr int TREE_BLOCK = 256;                                 // 4 games per workgroup
+constexpr int TREE_GAMES_PER_BLOCK = TREE_BLOCK / 64;
+constexpr u32 TN_PRIORS = 1u, TN_UNIFORM = 2u, TN_TERMINAL = 4u, TN_TURN = 8u;      // node flags
+constexpr u32 TG_OVERFLOW = 1u, TG_LEAF_TURN = 2u, TG_LEAF_TERMINAL = 4u;          // game-header flags
+constexpr int TREE_CHILD_PAIR = 1 << 30;
+
+struct TreeGame {                      // 128 B, include/qttt_tree.h
+    int32_t used, root, depth, leaf;
+    u32 flags, pad[3];
+    int32_t path_node[QTTT_TREE_MAX_DEPTH];
+    uint8_t path_action[QTTT_TREE_MAX_DEPTH];
+    uint8_t pad2[128 - 82];
+};
+static_assert(sizeof(TreeGame) == QTTT_TREE_GAME_BYTES, "game header");
+struct TreeNodeHdr {                   // 32 B
+    u64 P, Q, legal;
+    u32 Ntot, flags;
+};
+struct TreeSlot {                      // 16 B: one action of one node
+    double W;
+    u32 N;
+    int32_t child;
+};
+static_assert(sizeof(TreeNodeHdr) + 36 * sizeof(TreeSlot) == QTTT_TREE_NODE_BYTES, "node record");
+
+struct TreeView {
+    TreeGame *games;
+    uint8_t *nodes;                    // [games][capacity] records of QTTT_TREE_NODE_BYTES
+    float *priors;                     // [games][capacity][36]
+    int64_t capacity;
+    __device__ __forceinline__ TreeNodeHdr *hdr(int64_t g, int32_t i) const {
+        return reinterpret_cast<TreeNodeHdr *>(nodes + (g * capacity + i) * (int64_t)QTTT_TREE_NODE_BYTES);
+    }
+    __device__ __forceinline__ TreeSlot *slots(int64_t g, int32_t i) const {
+        return reinterpret_cast<TreeSlot *>(nodes + (g * capacity + i) * (int64_t)QTTT_TREE_NODE_BYTES + 32);
+    }
+    __device__ __forceinline__ float *prior(int64_t g, int32_t i) const { return priors + (g * capacity + i) * 36; }
+};
+__host__ __device__ inline TreeView tree_view(void *tree, int64_t games, int64_t capacity) {
+    TreeView v;
+    uint8_t *b = reinterpret_cast<uint8_t *>(tree);
+    v.games = reinterpret_cast<TreeGame *>(b);
+    v.nodes = b + games * (int64_t)QTTT_TREE_GAME_BYTES;
+    v.priors = reinterpret_cast<float *>(v.nodes + games * capacity * (int64_t)QTTT_TREE_NODE_BYTES);
+    v.capacity = capacity;
+    return v;
+}
+
+// 1 / len(actions) (mcts.py:289) for 0..36 legal actions, rounded by the host compiler
+struct UniformPriors {
+    double p[37];
+    constexpr UniformPriors() : p() {
+        for (int k = 1; k <= 36; ++k) p[k] = 1.0 / (double)k;
+    }
+};
+__constant__ UniformPriors g_uniform_priors = UniformPriors();
+
+// The selection score's sqrt(Ntot) (mcts.py:283).  llvm.sqrt.f64 is lowered correctly rounded on gfx950;
+// tests/test_tree_gpu.py checks it for every Ntot below QTTT_TREE_MAX_ROLLOUTS against the host's sqrt.
+__device__ __forceinline__ double tree_sqrt(u32 ntot) { return __builtin_sqrt((double)ntot); }
+
+// the node record of a position: GameState's bookkeeping (mcts.py:20-27,52-65) from the packed state
+__device__ __forceinline__ TreeNodeHdr tree_node_of(u64 P, u64 Q, bool turn, const uint8_t *lut) {
+    const Lite s = lite_unpack(P);
+    int w, t;
+    lite_update_winner(s, lut, w, t);
+    TreeNodeHdr h;
+    h.P = P; h.Q = Q;
+    h.legal = legal_mask_of(s.cl);
+    h.Ntot = 0;
+    h.flags = (t ? TN_TERMINAL : 0u) | (turn ? TN_TURN : 0u) | ((u32)(w + 1) << 8);
+    return h;
+}
+
+// a fresh node: header (by lane `writer`) and 36 empty slots (lanes 0..35)
+__device__ __forceinline__ void tree_write_node(const TreeView &v, int64_t g, int32_t i, const TreeNodeHdr &h, u32 lane,
+                                                u32 writer) {
+    if (lane == writer) *v.hdr(g, i) = h;
+    if (lane < 36u) {
+        TreeSlot s;
+        s.W = 0.0; s.N = 0u; s.child = -1;
+        v.slots(g, i)[lane] = s;
+    }
+}
+
+// wave argmax of (valid, score) with ties to the lowest lane: every lane ends with the winning lane, or -1
+__device__ __forceinline__ int wave_argmax(bool valid, double score, u32 lane) {
+    int idx = valid ? (int)lane : -1;
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const double os = __shfl_xor(score, m);
+        const int oi = __shfl_xor(idx, m);
+        const bool take = oi >= 0 && (idx < 0 || os > score || (os == score && oi < idx));
+        score = take ? os : score;
+        idx = take ? oi : idx;
+    }
+    return idx;
+}
+
+__device__ __forceinline__ double tree_prior(const TreeView &v, int64_t g, int32_t node, const TreeNodeHdr &h, u32 a) {
+    if (h.flags & TN_UNIFORM) return g_uniform_priors.p[__builtin_popcountll(h.legal)];
+    return (double)v.prior(g, node)[a];
+}
+
+// _uct_select's score (mcts.py:282-284) in the reference's order, no contraction into FMAs
+__device__ __forceinline__ double tree_score(double W, u32 N, double prior, double sq, double c_puct) {
+#pragma clang fp contract(off)
+    const double q = N ? W / (double)N : 0.0;
+    const double u = prior * sq / (double)(1u + N);
+    return q + c_puct * u;
+}
+
+__global__ __launch_bounds__(TREE_BLOCK) void tree_reset_kernel(void *tree, int64_t games, int64_t capacity,
+                                                                const u64 *pP, const u64 *pQ) {
+    __shared__ __attribute__((aligned(16))) uint8_t lut[LINE_LUT_BYTES];
+    fill_line_lut<TREE_BLOCK>(lut);
+    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
+    const u32 lane = threadIdx.x & 63u;
+    if (g >= games) return;
+    const TreeView v = tree_view(tree, games, capacity);
+    const u64 P = pP[g], Q = pQ[g];
+    const TreeNodeHdr h = tree_node_of(P, Q, (lite_unpack(P).n & 1u) == 0u, lut);       // mcts.py:141
+    tree_write_node(v, g, 0, h, lane, 0u);
+    if (lane == 0u) {
+        TreeGame *gh = &v.games[g];
+        gh->used = 1; gh->root = 0; gh->depth = 0; gh->leaf = 0;
+        gh->flags = (h.flags & TN_TURN ? TG_LEAF_TURN : 0u) | (h.flags & TN_TERMINAL ? TG_LEAF_TERMINAL : 0u);
+    }
+}
+
+__global__ __launch_bounds__(TREE_BLOCK) void tree_select_kernel(void *tree, int64_t games, int64_t capacity, u64 seed,
+                                                                 u32 rollout_idx, u64 board_offset, double c_puct,
+                                                                 u64 *leafP, u64 *leafQ) {
+    __shared__ __attribute__((aligned(16))) uint8_t lut[LINE_LUT_BYTES];
+    fill_line_lut<TREE_BLOCK>(lut);                              // ends with the workgroup barrier
+    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
+    const u32 lane = threadIdx.x & 63u;
+    if (g >= games) return;
+    const TreeView v = tree_view(tree, games, capacity);
+    TreeGame *gh = &v.games[g];
+    int32_t node = gh->root, used = gh->used;
+    // the collapse choices of this rollout: bit d = the child at path depth d (qttt_hash's low word)
+    const u64 key = launch_key(seed, QTTT_TREE_SELECT_BASE + rollout_idx);
+    const u32 bits = lowbias32(fold_id(board_offset + (u64)g) ^ (u32)key);
+    u32 overflow = 0u;
+    int32_t depth = 0;
+    TreeNodeHdr h = *v.hdr(g, node);
+    while ((h.flags & TN_PRIORS) && !(h.flags & TN_TERMINAL) && h.legal != 0ull && depth < QTTT_TREE_MAX_DEPTH) {
+        const bool legal = lane < 36u && ((h.legal >> lane) & 1ull);
+        TreeSlot s;
+        s.W = 0.0; s.N = 0u; s.child = -1;
+        if (lane < 36u) s = v.slots(g, node)[lane];
+        double score = 0.0;
+        if (legal) score = tree_score(s.W, s.N, tree_prior(v, g, node, h, lane), tree_sqrt(h.Ntot), c_puct);
+        const int a = wave_argmax(legal, score, lane);
+        const int32_t child = __shfl(s.child, a);
+        const u32 bit = (bits >> depth) & 1u;
+        if (child >= 0) {                                        // descend (mcts.py:275-276)
+            if (lane == 0u) { gh->path_node[depth] = node; gh->path_action[depth] = (uint8_t)a; }
+            ++depth;
+            node = (child & (TREE_CHILD_PAIR - 1)) + ((child & TREE_CHILD_PAIR) ? (int32_t)bit : 0);
+            h = *v.hdr(g, node);
+            continue;
+        }
+        // _expand_child (mcts.py:210-221): both collapse children at once, as qttt_expand
+        const u32 pr = (u32)g_pair_lut.b[a];
+        const u32 act = (pr & 0xFu) | ((pr >> 4) << 8);
+        u32 Q0 = (u32)h.Q, Q1 = (u32)(h.Q >> 32), P0a, P1a, P0b, P1b, xo0, xo1;
+        const u32 kids = step_core_both((u32)h.P, (u32)(h.P >> 32), Q0, Q1, act, lut, P0a, P1a, P0b, P1b, xo0, xo1);
+        if (kids == 0u || (int64_t)used + kids > capacity) {     // cannot happen for a legal action / does not fit
+            overflow = kids == 0u ? 0u : TG_OVERFLOW;
+            break;
+        }
+        const bool turn = !(h.flags & TN_TURN);
+        TreeNodeHdr c[2];
+        const u64 kidP[2] = {(u64)P0a | ((u64)P1a << 32), (u64)P0b | ((u64)P1b << 32)};
+        const u32 xo[2] = {xo0, xo1};
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {                            // expand_bookkeeping's winner / terminal / legal rules
+            int w, t;
+            update_winner_from_step(kidP[k], xo[k], lut, w, t);
+            const u32 cl = (u32)(kidP[k] >> (32u + P1_CL_SHIFT)) & 0x1FFu;
+            c[k].P = kidP[k];
+            c[k].Q = (u64)Q0 | ((u64)Q1 << 32);
+            c[k].legal = legal_mask_of(__builtin_popcount(cl) == 8 ? 0x1FFu : cl);
+            c[k].Ntot = 0u;
+            c[k].flags = (t ? TN_TERMINAL : 0u) | (turn ? TN_TURN : 0u) | ((u32)(w + 1) << 8);
+        }
+        tree_write_node(v, g, used, c[0], lane, 0u);
+        if (kids == 2u) tree_write_node(v, g, used + 1, c[1], lane, 1u);
+        if (lane == 0u) {
+            v.slots(g, node)[a].child = used | (kids == 2u ? TREE_CHILD_PAIR : 0);
+            gh->path_node[depth] = node;
+            gh->path_action[depth] = (uint8_t)a;
+        }
+        ++depth;
+        const u32 pick = kids == 2u ? bit : 0u;
+        node = used + (int32_t)pick;
+        h = pick ? c[1] : c[0];
+        used += (int32_t)kids;
+        break;                                                   // a fresh node has no priors: it is the leaf
+    }
+    if (lane == 0u) {
+        gh->used = used;
+        gh->depth = depth;
+        gh->leaf = node;
+        gh->flags = (gh->flags & TG_OVERFLOW) | overflow | (h.flags & TN_TURN ? TG_LEAF_TURN : 0u) |
+                    (h.flags & TN_TERMINAL ? TG_LEAF_TERMINAL : 0u);
+        leafP[g] = h.P;
+        leafQ[g] = h.Q;
+    }
+}
+
+// lane d < depth updates the d-th edge of the path; the leaf's priors go in with it
+__global__ __launch_bounds__(TREE_BLOCK) void tree_backup_kernel(void *tree, int64_t games, int64_t capacity,
+                                                                 const int8_t *result, u32 n_sims,
+                                                                 const float *leaf_probs) {
+    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
+    const u32 lane = threadIdx.x & 63u;
+    if (g >= games) return;
+    const TreeView v = tree_view(tree, games, capacity);
+    const TreeGame *gh = &v.games[g];
+    const int32_t depth = gh->depth, leaf = gh->leaf;
+    const u32 gflags = gh->flags;
+    int r = 0;
+    for (u32 s = lane; s < n_sims; s += 64u) r += (int)result[g * (int64_t)n_sims + s];
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) r += __shfl_xor(r, m);
+    if (!(gflags & TG_LEAF_TURN)) r = -r;                        // r if leaf.turn else -r (mcts.py:171)
+    const double val = (double)r / (double)n_sims;               // mcts.py:173
+    if ((int32_t)lane < depth) {
+        const int32_t node = gh->path_node[lane];
+        const u32 a = gh->path_action[lane];
+        const double rv = ((depth - (int32_t)lane) & 1) ? -val : val;     // deepest edge first: r = -r (mcts.py:179)
+        TreeSlot *s = &v.slots(g, node)[a];
+        s->W = s->W + rv;
+        s->N = s->N + 1u;
+        TreeNodeHdr *h = v.hdr(g, node);
+        h->Ntot = h->Ntot + 1u;
+    }
+    TreeNodeHdr *lh = v.hdr(g, leaf);
+    const u32 lf = lh->flags;
+    if ((lf & (TN_PRIORS | TN_TERMINAL)) == 0u) {                // _simulate (mcts.py:188-191)
+        if (leaf_probs && lane < 36u) v.prior(g, leaf)[lane] = leaf_probs[g * 36 + lane];
+        if (lane == 0u) lh->flags = lf | TN_PRIORS | (leaf_probs ? 0u : TN_UNIFORM);
+    }
+}
+
+__global__ __launch_bounds__(TREE_BLOCK) void tree_sync_kernel(void *tree, int64_t games, int64_t capacity,
+                                                               const u64 *pP, const u64 *pQ) {
+    __shared__ __attribute__((aligned(16))) uint8_t lut[LINE_LUT_BYTES];
+    fill_line_lut<TREE_BLOCK>(lut);
+    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
+    const u32 lane = threadIdx.x & 63u;
+    if (g >= games) return;
+    const TreeView v = tree_view(tree, games, capacity);
+    TreeGame *gh = &v.games[g];
+    const int32_t root = gh->root, used = gh->used;
+    const u64 P = pP[g], Q = pQ[g];
+    const TreeNodeHdr h = *v.hdr(g, root);
+    if (h.P == P && h.Q == Q) return;                            // the game did not move
+    // the root child equal to the position (mcts.py:325-329): lane a looks at action a's children
+    int32_t found = -1;
+    if (lane < 36u) {
+        const int32_t c = v.slots(g, root)[lane].child;
+        if (c >= 0) {
+            const int32_t c0 = c & (TREE_CHILD_PAIR - 1);
+            const TreeNodeHdr *h0 = v.hdr(g, c0);
+            if (h0->P == P && h0->Q == Q) found = c0;
+            else if (c & TREE_CHILD_PAIR) {
+                const TreeNodeHdr *h1 = v.hdr(g, c0 + 1);
+                if (h1->P == P && h1->Q == Q) found = c0 + 1;
+            }
+        }
+    }
+    const u64 hit = __ballot(found >= 0);
+    if (hit) {
+        const int32_t nr = __shfl(found, __builtin_ctzll(hit));
+        if (lane == 0u) gh->root = nr;
+        return;
+    }
+    if ((int64_t)used + 1 > capacity) {                          // a fresh root does not fit
+        if (lane == 0u) gh->flags |= TG_OVERFLOW;
+        return;
+    }
+    const TreeNodeHdr f = tree_node_of(P, Q, !(h.flags & TN_TURN), lut);      // _expand_child of the move (:320-323)
+    tree_write_node(v, g, used, f, lane, 0u);
+    if (lane == 0u) { gh->root = used; gh->used = used + 1; }
+}
+
+struct TreeRootOut {
+    int32_t *N;
+    double *W, *Q, *P;
+    int32_t *Ntot;
+    uint8_t *choose;
+    int32_t *nodes_used;
+    uint8_t *overflow;
+};
+
+__global__ __launch_bounds__(TREE_BLOCK) void tree_root_kernel(const void *tree, int64_t games, int64_t capacity,
+                                                               TreeRootOut o) {
+    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
+    const u32 lane = threadIdx.x & 63u;
+    if (g >= games) return;
+    const TreeView v = tree_view(const_cast<void *>(tree), games, capacity);
+    const TreeGame *gh = &v.games[g];
+    const int32_t root = gh->root;
+    const TreeNodeHdr h = *v.hdr(g, root);
+    const bool legal = lane < 36u && ((h.legal >> lane) & 1ull);
+    TreeSlot s;
+    s.W = 0.0; s.N = 0u; s.child = -1;
+    if (legal) s = v.slots(g, root)[lane];
+    const double q = s.N ? s.W / (double)s.N : 0.0;
+    if (lane < 36u) {
+        const int64_t j = g * 36 + lane;
+        if (o.N) o.N[j] = (int32_t)s.N;
+        if (o.W) o.W[j] = s.W;
+        if (o.Q) o.Q[j] = q;
+        if (o.P) o.P[j] = (legal && (h.flags & TN_PRIORS)) ? tree_prior(v, g, root, h, lane) : 0.0;
+    }
+    // choose (mcts.py:308-315): -inf for unvisited actions, ties to the lowest
+    const int a = wave_argmax(legal, s.N ? q : -__builtin_inf(), lane);
+    if (lane == 0u) {
+        if (o.Ntot) o.Ntot[g] = (int32_t)h.Ntot;
+        if (o.choose) o.choose[g] = a < 0 ? (uint8_t)255 : (uint8_t)a;
+        if (o.nodes_used) o.nodes_used[g] = gh->used;
+        if (o.overflow) o.overflow[g] = (gh->flags & TG_OVERFLOW) ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void tree_sqrt_kernel(u32 first, int64_t n, double *out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = tree_sqrt(first + (u32)i);
+}
+
+}  // namespace
+
+#endif  // QTTT_TREE_KERNELS_H

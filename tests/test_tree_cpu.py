@@ -1,0 +1,177 @@
+"""CPU tests of the batched search trees (include/qttt_tree.h, qtttgym_amd/tree.py): the float64 model against the
+reference's own MCTS traces, the header, the binding table, argument errors and the Python bounds.  No GPU."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "tree_traces.npz")
+HEADER = os.path.join(ROOT, "include", "qttt_tree.h")
+
+
+def _lib():
+    from qtttgym_amd import _native
+    return _native.lib()
+
+
+def test_model_reproduces_the_reference_mcts_traces():
+    import tree_model
+    for grp in tree_model.golden_groups(GOLDEN):
+        m = tree_model.TreeModel(grp["n_sims"], seed=grp["seed"], board_offset=grp["offset"])
+        m.reset(grp["roots"])
+        rec = grp["records"]
+        done = 0
+        for ci, c in enumerate(grp["checkpoints"]):
+            for _ in range(c - done):
+                m.rollout()
+            done = c
+            st = m.root_stats()
+            assert np.array_equal(st["N"], rec["N"][:, ci]), (ci, c)
+            assert np.array_equal(st["W"], rec["W"][:, ci]), (ci, c)
+            assert np.array_equal(st["Q"], rec["Q"][:, ci]), (ci, c)
+            assert np.array_equal(st["Ntot"], rec["Ntot"][:, ci])
+            assert np.array_equal(st["choose"], rec["choose"][:, ci])
+            assert np.array_equal(st["nodes_used"], rec["n_nodes"][:, ci])
+        assert np.array_equal(m.root_stats()["choose"][grp["sync_action"] != 255],
+                              grp["sync_action"][grp["sync_action"] != 255])
+        new, _ = tree_model.after_move(_positions(m), grp["sync_action"], grp["sync_bit"])
+        m.sync(new)
+        for _ in range(grp["after"]):
+            m.rollout()
+        st = m.root_stats()
+        for k in ("N", "W", "Q", "Ntot", "choose"):
+            assert np.array_equal(st[k], rec[k][:, -1]), k
+
+
+def _positions(m):
+    import tree_model
+    return tree_model._batch([st["nodes"][st["root"]].rec for st in m.games], m.dtype)
+
+
+def test_header_is_plain_c99_and_included_by_qttt_h():
+    src = open(os.path.join(ROOT, "include", "qttt.h")).read()
+    assert '#include "qttt_tree.h"' in src
+    assert not re.search(r"\bqttt_tree_\w+\s*\(", src.split('#include "qttt_nn.h"')[0])
+    out = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-fsyntax-only", "-x", "c",
+                          "-I" + os.path.join(ROOT, "include"), "-"], input='#include "qttt.h"\nint main(void){return 0;}\n',
+                         capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+
+
+def _declared(path):
+    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    return set(re.findall(r"^(?:int|int64_t)\s+(qttt_\w+)\s*\(", src, flags=re.M))
+
+
+def test_binding_header_exports_and_integration_md_agree():
+    from qtttgym_amd import _native
+    names = _declared(HEADER)
+    assert names == set(_native.TREE_SIGNATURES) and len(names) == 7
+    lib = ctypes.CDLL(_native.LIB_PATH)
+    for n in names:
+        assert hasattr(lib, n), n
+    integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for n in names:
+        assert n in integ, n
+    # the tree table is checked after the policy-rollout one (a stale build names qttt_rollout_policy first)
+    order = list(_native.SIGNATURES) + list(_native.NN_SIGNATURES) + list(_native.POLICY_ROLLOUT_SIGNATURES) \
+        + list(_native.TREE_SIGNATURES)
+    assert order.index("qttt_rollout_policy") < order.index("qttt_tree_bytes")
+
+
+def test_tree_bytes():
+    L = _lib()
+    assert L.qttt_tree_bytes(0, 1) == 0
+    assert L.qttt_tree_bytes(1, 1) == 128 + 608 + 144
+    assert L.qttt_tree_bytes(3, 100) == 3 * (128 + 100 * 752)
+    assert L.qttt_tree_bytes(-1, 1) == -2
+    assert L.qttt_tree_bytes(1, 0) == -2
+    assert L.qttt_tree_bytes(1, (1 << 30) + 1) == -2
+    assert L.qttt_tree_bytes(1 << 40, 1 << 30) == -2
+
+
+def test_return_codes_in_documented_order_without_device_work():
+    L = _lib()
+    fake = 0x1000                       # never dereferenced: every call below fails its checks first
+    ERR_NULL, ERR_SIZE, ERR_ACTION = -1, -2, -3
+    # sizes first, even with null pointers
+    assert L.qttt_tree_reset(None, -1, 1, None, None) == ERR_SIZE
+    assert L.qttt_tree_reset(None, 1, 0, None, None) == ERR_SIZE
+    assert L.qttt_tree_select(None, 1, 8, 0, 0, -1, 1.0, None, None) == ERR_SIZE
+    assert L.qttt_tree_select(None, 1, 8, 0, 1 << 24, 0, 1.0, None, None) == ERR_SIZE
+    assert L.qttt_tree_backup(None, 1, 8, None, 0, None, None) == ERR_SIZE
+    assert L.qttt_tree_backup(None, 1, 8, None, 129, None, None) == ERR_SIZE
+    assert L.qttt_tree_sync(None, -5, 8, None, None) == ERR_SIZE
+    assert L.qttt_tree_root(None, 1, -1, *([None] * 8), None) == ERR_SIZE
+    assert L.qttt_tree_sqrt(0, -1, None, None) == ERR_SIZE
+    # games == 0: nothing to do, no pointer looked at
+    assert L.qttt_tree_reset(None, 0, 1, None, None) == 0
+    assert L.qttt_tree_select(None, 0, 1, 0, 0, 0, 1.0, None, None) == 0
+    assert L.qttt_tree_backup(None, 0, 1, None, 4, None, None) == 0
+    assert L.qttt_tree_sync(None, 0, 1, None, None) == 0
+    assert L.qttt_tree_root(None, 0, 1, *([None] * 8), None) == 0
+    assert L.qttt_tree_sqrt(0, 0, None, None) == 0
+    # then null pointers
+    assert L.qttt_tree_reset(None, 1, 1, fake, None) == ERR_NULL
+    assert L.qttt_tree_reset(fake, 1, 1, None, None) == ERR_NULL
+    assert L.qttt_tree_select(fake, 1, 1, 0, 0, 0, 1.0, None, None) == ERR_NULL
+    assert L.qttt_tree_backup(fake, 1, 1, None, 4, None, None) == ERR_NULL
+    assert L.qttt_tree_sync(fake, 1, 1, None, None) == ERR_NULL
+    assert L.qttt_tree_root(None, 1, 1, *([None] * 8), None) == ERR_NULL
+    assert L.qttt_tree_sqrt(0, 1, None, None) == ERR_NULL
+    # then alignment
+    assert L.qttt_tree_reset(fake + 8, 1, 1, fake, None) == ERR_ACTION
+    assert L.qttt_tree_select(fake + 4, 1, 1, 0, 0, 0, 1.0, fake, None) == ERR_ACTION
+    assert L.qttt_tree_backup(fake, 1, 1, fake, 4, fake + 2, None) == ERR_ACTION
+    assert L.qttt_tree_sync(fake + 1, 1, 1, fake, None) == ERR_ACTION
+    for k in range(8):
+        args = [None] * 8
+        if k in (0, 4, 6):
+            args[k] = fake + 2              # N, Ntot, nodes_used: 4-byte
+        elif k in (1, 2, 3):
+            args[k] = fake + 4              # W, Q, P: 8-byte
+        else:
+            continue
+        assert L.qttt_tree_root(fake, 1, 1, *args, None) == ERR_ACTION, k
+    assert L.qttt_tree_sqrt(0, 1, fake + 4, None) == ERR_ACTION
+
+
+def test_python_bounds_raise_before_any_launch():
+    from qtttgym_amd import _native, tree
+    # a TreeSearch without a device: only the host-side bookkeeping is exercised
+    t = tree.TreeSearch.__new__(tree.TreeSearch)
+    t.num_games, t.capacity, t.num_simulations = 4, 21, 10
+    t.rollout_idx, t._bound = 0, None
+    with pytest.raises(RuntimeError):
+        t.contemplate(1)
+    t._bound = 1
+    with pytest.raises(ValueError, match="capacity"):
+        t.contemplate(11)                   # 1 + 2 * 11 > 21
+    t.rollout_idx = t.max_rollouts - 3
+    with pytest.raises(ValueError, match="bound"):
+        t.contemplate(4)
+    assert t.max_rollouts == (1 << 31) // (10 * 16)
+    t.num_simulations = 1
+    assert t.max_rollouts == 1 << 24
+    t._bound = 21
+    t._check_env = lambda env: None
+    with pytest.raises(ValueError, match="capacity"):
+        t.sync(None)
+    with pytest.raises(ValueError):
+        tree.TreeSearch(4, 0, device="cuda")
+    with pytest.raises(ValueError):
+        tree.TreeSearch(4, 10, num_simulations=0, device="cuda")
+
+
+def test_uniform_prior_and_sqrt_rounding_on_the_host_side():
+    """The host's math.sqrt is the reference; the device's is checked against it on the GPU (test_tree_gpu.py)."""
+    import math
+    assert all(1 / k == float(np.float64(1.0) / np.float64(k)) for k in range(1, 37))
+    assert math.sqrt(2) == float(np.sqrt(np.float64(2)))

@@ -1,0 +1,212 @@
+"""A float64 Python restatement of the batched search tree of include/qttt_tree.h (qtttgym_amd.TreeSearch), built on the
+C oracle's expand / rollout / counter hash.  Test infrastructure: tests/test_tree_cpu.py ties it to the reference's own
+MCTS class (tests/golden/tree_traces.npz), tests/test_tree_gpu.py runs the device in lockstep with it.
+
+Per game a plain list of nodes (the reference's node dict never merges two paths: its keys hold the full move
+history).  The arithmetic is the reference's, in Python floats: score = Q + c_puct * (P * sqrt(Ntot) / (1 + N)),
+W += r, Q = W / N.
+"""
+import math
+
+import numpy as np
+
+import oracle
+
+SIM_STRIDE = 16
+SELECT_BASE = 1 << 31
+
+
+def _one(rec):
+    ob = oracle.OracleBoards.__new__(oracle.OracleBoards)
+    ob.n = 1
+    ob.b = np.array([rec], dtype=rec.dtype)
+    return ob
+
+
+def _batch(recs, dtype):
+    ob = oracle.OracleBoards.__new__(oracle.OracleBoards)
+    ob.n = len(recs)
+    ob.b = np.array(recs, dtype=dtype)
+    return ob
+
+
+def position_key(rec):
+    """What identifies a position: Board.board, .moves, .qstructs (the fields the reference's hash and state hold)."""
+    n, nq = int(rec["n_moves"]), int(rec["n_q"])
+    return (bytes(np.asarray(rec["board"]).tobytes()), bytes(np.asarray(rec["moves"])[:n].tobytes()), n,
+            bytes(np.asarray(rec["q"])[:nq].tobytes()), nq)
+
+
+class Node:
+    __slots__ = ("rec", "turn", "terminal", "legal", "Ntot", "N", "W", "P", "children")
+
+    def __init__(self, rec, turn):
+        self.rec = rec
+        ob = _one(rec)
+        w, t, legal, _ = oracle.node_info(ob)
+        self.turn, self.terminal = bool(turn), bool(t[0])
+        self.legal = [a for a in range(36) if (int(legal[0]) >> a) & 1]
+        self.Ntot = 0
+        self.N = [0] * 36
+        self.W = [0.0] * 36
+        self.P = None
+        self.children = [None] * 36
+
+
+class TreeModel:
+    def __init__(self, n_sims, seed=0, board_offset=0, c_puct=1.0):
+        self.n_sims, self.seed, self.board_offset, self.c_puct = int(n_sims), int(seed), int(board_offset), float(c_puct)
+        self.games = []
+        self.k = 0
+
+    # ---- MCTS.reset
+    def reset(self, ob):
+        self.dtype = ob.b.dtype
+        self.games = []
+        for g in range(ob.n):
+            rec = ob.b[g].copy()
+            root = Node(rec, int(rec["n_moves"]) % 2 == 0)
+            self.games.append({"nodes": [root], "root": 0, "path": [], "leaf": 0})
+        self.k = 0
+
+    def _score(self, node, a):
+        U = node.P[a] * math.sqrt(node.Ntot) / (1 + node.N[a])
+        Q = node.W[a] / node.N[a] if node.N[a] else 0.0
+        return Q + self.c_puct * U
+
+    # ---- _select with _expand_child; returns the leaves as OracleBoards
+    def select(self):
+        bits_of = lambda g: oracle.hash64(self.seed, self.board_offset + g, SELECT_BASE + self.k) & 0xFFFFFFFF
+        leaves = []
+        for g, st in enumerate(self.games):
+            nodes = st["nodes"]
+            i = st["root"]
+            path = []
+            bits = bits_of(g)
+            while nodes[i].P is not None and not nodes[i].terminal and nodes[i].legal:
+                node = nodes[i]
+                a = max(node.legal, key=lambda x: self._score(node, x))      # first maximum, as Python's max
+                if node.children[a] is None:
+                    nch, kids, _, _, _, _ = oracle.expand(_one(node.rec), np.array([a], dtype=np.uint8))
+                    node.children[a] = []
+                    for c in range(int(nch[0])):
+                        nodes.append(Node(kids[c].b[0].copy(), not node.turn))
+                        node.children[a].append(len(nodes) - 1)
+                kids = node.children[a]
+                path.append((i, a))
+                i = kids[(bits >> (len(path) - 1)) & 1] if len(kids) == 2 else kids[0]
+            st["path"], st["leaf"] = path, i
+            leaves.append(nodes[i].rec)
+        return _batch(leaves, self.dtype)
+
+    def playouts(self, leaves):
+        """result i8[G, n_sims] of the uniform playouts of rollout k (oracle.rollout, the draws of qttt_rollout_many)."""
+        S = self.n_sims
+        out = np.empty((leaves.n, S), dtype=np.int8)
+        for s in range(S):
+            out[:, s] = oracle.rollout(leaves, self.seed, self.k * S * SIM_STRIDE + s * SIM_STRIDE, self.board_offset)[0]
+        return out
+
+    # ---- _backpropogate and the leaf's priors
+    def backup(self, result, probs=None):
+        S = self.n_sims
+        for g, st in enumerate(self.games):
+            nodes = st["nodes"]
+            leaf = nodes[st["leaf"]]
+            r_tot = 0
+            for s in range(S):
+                r = int(result[g][s])
+                r_tot += r if leaf.turn else -r
+            r = r_tot / S
+            for i, a in reversed(st["path"]):
+                r = -r
+                node = nodes[i]
+                node.W[a] += r
+                node.N[a] += 1
+                node.Ntot += 1
+            if not leaf.terminal and leaf.P is None:
+                if probs is None:
+                    leaf.P = {a: 1 / len(leaf.legal) for a in leaf.legal}
+                else:
+                    leaf.P = {a: float(np.float32(probs[g][a])) for a in leaf.legal}
+        self.k += 1
+
+    def rollout(self):
+        self.backup(self.playouts(self.select()))
+
+    # ---- MCTS.sync: ob = the games' positions after the move
+    def sync(self, ob):
+        for g, st in enumerate(self.games):
+            nodes = st["nodes"]
+            root = nodes[st["root"]]
+            key = position_key(ob.b[g])
+            if position_key(root.rec) == key:
+                continue
+            found = None
+            for a in range(36):
+                for c in (root.children[a] or ()):
+                    if found is None and position_key(nodes[c].rec) == key:
+                        found = c
+            if found is None:
+                nodes.append(Node(ob.b[g].copy(), not root.turn))
+                found = len(nodes) - 1
+            st["root"] = found
+
+    # ---- the roots' statistics, as qttt_tree_root
+    def root_stats(self):
+        G = len(self.games)
+        o = {"N": np.zeros((G, 36), np.int32), "W": np.zeros((G, 36)), "Q": np.zeros((G, 36)), "P": np.zeros((G, 36)),
+             "Ntot": np.zeros(G, np.int32), "choose": np.zeros(G, np.uint8), "nodes_used": np.zeros(G, np.int32)}
+        for g, st in enumerate(self.games):
+            n = st["nodes"][st["root"]]
+            for a in n.legal:
+                o["N"][g, a] = n.N[a]
+                o["W"][g, a] = n.W[a]
+                o["Q"][g, a] = n.W[a] / n.N[a] if n.N[a] else 0.0
+                o["P"][g, a] = n.P[a] if n.P is not None else 0.0
+            o["Ntot"][g] = n.Ntot
+            o["choose"][g] = choose(n)
+            o["nodes_used"][g] = len(st["nodes"])
+        return o
+
+
+def choose(n):
+    """MCTS.choose (mcts.py:308-315); 255 when there is no legal action."""
+    if not n.legal:
+        return 255
+    return max(n.legal, key=lambda a: n.W[a] / n.N[a] if n.N[a] else -math.inf)
+
+
+# ---------------------------------------------------------------- tests/golden/tree_traces.npz
+def golden_groups(path):
+    """Per group of the fixture: dict(seed, offset, n_sims, after, checkpoints, roots (OracleBoards), sync_action,
+    sync_bit, records: dict of arrays [roots, len(checkpoints) + 1, ...] (the last record: after the sync))."""
+    z = np.load(path)
+    out = []
+    rec0 = 0
+    for gi in range(len(z["g_seed"])):
+        sel = np.nonzero(z["r_group"] == gi)[0]
+        nr = int(z["g_records"][gi])
+        rows = {k[2:]: z[k][rec0:rec0 + len(sel) * nr].reshape((len(sel), nr) + z[k].shape[1:])
+                for k in z.files if k.startswith("c_")}
+        rec0 += len(sel) * nr
+        out.append({"seed": int(z["g_seed"][gi]), "offset": int(z["g_offset"][gi]), "n_sims": int(z["g_n_sims"][gi]),
+                    "after": int(z["g_after"][gi]), "checkpoints": [int(c) for c in z["g%d_checkpoints" % gi]],
+                    "roots": oracle.boards_from_arrays(z["r_board"][sel], z["r_moves"][sel], z["r_n_moves"][sel],
+                                                       z["r_qmask"][sel], z["r_n_q"][sel]),
+                    "arrays": {k: z["r_" + k][sel] for k in ("board", "moves", "n_moves", "qmask", "n_q")},
+                    "sync_action": z["r_sync_action"][sel], "sync_bit": z["r_sync_bit"][sel], "records": rows})
+    return out
+
+
+def after_move(ob, action36, bits):
+    """The positions after the sync move: board g plays ind2move(action36[g]) with collapse bit bits[g]; 255 = the game
+    does not move."""
+    new = ob.copy()
+    acts = np.zeros((ob.n, 2), dtype=np.uint8)
+    for g, a in enumerate(action36):
+        acts[g] = oracle.ind2move(int(a)) if a != 255 else (0, 1)
+    new.step(acts, np.asarray(bits, dtype=np.uint8))
+    frozen = np.asarray(action36) == 255
+    new.b[frozen] = ob.b[frozen]
+    return new, acts

@@ -1,0 +1,106 @@
+#!/usr/bin/env python3
+"""Times qtttgym_amd.TreeSearch's rollout (select -> playouts -> backup) on the MI355X and prints one JSON line per
+(games, mode): microseconds per rollout split into select / playouts / backup (HIP events around each launch, summed
+over the measured rollouts), the playouts alone re-run on the same leaves as the floor, and the nodes used.
+
+    python tools/treebench.py [--games 4096,65536,262144] [--modes uniform,f32,bf16] [--sims 10] [--rollouts 32]
+                              [--warmup 4] [--out profiles/tree/treebench.jsonl]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from qtttgym_amd import PolicyValueNet, TreeSearch, VecEnv, recommended_env  # noqa: E402
+from qtttgym_amd import _native  # noqa: E402
+recommended_env(apply=True)
+
+
+def _net(dtype):
+    import numpy as np
+    from qtttgym_amd.policy_value import SHAPES
+    with np.load(os.path.join(ROOT, "tests", "golden", "model_eval.npz")) as d:
+        sd = {k: torch.from_numpy(d[k.replace(".", "_")]) for k in SHAPES}
+    return PolicyValueNet(sd, device="cuda", dtype=dtype)
+
+
+def run(G, mode, sims, rollouts, warmup):
+    net = None if mode == "uniform" else _net(torch.float32 if mode == "f32" else torch.bfloat16)
+    env = VecEnv(G, seed=1)
+    env.step_random_many(2)                                  # positions two plies in: most games open
+    t = TreeSearch(G, capacity=1 + 2 * (rollouts + warmup), num_simulations=sims, net=net, seed=2)
+    t.reset(env)
+    t.contemplate(warmup)
+    L, stream = t._lib, torch.cuda.current_stream()
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(rollouts)]
+    tree, leaf = t.tree.data_ptr(), t.leaf.state.data_ptr()
+    stride = sims * _native.SIM_STRIDE
+    torch.cuda.synchronize()
+    for r in range(rollouts):
+        k = t.rollout_idx
+        e = ev[r]
+        e[0].record(stream)
+        _native.check(L.qttt_tree_select(tree, G, t.capacity, t.seed, k, t.board_offset, t.c_puct, leaf,
+                                         stream.cuda_stream), "select")
+        e[1].record(stream)
+        if net is None:
+            t.leaf.rollout_many(sims, step_idx0=k * stride, out=t._out)
+            res, probs = t._out.data_ptr(), None
+        else:
+            t.leaf.rollout_policy(net, sims, step_idx0=k * stride, out=t._out)
+            res, probs = t._out["result"].data_ptr(), t._out["probs"].data_ptr()
+        e[2].record(stream)
+        _native.check(L.qttt_tree_backup(tree, G, t.capacity, res, sims, probs, stream.cuda_stream), "backup")
+        e[3].record(stream)
+        t.rollout_idx, t._bound = k + 1, t._bound + 2
+    torch.cuda.synchronize()
+    sel = sum(e[0].elapsed_time(e[1]) for e in ev) * 1e3 / rollouts
+    play = sum(e[1].elapsed_time(e[2]) for e in ev) * 1e3 / rollouts
+    back = sum(e[2].elapsed_time(e[3]) for e in ev) * 1e3 / rollouts
+    total = sum(e[0].elapsed_time(e[3]) for e in ev) * 1e3 / rollouts
+    # the floor: the same playouts on the same (last) leaves, back to back
+    f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    f0.record(stream)
+    for r in range(rollouts):
+        if net is None:
+            t.leaf.rollout_many(sims, step_idx0=r * stride, out=t._out)
+        else:
+            t.leaf.rollout_policy(net, sims, step_idx0=r * stride, out=t._out)
+    f1.record(stream)
+    torch.cuda.synchronize()
+    used = t.nodes_used().float()
+    return {"games": G, "mode": mode, "n_sims": sims, "rollouts": rollouts, "us_per_rollout": round(total, 2),
+            "us_select": round(sel, 2), "us_playouts": round(play, 2), "us_backup": round(back, 2),
+            "us_playouts_alone": round(f0.elapsed_time(f1) * 1e3 / rollouts, 2),
+            "nodes_used_mean": round(float(used.mean()), 2), "nodes_used_max": int(used.max())}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--games", default="4096,65536,262144")
+    ap.add_argument("--modes", default="uniform,f32,bf16")
+    ap.add_argument("--sims", type=int, default=10)
+    ap.add_argument("--rollouts", type=int, default=32)
+    ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    rows = []
+    for G in [int(x) for x in args.games.split(",")]:
+        for mode in args.modes.split(","):
+            row = run(G, mode, args.sims, args.rollouts, args.warmup)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for row in rows:
+                f.write(json.dumps(row) + "\n")
+
+
+if __name__ == "__main__":
+    main()
