@@ -90,8 +90,9 @@ int qttt_step_observe(void *state, const uint8_t *actions, const uint8_t *bits, 
 /* n_steps consecutive qttt_step launches enqueued back to back from C, so a replay / rollout
  * loop is not paced by the host interpreter.  Step t (0-based) reads actions + t*2n and
  * bits + t*n (when bits != NULL), uses step_idx0 + t, and writes reward + t*out_stride and
- * terminated + t*out_stride (out_stride 0: every step overwrites the same n outputs; with
- * QTTT_FLAG_FUSED only the last step's outputs are then written). */
+ * terminated + t*out_stride (out_stride 0: only the LAST step's outputs are written, to the
+ * first n elements: the earlier steps would be overwritten and store none — with and without
+ * QTTT_FLAG_FUSED; reward and terminated are still required and checked for every step). */
 int qttt_step_many(void *state, const uint8_t *actions, const uint8_t *bits, uint64_t seed,
                    uint32_t step_idx0, int64_t board_offset, uint32_t flags, float *reward,
                    uint8_t *terminated, int64_t out_stride, int64_t n, int32_t n_steps,

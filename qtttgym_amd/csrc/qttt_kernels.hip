@@ -303,8 +303,10 @@ int qttt_reset(void *state, int64_t n, void *stream) {
 
 // One step of the record's boards: qttt_env_step's modes STEP, STEP_OBSERVE (obs) and STEP_RANDOM (sample: the policy
 // draws the actions, and writes them to `actions` when that is not null).
+// quiet (internal, plain STEP only: qttt_step_many's steps whose outputs the next step overwrites): the same checks and
+// the same launches, but of step_quiet_kernel, which stores the planes and neither reward nor terminated.
 static int launch_step(const qttt_env &e, uint8_t *actions, const uint8_t *bits, uint32_t step_idx, void *stream,
-                       bool sample, const ObsOut *obs) {
+                       bool sample, const ObsOut *obs, bool quiet = false) {
     const int64_t n = e.n, board_offset = e.board_offset;
     if (n < 0 || board_offset < 0) return QTTT_ERR_SIZE;
     if (n == 0) return 0;
@@ -334,9 +336,25 @@ static int launch_step(const qttt_env &e, uint8_t *actions, const uint8_t *bits,
     const bool devstep = step_ctr && !bits;
     const StepKeySource<true> sk = {step_ctr, (u64)e.seed};
     const bool ob = obs != nullptr, sm = sample && !ob, hb = bits && !sm;
+    const bool qt = quiet && !sm && !ob && !devstep;
     // `groups` lane-groups of bpl boards from board i0, in blk-thread workgroups (four boards per lane come with
     // QTTT_BLOCK threads: resolve_shape)
     auto launch = [&](int bpl, int blk, int64_t i0, int64_t groups, u32 key_fold, u32 id_base) {
+        if (qt) {
+            with_bools([&](auto HB, auto AR) {
+                with_int<4, 2, 1>(bpl, [&](auto BPL) {
+                    with_int<QTTT_BLOCK, 1024, 256>(blk, [&](auto BLK) {
+                        if constexpr (BPL != 4 || BLK == QTTT_BLOCK) {
+                            const int grid = blocks_for(groups, BLK);
+                            hipLaunchKernelGGL((step_quiet_kernel<BLK, BPL, HB, AR>), dim3(grid), dim3(BLK), 0, s, p.P, p.Q,
+                                               (const uint16_t *)a16, bits, key_fold, id_base, i0,
+                                               (u32)(groups - (int64_t)(grid - 1) * BLK));
+                        }
+                    });
+                });
+            }, hb, (e.flags & QTTT_FLAG_AUTO_RESET) != 0);
+            return;
+        }
         with_bools([&](auto DEV, auto HB, auto AR, auto SM, auto OB) {
             with_int<4, 2, 1>(bpl, [&](auto BPL) {
                 with_int<QTTT_BLOCK, 1024, 256>(blk, [&](auto BLK) {
@@ -477,11 +495,13 @@ int qttt_step_many(void *state, const uint8_t *actions, const uint8_t *bits, uin
             }, bits != nullptr, (flags & QTTT_FLAG_AUTO_RESET) != 0);
         });
     }
+    // With out_stride == 0 every step writes the same n outputs and only the last step's can ever be read: the earlier
+    // steps run without them (step_quiet_kernel: 34 instead of 39 bytes per board), after the same argument checks.
     for (int32_t t = 0; t < n_steps; ++t) {
-        int rc = qttt_step(state, actions + (int64_t)t * 2 * n, bits ? bits + (int64_t)t * n : nullptr,
-                           seed, step_idx0 + (uint32_t)t, board_offset, flags,
-                           reward + (int64_t)t * out_stride, terminated + (int64_t)t * out_stride,
-                           n, stream);
+        const qttt_env e = {state, n, board_offset, seed, flags, 0u, reward + (int64_t)t * out_stride,
+                            terminated + (int64_t)t * out_stride};
+        int rc = launch_step(e, const_cast<uint8_t *>(actions + (int64_t)t * 2 * n), bits ? bits + (int64_t)t * n : nullptr,
+                             step_idx0 + (uint32_t)t, stream, false, nullptr, out_stride == 0 && t < n_steps - 1);
         if (rc != 0) return rc;
     }
     return 0;

@@ -32,8 +32,10 @@ template <> struct StepKeySource<true> {
     u64 seed;
 };
 
-template <int BLOCK, int BPL, bool HAS_BITS, bool AUTO_RESET, bool SAMPLE = false, bool OBS = false, bool DEVSTEP = false>
-__global__ __launch_bounds__(BLOCK) void step_kernel(
+// OUT: reward and terminated are formed and stored.  Without it (step_quiet_kernel, below) the step moves the two planes
+// only: 34 bytes per board instead of 39.
+template <int BLOCK, int BPL, bool HAS_BITS, bool AUTO_RESET, bool SAMPLE, bool OBS, bool DEVSTEP, bool OUT>
+__device__ __forceinline__ void step_body(
     u64 *__restrict__ pP, u64 *__restrict__ pQ, uint16_t *__restrict__ actions,
     const uint8_t *__restrict__ bits, u32 key_fold, u32 key_hi, u32 id_base,
     u32 *__restrict__ reward_bits, uint8_t *__restrict__ terminated, ObsOut obs, int64_t i_begin,
@@ -163,15 +165,19 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(
             }
             p.v[k] = (u64)P0 | ((u64)P1 << 32);
             q.v[k] = (u64)Q0 | ((u64)Q1 << 32);
-            rw.v[k] = 0x80000000u | (win << 23);                         // env.py:49: -1.0f / -0.0f
-            tm.v[k] = (uint8_t)(P1 >> 31);
+            if (OUT) {
+                rw.v[k] = 0x80000000u | (win << 23);                     // env.py:49: -1.0f / -0.0f
+                tm.v[k] = (uint8_t)(P1 >> 31);
+            }
             if (OBS) obs_board(P0, P1, Q0, T, g * BPL + (u32)k, olut);
         }
         store_stream_sbase(pP + ib, g * (u32)sizeof(V64), p);          // block-uniform base + 32-bit lane offset, like the loads
         store_stream_sbase(pQ + ib, g * (u32)sizeof(V64), q);
         if (SAMPLE && actions) store_stream(&reinterpret_cast<V16 *>(actions + ib)[g], act);
-        store_stream(&reinterpret_cast<V32 *>(reward_bits + ib)[g], rw);
-        store_stream(&reinterpret_cast<V8 *>(terminated + ib)[g], tm);
+        if (OUT) {
+            store_stream(&reinterpret_cast<V32 *>(reward_bits + ib)[g], rw);
+            store_stream(&reinterpret_cast<V8 *>(terminated + ib)[g], tm);
+        }
     }
     if (OBS) {
         // a wave's boards [64w * BPL, 64(w+1) * BPL) start on a multiple of 4 bytes in every tile
@@ -198,6 +204,29 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(
         o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3;
     }
 #endif
+}
+
+template <int BLOCK, int BPL, bool HAS_BITS, bool AUTO_RESET, bool SAMPLE = false, bool OBS = false, bool DEVSTEP = false>
+__global__ __launch_bounds__(BLOCK) void step_kernel(
+    u64 *__restrict__ pP, u64 *__restrict__ pQ, uint16_t *__restrict__ actions,
+    const uint8_t *__restrict__ bits, u32 key_fold, u32 key_hi, u32 id_base,
+    u32 *__restrict__ reward_bits, uint8_t *__restrict__ terminated, ObsOut obs, int64_t i_begin,
+    u32 last_groups, StepKeySource<DEVSTEP> sk) {
+    step_body<BLOCK, BPL, HAS_BITS, AUTO_RESET, SAMPLE, OBS, DEVSTEP, true>(
+        pP, pQ, actions, bits, key_fold, key_hi, id_base, reward_bits, terminated, obs, i_begin, last_groups, sk);
+}
+
+// The plain step (recorded actions; no policy, no observation, host-side step index) WITHOUT its outputs: the launches
+// of qttt_step_many whose reward / terminated the next launch overwrites (out_stride == 0, every step but the last).
+// A kernel of its own rather than a null-pointer test in step_kernel (see DEVSTEP above on what extra arguments and a
+// branch cost the ordinary kernel).  The launch key's high word is not needed: only the policy and DEVSTEP read it.
+template <int BLOCK, int BPL, bool HAS_BITS, bool AUTO_RESET>
+__global__ __launch_bounds__(BLOCK) void step_quiet_kernel(
+    u64 *__restrict__ pP, u64 *__restrict__ pQ, const uint16_t *__restrict__ actions,
+    const uint8_t *__restrict__ bits, u32 key_fold, u32 id_base, int64_t i_begin, u32 last_groups) {
+    step_body<BLOCK, BPL, HAS_BITS, AUTO_RESET, false, false, false, false>(
+        pP, pQ, const_cast<uint16_t *>(actions), bits, key_fold, 0u, id_base, nullptr, nullptr,
+        ObsOut{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, i_begin, last_groups, StepKeySource<false>{});
 }
 
 //@isa lane

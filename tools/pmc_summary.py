@@ -8,7 +8,14 @@ extra_bytes_per_board / key_suffix: e.g. `30 gym` for the step kernel that also 
 
 FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports half the bytes of a wide
 coalesced read (MI355X_MICROARCH.md §HBM), so it is doubled.  Only the step kernel's
-dispatches are used."""
+dispatches are used.
+
+qttt_step_many without output buffers runs every step but its last through step_quiet_kernel (no reward / terminated
+stores).  With PMC_REGION="K,W,R" (bench.py's --steps, --warmup and the `regions` of its JSON line) only the TIMED
+dispatches are folded — the last R * (W + K) step dispatches of the process are the R regions, the last K of each are
+timed, as in tools/trace_summary.py — and the entry is the mean over them, full and quiet dispatches weighted by their
+count (K - 1 quiet + 1 full per region), with the two kinds listed beside it.  Without PMC_REGION every dispatch of
+either kind is averaged (the recording pass and the warm-up passes included)."""
 import csv
 import glob
 import json
@@ -20,15 +27,31 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL_FILTER = os.environ.get("PMC_KERNEL_FILTER", "step_kernel")
 
 
+QUIET_FILTER = "step_quiet_kernel"
+REGION = tuple(int(x) for x in os.environ["PMC_REGION"].split(",")) if os.environ.get("PMC_REGION") else None
+
+
 def mean_counter(d, name):
-    vals = []
+    """(mean over the folded dispatches, their number, {kind: (mean, number)}) of one counter"""
+    rows = []
     for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
-            if r["Counter_Name"] == name and KERNEL_FILTER in r["Kernel_Name"]:
-                vals.append(float(r["Counter_Value"]))
-    if not vals:
+            quiet = KERNEL_FILTER == "step_kernel" and QUIET_FILTER in r["Kernel_Name"]
+            if r["Counter_Name"] == name and (quiet or KERNEL_FILTER in r["Kernel_Name"]):
+                rows.append((int(r["Dispatch_Id"]), "quiet" if quiet else "full", float(r["Counter_Value"])))
+    rows.sort()
+    if REGION:
+        K, W, R = REGION
+        tail = rows[-R * (W + K):]
+        rows = [x for r in range(R) for x in tail[r * (W + K) + W:(r + 1) * (W + K)]]
+    if not rows:
         raise SystemExit("no %s rows for step_kernel under %s" % (name, d))
-    return sum(vals) / len(vals), len(vals)
+    kinds = {}
+    for kind in ("full", "quiet"):
+        v = [x[2] for x in rows if x[1] == kind]
+        if v:
+            kinds[kind] = (sum(v) / len(v), len(v))
+    return sum(x[2] for x in rows) / len(rows), len(rows), kinds
 
 
 STEP_SOURCES = ("qttt_state.h", "qttt_step_core.h", "qttt_observation.h", "qttt_step_kernels.h")
@@ -50,8 +73,8 @@ def main():
     state_bytes = int(sys.argv[5]) if len(sys.argv) > 5 else 16
     extra = int(sys.argv[6]) if len(sys.argv) > 6 else 0
     suffix = sys.argv[7] if len(sys.argv) > 7 else ""
-    fetch_kib, nf = mean_counter(fetch_dir, "FETCH_SIZE")
-    write_kib, nw = mean_counter(write_dir, "WRITE_SIZE")
+    fetch_kib, nf, fetch_kinds = mean_counter(fetch_dir, "FETCH_SIZE")
+    write_kib, nw, write_kinds = mean_counter(write_dir, "WRITE_SIZE")
     entry = {
         "FETCH_SIZE_KiB_raw": fetch_kib, "WRITE_SIZE_KiB": write_kib,
         "read_bytes": 2 * fetch_kib * 1024, "write_bytes": write_kib * 1024,
@@ -61,6 +84,20 @@ def main():
         "note": "FETCH_SIZE doubled (gfx950 half-count of wide coalesced reads); separate --pmc passes",
         "step_sources_sha256": step_sources_sha256(),
     }
+    if "quiet" in fetch_kinds or "quiet" in write_kinds:
+        # the two kinds of dispatch beside their count-weighted mean above; the algorithmic figure likewise
+        for kind, out_bytes in (("full", 5), ("quiet", 0)):
+            if kind in fetch_kinds and kind in write_kinds:
+                (fk, fn), (wk, wn) = fetch_kinds[kind], write_kinds[kind]
+                entry[kind] = {"FETCH_SIZE_KiB_raw": fk, "WRITE_SIZE_KiB": wk, "dispatches": [fn, wn],
+                               "hbm_bytes_per_launch": 2 * fk * 1024 + wk * 1024,
+                               "algorithmic_bytes_per_launch": (2 * state_bytes + 2 + out_bytes + extra) * int(boards)}
+        if "full" in entry and "quiet" in entry:
+            nq, nfl = entry["quiet"]["dispatches"][1], entry["full"]["dispatches"][1]
+            entry["algorithmic_bytes_per_launch"] = (nq * entry["quiet"]["algorithmic_bytes_per_launch"] +
+                                                     nfl * entry["full"]["algorithmic_bytes_per_launch"]) / (nq + nfl)
+    if REGION:
+        entry["timed_region_steps_warmup_regions"] = list(REGION)
     path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
     d = json.load(open(path)) if os.path.exists(path) else {}
     d["%s@%dB%s" % (boards, state_bytes, ("+" + suffix) if suffix else "")] = entry

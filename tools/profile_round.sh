@@ -41,13 +41,14 @@ find "$out" -name "*agent_info.csv" -delete 2>/dev/null
 python3 "$R/tools/trace_rows_summary.py" "$out/kt_rows" > "$out/kernel_trace_rows.csv" 2> "$out/kernel_trace_rows.err"
 for d in kt_full kt_rows kt_fused; do find "$out/$d" -name "*kernel_trace.csv" -delete 2>/dev/null; done
 tag=$(basename "$out" | sed 's/^prof_//')
-python3 "$R/tools/pmc_summary.py" 1048576 "$out/pmc_f" "$out/pmc_w" "$tag step_kernel<1024,2,false,true,false,false> via bench.py --steps 20 --warmup 5 --regions 3 --no-legs" 16 > "$out/pmc_traffic_1M.json"
-python3 "$R/tools/pmc_summary.py" 16777216 "$out/pmc_f16" "$out/pmc_w16" "$tag step_kernel<256,2,false,true,false,false> via bench.py --boards 16777216 --steps 10 --warmup 2 --regions 2 --no-legs" 16 > "$out/pmc_traffic_16M.json"
+PMC_REGION=20,5,3 python3 "$R/tools/pmc_summary.py" 1048576 "$out/pmc_f" "$out/pmc_w" "$tag timed regions, 19 x step_quiet_kernel<1024,2,false,true> + 1 x step_kernel<1024,2,false,true,false,false,false> each, via bench.py --steps 20 --warmup 5 --regions 3 --no-legs" 16 > "$out/pmc_traffic_1M.json"
+PMC_REGION=10,2,2 python3 "$R/tools/pmc_summary.py" 16777216 "$out/pmc_f16" "$out/pmc_w16" "$tag timed regions, 9 x step_quiet_kernel<256,2,false,true> + 1 x step_kernel<256,2,false,true,false,false,false> each, via bench.py --boards 16777216 --steps 10 --warmup 2 --regions 2 --no-legs" 16 > "$out/pmc_traffic_16M.json"
 cp "$R/profiles/pmc_traffic.json" "$out/pmc_traffic.json"
 for n in pmc_f pmc_w pmc_f16 pmc_w16; do python3 - "$out/$n" "$out/${n}_step_kernel_counter_collection.csv" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True)[0]
-rows = [r for r in csv.DictReader(open(f)) if "step_kernel" in r["Kernel_Name"]]
+rows = [r for r in csv.DictReader(open(f)) if "step_kernel" in r["Kernel_Name"] or "step_quiet_kernel" in r["Kernel_Name"]]
+rows.sort(key=lambda r: int(r["Dispatch_Id"]))
 w = csv.DictWriter(open(sys.argv[2], "w"), fieldnames=rows[0].keys()); w.writeheader(); w.writerows(rows[-48:])
 PY
 done

@@ -14,6 +14,10 @@ duration of dispatch k, the idle gap end[k] -> begin[k+1], and the period begin[
 (= what an event pair around K back-to-back launches divides by K), averaged over all regions and listed
 dispatch by dispatch for the median region.  UNPROFILED_US (optional 6th argument) = the un-profiled
 bench.py line's us per launch, printed beside the profiled period.
+
+With the default substring the dispatches of step_quiet_kernel (qttt_step_many's steps that store no reward /
+terminated: every timed step of a replay region but its last) count as step dispatches too, and the timed average is
+also printed for the two kernels separately.
 """
 import csv
 import glob
@@ -27,7 +31,8 @@ def main():
     pat = sys.argv[5] if len(sys.argv) > 5 else "step_kernel"
     unprofiled = float(sys.argv[6]) if len(sys.argv) > 6 else None
     f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
-    rows = [r for r in csv.DictReader(open(f)) if pat in r["Kernel_Name"]]
+    quiet = "step_quiet_kernel" if pat == "step_kernel" else None
+    rows = [r for r in csv.DictReader(open(f)) if pat in r["Kernel_Name"] or (quiet and quiet in r["Kernel_Name"])]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     dur = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in rows]
     name = re.search(r"%s<[^>]*>" % re.escape(pat), rows[-1]["Kernel_Name"])
@@ -38,10 +43,13 @@ def main():
         rows[-1].get("Grid_Size") or rows[-1].get("Grid_Size_X")))
     print("all %d dispatches          : avg %.1f ns  min %d  max %d" % (len(dur), sum(dur) / len(dur), min(dur), max(dur)))
     tail = rows[-R * (W + K):]
-    timed, spans = [], []
+    timed, spans, by_kernel = [], [], {}
     for r in range(R):
         reg = tail[r * (W + K) + W:(r + 1) * (W + K)]
         timed += [int(x["End_Timestamp"]) - int(x["Start_Timestamp"]) for x in reg]
+        for x in reg:
+            by_kernel.setdefault("quiet" if quiet and quiet in x["Kernel_Name"] else "full", []).append(
+                int(x["End_Timestamp"]) - int(x["Start_Timestamp"]))
         spans.append((int(reg[-1]["End_Timestamp"]) - int(reg[0]["Start_Timestamp"])) / K)
     regs = []
     for r in range(R):
@@ -52,6 +60,10 @@ def main():
     order = sorted(range(R), key=lambda r: spans[r])
     spans.sort()
     print("timed: %d regions x %d      : avg %.1f ns  min %d  max %d" % (R, K, sum(timed) / len(timed), min(timed), max(timed)))
+    if len(by_kernel) > 1:
+        for k in ("full", "quiet"):
+            v = by_kernel[k]
+            print("timed, %-5s dispatches only : %d x avg %.1f ns  min %d  max %d" % (k, len(v), sum(v) / len(v), min(v), max(v)))
     print("timed span / K per region  : median %.1f ns  min %.1f  max %.1f" % (spans[len(spans) // 2], spans[0], spans[-1]))
     gaps = [b[k + 1] - e[k] for b, e in regs for k in range(K - 1)]
     periods = [b[k + 1] - b[k] for b, e in regs for k in range(K - 1)]
