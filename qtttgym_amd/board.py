@@ -21,13 +21,12 @@ import threading
 import torch
 
 from . import _native
-from .vec_env import _raw_stream
+from ._host import _current_device, _raw_stream
 
 try:                                              # optional host-side accelerator (csrc/fastboard.c); never a compute path
     from . import _fastboard
 except ImportError:
     _fastboard = None
-_current_device = getattr(torch._C, "_cuda_getDevice", torch.cuda.current_device)
 
 
 class QEvalClassic:

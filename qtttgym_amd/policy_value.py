@@ -7,6 +7,7 @@ as the kernel's MFMA B fragments; the layout is documented in include/qttt_nn.h.
 import torch
 
 from . import _native
+from ._host import resolve_device
 
 HIDDEN = 256
 HEAD_COLS = 48                       # 36 logits, the value, 11 zero columns
@@ -90,20 +91,11 @@ class PolicyValueNet:
         sd = _state_dict(source)
         self.dtype = dtype
         self.precision = _PRECISION[dtype]
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _native.QtttNativeError(
-                "PolicyValueNet runs on an MI355X through libqttt_hip.so only (device=%r); there is no CPU path"
-                % (device,))
-        if not torch.cuda.is_available():
-            raise _native.QtttNativeError("no HIP device visible (torch.cuda.is_available() is False)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = resolve_device(device, "PolicyValueNet")
         nbytes = int(_native.lib().qttt_nn_weights_bytes(self.precision))
         if nbytes != weights_bytes(dtype):
             raise _native.QtttNativeError("libqttt_hip.so blob size %d != %d (stale build?)" % (nbytes, weights_bytes(dtype)))
-        with torch.cuda.device(self.device):
-            self.blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self.load_state_dict(sd)
 
     def load_state_dict(self, source):

@@ -10,10 +10,16 @@ ValueError before launching work that could pass it.
 import torch
 
 from . import _native
-from .vec_env import VecEnv, _ptr, _raw_stream
+from ._host import LibCaller, _ptr, check_net, out_rows, out_tensor, resolve_device
+from .vec_env import VecEnv
 
 
-class TreeSearch:
+class TreeSearch(LibCaller):
+    # the roots' statistics (qttt_tree_root): name -> (dtype, per-game shape)
+    _ROOT_ROWS = {"N": (torch.int32, (36,)), "W": (torch.float64, (36,)), "Q": (torch.float64, (36,)),
+                  "P": (torch.float64, (36,)), "Ntot": (torch.int32, ()), "choose": (torch.uint8, ()),
+                  "nodes_used": (torch.int32, ()), "overflow": (torch.uint8, ())}
+
     def __init__(self, num_games, capacity, num_simulations=10, c_puct=1.0, net=None, seed=0, board_offset=0,
                  device=None):
         self.num_games, self.capacity = int(num_games), int(capacity)
@@ -28,37 +34,25 @@ class TreeSearch:
             raise ValueError("board_offset must be >= 0")
         if device is None:
             device = net.device if net is not None else "cuda"
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _native.QtttNativeError("TreeSearch runs on an MI355X through libqttt_hip.so only (device=%r)" % (device,))
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if net is not None and getattr(net, "device", None) != self.device:
-            raise ValueError("net must be a PolicyValueNet on %s" % (self.device,))
-        self._lib = _native.lib()
-        G = self.num_games
+        self._open(resolve_device(device, "TreeSearch"))
+        if net is not None:
+            check_net(net, self.device)
+        G, S, dev = self.num_games, self.num_simulations, self.device
         nbytes = int(self._lib.qttt_tree_bytes(G, self.capacity))
         if nbytes < 0:
             raise ValueError("qttt_tree_bytes(%d, %d) failed" % (G, self.capacity))
-        with torch.cuda.device(self.device):
-            self.tree = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
-            leaf_state = torch.zeros(int(self._lib.qttt_state_bytes(G)), dtype=torch.uint8, device=self.device)
-            self.leaf = VecEnv.from_state(leaf_state, G, seed=self.seed, board_offset=self.board_offset)
-            S = self.num_simulations
-            if net is None:
-                self._out = torch.empty((G, S), dtype=torch.int8, device=self.device)
-            else:
-                self._out = {"result": torch.empty((G, S), dtype=torch.int8, device=self.device),
-                             "probs": torch.empty((G, 36), dtype=torch.float32, device=self.device)}
+        self.tree = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        leaf_state = torch.zeros(int(self._lib.qttt_state_bytes(G)), dtype=torch.uint8, device=dev)
+        self.leaf = VecEnv.from_state(leaf_state, G, seed=self.seed, board_offset=self.board_offset)
+        # what the playouts write and the backup reads
+        if net is None:
+            self._out = out_tensor(torch.int8, (S,), G, dev)
+        else:
+            self._out = out_rows(VecEnv._policy_rows(S), G, dev, keys=("result", "probs"))
         self.rollout_idx = 0          # k of include/qttt_tree.h: rollouts since the last reset
         self._bound = None            # upper bound on the nodes used (None: not reset yet)
 
     # ------------------------------------------------------------------ helpers
-    def _call(self, fn, name, *args):
-        with torch.cuda.device(self.device):
-            rc = fn(*args, _raw_stream(self.device.index))
-        _native.check(rc, name)
-
     def _check_env(self, env):
         if env.num_envs != self.num_games or env.state.device != self.device:
             raise ValueError("env must hold %d boards on %s" % (self.num_games, self.device))
@@ -74,8 +68,7 @@ class TreeSearch:
         """MCTS.reset (mcts.py:139-164) of every game at env's positions (their full state, open entanglements
         included)."""
         self._check_env(env)
-        self._call(self._lib.qttt_tree_reset, "qttt_tree_reset", self.tree.data_ptr(), self.num_games, self.capacity,
-                   env.state.data_ptr())
+        self._call("qttt_tree_reset", self.tree.data_ptr(), self.num_games, self.capacity, env.state.data_ptr())
         self.rollout_idx, self._bound = 0, 1
 
     def contemplate(self, rollouts):
@@ -91,19 +84,18 @@ class TreeSearch:
         if self._bound + 2 * r > self.capacity:
             raise ValueError("%d rollouts could use %d nodes, more than capacity %d"
                              % (r, self._bound + 2 * r, self.capacity))
-        L, G, cap, S = self._lib, self.num_games, self.capacity, self.num_simulations
+        G, cap, S = self.num_games, self.capacity, self.num_simulations
         tree, leaf = self.tree.data_ptr(), self.leaf.state.data_ptr()
         stride = S * _native.SIM_STRIDE
         for _ in range(r):
             k = self.rollout_idx
-            self._call(L.qttt_tree_select, "qttt_tree_select", tree, G, cap, self.seed, k, self.board_offset,
-                       self.c_puct, leaf)
+            self._call("qttt_tree_select", tree, G, cap, self.seed, k, self.board_offset, self.c_puct, leaf)
             if self.net is None:
                 self.leaf.rollout_many(S, step_idx0=k * stride, out=self._out)
-                self._call(L.qttt_tree_backup, "qttt_tree_backup", tree, G, cap, self._out.data_ptr(), S, None)
+                self._call("qttt_tree_backup", tree, G, cap, self._out.data_ptr(), S, None)
             else:
                 self.leaf.rollout_policy(self.net, S, step_idx0=k * stride, out=self._out)
-                self._call(L.qttt_tree_backup, "qttt_tree_backup", tree, G, cap, self._out["result"].data_ptr(), S,
+                self._call("qttt_tree_backup", tree, G, cap, self._out["result"].data_ptr(), S,
                            self._out["probs"].data_ptr())
             self.rollout_idx = k + 1
             self._bound += 2
@@ -111,16 +103,7 @@ class TreeSearch:
     def root_stats(self):
         """The roots' statistics: N i32[G,36], W / Q / P f64[G,36], Ntot i32[G], choose u8[G], nodes_used i32[G],
         overflow bool[G]."""
-        G, dev = self.num_games, self.device
-        with torch.cuda.device(dev):
-            o = {"N": torch.empty((G, 36), dtype=torch.int32, device=dev),
-                 "W": torch.empty((G, 36), dtype=torch.float64, device=dev),
-                 "Q": torch.empty((G, 36), dtype=torch.float64, device=dev),
-                 "P": torch.empty((G, 36), dtype=torch.float64, device=dev),
-                 "Ntot": torch.empty(G, dtype=torch.int32, device=dev),
-                 "choose": torch.empty(G, dtype=torch.uint8, device=dev),
-                 "nodes_used": torch.empty(G, dtype=torch.int32, device=dev),
-                 "overflow": torch.empty(G, dtype=torch.uint8, device=dev)}
+        o = out_rows(self._ROOT_ROWS, self.num_games, self.device)
         self._root(**o)
         o["overflow"] = o["overflow"].bool()
         return o
@@ -128,19 +111,17 @@ class TreeSearch:
     def _root(self, N=None, W=None, Q=None, P=None, Ntot=None, choose=None, nodes_used=None, overflow=None):
         if self._bound is None:
             raise RuntimeError("reset() first")
-        self._call(self._lib.qttt_tree_root, "qttt_tree_root", self.tree.data_ptr(), self.num_games, self.capacity,
-                   _ptr(N), _ptr(W), _ptr(Q), _ptr(P), _ptr(Ntot), _ptr(choose), _ptr(nodes_used), _ptr(overflow))
+        self._call("qttt_tree_root", self.tree.data_ptr(), self.num_games, self.capacity, _ptr(N), _ptr(W), _ptr(Q),
+                   _ptr(P), _ptr(Ntot), _ptr(choose), _ptr(nodes_used), _ptr(overflow))
 
     def choose(self):
         """MCTS.choose (mcts.py:308-315) per game: action36 u8[G], 255 where the root has no legal action."""
-        with torch.cuda.device(self.device):
-            a = torch.empty(self.num_games, dtype=torch.uint8, device=self.device)
+        a = out_tensor(*self._ROOT_ROWS["choose"], self.num_games, self.device)
         self._root(choose=a)
         return a
 
     def nodes_used(self):
-        with torch.cuda.device(self.device):
-            n = torch.empty(self.num_games, dtype=torch.int32, device=self.device)
+        n = out_tensor(*self._ROOT_ROWS["nodes_used"], self.num_games, self.device)
         self._root(nodes_used=n)
         return n
 
@@ -153,6 +134,5 @@ class TreeSearch:
             raise RuntimeError("reset() first")
         if self._bound + 1 > self.capacity:
             raise ValueError("a sync could use %d nodes, more than capacity %d" % (self._bound + 1, self.capacity))
-        self._call(self._lib.qttt_tree_sync, "qttt_tree_sync", self.tree.data_ptr(), self.num_games, self.capacity,
-                   env.state.data_ptr())
+        self._call("qttt_tree_sync", self.tree.data_ptr(), self.num_games, self.capacity, env.state.data_ptr())
         self._bound += 1
