@@ -1,5 +1,5 @@
 // qttt_aux_kernels.h — kernels beside the step: observation of stored boards, check_win, export /
-// import of Board attributes, the single-record Board façade op, action sampling.
+// import of Board attributes, the single-record Board façade op, action sampling, the two reset fills.
 #ifndef QTTT_AUX_KERNELS_H
 #define QTTT_AUX_KERNELS_H
 #include "qttt_step_core.h"
@@ -672,6 +672,50 @@ __global__ __launch_bounds__(QTTT_BLOCK) void sample_actions_kernel(
 
 // the device-side step counter of qttt_env.step_counter, advanced on the stream (one lane)
 __global__ void counter_add_kernel(u32 *counter, u32 by) { *counter += by; }
+
+// the empty board is the all-zero state: 16 bytes of zeros per lane, with the step kernel's own
+// non-temporal stores
+__global__ __launch_bounds__(256) void reset_kernel(u32x4 *state, int64_t n16) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n16) __builtin_nontemporal_store(u32x4{0u, 0u, 0u, 0u}, &state[i]);
+}
+
+// Env.reset INCLUDING the observation it returns (env.py:55-57,68-85): the empty board's observation is constant
+// (classical -1, no quantum states: 255 pad and length 0, turn 0), so state and observation are seven byte fills in
+// one launch.  The seven buffers' 16-byte pieces are numbered through (first[k] = pieces in front of buffer k): every
+// thread of the grid stores one piece, non-temporally; the unaligned head / tail of a caller's odd pointer is written
+// bytewise by the first workgroup.
+struct FillSegs {
+    uint8_t *p[7];
+    int64_t bytes[7];
+    int64_t first[8];                                        // prefix sums of the 16-byte piece counts
+    u32 word[7];                                             // the fill byte, four times
+};
+// bytes in front of p's next 16-byte boundary, nb at most (the host sizes the launch with it too: qttt_reset_observe)
+__host__ __device__ __forceinline__ int64_t fill_head(const uint8_t *p, int64_t nb) {
+    const int64_t h = (int64_t)((16u - (u32)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u);
+    return h < nb ? h : nb;
+}
+// (extern "C": the kernel keeps the unmangled symbol it has always had in the code object, profiles and traces)
+extern "C" __global__ __launch_bounds__(256) void reset_observe_kernel(FillSegs f) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g < f.first[7]) {
+        int k = 0;
+#pragma unroll
+        for (int j = 1; j < 7; ++j) k += g >= f.first[j] ? 1 : 0;
+        const u32 w = f.word[k];
+        uint8_t *p = f.p[k];
+        __builtin_nontemporal_store(u32x4{w, w, w, w}, reinterpret_cast<u32x4 *>(p + fill_head(p, f.bytes[k])) + (g - f.first[k]));
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 7 * 32) {           // 16 head + 16 tail bytes per buffer
+        const int k = threadIdx.x >> 5;
+        const int64_t j = threadIdx.x & 15;
+        uint8_t *p = f.p[k];
+        const int64_t nb = f.bytes[k], head = fill_head(p, nb), nvec = f.first[k + 1] - f.first[k];
+        if ((threadIdx.x & 31) < 16) { if (j < head) p[j] = (uint8_t)f.word[k]; }
+        else { const int64_t off = head + (nvec << 4) + j; if (off < nb) p[off] = (uint8_t)f.word[k]; }
+    }
+}
 
 }  // namespace
 

@@ -148,6 +148,50 @@ def _argument_table(L, _native):
     return rows
 
 
+def test_misaligned_pointers_are_refused_before_any_launch():
+    """The last check of every entry, after size, empty batch and null: a pointer the kernel's vector accesses cannot
+    take is QTTT_ERR_ACTION.  The rows pass fake non-null addresses, which is safe only because the check precedes any
+    launch: they run where no GPU is visible."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("fake addresses: only where no launch could reach a device")
+    from qtttgym_amd import _native
+    L = _native.lib()
+    N, F, n = None, 0x10000, 8                        # F: never dereferenced, 16-byte aligned
+    obs = (F,) * 6                                    # classical, q_p1, q_p1_len, q_p2, q_p2_len, turn
+    rows = [
+        ("qttt_step", (F, F + 1, N, 0, 0, 0, 0, F, F, n, N)),                             # actions: u16 pairs
+        ("qttt_step_random", (F, 0, 0, 0, 0, F + 1, F, F, n, N)),
+        ("qttt_sample_actions", (F, 0, 0, 0, 0, F + 1, n, N)),
+        ("qttt_step_many", (F, F + 1, N, 0, 0, 0, 0, F, F, 0, n, 2, N)),
+        ("qttt_step_many", (F, F + 1, N, 0, 0, 0, 2, F, F, 0, n, 2, N)),                  # QTTT_FLAG_FUSED
+        ("qttt_step_random_many", (F, 0, 0, 0, 0, F + 1, N, N, 0, N, n, 4, N)),
+        ("qttt_step_random_many", (F, 0, 0, 0, 0, N, F + 2, F, 0, N, n, 4, N)),           # reward: 4-byte
+        ("qttt_step_random_many", (F, 0, 0, 0, 0, N, N, N, 0, F + 2, n, 4, N)),           # returns: 4-byte
+        ("qttt_observe", (F, F, F + 1, F, F, F, F, n, N)),                                # q_p1: 2-byte
+        ("qttt_observe", (F, F, F, F, F + 4, F, F, n, N)),                                # q_p2: 8-byte
+        ("qttt_step_observe", (F, F, N, 0, 0, 0, 0, F, F, F, F + 1, F, F, F, F, n, N)),
+        ("qttt_step_observe", (F, F, N, 0, 0, 0, 0, F, F, F, F, F, F + 4, F, F, n, N)),
+        ("qttt_step_observe", (F, F + 1, N, 0, 0, 0, 0, F, F) + obs + (n, N)),
+        ("qttt_export", (F, N, N, N, F + 1, N, n, N)),                                    # qmask: 2-byte
+        ("qttt_encode", (F, F + 8, N, n, N)),                                             # vec: 16-byte
+        ("qttt_encode", (F, F, F + 2, n, N)),                                             # mask: 4-byte
+        ("qttt_evaluate", (F, F, 0, F + 2, N, N, n, N)),                                  # value: 4-byte
+        ("qttt_rollout_policy", (F, F + 8, 0, 0, 0, 0, 1, F, N, N, N, N, n, N)),          # weights: 16-byte
+        ("qttt_rollout_policy", (F, F, 1, 0, 0, 0, 1, F, N, N, F + 2, N, n, N)),          # leaf_value: 4-byte
+        ("qttt_rollout_policy", (F, F, 1, 0, 0, 0, 1, F, N, N, N, F + 2, n, N)),          # leaf_probs: 4-byte
+    ]
+    # the per-child rows of expand / expand_rollout: winner, terminal 2-byte; legal, key, state_key 16-byte
+    for k, off in ((5, 1), (6, 1), (7, 8), (8, 8), (9, 8)):
+        args = [F, F, F, F, N, N, N, N, N, N]
+        args[k] = F + off
+        rows.append(("qttt_expand", tuple(args) + (n, N)))
+        rows.append(("qttt_expand_rollout", tuple(args) + (0, 0, 0, 1, F, N, n, N)))
+    rows.append(("qttt_expand_rollout", (F, F, N, N, N, N, N, N, N, N, 0, 0, 0, 1, F + 2, N, n, N)))   # value_sum: 4-byte
+    for fn, args in rows:
+        assert getattr(L, fn)(*args) == -3, (fn, args)
+
+
 def test_header_is_plain_c_and_the_env_record_layout_matches_the_binding(tmp_path):
     """include/qttt.h must stay a C header (the reference side would bind it through ctypes / cffi / cgo):
     gcc -std=c99 -pedantic compiles it, and sizeof / offsetof of struct qttt_env as a C compiler sees them are

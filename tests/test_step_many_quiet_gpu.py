@@ -64,7 +64,7 @@ def _check(n, auto_reset, explicit_bits, off=0, launch_shape=None, misalign=Fals
         assert torch.equal(r.view(torch.int32), rs.view(torch.int32)) and torch.equal(tm, ts), tag
 
 
-# one batch size per row of auto_tuning() (qttt_kernels.hip), and an odd one with a ragged tail
+# one batch size per row of auto_tuning() (csrc/qttt_launch.h), and an odd one with a ragged tail
 @pytest.mark.parametrize("n,shape", [(4096, (1, 256)), (458752 + 2048, (1, 1024)), (655360, (2, 512)),
                                      (1048576, (2, 1024)), (1572864 + 4096, (2, 256)), (5003, (1, 256))])
 @pytest.mark.parametrize("auto_reset", [False, True])
