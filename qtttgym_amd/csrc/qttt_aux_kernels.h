@@ -5,6 +5,7 @@
 #include "qttt_step_core.h"
 #include "qttt_observation.h"
 #include "qttt_board_forms.h"
+#include "qttt_search_core.h"
 
 namespace {
 
@@ -632,11 +633,9 @@ __device__ __forceinline__ u32 sampled_action(const uint8_t *plut, u64 Pw, u64 b
     const u32 P1 = (u32)(Pw >> 32);
     const u32 cl = (auto_reset && (P1 >> 31)) ? 0u : (P1 >> P1_CL_SHIFT) & 0x1FFu;
     const u32 empty = ~cl & 0x1FFu;
-    const u32 h1 = lowbias32(fold_id(board_id) ^ key_lo);
-    const u32 h2 = lowbias32(h1 ^ key_hi);
     // fewer than two empty squares: rank_pair gives (0,0) and nth_bit[..][0] twice -> a == b, a noop;
     // the spec says (0,0)
-    return (empty & (empty - 1u)) ? policy_action(plut, empty, h2) : 0u;
+    return (empty & (empty - 1u)) ? policy_action(plut, empty, counter_draw(fold_id(board_id), (u64)key_lo | ((u64)key_hi << 32)).h2) : 0u;
 }
 
 // step_ctr (nullable): the step index is key_hi + *step_ctr and the launch key is made here (qttt_env.step_counter,

@@ -46,9 +46,10 @@
 //
 // Files: qttt_state.h (layout, loads/stores, shared tables) -> qttt_step_core.h (the step) ->
 // qttt_observation.h -> qttt_step_kernels.h; qttt_board_forms.h (unpacked views, winner, legal mask,
-// tuple hash) -> qttt_aux_kernels.h (the cold kernels, the reset fills), qttt_mcts_kernels.h, qttt_nn_kernels.h (the
-// policy/value network) -> qttt_policy_rollout_kernels.h (network-guided playouts); qttt_tree_kernels.h (the batched
-// search trees).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
+// tuple hash) -> qttt_search_core.h (the search rules several kernels share: counter draw, pair-action decode, expansion
+// of a pair, the uniform playout) -> qttt_aux_kernels.h (the cold kernels, the reset fills), qttt_mcts_kernels.h,
+// qttt_nn_kernels.h (the policy/value network) -> qttt_policy_rollout_kernels.h (network-guided playouts);
+// qttt_tree_kernels.h (the batched search trees).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
 // qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
@@ -565,10 +566,8 @@ int qttt_step_random(void *state, uint64_t seed, uint32_t step_idx, int64_t boar
 }
 
 uint64_t qttt_hash(uint64_t seed, uint64_t board_id, uint32_t step_idx) {
-    const u64 key = launch_key(seed, step_idx);
-    const u32 h1 = lowbias32(fold_id(board_id) ^ (u32)key);
-    const u32 h2 = lowbias32(h1 ^ (u32)(key >> 32));
-    return ((u64)h2 << 32) | h1;
+    const Draw d = counter_draw(fold_id(board_id), launch_key(seed, step_idx));
+    return ((u64)d.h2 << 32) | d.h1;
 }
 
 // ---------------------------------------------------------------- the network (include/qttt_nn.h, qttt_policy_rollout.h)

@@ -3,22 +3,12 @@
 #define QTTT_MCTS_KERNELS_H
 #include "qttt_step_core.h"
 #include "qttt_board_forms.h"
+#include "qttt_search_core.h"
 #include "qttt_aux_kernels.h"
 
 namespace {
 
 // ====================================================================== §8(f) rows
-// ind2move (mcts.py:339-343): lexicographic pairs (0,1),(0,2)..(7,8) as lo | hi<<4
-struct PairLut {
-    uint8_t b[36];
-    constexpr PairLut() : b() {
-        int a = 0;
-        for (int i = 0; i < 9; ++i)
-            for (int j = i + 1; j < 9; ++j) b[a++] = (uint8_t)(i | (j << 4));
-    }
-};
-__constant__ PairLut g_pair_lut = PairLut();
-
 // Two boards per lane (one 16-byte load per plane, 16-byte stores of the two legal masks and the two
 // keys): the CPython tuple hash is a dependent chain per board, two chains in one lane interleave
 // (fast_py_hash_pair).  The last board of an odd batch is handled alone.
@@ -103,11 +93,9 @@ __global__ __launch_bounds__(BLOCK) void node_info_kernel(
     }
 }
 
-// MCTS._step (mcts.py:233-267): both values of the collapse bit computed directly instead of
-// re-sampling make_move until the other branch appears.  The two children's bookkeeping (winner, legal
-// mask, keys) is computed as a pair — with PYKEY two independent hash chains in one lane, as in node_info — and
-// masked by n_children afterwards (child 1 is a valid state even when there is no collapse: it equals
-// child 0).  Every per-child output is nullable; PYKEY (the CPython-exact key) is its own instantiation.
+// The bookkeeping of the two children of an expansion (expand_pair) — winner, legal mask, keys — is computed as a
+// pair — with PYKEY two independent hash chains in one lane, as in node_info — and masked by n_children afterwards.
+// Every per-child output is nullable; PYKEY (the CPython-exact key) is its own instantiation.
 struct ExpandOut {
     uint8_t *n_children;        // [n]
     int8_t *winner;             // [n,2]
@@ -116,40 +104,37 @@ struct ExpandOut {
     int64_t *key;               // [n,2] CPython tuple hash (PYKEY)
     u64 *skey;                  // [n,2] native position key
 };
-// the bookkeeping of the two children of one pair, from their packed words (shared by expand_kernel and
-// expand_rollout_kernel's writer lanes)
 template <bool PYKEY>
-__device__ __forceinline__ void expand_bookkeeping(u32 kids, const u64 kidP[2], const u64 kidQ[2], u32 xo0, u32 xo1,
-                                                   const ExpandOut &o, int64_t i, const uint8_t *lut, const u64 *htbl, const u64 *ltbl) {
+__device__ __forceinline__ void expand_bookkeeping(const Expansion &e, const ExpandOut &o, int64_t i, const uint8_t *lut,
+                                                   const u64 *htbl, const u64 *ltbl) {
     typedef Vec<u64, 2> V64;
-    const bool h0 = kids >= 1u, h1 = kids >= 2u;
-    if (o.n_children) o.n_children[i] = (uint8_t)kids;
+    const bool h0 = e.kids >= 1u, h1 = e.kids >= 2u;
+    if (o.n_children) o.n_children[i] = (uint8_t)e.kids;
     if (o.skey) {
         V64 k2;
-        k2.v[0] = h0 ? state_key(kidP[0], (u32)kidQ[0]) : 0ull;
-        k2.v[1] = h1 ? state_key(kidP[1], (u32)kidQ[1]) : 0ull;
+        k2.v[0] = h0 ? state_key(e.P[0], (u32)e.Q) : 0ull;
+        k2.v[1] = h1 ? state_key(e.P[1], (u32)e.Q) : 0ull;
         store_stream(&reinterpret_cast<V64 *>(o.skey)[i], k2);
     }
-    if (o.winner || o.terminal) {                    // from the line test the step just made (update_winner, mcts.py:52-65)
+    if (o.winner || o.terminal) {
         int w0, t0, w1, t1;
-        update_winner_from_step(kidP[0], xo0, lut, w0, t0);
-        update_winner_from_step(kidP[1], xo1, lut, w1, t1);
+        update_winner_from_step(e.P[0], e.xo[0], lut, w0, t0);
+        update_winner_from_step(e.P[1], e.xo[1], lut, w1, t1);
         const u32 wv = (u32)((h0 ? w0 : -1) & 0xFF) | ((u32)((h1 ? w1 : -1) & 0xFF) << 8);
         const u32 tv = (h0 ? (u32)t0 : 0u) | ((h1 ? (u32)t1 : 0u) << 8);
         if (o.winner) reinterpret_cast<uint16_t *>(o.winner)[i] = (uint16_t)wv;      // [n,2] rows: 2-byte / 16-byte aligned by the host check
         if (o.terminal) reinterpret_cast<uint16_t *>(o.terminal)[i] = (uint16_t)tv;
     }
-    if (o.legal) {                                   // GameState.actions (mcts.py:20-27): a function of the classical squares,
-        V64 l2;                                      // the implicit autofill (eight classical squares) counted as the ninth
-        const u32 c0 = (u32)(kidP[0] >> (32u + P1_CL_SHIFT)) & 0x1FFu, c1 = (u32)(kidP[1] >> (32u + P1_CL_SHIFT)) & 0x1FFu;
-        l2.v[0] = h0 ? ltbl[__builtin_popcount(c0) == 8 ? 0x1FFu : c0] : 0ull;
-        l2.v[1] = h1 ? ltbl[__builtin_popcount(c1) == 8 ? 0x1FFu : c1] : 0ull;
+    if (o.legal) {                                   // GameState.actions (mcts.py:20-27): a function of the classical squares
+        V64 l2;
+        l2.v[0] = h0 ? ltbl[classical_with_autofill(e.P[0])] : 0ull;
+        l2.v[1] = h1 ? ltbl[classical_with_autofill(e.P[1])] : 0ull;
         store_stream(&reinterpret_cast<V64 *>(o.legal)[i], l2);
     }
     if (PYKEY) {
-        const Lite s0 = lite_unpack(kidP[0]), s1 = lite_unpack(kidP[1]);
+        const Lite s0 = lite_unpack(e.P[0]), s1 = lite_unpack(e.P[1]);
         int64_t k0, k1;
-        fast_py_hash_pair(s0, (u32)(kidP[0] >> 32), (u32)kidQ[0], s1, (u32)(kidP[1] >> 32), (u32)kidQ[1], htbl, k0, k1);
+        fast_py_hash_pair(s0, (u32)(e.P[0] >> 32), (u32)e.Q, s1, (u32)(e.P[1] >> 32), (u32)e.Q, htbl, k0, k1);
         V64 k2;
         k2.v[0] = h0 ? (u64)k0 : 0ull;     k2.v[1] = h1 ? (u64)k1 : 0ull;
         store_stream(&reinterpret_cast<V64 *>(o.key)[i], k2);
@@ -175,58 +160,14 @@ __global__ __launch_bounds__(BLOCK) void expand_kernel(
     if (out.legal) lw.store(ltbl);
     fill_line_lut<BLOCK>(lut);                       // computed; ends with the workgroup barrier
     if (i >= n) return;
-    const u32 pr = a < 36u ? (u32)g_pair_lut.b[a] : 0u;            // (0,0) = a noop for bad indices
-    const u32 act = (pr & 0xFu) | ((pr >> 4) << 8);
-    // both children in one pass: validity, components, append, qstructs and classical update are shared, only the
-    // path reversal and the line test run per child (step_core_both)
-    u32 Q0 = (u32)Q, Q1 = (u32)(Q >> 32), P0a, P1a, P0b, P1b, xo0, xo1;
-    const u32 kids = step_core_both((u32)P, (u32)(P >> 32), Q0, Q1, act, lut, P0a, P1a, P0b, P1b, xo0, xo1);   // mcts.py:245
-    u64 kidP[2], kidQ[2];
-    kidP[0] = (u64)P0a | ((u64)P1a << 32);
-    kidP[1] = (u64)P0b | ((u64)P1b << 32);
-    kidQ[0] = kidQ[1] = (u64)Q0 | ((u64)Q1 << 32);
-    store_stream(&c0P[i], kidP[0]); store_stream(&c0Q[i], kidQ[0]);
-    store_stream(&c1P[i], kidP[1]); store_stream(&c1Q[i], kidQ[1]);
-    expand_bookkeeping<PYKEY>(kids, kidP, kidQ, xo0, xo1, out, i, lut, htbl, ltbl);
+    const Expansion e = expand_pair(P, Q, pair_action<true>(a), lut);
+    store_stream(&c0P[i], e.P[0]); store_stream(&c0Q[i], e.Q);
+    store_stream(&c1P[i], e.P[1]); store_stream(&c1Q[i], e.Q);
+    expand_bookkeeping<PYKEY>(e, out, i, lut, htbl, ltbl);
 }
 
-// MCTS._simulate (mcts.py:185-198) under the uniform priors of mcts.py:287-292: play uniform-legal
-// random moves to the end with the board in registers.  Ply p uses the counter hash of
-// (seed, board id, step_idx0 + p) exactly like qttt_sample_actions + qttt_step would.
-// The launch keys of a playout's plies come from a table in LDS (splitmix64 of (seed, step index): 25 scalar instructions
-// per ply when the step index is wave-uniform, and ~30 VECTOR instructions per ply when it differs per lane — the
-// simulations of rollout_many / expand_rollout use step_idx0 + slot * QTTT_SIM_STRIDE + ply).  A table row = the nine keys
-// of one slot; PLAYOUT_KEY_SLOTS rows fit one key per thread of a 256-thread workgroup.  More slots than that: the keys are
-// computed in the loop (TABLE = false).
-constexpr u32 PLAYOUT_PLIES = 9u, PLAYOUT_KEY_SLOTS = 28u;
-template <int BLOCK>
-__device__ __forceinline__ void fill_playout_keys_nosync(u64 *keytab, u64 seed, u32 step_idx0, u32 n_slots) {
-    for (u32 k = threadIdx.x; k < n_slots * PLAYOUT_PLIES; k += BLOCK) {
-        const u32 slot = k / PLAYOUT_PLIES, ply = k - slot * PLAYOUT_PLIES;
-        keytab[k] = launch_key(seed, step_idx0 + slot * QTTT_SIM_STRIDE + ply);
-    }
-}
-// one playout of the board in (P0, P1, Q0, Q1) to the end; returns the number of plies played.  TABLE: `keys` = the nine
-// keys of this lane's slot (LDS); else they are launch_key(seed, step_idx0 + ply).
-template <bool TABLE>
-__device__ __forceinline__ u32 playout(u32 &P0, u32 &P1, u32 &Q0, u32 &Q1, u32 id, u64 seed, u32 step_idx0, const u64 *keys,
-                                       const uint8_t *lut, const uint8_t *plut, const uint8_t *nth9) {
-    u32 played = 0;
-    u64 key_tab = TABLE ? keys[0] : 0ull;
-    for (u32 p = 0; p < PLAYOUT_PLIES; ++p) {
-        const u32 empty = ~(P1 >> P1_CL_SHIFT) & 0x1FFu;
-        if ((P1 >> 31) || (empty & (empty - 1u)) == 0u) break;   // terminal (mcts.py:188) / nothing legal
-        const u64 key = TABLE ? key_tab : launch_key(seed, step_idx0 + p);
-        if (TABLE) key_tab = keys[p + 1u < PLAYOUT_PLIES ? p + 1u : p];      // the next ply's, requested a ply ahead
-        const u32 h1 = lowbias32(id ^ (u32)key);
-        const u32 h2 = lowbias32(h1 ^ (u32)(key >> 32));
-        const u32 act = policy_action_nth9(plut, nth9, empty, h2);   // the k-th legal pair, squares a < b
-        step_core<false, true>(P0, P1, Q0, Q1, act, h1 >> 31, lut);   // legal and sorted
-        played += 1u;
-    }
-    return played;
-}
-
+// MCTS._simulate (mcts.py:185-198) of every board: one playout() each (qttt_search_core.h), ply p on step index
+// step_idx0 + p.
 __global__ __launch_bounds__(QTTT_BLOCK) void rollout_kernel(
     const u64 *pP, const u64 *pQ, u64 seed, u32 step_idx0, u64 board_offset,
     int8_t *result, uint8_t *plies, u64 *fP, u64 *fQ, int64_t n) {
@@ -246,7 +187,7 @@ __global__ __launch_bounds__(QTTT_BLOCK) void rollout_kernel(
     const u64 oP = (u64)P0 | ((u64)P1 << 32), oQ = (u64)Q0 | ((u64)Q1 << 32);
     int w, t;
     lite_update_winner(lite_unpack(oP), lut, w, t);
-    result[i] = (int8_t)(w < 0 ? 0 : (w ? 1 : -1));       // MCTS._reward, mcts.py:200-209
+    result[i] = (int8_t)(w < 0 ? 0 : (w ? 1 : -1));       // reward_of_winner(w), spelled out: the helper reorders this kernel's last stores
     plies[i] = (uint8_t)played;
     if (fP) { fP[i] = oP; fQ[i] = oQ; }
 }
@@ -275,11 +216,10 @@ __global__ __launch_bounds__(QTTT_BLOCK) void rollout_many_kernel(
     if (j >= n_lanes) return;
     u32 P0 = (u32)P, P1 = (u32)(P >> 32), Q0 = (u32)Q, Q1 = (u32)(Q >> 32);
     const u32 id = fold_id(board_offset + (u64)i);
-    const u32 played = table ? playout<true>(P0, P1, Q0, Q1, id, seed, 0u, keytab + sim * PLAYOUT_PLIES, lut, plut, nth9)
-                             : playout<false>(P0, P1, Q0, Q1, id, seed, step_idx0 + sim * QTTT_SIM_STRIDE, nullptr, lut, plut, nth9);
+    const u32 played = playout_slot(P0, P1, Q0, Q1, id, seed, step_idx0, sim, table, keytab, lut, plut, nth9);
     int w, t;
     lite_update_winner(lite_unpack((u64)P0 | ((u64)P1 << 32)), lut, w, t);
-    result[j] = (int8_t)(w < 0 ? 0 : (w ? 1 : -1));
+    result[j] = (int8_t)reward_of_winner(w);
     if (plies) plies[j] = (uint8_t)played;
 }
 
@@ -327,30 +267,27 @@ __global__ __launch_bounds__(BLOCK) void expand_rollout_kernel(
     int r = 0;
     u32 kids = 0;
     if (valid) {
-        const u32 pr = a < 36u ? (u32)g_pair_lut.b[a] : 0u;
-        const u32 act = (pr & 0xFu) | ((pr >> 4) << 8);
-        u32 Q0 = (u32)Q, Q1 = (u32)(Q >> 32), P0a, P1a, P0b, P1b, xo0, xo1;
-        kids = step_core_both((u32)P, (u32)(P >> 32), Q0, Q1, act, lut, P0a, P1a, P0b, P1b, xo0, xo1);
+        // expand_pair(), spelled out: through the helper this kernel's instruction stream changes
+        u32 Q0 = (u32)Q, Q1 = (u32)(Q >> 32), P0a, P1a, P0b, P1b;
+        Expansion x;
+        x.kids = kids = step_core_both((u32)P, (u32)(P >> 32), Q0, Q1, pair_action<true>(a), lut, P0a, P1a, P0b, P1b, x.xo[0], x.xo[1]);
+        x.P[0] = (u64)P0a | ((u64)P1a << 32);
+        x.P[1] = (u64)P0b | ((u64)P1b << 32);
+        x.Q = (u64)Q0 | ((u64)Q1 << 32);
         if (rem == 0u) {                                        // this pair's writer
-            u64 kidP[2], kidQ[2];
-            kidP[0] = (u64)P0a | ((u64)P1a << 32);
-            kidP[1] = (u64)P0b | ((u64)P1b << 32);
-            kidQ[0] = kidQ[1] = (u64)Q0 | ((u64)Q1 << 32);
-            if (c0P) { c0P[i] = kidP[0]; c0Q[i] = kidQ[0]; }
-            if (c1P) { c1P[i] = kidP[1]; c1Q[i] = kidQ[1]; }
-            expand_bookkeeping<PYKEY>(kids, kidP, kidQ, xo0, xo1, out, i, lut, htbl, ltbl);
+            if (c0P) { c0P[i] = x.P[0]; c0Q[i] = x.Q; }
+            if (c1P) { c1P[i] = x.P[1]; c1Q[i] = x.Q; }
+            expand_bookkeeping<PYKEY>(x, out, i, lut, htbl, ltbl);
         }
         if (child < kids) {
             u32 P0 = child ? P0b : P0a, P1 = child ? P1b : P1a;
+            const u32 leaf_P1 = P1;
             const u32 slot = child * n_sims + sim, id = fold_id(board_offset + (u64)i);
-            if (table) playout<true>(P0, P1, Q0, Q1, id, seed, 0u, keytab + slot * PLAYOUT_PLIES, lut, plut, nth9);
-            else playout<false>(P0, P1, Q0, Q1, id, seed, step_idx0 + slot * QTTT_SIM_STRIDE, nullptr, lut, plut, nth9);
+            playout_slot(P0, P1, Q0, Q1, id, seed, step_idx0, slot, table, keytab, lut, plut, nth9);
             int w, t;
             lite_update_winner(lite_unpack((u64)P0 | ((u64)P1 << 32)), lut, w, t);
-            r = w < 0 ? 0 : (w ? 1 : -1);                       // MCTS._reward, mcts.py:200-209
-            // leaf.turn (mcts.py:174): the child has one real move more than the parent
-            const u32 child_real = ((child ? P1b : P1a) >> P1_N_SHIFT) & 0xFu;
-            if (r) atomicAdd(&acc[pl * 2u + child], (child_real & 1u) ? -r : r);
+            r = reward_of_winner(w);
+            if (r) atomicAdd(&acc[pl * 2u + child], leaf_turn_signed(r, leaf_P1));
         }
         if (result) result[(i * 2 + child) * (int64_t)n_sims + sim] = (int8_t)r;
     }
@@ -409,18 +346,17 @@ __global__ __launch_bounds__(BLOCK) void expand_rollout_jobs_kernel(
     // ---- 1. the expansions
     u32 kids = 0;
     if (valid) {
-        const u32 pr = a < 36u ? (u32)g_pair_lut.b[a] : 0u;
-        const u32 act = (pr & 0xFu) | ((pr >> 4) << 8);
-        u32 Q0 = (u32)Q, Q1 = (u32)(Q >> 32), P0a, P1a, P0b, P1b, xo0, xo1;
-        kids = step_core_both((u32)P, (u32)(P >> 32), Q0, Q1, act, lut, P0a, P1a, P0b, P1b, xo0, xo1);
-        u64 kidP[2], kidQ[2];
-        kidP[0] = (u64)P0a | ((u64)P1a << 32);
-        kidP[1] = (u64)P0b | ((u64)P1b << 32);
-        kidQ[0] = kidQ[1] = (u64)Q0 | ((u64)Q1 << 32);
-        kidPs[2u * t] = kidP[0]; kidPs[2u * t + 1u] = kidP[1]; kidQs[t] = kidQ[0];
-        if (c0P) { store_stream(&c0P[i], kidP[0]); store_stream(&c0Q[i], kidQ[0]); }
-        if (c1P) { store_stream(&c1P[i], kidP[1]); store_stream(&c1Q[i], kidQ[1]); }
-        expand_bookkeeping<PYKEY>(kids, kidP, kidQ, xo0, xo1, out, i, lut, htbl, ltbl);
+        // expand_pair(), spelled out: through the helper this kernel's instruction stream changes
+        u32 Q0 = (u32)Q, Q1 = (u32)(Q >> 32), P0a, P1a, P0b, P1b;
+        Expansion x;
+        x.kids = kids = step_core_both((u32)P, (u32)(P >> 32), Q0, Q1, pair_action<true>(a), lut, P0a, P1a, P0b, P1b, x.xo[0], x.xo[1]);
+        x.P[0] = (u64)P0a | ((u64)P1a << 32);
+        x.P[1] = (u64)P0b | ((u64)P1b << 32);
+        x.Q = (u64)Q0 | ((u64)Q1 << 32);
+        kidPs[2u * t] = x.P[0]; kidPs[2u * t + 1u] = x.P[1]; kidQs[t] = x.Q;
+        if (c0P) { store_stream(&c0P[i], x.P[0]); store_stream(&c0Q[i], x.Q); }
+        if (c1P) { store_stream(&c1P[i], x.P[1]); store_stream(&c1Q[i], x.Q); }
+        expand_bookkeeping<PYKEY>(x, out, i, lut, htbl, ltbl);
         if (result)                                             // children that do not exist: every simulation reads 0
             for (u32 c = kids; c < 2u; ++c)
                 for (u32 s = 0; s < n_sims; ++s) result[(i * 2 + c) * (int64_t)n_sims + s] = 0;
@@ -451,15 +387,12 @@ __global__ __launch_bounds__(BLOCK) void expand_rollout_jobs_kernel(
         const u32 e = unit_tbl[u], pl = e >> 1, child = e & 1u;
         const u64 cP = kidPs[e], cQ = kidQs[pl];
         u32 P0 = (u32)cP, P1 = (u32)(cP >> 32), Q0 = (u32)cQ, Q1 = (u32)(cQ >> 32);
-        const u32 child_real = (P1 >> P1_N_SHIFT) & 0xFu;
+        const u32 leaf_P1 = P1;
         const int64_t ip = base + pl;
         const u32 slot = child * n_sims + sim, id = fold_id(board_offset + (u64)ip);
-        if (table) playout<true>(P0, P1, Q0, Q1, id, seed, 0u, keytab + slot * PLAYOUT_PLIES, lut, plut, nth9);
-        else playout<false>(P0, P1, Q0, Q1, id, seed, step_idx0 + slot * QTTT_SIM_STRIDE, nullptr, lut, plut, nth9);
-        int w, tm;
-        lite_update_winner(lite_unpack((u64)P0 | ((u64)P1 << 32)), lut, w, tm);
-        const int r = w < 0 ? 0 : (w ? 1 : -1);                 // MCTS._reward, mcts.py:200-209
-        if (r) atomicAdd(&acc[e], (child_real & 1u) ? -r : r);  // leaf.turn (mcts.py:174)
+        playout_slot(P0, P1, Q0, Q1, id, seed, step_idx0, slot, table, keytab, lut, plut, nth9);
+        const int r = playout_reward((u64)P0 | ((u64)P1 << 32), lut);
+        if (r) atomicAdd(&acc[e], leaf_turn_signed(r, leaf_P1));
         if (result) result[(ip * 2 + child) * (int64_t)n_sims + sim] = (int8_t)r;
     }
     __syncthreads();

@@ -2,7 +2,8 @@
 // (board, simulation) lanes in ONE launch: every ply runs Model.forward(node.to_vector()) (get_action_probs, :294-300),
 // samples an action from Categorical(logits) (sample_action, :302-303) and one collapse child (:202), until the game
 // ends.  The network part is evaluate_kernel's (qttt_nn_kernels.h: the same encode, trunk, head, mask and softmax
-// functions on the same tile mapping); the step is playout()'s (qttt_mcts_kernels.h).
+// functions on the same tile mapping); the draw, the stopping rule, the step and the reward are the uniform playout's
+// (qttt_search_core.h).
 //
 // Mapping: a 256-thread workgroup owns a tile of M lanes (64 f32 / 128 bf16), lane j = i * n_sims + s
 // plays simulation s of board i (rollout_many_kernel's order).  The tile's packed states stay in LDS for the whole launch
@@ -15,15 +16,9 @@
 #ifndef QTTT_POLICY_ROLLOUT_KERNELS_H
 #define QTTT_POLICY_ROLLOUT_KERNELS_H
 #include "qttt_nn_kernels.h"
-#include "qttt_mcts_kernels.h"
+#include "qttt_search_core.h"
 
 namespace {
-
-// playout()'s stopping rule: the done bit, or fewer than two empty squares (nothing legal; mcts.py:188)
-__device__ __forceinline__ bool policy_lane_live(u32 P1) {
-    const u32 empty = ~(P1 >> P1_CL_SHIFT) & 0x1FFu;
-    return !(P1 >> 31) && (empty & (empty - 1u)) != 0u;
-}
 
 // Categorical(logits).sample() by inverse CDF on the head row o with legal mask lm (not empty) and nn_softmax_stats' max
 // and exp-sum: the smallest legal a whose running sum of expf(o[a] - mx), in ascending action order (the order of `sum`),
@@ -83,7 +78,7 @@ __global__ __launch_bounds__(QTTT_NN_BLOCK) void rollout_policy_kernel(
         sQ[tid] = Q;
         id = fold_id(board_offset + (u64)board);
         t0 = step_idx0 + sim * QTTT_SIM_STRIDE;
-        alive = policy_lane_live(P1);
+        alive = playout_live(P1);
     }
     fill_line_lut<QTTT_NN_BLOCK>(lut);                          // ends with the workgroup barrier
     float *O = reinterpret_cast<float *>(H);
@@ -118,17 +113,14 @@ __global__ __launch_bounds__(QTTT_NN_BLOCK) void rollout_policy_kernel(
                 if (leaf_value && sim == 0u) leaf_value[board] = o[36];
             }
             if (alive) {
-                const u64 key = launch_key(seed, t0 + p);
-                const u32 h1 = lowbias32(id ^ (u32)key);
-                const u32 h2 = lowbias32(h1 ^ (u32)(key >> 32));
-                const u32 a = nn_sample_action(o, lm, mx, sum, h2), bit = h1 >> 31;
-                const u32 pr = (u32)g_pair_lut.b[a];
-                step_core<false, true>(P0, P1, Q0, Q1, (pr & 0xFu) | ((pr >> 4) << 8), bit, lut);   // legal and sorted
+                const Draw d = counter_draw(id, launch_key(seed, t0 + p));
+                const u32 a = nn_sample_action(o, lm, mx, sum, d.h2), bit = d.h1 >> 31;
+                step_core<false, true>(P0, P1, Q0, Q1, pair_action<false>(a), bit, lut);   // legal and sorted
                 if (trace) trace[j * PLAYOUT_PLIES + p] = (uint8_t)(a | bit << 6);
                 played += 1u;
                 sP[tid] = (u64)P0 | ((u64)P1 << 32);
                 sQ[tid] = (u64)Q0 | ((u64)Q1 << 32);
-                alive = policy_lane_live(P1);
+                alive = playout_live(P1);
             }
         }
         if (p == 0u && leaf_probs) {                            // evaluate_kernel's probs rows, for the s == 0 lanes
@@ -146,7 +138,7 @@ __global__ __launch_bounds__(QTTT_NN_BLOCK) void rollout_policy_kernel(
     if (!owner) return;
     int w, t;
     lite_update_winner(lite_unpack((u64)P0 | ((u64)P1 << 32)), lut, w, t);
-    result[j] = (int8_t)(w < 0 ? 0 : (w ? 1 : -1));             // AlphaZero._reward (alphazero.py:207-215)
+    result[j] = (int8_t)reward_of_winner(w);
     if (plies) plies[j] = (uint8_t)played;
     if (trace)
         for (u32 p = played; p < PLAYOUT_PLIES; ++p) trace[j * PLAYOUT_PLIES + p] = 0xFFu;

@@ -11,7 +11,7 @@
 #define QTTT_TREE_KERNELS_H
 #include "qttt_step_core.h"
 #include "qttt_board_forms.h"
-#include "qttt_mcts_kernels.h"
+#include "qttt_search_core.h"
 #include "qttt_tree.h"
 
 namespace {
@@ -77,17 +77,21 @@ __constant__ UniformPriors g_uniform_priors = UniformPriors();
 // tests/test_tree_gpu.py checks it for every Ntot below QTTT_TREE_MAX_ROLLOUTS against the host's sqrt.
 __device__ __forceinline__ double tree_sqrt(u32 ntot) { return __builtin_sqrt((double)ntot); }
 
-// the node record of a position: GameState's bookkeeping (mcts.py:20-27,52-65) from the packed state
+// a fresh node's record from GameState's bookkeeping (mcts.py:20-27,52-65): winner w, terminal t, the legal-action mask
+__device__ __forceinline__ TreeNodeHdr tree_node(u64 P, u64 Q, bool turn, int w, int t, u64 legal) {
+    TreeNodeHdr h;
+    h.P = P; h.Q = Q;
+    h.legal = legal;
+    h.Ntot = 0;
+    h.flags = (t ? TN_TERMINAL : 0u) | (turn ? TN_TURN : 0u) | ((u32)(w + 1) << 8);
+    return h;
+}
+// the node record of a position given as its packed state alone
 __device__ __forceinline__ TreeNodeHdr tree_node_of(u64 P, u64 Q, bool turn, const uint8_t *lut) {
     const Lite s = lite_unpack(P);
     int w, t;
     lite_update_winner(s, lut, w, t);
-    TreeNodeHdr h;
-    h.P = P; h.Q = Q;
-    h.legal = legal_mask_of(s.cl);
-    h.Ntot = 0;
-    h.flags = (t ? TN_TERMINAL : 0u) | (turn ? TN_TURN : 0u) | ((u32)(w + 1) << 8);
-    return h;
+    return tree_node(P, Q, turn, w, t, legal_mask_of(s.cl));
 }
 
 // a fresh node: header (by lane `writer`) and 36 empty slots (lanes 0..35)
@@ -181,10 +185,9 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_select_kernel(void *tree, int
             continue;
         }
         // _expand_child (mcts.py:210-221): both collapse children at once, as qttt_expand
-        const u32 pr = (u32)g_pair_lut.b[a];
-        const u32 act = (pr & 0xFu) | ((pr >> 4) << 8);
+        // expand_pair(), spelled out: through the helper this kernel's instruction stream changes
         u32 Q0 = (u32)h.Q, Q1 = (u32)(h.Q >> 32), P0a, P1a, P0b, P1b, xo0, xo1;
-        const u32 kids = step_core_both((u32)h.P, (u32)(h.P >> 32), Q0, Q1, act, lut, P0a, P1a, P0b, P1b, xo0, xo1);
+        const u32 kids = step_core_both((u32)h.P, (u32)(h.P >> 32), Q0, Q1, pair_action<false>(a), lut, P0a, P1a, P0b, P1b, xo0, xo1);
         if (kids == 0u || (int64_t)used + kids > capacity) {     // cannot happen for a legal action / does not fit
             overflow = kids == 0u ? 0u : TG_OVERFLOW;
             break;
@@ -194,15 +197,10 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_select_kernel(void *tree, int
         const u64 kidP[2] = {(u64)P0a | ((u64)P1a << 32), (u64)P0b | ((u64)P1b << 32)};
         const u32 xo[2] = {xo0, xo1};
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {                            // expand_bookkeeping's winner / terminal / legal rules
+        for (int k = 0; k < 2; ++k) {
             int w, t;
             update_winner_from_step(kidP[k], xo[k], lut, w, t);
-            const u32 cl = (u32)(kidP[k] >> (32u + P1_CL_SHIFT)) & 0x1FFu;
-            c[k].P = kidP[k];
-            c[k].Q = (u64)Q0 | ((u64)Q1 << 32);
-            c[k].legal = legal_mask_of(__builtin_popcount(cl) == 8 ? 0x1FFu : cl);
-            c[k].Ntot = 0u;
-            c[k].flags = (t ? TN_TERMINAL : 0u) | (turn ? TN_TURN : 0u) | ((u32)(w + 1) << 8);
+            c[k] = tree_node(kidP[k], (u64)Q0 | ((u64)Q1 << 32), turn, w, t, legal_mask_of(classical_with_autofill(kidP[k])));
         }
         tree_write_node(v, g, used, c[0], lane, 0u);
         if (kids == 2u) tree_write_node(v, g, used + 1, c[1], lane, 1u);

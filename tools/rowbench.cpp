@@ -86,8 +86,8 @@ __global__ __launch_bounds__(BLOCK) void step_random_fused2_kernel(
         u32 act[2], win[2];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const u32 h1 = lowbias32(id[k] ^ (u32)key);
-            const u32 h2 = lowbias32(h1 ^ (u32)(key >> 32));
+            const Draw d = counter_draw(id[k], key);
+            const u32 h1 = d.h1, h2 = d.h2;
             const u32 keep = ~(u32)((int)P1[k] >> 31);
             P0[k] &= keep; P1[k] &= keep; Q0[k] &= keep; Q1[k] &= keep;
             const u32 empty = ~(P1[k] >> P1_CL_SHIFT) & 0x1FFu;

@@ -49,21 +49,16 @@ __global__ __launch_bounds__(BLOCK) void xr_ksims_kernel(const u64 *pP, const u6
     fill_playout_keys_nosync<BLOCK>(keytab, seed, step_idx0, 2u * n_sims);
     fill_line_lut<BLOCK>(lut);
     if (valid) {
-        const u32 pr = a < 36u ? (u32)g_pair_lut.b[a] : 0u;
-        const u32 act = (pr & 0xFu) | ((pr >> 4) << 8);
-        u32 Q0 = (u32)Q, Q1 = (u32)(Q >> 32), P0a, P1a, P0b, P1b, xo0, xo1;
-        const u32 kids = step_core_both((u32)P, (u32)(P >> 32), Q0, Q1, act, lut, P0a, P1a, P0b, P1b, xo0, xo1);
+        const Expansion e = expand_pair(P, Q, pair_action<true>(a), lut);
+        const u32 kids = e.kids, Q0 = (u32)e.Q, Q1 = (u32)(e.Q >> 32);
         if (child < kids) {
-            const u32 cP0 = child ? P0b : P0a, cP1 = child ? P1b : P1a, id = fold_id(board_offset + (u64)i);
-            const u32 child_real = (cP1 >> P1_N_SHIFT) & 0xFu;
+            const u64 cP = child ? e.P[1] : e.P[0];
+            const u32 cP0 = (u32)cP, cP1 = (u32)(cP >> 32), id = fold_id(board_offset + (u64)i);
             int sum = 0;
             for (u32 s = grp * KS; s < grp * KS + KS && s < n_sims; ++s) {
                 u32 P0 = cP0, P1 = cP1, q0 = Q0, q1 = Q1;
-                playout<true>(P0, P1, q0, q1, id, seed, 0u, keytab + (child * n_sims + s) * PLAYOUT_PLIES, lut, plut, nth9);
-                int w, t;
-                lite_update_winner(lite_unpack((u64)P0 | ((u64)P1 << 32)), lut, w, t);
-                const int r = w < 0 ? 0 : (w ? 1 : -1);
-                sum += (child_real & 1u) ? -r : r;
+                playout_slot(P0, P1, q0, q1, id, seed, step_idx0, child * n_sims + s, true, keytab, lut, plut, nth9);
+                sum += leaf_turn_signed(playout_reward((u64)P0 | ((u64)P1 << 32), lut), cP1);
             }
             if (sum) atomicAdd(&acc[pl * 2u + child], sum);
         }
@@ -102,12 +97,10 @@ __global__ __launch_bounds__(BLOCK) void xr_jobs_kernel(const u64 *pP, const u64
     fill_line_lut<BLOCK>(lut);
     u32 kids = 0;
     if (valid) {
-        const u32 pr = a < 36u ? (u32)g_pair_lut.b[a] : 0u;
-        const u32 act = (pr & 0xFu) | ((pr >> 4) << 8);
-        u32 Q0 = (u32)Q, Q1 = (u32)(Q >> 32), P0a, P1a, P0b, P1b, xo0, xo1;
-        kids = step_core_both((u32)P, (u32)(P >> 32), Q0, Q1, act, lut, P0a, P1a, P0b, P1b, xo0, xo1);
-        kidPs[2u * t] = (u64)P0a | ((u64)P1a << 32); kidPs[2u * t + 1u] = (u64)P0b | ((u64)P1b << 32);
-        kidQs[t] = (u64)Q0 | ((u64)Q1 << 32);
+        const Expansion x = expand_pair(P, Q, pair_action<true>(a), lut);
+        kids = x.kids;
+        kidPs[2u * t] = x.P[0]; kidPs[2u * t + 1u] = x.P[1];
+        kidQs[t] = x.Q;
     }
     u32 incl = kids;
 #pragma unroll
@@ -134,19 +127,17 @@ __global__ __launch_bounds__(BLOCK) void xr_jobs_kernel(const u64 *pP, const u64
             const u32 e = unit_tbl[u], pl = e >> 1, child = e & 1u;
             const u64 cP = kidPs[e], cQ = kidQs[pl];
             u32 P0 = (u32)cP, P1 = (u32)(cP >> 32), Q0 = (u32)cQ, Q1 = (u32)(cQ >> 32);
-            const u32 child_real = (P1 >> P1_N_SHIFT) & 0xFu;
-            playout<true>(P0, P1, Q0, Q1, fold_id(board_offset + (u64)(base + pl)), seed, 0u,
-                          keytab + (child * n_sims + sim) * PLAYOUT_PLIES, lut, plut, nth9);
-            int w, tm;
-            lite_update_winner(lite_unpack((u64)P0 | ((u64)P1 << 32)), lut, w, tm);
-            const int r = w < 0 ? 0 : (w ? 1 : -1);
-            if (r) atomicAdd(&acc[e], (child_real & 1u) ? -r : r);
+            const u32 leaf_P1 = P1;
+            playout_slot(P0, P1, Q0, Q1, fold_id(board_offset + (u64)(base + pl)), seed, step_idx0, child * n_sims + sim, true,
+                         keytab, lut, plut, nth9);
+            const int r = playout_reward((u64)P0 | ((u64)P1 << 32), lut);
+            if (r) atomicAdd(&acc[e], leaf_turn_signed(r, leaf_P1));
         }
     } else {
         // one ply loop: `ply` counts the plies of the CURRENT job; a lane that ends a playout finishes it and takes its
         // next job in the same trip.  Exit: every lane's job index runs past `jobs` (each trip either plays a ply of a
         // playout of at most nine plies or advances j by BLOCK: at most ceil(jobs / BLOCK) * 10 trips).
-        u32 j = t, ply = 0, P0 = 0, P1 = 0, Q0 = 0, Q1 = 0, e = 0, id = 0, child_real = 0;
+        u32 j = t, ply = 0, P0 = 0, P1 = 0, Q0 = 0, Q1 = 0, e = 0, id = 0, leaf_P1 = 0;
         const u64 *keys = keytab;
         bool active = j < jobs;
         auto take = [&]() {
@@ -155,7 +146,7 @@ __global__ __launch_bounds__(BLOCK) void xr_jobs_kernel(const u64 *pP, const u64
             const u32 pl = e >> 1, child = e & 1u;
             const u64 cP = kidPs[e], cQ = kidQs[pl];
             P0 = (u32)cP; P1 = (u32)(cP >> 32); Q0 = (u32)cQ; Q1 = (u32)(cQ >> 32);
-            child_real = (P1 >> P1_N_SHIFT) & 0xFu;
+            leaf_P1 = P1;
             id = fold_id(board_offset + (u64)(base + pl));
             keys = keytab + (child * n_sims + sim) * PLAYOUT_PLIES;
             ply = 0;
@@ -163,23 +154,17 @@ __global__ __launch_bounds__(BLOCK) void xr_jobs_kernel(const u64 *pP, const u64
         if (active) take();
         while (__builtin_amdgcn_ballot_w64(active) != 0ull) {
             if (active) {
-                u32 empty = ~(P1 >> P1_CL_SHIFT) & 0x1FFu;
-                bool over = (P1 >> 31) || (empty & (empty - 1u)) == 0u || ply >= PLAYOUT_PLIES;
+                bool over = !playout_live(P1) || ply >= PLAYOUT_PLIES;
                 if (!over) {
-                    const u64 key = keys[ply];
-                    const u32 h1 = lowbias32(id ^ (u32)key);
-                    const u32 h2 = lowbias32(h1 ^ (u32)(key >> 32));
-                    const u32 act = policy_action_nth9(plut, nth9, empty, h2);
-                    step_core<false, true>(P0, P1, Q0, Q1, act, h1 >> 31, lut);
+                    const Draw d = counter_draw(id, keys[ply]);
+                    const u32 act = policy_action_nth9(plut, nth9, ~(P1 >> P1_CL_SHIFT) & 0x1FFu, d.h2);
+                    step_core<false, true>(P0, P1, Q0, Q1, act, d.h1 >> 31, lut);
                     ++ply;
-                    empty = ~(P1 >> P1_CL_SHIFT) & 0x1FFu;
-                    over = (P1 >> 31) || (empty & (empty - 1u)) == 0u || ply >= PLAYOUT_PLIES;
+                    over = !playout_live(P1) || ply >= PLAYOUT_PLIES;
                 }
                 if (over) {
-                    int w, tm;
-                    lite_update_winner(lite_unpack((u64)P0 | ((u64)P1 << 32)), lut, w, tm);
-                    const int r = w < 0 ? 0 : (w ? 1 : -1);
-                    if (r) atomicAdd(&acc[e], (child_real & 1u) ? -r : r);
+                    const int r = playout_reward((u64)P0 | ((u64)P1 << 32), lut);
+                    if (r) atomicAdd(&acc[e], leaf_turn_signed(r, leaf_P1));
                     j += BLOCK;
                     active = j < jobs;
                     if (active) take();
