@@ -10,8 +10,10 @@
  *
  * Buffer layout (all little-endian, byte offsets):
  *   game header g at 128 g, 128 B:  i32 used (nodes allocated) | i32 root | i32 depth (path length of the last select)
- *                                   | i32 leaf | u32 flags (bit 0 overflow, 1 leaf turn, 2 leaf terminal) | 12 B 0
- *                                   | i32 path_node[10] at 32 | u8 path_action[10] at 72 | 0 to 128
+ *                                   | i32 leaf | u32 flags (bit 0 overflow, 1 leaf turn, 2 leaf terminal) | 12 B padding
+ *                                   | i32 path_node[10] at 32 | u8 path_action[10] at 72 | padding to 128
+ *                                   (no entry writes the padding, and a select writes only the first `depth` path
+ *                                   entries: those bytes keep what the caller's buffer held)
  *   node i of game g at 128 games + QTTT_TREE_NODE_BYTES (g capacity + i), 608 B:
  *     header 32 B:  u64 P, u64 Q (the packed state, planes P / Q of the state layout) | u64 legal (bit a = action a)
  *                   | u32 Ntot | u32 flags (bit 0 has priors, 1 uniform priors, 2 terminal, 3 turn (True = the first
@@ -30,7 +32,8 @@
  *
  * Exactness: W, Q and the selection score are IEEE doubles in the reference's order of operations, without
  * contraction: score = Q + c_puct * ((P * sqrt(Ntot)) / (1 + N)), Q = W / N (0 while N = 0), argmax over the legal
- * actions with ties to the lowest action.  qttt_tree_sqrt exports the select kernel's sqrt(Ntot).
+ * actions with ties to the lowest action.  qttt_tree_sqrt exports the select kernel's sqrt(Ntot) and
+ * qttt_tree_score its score.
  *
  * Errors, in this order, before any device work: QTTT_ERR_SIZE for games < 0, capacity outside
  * 1..QTTT_TREE_MAX_CAPACITY (qttt_tree_bytes returns it too), board_offset < 0, rollout_idx >= QTTT_TREE_MAX_ROLLOUTS,
@@ -89,6 +92,13 @@ int qttt_tree_root(const void *tree, int64_t games, int64_t capacity, int32_t *N
 
 /* out[i] = the select kernel's sqrt((double)(first + i)), i < n (so that its rounding can be checked). */
 int qttt_tree_sqrt(uint32_t first, int64_t n, double *out, void *stream);
+
+/* out[i] = the select kernel's score of an action with statistics W[i], N[i], prior[i] in a node with Ntot[i] visits,
+ * i < n (so that its order of operations can be checked bit for bit).  Errors as qttt_tree_sqrt: QTTT_ERR_SIZE for
+ * n < 0; 0 for n == 0; QTTT_ERR_NULL for a null array; QTTT_ERR_ACTION for W / prior / out not 8-byte or N / Ntot not
+ * 4-byte aligned. */
+int qttt_tree_score(const double *W, const uint32_t *N, const double *prior, const uint32_t *Ntot, double c_puct,
+                    int64_t n, double *out, void *stream);
 
 #ifdef __cplusplus
 }

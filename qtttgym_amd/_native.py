@@ -91,6 +91,7 @@ TREE_SIGNATURES = {
     "qttt_tree_sync": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "qttt_tree_root": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qttt_tree_sqrt": (_i32, [_u32, _i64, _vp, _vp]),
+    "qttt_tree_score": (_i32, [_vp, _vp, _vp, _vp, _f64, _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -676,4 +676,14 @@ int qttt_tree_sqrt(uint32_t first, int64_t n, double *out, void *stream) {
     return launch(tree_sqrt_kernel, ceil_div(n, 256), 256, stream, first, n, out);
 }
 
+int qttt_tree_score(const double *W, const uint32_t *N, const double *prior, const uint32_t *Ntot, double c_puct,
+                    int64_t n, double *out, void *stream) {
+    if (n < 0) return QTTT_ERR_SIZE;
+    if (n == 0) return 0;
+    if (any_null(W, N, prior, Ntot, out)) return QTTT_ERR_NULL;
+    if (misaligned(W, 8) || misaligned(prior, 8) || misaligned(out, 8) || misaligned(N, 4) || misaligned(Ntot, 4))
+        return QTTT_ERR_ACTION;
+    return launch(tree_score_kernel, ceil_div(n, 256), 256, stream, W, N, prior, Ntot, c_puct, n, out);
+}
+
 }  // extern "C"

@@ -349,6 +349,12 @@ __global__ __launch_bounds__(256) void tree_sqrt_kernel(u32 first, int64_t n, do
     if (i < n) out[i] = tree_sqrt(first + (u32)i);
 }
 
+__global__ __launch_bounds__(256) void tree_score_kernel(const double *W, const u32 *N, const double *prior, const u32 *Ntot,
+                                                         double c_puct, int64_t n, double *out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = tree_score(W[i], N[i], prior[i], tree_sqrt(Ntot[i]), c_puct);
+}
+
 }  // namespace
 
 #endif  // QTTT_TREE_KERNELS_H

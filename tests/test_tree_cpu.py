@@ -73,7 +73,7 @@ def _declared(path):
 def test_binding_header_exports_and_integration_md_agree():
     from qtttgym_amd import _native
     names = _declared(HEADER)
-    assert names == set(_native.TREE_SIGNATURES) and len(names) == 7
+    assert names == set(_native.TREE_SIGNATURES) and len(names) == 8
     lib = ctypes.CDLL(_native.LIB_PATH)
     for n in names:
         assert hasattr(lib, n), n
@@ -111,6 +111,7 @@ def test_return_codes_in_documented_order_without_device_work():
     assert L.qttt_tree_sync(None, -5, 8, None, None) == ERR_SIZE
     assert L.qttt_tree_root(None, 1, -1, *([None] * 8), None) == ERR_SIZE
     assert L.qttt_tree_sqrt(0, -1, None, None) == ERR_SIZE
+    assert L.qttt_tree_score(None, None, None, None, 1.0, -1, None, None) == ERR_SIZE
     # games == 0: nothing to do, no pointer looked at
     assert L.qttt_tree_reset(None, 0, 1, None, None) == 0
     assert L.qttt_tree_select(None, 0, 1, 0, 0, 0, 1.0, None, None) == 0
@@ -118,6 +119,7 @@ def test_return_codes_in_documented_order_without_device_work():
     assert L.qttt_tree_sync(None, 0, 1, None, None) == 0
     assert L.qttt_tree_root(None, 0, 1, *([None] * 8), None) == 0
     assert L.qttt_tree_sqrt(0, 0, None, None) == 0
+    assert L.qttt_tree_score(None, None, None, None, 1.0, 0, None, None) == 0
     # then null pointers
     assert L.qttt_tree_reset(None, 1, 1, fake, None) == ERR_NULL
     assert L.qttt_tree_reset(fake, 1, 1, None, None) == ERR_NULL
@@ -126,6 +128,10 @@ def test_return_codes_in_documented_order_without_device_work():
     assert L.qttt_tree_sync(fake, 1, 1, None, None) == ERR_NULL
     assert L.qttt_tree_root(None, 1, 1, *([None] * 8), None) == ERR_NULL
     assert L.qttt_tree_sqrt(0, 1, None, None) == ERR_NULL
+    for k in range(5):                      # W, N, prior, Ntot, out: each required, looked at before any alignment
+        args = [fake + 1] * 5
+        args[k] = None
+        assert L.qttt_tree_score(*args[:4], 1.0, 1, args[4], None) == ERR_NULL, k
     # then alignment
     assert L.qttt_tree_reset(fake + 8, 1, 1, fake, None) == ERR_ACTION
     assert L.qttt_tree_select(fake + 4, 1, 1, 0, 0, 0, 1.0, fake, None) == ERR_ACTION
@@ -141,6 +147,10 @@ def test_return_codes_in_documented_order_without_device_work():
             continue
         assert L.qttt_tree_root(fake, 1, 1, *args, None) == ERR_ACTION, k
     assert L.qttt_tree_sqrt(0, 1, fake + 4, None) == ERR_ACTION
+    for k in range(5):
+        args = [fake] * 5
+        args[k] = fake + (2 if k in (1, 3) else 4)       # N, Ntot: 4-byte; W, prior, out: 8-byte
+        assert L.qttt_tree_score(*args[:4], 1.0, 1, args[4], None) == ERR_ACTION, k
 
 
 def test_python_bounds_raise_before_any_launch():
@@ -175,3 +185,63 @@ def test_uniform_prior_and_sqrt_rounding_on_the_host_side():
     import math
     assert all(1 / k == float(np.float64(1.0) / np.float64(k)) for k in range(1, 37))
     assert math.sqrt(2) == float(np.sqrt(np.float64(2)))
+
+
+def _game_view(d):
+    """One game of TreeModel.dump() as plain values that compare with == (the records as bytes)."""
+    return (d["used"], d["root"], d["path"], d["leaf"],
+            [(n["rec"].tobytes(), n["turn"], n["terminal"], n["winner"], n["legal"], n["Ntot"], n["N"], n["W"],
+              n["children"], n["P"]) for n in d["nodes"]])
+
+
+@pytest.mark.parametrize("capacity", [1, 2, 3, 8])
+def test_model_with_capacity_diverges_exactly_at_the_first_expansion_that_does_not_fit(capacity):
+    """include/qttt_tree.h's overflow rule in the model: TreeModel(capacity=c) is TreeModel() until, per game, the first
+    expansion whose nodes do not fit; that select ends on the node it stood on, without the edge, nothing is allocated,
+    and the flag stays."""
+    import tree_model
+    grp = tree_model.golden_groups(GOLDEN)[0]
+    roots = tree_model._batch(list(grp["roots"].b[:12]), grp["roots"].b.dtype)
+    kw = dict(seed=grp["seed"], board_offset=grp["offset"])
+    free, capped = tree_model.TreeModel(grp["n_sims"], **kw), tree_model.TreeModel(grp["n_sims"], capacity=capacity, **kw)
+    free.reset(roots)
+    capped.reset(roots)
+    assert not capped.root_stats()["overflow"].any()
+    diverged = [False] * roots.n
+    for k in range(10):
+        before = free.dump()
+        lf, lc = free.select(), capped.select()
+        a, b = free.dump(), capped.dump()
+        for g in range(roots.n):
+            if diverged[g]:
+                assert b[g]["overflow"] and b[g]["used"] <= capacity          # sticky, and never past the pool
+                continue
+            if a[g]["used"] <= capacity:                                      # the expansion (if any) fits
+                assert not b[g]["overflow"] and _game_view(a[g]) == _game_view(b[g]), (k, g)
+                assert lf.b[g].tobytes() == lc.b[g].tobytes()
+                continue
+            # the first expansion that does not fit: the path loses its last edge, the leaf is that edge's node
+            diverged[g] = True
+            assert b[g]["overflow"] and b[g]["used"] == before[g]["used"], (k, g)
+            assert b[g]["path"] == a[g]["path"][:-1] and b[g]["leaf"] == a[g]["path"][-1][0], (k, g)
+            assert b[g]["nodes"][b[g]["leaf"]]["P"] is not None
+            # nothing but the path and the flag changed in that game
+            assert _game_view(b[g])[4] == _game_view(before[g])[4], (k, g)
+        free.backup(free.playouts(lf))
+        capped.backup(capped.playouts(lc))
+    assert any(diverged) and capped.root_stats()["overflow"].tolist() == diverged
+    # a sync: a fresh root that does not fit sets the flag and leaves the root; reset clears it
+    full = [g for g in range(roots.n) if capped.dump()[g]["used"] == capacity]
+    st0 = capped.root_stats()
+    lmask = [[a for a in range(36) if st0["N"][g, a] == 0 and a in capped.games[g]["nodes"][capped.games[g]["root"]].legal]
+             for g in range(roots.n)]
+    act = np.array([lm[-1] if lm else 255 for lm in lmask], dtype=np.uint8)      # a never-visited action: no child
+    new, _ = tree_model.after_move(_positions(capped), act, np.zeros(roots.n, np.uint8))
+    roots_before = [st["root"] for st in capped.games]
+    capped.sync(new)
+    d = capped.dump()
+    for g in full:
+        if act[g] != 255:
+            assert d[g]["overflow"] and d[g]["root"] == roots_before[g] and d[g]["used"] == capacity, g
+    capped.reset(roots)
+    assert not capped.root_stats()["overflow"].any()

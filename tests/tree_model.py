@@ -1,10 +1,15 @@
 """A float64 Python restatement of the batched search tree of include/qttt_tree.h (qtttgym_amd.TreeSearch), built on the
 C oracle's expand / rollout / counter hash.  Test infrastructure: tests/test_tree_cpu.py ties it to the reference's own
-MCTS class (tests/golden/tree_traces.npz), tests/test_tree_gpu.py runs the device in lockstep with it.
+MCTS class (tests/golden/tree_traces.npz), tests/test_tree_gpu.py and tests/test_tree_whole_gpu.py run the device in
+lockstep with it.
 
 Per game a plain list of nodes (the reference's node dict never merges two paths: its keys hold the full move
 history).  The arithmetic is the reference's, in Python floats: score = Q + c_puct * (P * sqrt(Ntot) / (1 + N)),
 W += r, Q = W / N.
+
+TreeModel(capacity=c) also restates the header's overflow rule: an expansion (in select) or a fresh root (in sync) that
+does not fit c nodes sets the game's sticky overflow flag and allocates nothing.  Node indices equal the device's: child
+0 at `used`, child 1 at `used + 1`, a fresh root appended.
 """
 import math
 
@@ -38,24 +43,26 @@ def position_key(rec):
 
 
 class Node:
-    __slots__ = ("rec", "turn", "terminal", "legal", "Ntot", "N", "W", "P", "children")
+    __slots__ = ("rec", "turn", "terminal", "winner", "legal", "Ntot", "N", "W", "P", "probs", "children")
 
     def __init__(self, rec, turn):
         self.rec = rec
         ob = _one(rec)
         w, t, legal, _ = oracle.node_info(ob)
-        self.turn, self.terminal = bool(turn), bool(t[0])
+        self.turn, self.terminal, self.winner = bool(turn), bool(t[0]), int(w[0])
         self.legal = [a for a in range(36) if (int(legal[0]) >> a) & 1]
         self.Ntot = 0
         self.N = [0] * 36
         self.W = [0.0] * 36
         self.P = None
+        self.probs = None             # the network's f32[36] row behind P (None: no priors yet, or uniform ones)
         self.children = [None] * 36
 
 
 class TreeModel:
-    def __init__(self, n_sims, seed=0, board_offset=0, c_puct=1.0):
+    def __init__(self, n_sims, seed=0, board_offset=0, c_puct=1.0, capacity=None):
         self.n_sims, self.seed, self.board_offset, self.c_puct = int(n_sims), int(seed), int(board_offset), float(c_puct)
+        self.capacity = None if capacity is None else int(capacity)       # None: the pool always fits
         self.games = []
         self.k = 0
 
@@ -66,7 +73,7 @@ class TreeModel:
         for g in range(ob.n):
             rec = ob.b[g].copy()
             root = Node(rec, int(rec["n_moves"]) % 2 == 0)
-            self.games.append({"nodes": [root], "root": 0, "path": [], "leaf": 0})
+            self.games.append({"nodes": [root], "root": 0, "path": [], "leaf": 0, "overflow": False})
         self.k = 0
 
     def _score(self, node, a):
@@ -88,6 +95,9 @@ class TreeModel:
                 a = max(node.legal, key=lambda x: self._score(node, x))      # first maximum, as Python's max
                 if node.children[a] is None:
                     nch, kids, _, _, _, _ = oracle.expand(_one(node.rec), np.array([a], dtype=np.uint8))
+                    if self.capacity is not None and len(nodes) + int(nch[0]) > self.capacity:
+                        st["overflow"] = True      # does not fit: the select ends here, this edge is not on the path
+                        break
                     node.children[a] = []
                     for c in range(int(nch[0])):
                         nodes.append(Node(kids[c].b[0].copy(), not node.turn))
@@ -129,6 +139,7 @@ class TreeModel:
                     leaf.P = {a: 1 / len(leaf.legal) for a in leaf.legal}
                 else:
                     leaf.P = {a: float(np.float32(probs[g][a])) for a in leaf.legal}
+                    leaf.probs = np.array(probs[g], dtype=np.float32)
         self.k += 1
 
     def rollout(self):
@@ -148,6 +159,9 @@ class TreeModel:
                     if found is None and position_key(nodes[c].rec) == key:
                         found = c
             if found is None:
+                if self.capacity is not None and len(nodes) + 1 > self.capacity:
+                    st["overflow"] = True          # a fresh root does not fit: the root stays where it was
+                    continue
                 nodes.append(Node(ob.b[g].copy(), not root.turn))
                 found = len(nodes) - 1
             st["root"] = found
@@ -156,7 +170,8 @@ class TreeModel:
     def root_stats(self):
         G = len(self.games)
         o = {"N": np.zeros((G, 36), np.int32), "W": np.zeros((G, 36)), "Q": np.zeros((G, 36)), "P": np.zeros((G, 36)),
-             "Ntot": np.zeros(G, np.int32), "choose": np.zeros(G, np.uint8), "nodes_used": np.zeros(G, np.int32)}
+             "Ntot": np.zeros(G, np.int32), "choose": np.zeros(G, np.uint8), "nodes_used": np.zeros(G, np.int32),
+             "overflow": np.zeros(G, bool)}
         for g, st in enumerate(self.games):
             n = st["nodes"][st["root"]]
             for a in n.legal:
@@ -167,7 +182,25 @@ class TreeModel:
             o["Ntot"][g] = n.Ntot
             o["choose"][g] = choose(n)
             o["nodes_used"][g] = len(st["nodes"])
+            o["overflow"][g] = st["overflow"]
         return o
+
+    # ---- the whole trees, node by node in allocation order (= the device's node indices)
+    def dump(self):
+        """Per game: used, root, overflow, the last select's path [(node, action)] and leaf, and nodes = per node rec,
+        turn, terminal, winner (-1 None, 0 False, 1 True), legal (the mask), Ntot, N[36], W[36], children (per action a
+        list of 0, 1 or 2 node indices) and P: None (no priors), "uniform", or the network's f32[36] row."""
+        out = []
+        for st in self.games:
+            nodes = []
+            for n in st["nodes"]:
+                P = None if n.P is None else ("uniform" if n.probs is None else n.probs)
+                nodes.append({"rec": n.rec, "turn": n.turn, "terminal": n.terminal, "winner": n.winner,
+                              "legal": sum(1 << a for a in n.legal), "Ntot": n.Ntot, "N": list(n.N), "W": list(n.W),
+                              "children": [list(c or ()) for c in n.children], "P": P})
+            out.append({"used": len(nodes), "root": st["root"], "overflow": st["overflow"], "path": list(st["path"]),
+                        "leaf": st["leaf"], "nodes": nodes})
+        return out
 
 
 def choose(n):
