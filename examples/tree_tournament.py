@@ -6,9 +6,13 @@ syncs after every move (strat_eval.play_game).  Finished games are frozen: their
 
     python examples/tree_tournament.py --p1 az:300 --p2 mcts:3000 [--games 1024] [--sims 10] [--dtype f32|bf16]
                                        [--weights tests/golden/model_eval.npz | --model model.pt]
+                                       [--compact [--carry N]]
 
 A player is mcts:R (uniform playouts and priors, MCTS(R)), az:R (the network's playouts and priors, AlphaZero(R)) or
 random (the uniform-legal policy).  Prints player 1's win, loss and draw counts and rates.
+
+--compact: every tree gives the nodes outside its new root's subtree back after each sync (TreeSearch.compact, the
+reference's _prune), so its pool holds 2 * R + carry nodes instead of every node of the game.
 """
 import argparse
 import os
@@ -41,8 +45,10 @@ def load_state_dict(args):
         return {k: torch.from_numpy(d[k.replace(".", "_")]) for k in SHAPES}
 
 
-def play(players, G, sims, net, seed):
-    """One half: players[0] moves first.  Returns winner i8[G] (1 = the first mover, 0 = the second, -1 = none)."""
+def play(players, G, sims, net, seed, carry=None):
+    """One half: players[0] moves first.  Returns winner i8[G] (1 = the first mover, 0 = the second, -1 = none).
+    carry: None = the trees never compact; else they compact after every sync and hold 2 * R + carry nodes (carry < 0:
+    2 * R + 2 of them)."""
     env = VecEnv(G, seed=seed)
     trees = []
     for i, (kind, R) in enumerate(players):
@@ -50,7 +56,8 @@ def play(players, G, sims, net, seed):
             trees.append(None)
             continue
         own_moves = 5 if i == 0 else 4
-        t = TreeSearch(G, capacity=1 + 2 * R * own_moves + 9, num_simulations=sims, net=net if kind == "az" else None,
+        capacity = 1 + 2 * R * own_moves + 9 if carry is None else 2 * R + (carry if carry >= 0 else 2 * R + 2)
+        t = TreeSearch(G, capacity=capacity, num_simulations=sims, net=net if kind == "az" else None,
                        seed=seed * 2 + 1 + i, device=env.device)
         t.reset(env)
         trees.append(t)
@@ -69,6 +76,8 @@ def play(players, G, sims, net, seed):
         for t in trees:
             if t is not None:
                 t.sync(env)
+                if carry is not None:
+                    t.compact()
     return env.node_info(python_key=False)["winner"]
 
 
@@ -83,6 +92,14 @@ def main():
     ap.add_argument("--weights", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                       "tests", "golden", "model_eval.npz"))
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32")
+    ap.add_argument("--compact", action="store_true",
+                    help="compact every tree after each sync; its capacity is then 2 * R + carry")
+    ap.add_argument("--carry", type=int, default=None,
+                    help="with --compact: room for the subtree a tree carries into its next move, beside the 2 * R "
+                         "nodes that move's rollouts can add.  Default 2 * R + 2 (R = the tree's own rollouts): what "
+                         "one move's rollouts and the two syncs until the next can allocate.  A kept subtree is "
+                         "measured at a small fraction of that (DESIGN.md section 12), so a smaller carry usually "
+                         "does; one that turns out too small raises ValueError before any node is lost")
     args = ap.parse_args()
     p1, p2 = parse_player(args.p1), parse_player(args.p2)
     half = args.games // 2
@@ -92,8 +109,15 @@ def main():
     if "az" in (p1[0], p2[0]):
         net = PolicyValueNet(load_state_dict(args), device="cuda",
                              dtype=torch.float32 if args.dtype == "f32" else torch.bfloat16)
-    w_a = play((p1, p2), half, args.sims, net, args.seed)                  # player 1 moves first
-    w_b = play((p2, p1), half, args.sims, net, args.seed + 1)              # player 2 moves first
+    if args.carry is not None and not args.compact:
+        raise SystemExit("--carry needs --compact")
+    carry = None
+    if args.compact:
+        if args.carry is not None and args.carry < 0:
+            raise SystemExit("--carry must be >= 0")
+        carry = args.carry if args.carry is not None else -1
+    w_a = play((p1, p2), half, args.sims, net, args.seed, carry)           # player 1 moves first
+    w_b = play((p2, p1), half, args.sims, net, args.seed + 1, carry)       # player 2 moves first
     wins = int((w_a == 1).sum()) + int((w_b == 0).sum())
     losses = int((w_a == 0).sum()) + int((w_b == 1).sum())
     draws = int((w_a == -1).sum()) + int((w_b == -1).sum())

@@ -6,7 +6,20 @@
  * bytes (16-byte aligned).  A rollout of the reference (MCTS._rollout, mcts.py:166-176; AlphaZero shares the tree code) is
  *   qttt_tree_select -> qttt_rollout_many or qttt_rollout_policy on the leaf buffer -> qttt_tree_backup
  * with no host synchronisation in between.  A move is qttt_tree_root (choose) -> the caller steps its games ->
- * qttt_tree_sync.
+ * qttt_tree_sync -> (optionally) qttt_tree_compact.
+ *
+ * Compaction (qttt_tree_compact, declared in qttt_tree_compact.h; the reference's _prune, mcts.py:222-231, 330-337).
+ * A sync leaves the nodes outside the new root's subtree allocated; qttt_tree_compact gives them back.  Per game it
+ * keeps the nodes reachable from the root in their old relative order, the root at index 0, and sets used to their
+ * number.  Nodes come from a bump counter and a node has one parent, so a child's index is larger than its parent's,
+ * before and after: one ascending sweep finds the reachable nodes and numbers them in a forwarding table (i32 per
+ * node, the caller's scratch buffer of qttt_tree_compact_bytes(games, capacity) bytes), a second moves each record
+ * down to its new index (never above its old one) with its child words rewritten; a collapse pair stays adjacent
+ * with bit 30 set.  W, N, Ntot, flags and priors move unchanged and no draw is addressed by a node index, so a search
+ * that goes on after the call computes bit for bit what it would have computed without it.  The recorded path is
+ * cleared as by qttt_tree_reset (depth 0, leaf 0, the leaf flags of the root); the overflow flag keeps its value; the
+ * header's padding and path entries are not written.  A game that is compact already (root 0, every node reachable)
+ * is left byte for byte as it is.  Records and priors at or beyond the new `used` are unspecified after the call.
  *
  * Buffer layout (all little-endian, byte offsets):
  *   game header g at 128 g, 128 B:  i32 used (nodes allocated) | i32 root | i32 depth (path length of the last select)
@@ -38,8 +51,9 @@
  * Errors, in this order, before any device work: QTTT_ERR_SIZE for games < 0, capacity outside
  * 1..QTTT_TREE_MAX_CAPACITY (qttt_tree_bytes returns it too), board_offset < 0, rollout_idx >= QTTT_TREE_MAX_ROLLOUTS,
  * n_sims outside 1..QTTT_TREE_MAX_SIMS; 0 with no device work for games == 0; QTTT_ERR_NULL for a null tree, state,
- * leaf_state or result; QTTT_ERR_ACTION for a tree not 16-byte aligned, leaf_probs / N / Ntot / nodes_used not 4-byte
- * aligned or W / Q / P not 8-byte aligned. */
+ * leaf_state, result
+ * or scratch; QTTT_ERR_ACTION for a tree not 16-byte aligned, leaf_probs / N / Ntot / nodes_used not 4-byte
+ * aligned or W / Q / P not 8-byte aligned, the scratch of qttt_tree_compact not 4-byte aligned. */
 #ifndef QTTT_TREE_H
 #define QTTT_TREE_H
 #include <stdint.h>

@@ -93,6 +93,11 @@ TREE_SIGNATURES = {
     "qttt_tree_sqrt": (_i32, [_u32, _i64, _vp, _vp]),
     "qttt_tree_score": (_i32, [_vp, _vp, _vp, _vp, _f64, _i64, _vp, _vp]),
 }
+# every symbol include/qttt_tree_compact.h declares (compaction of the search trees; qttt.h includes it)
+TREE_COMPACT_SIGNATURES = {
+    "qttt_tree_compact_bytes": (_i64, [_i64, _i64]),
+    "qttt_tree_compact": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+}
 
 _lib = None
 
@@ -155,7 +160,8 @@ def lib():
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(NN_SIGNATURES.items())
-                                  + list(POLICY_ROLLOUT_SIGNATURES.items()) + list(TREE_SIGNATURES.items())):
+                                  + list(POLICY_ROLLOUT_SIGNATURES.items()) + list(TREE_SIGNATURES.items())
+                                  + list(TREE_COMPACT_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

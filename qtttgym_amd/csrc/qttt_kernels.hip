@@ -656,6 +656,21 @@ int qttt_tree_sync(void *tree, int64_t games, int64_t capacity, const void *stat
     return launch(tree_sync_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity, p.P, p.Q);
 }
 
+int64_t qttt_tree_compact_bytes(int64_t games, int64_t capacity) {
+    if (tree_size_bad(games, capacity)) return QTTT_ERR_SIZE;
+    if (games > 0 && 4 * capacity > INT64_MAX / games) return QTTT_ERR_SIZE;
+    return 4 * games * capacity;
+}
+
+int qttt_tree_compact(void *tree, int64_t games, int64_t capacity, void *scratch, void *stream) {
+    if (tree_size_bad(games, capacity)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, scratch)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(scratch, 4)) return QTTT_ERR_ACTION;
+    return launch(tree_compact_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (int32_t *)scratch);
+}
+
 int qttt_tree_root(const void *tree, int64_t games, int64_t capacity, int32_t *N, double *W, double *Q, double *P,
                    int32_t *Ntot, uint8_t *choose, int32_t *nodes_used, uint8_t *overflow, void *stream) {
     if (tree_size_bad(games, capacity)) return QTTT_ERR_SIZE;

@@ -5,7 +5,8 @@
 // over the wave picks the argmax.  The one-lane-per-board mapping of the step kernels fits a state that
 // lives in registers; a tree node is 36-wide and lives in HBM, so here a lane per action is the natural unit.
 // A wave owns its game: node allocation needs no atomics, and no kernel re-reads what it wrote itself (a freshly
-// expanded child has no priors, so select ends on it; the child's header is still in registers).
+// expanded child has no priors, so select ends on it; the child's header is still in registers).  The one exception
+// is tree_compact_kernel, whose lanes hand each other marks through memory, with tree_wave_sync() in between.
 // Buffer layout: include/qttt_tree.h.
 #ifndef QTTT_TREE_KERNELS_H
 #define QTTT_TREE_KERNELS_H
@@ -13,6 +14,7 @@
 #include "qttt_board_forms.h"
 #include "qttt_search_core.h"
 #include "qttt_tree.h"
+#include "qttt_tree_compact.h"
 
 namespace {
 
@@ -40,6 +42,7 @@ struct TreeSlot {                      // 16 B: one action of one node
     int32_t child;
 };
 static_assert(sizeof(TreeNodeHdr) + 36 * sizeof(TreeSlot) == QTTT_TREE_NODE_BYTES, "node record");
+typedef u32 __attribute__((ext_vector_type(4), may_alias)) TreeVec;      // 16 B of a node record, whatever they hold
 
 struct TreeView {
     TreeGame *games;
@@ -302,6 +305,119 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_sync_kernel(void *tree, int64
     const TreeNodeHdr f = tree_node_of(P, Q, !(h.flags & TN_TURN), lut);      // _expand_child of the move (:320-323)
     tree_write_node(v, g, used, f, lane, 0u);
     if (lane == 0u) { gh->root = used; gh->used = used + 1; }
+}
+
+// Everything one lane stored before this point is what every lane of the wave loads after it (the forwarding table
+// and the LDS window of tree_compact_kernel are handed from lane to lane of one wave, never between waves).
+__device__ __forceinline__ void tree_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// a child word's nodes as [c0, c0 + n), or n = 0 when it is -1 or does not lie in (parent, used): the compaction
+// never follows an index that a well-formed tree cannot hold
+__device__ __forceinline__ int tree_child_span(int32_t child, int32_t parent, int32_t used, int32_t &c0) {
+    c0 = child & (TREE_CHILD_PAIR - 1);
+    const int n = (child & TREE_CHILD_PAIR) ? 2 : 1;
+    return (child >= 0 && c0 > parent && c0 <= used - n) ? n : 0;
+}
+
+// MCTS._prune as done by sync (mcts.py:222-231, 330-337): stable, in-place compaction of the nodes reachable from the
+// root.  fwd = i32[games][capacity] scratch, fwd[g][i] = the new index of node i or -1.
+//
+// Why two ascending sweeps are enough: a child's index is larger than its parent's (bump allocation) and a node has one
+// parent, so when sweep A reaches node i every mark i can ever get has been made, and fwd[i] = the number of reachable
+// nodes before it.  Sweep B moves record i to fwd[i] <= i; it holds one record at a time: every lane's loads of record
+// i are in registers before its stores (the stored values depend on them), the destination fwd[i] is either i itself
+// (each lane rewrites exactly the bytes it loaded) or a record below i, and every reachable record below i has been
+// read already, so a store never lands on a record that is still to be read.
+//
+// Sweep A reads the marks 64 at a time: lane l of a chunk holds node base + l.  Marks made by parents of earlier chunks
+// come from fwd (-2 = marked); a child that falls into its parent's own chunk is marked in the wave's 64-entry LDS
+// window instead, and the chunk's reachable set is re-read from the window after every node.  The nodes of a chunk
+// are taken in ascending order and a child lies above its parent, so a window bit set while node j is processed
+// belongs to a node above j that has not been passed yet: nothing is missed and nothing is visited twice.
+//
+// Every loop is bounded by `used` (the chunk loops) or by 64 (the nodes of a chunk); no atomics, no waiting on memory.
+__global__ __launch_bounds__(TREE_BLOCK) void tree_compact_kernel(void *tree, int64_t games, int64_t capacity,
+                                                                  int32_t *fwd_all) {
+    __shared__ int32_t window[TREE_GAMES_PER_BLOCK][64];
+    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
+    const u32 lane = threadIdx.x & 63u;
+    if (g >= games) return;
+    const TreeView v = tree_view(tree, games, capacity);
+    TreeGame *gh = &v.games[g];
+    const int32_t root = gh->root, used = gh->used;
+    if (used < 1 || (int64_t)used > capacity || root < 0 || root >= used) return;      // not a tree of this pool
+    if (root == 0 && used == 1) return;                                               // already compact
+    int32_t *fwd = fwd_all + g * capacity;
+    int32_t *win = window[threadIdx.x / 64];
+    const u32 gflags = gh->flags, rflags = v.hdr(g, root)->flags;
+
+    // ---- sweep A: reachability and the new indices
+    for (int32_t i = root + (int32_t)lane; i < used; i += 64) fwd[i] = -1;
+    int32_t count = 0;
+    for (int32_t base = root; base < used; base += 64) {
+        tree_wave_sync();                                        // the -1s and the marks of the earlier chunks
+        const int32_t i = base + (int32_t)lane;
+        win[lane] = (i == root || (i < used && fwd[i] != -1)) ? 1 : 0;
+        u64 reach = 0ull, passed = 0ull;
+        for (int it = 0; it <= 64; ++it) {                       // a node per turn, and the turn that finds none left
+            tree_wave_sync();
+            reach = __ballot(win[lane] != 0);
+            const u64 pending = reach & ~passed;
+            if (!pending) break;
+            const int j = __builtin_ctzll(pending);
+            passed = j == 63 ? ~0ull : (2ull << j) - 1ull;
+            const int32_t node = base + j;
+            if (lane < 36u) {
+                int32_t c0;
+                const int n = tree_child_span(v.slots(g, node)[lane].child, node, used, c0);
+                if (n) {
+                    if (c0 < base + 64) win[c0 - base] = 1;
+                    else fwd[c0] = -2;
+                }
+                if (n == 2) {                                    // the other half of a pair
+                    if (c0 + 1 < base + 64) win[c0 + 1 - base] = 1;
+                    else fwd[c0 + 1] = -2;
+                }
+            }
+        }
+        if (i < used && ((reach >> lane) & 1ull)) fwd[i] = count + __builtin_popcountll(reach & ((1ull << lane) - 1ull));
+        count += __builtin_popcountll(reach);
+    }
+    if (root == 0 && count == used) return;                      // already compact: not a byte of the tree changes
+    tree_wave_sync();
+
+    // ---- sweep B: move the reachable records down, in ascending order, with their child words rewritten.  A record
+    // is 38 vectors of 16 B: the header is two (lane 36 and 37), slot a is vector 2 + a (lane a), its child the last word
+    int32_t dst = 0;
+    for (int32_t base = root; base < used; base += 64) {
+        const int32_t i = base + (int32_t)lane;
+        const u64 reach = __ballot(i < used && fwd[i] >= 0);
+        for (u64 pending = reach; pending; pending &= pending - 1ull, ++dst) {      // at most 64 nodes
+            const int32_t node = base + __builtin_ctzll(pending);
+            const u32 nflags = v.hdr(g, node)->flags;
+            const bool network = (nflags & TN_PRIORS) && !(nflags & TN_UNIFORM);
+            const u32 vec = lane < 36u ? lane + 2u : lane - 36u;
+            TreeVec r = {0u, 0u, 0u, 0u};
+            float p = 0.0f;
+            if (lane < 38u) r = reinterpret_cast<const TreeVec *>(v.hdr(g, node))[vec];
+            if (lane < 36u) {
+                int32_t c0;
+                const int32_t child = (int32_t)r.w;
+                const int n = tree_child_span(child, node, used, c0);
+                r.w = n ? (u32)(fwd[c0] | (child & TREE_CHILD_PAIR)) : ~0u;
+                if (network) p = v.prior(g, node)[lane];
+            }
+            if (lane < 38u) reinterpret_cast<TreeVec *>(v.hdr(g, dst))[vec] = r;
+            if (lane < 36u && network) v.prior(g, dst)[lane] = p;
+        }
+    }
+    if (lane == 0u) {                                            // as tree_reset_kernel's, for this root
+        gh->used = count; gh->root = 0; gh->depth = 0; gh->leaf = 0;
+        gh->flags = (gflags & TG_OVERFLOW) | (rflags & TN_TURN ? TG_LEAF_TURN : 0u) | (rflags & TN_TERMINAL ? TG_LEAF_TERMINAL : 0u);
+    }
 }
 
 struct TreeRootOut {

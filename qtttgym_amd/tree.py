@@ -2,10 +2,11 @@
 G independent games, kept on the device (include/qttt_tree.h).
 
 A rollout is select -> playouts from the leaf (VecEnv.rollout_many, or VecEnv.rollout_policy under a network) ->
-backup, three launches on the current stream with no host synchronisation.  The device pool has no compaction (the
-reference's _prune): nodes that sync leaves behind stay allocated, so `capacity` must cover every rollout and sync
-since the last reset.  The host keeps an upper bound on the nodes used (+2 per rollout, +1 per sync) and raises
-ValueError before launching work that could pass it.
+backup, three launches on the current stream with no host synchronisation.  Nodes that sync leaves behind stay
+allocated until compact() (the reference's _prune) gives them back: with a compact() after every sync, `capacity` has
+to hold the kept subtree and one move's rollouts; without it, every rollout and sync since the last reset.  The host
+keeps an upper bound on the nodes used (+2 per rollout, +1 per sync; compact() replaces it by the real maximum) and
+raises ValueError before launching work that could pass it.
 """
 import torch
 
@@ -51,6 +52,7 @@ class TreeSearch(LibCaller):
             self._out = out_rows(VecEnv._policy_rows(S), G, dev, keys=("result", "probs"))
         self.rollout_idx = 0          # k of include/qttt_tree.h: rollouts since the last reset
         self._bound = None            # upper bound on the nodes used (None: not reset yet)
+        self._scratch = None          # compact()'s forwarding table, allocated by its first call
 
     # ------------------------------------------------------------------ helpers
     def _check_env(self, env):
@@ -136,3 +138,21 @@ class TreeSearch(LibCaller):
             raise ValueError("a sync could use %d nodes, more than capacity %d" % (self._bound + 1, self.capacity))
         self._call("qttt_tree_sync", self.tree.data_ptr(), self.num_games, self.capacity, env.state.data_ptr())
         self._bound += 1
+
+    def compact(self, update_bound=True):
+        """MCTS._prune as sync does it (mcts.py:222-231, 330-337): every game keeps the nodes reachable from its root,
+        in their old order with the root at index 0, and gives the rest back.  The search goes on bit for bit as if
+        nothing had been compacted: rollout_idx is not reset, the draws go on.  update_bound=True reads nodes_used
+        back and makes its maximum the host's bound, which is what lets contemplate() accept the next move's rollouts
+        in a small `capacity`: one host read-back (a device synchronisation) per call, so call it once per move,
+        never per rollout.  update_bound=False reads nothing back; the old bound stays, still valid."""
+        if self._bound is None:
+            raise RuntimeError("reset() first")
+        if self._scratch is None:
+            nbytes = int(self._lib.qttt_tree_compact_bytes(self.num_games, self.capacity))
+            if nbytes < 0:
+                raise ValueError("qttt_tree_compact_bytes(%d, %d) failed" % (self.num_games, self.capacity))
+            self._scratch = torch.empty(max(nbytes // 4, 1), dtype=torch.int32, device=self.device)
+        self._call("qttt_tree_compact", self.tree.data_ptr(), self.num_games, self.capacity, self._scratch.data_ptr())
+        if update_bound:
+            self._bound = int(self.nodes_used().max()) if self.num_games else 1

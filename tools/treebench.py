@@ -5,6 +5,13 @@ over the measured rollouts), the playouts alone re-run on the same leaves as the
 
     python tools/treebench.py [--games 4096,65536,262144] [--modes uniform,f32,bf16] [--sims 10] [--rollouts 32]
                               [--warmup 4] [--out profiles/tree/treebench.jsonl]
+
+--compact-games 4096,65536 adds the compaction leg (uniform playouts): per move contemplate(R) -> choose -> step ->
+sync -> compact(), timed with HIP events around contemplate and around compact (its launch alone; the read-back of the
+bound comes after the second event), medians over the moves of --compact-reps games from the empty board, with the
+mean nodes used before and after each compaction.
+
+    python tools/treebench.py --games "" --compact-games 4096,65536 [--compact-rollouts 300] [--compact-reps 3]
 """
 import argparse
 import json
@@ -80,6 +87,46 @@ def run(G, mode, sims, rollouts, warmup):
             "nodes_used_mean": round(float(used.mean()), 2), "nodes_used_max": int(used.max())}
 
 
+def run_compact(G, sims, R, reps, moves=4):
+    """contemplate(R) + a move + sync + compact(), `moves` times per game from the empty board, `reps` games (the
+    first one more as warm-up).  One JSON row: medians over every timed (game, move)."""
+    import statistics
+    from qtttgym_amd.actions import action36_to_pairs
+    stream = torch.cuda.current_stream()
+    t = TreeSearch(G, capacity=4 * R + 2, num_simulations=sims, seed=2)
+    us_c, us_k, before, after = [], [], [], []
+    for rep in range(reps + 1):
+        env = VecEnv(G, seed=1 + rep)
+        t.reset(env)
+        for mv in range(moves):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            e[0].record(stream)
+            t.contemplate(R)
+            e[1].record(stream)
+            env.step_raw(action36_to_pairs(t.choose()).contiguous())
+            t.sync(env)
+            b = t.nodes_used().float().mean()
+            e[2].record(stream)
+            t.compact(update_bound=False)
+            e[3].record(stream)
+            torch.cuda.synchronize()
+            t.compact()                              # already compact: only the bound is read back
+            if rep:
+                us_c.append(e[0].elapsed_time(e[1]) * 1e3)
+                us_k.append(e[2].elapsed_time(e[3]) * 1e3)
+                before.append(float(b))
+                after.append(float(t.nodes_used().float().mean()))
+    return {"games": G, "mode": "uniform", "leg": "compact", "n_sims": sims, "rollouts": R, "moves": moves, "reps": reps,
+            "us_contemplate_median": round(statistics.median(us_c), 1),
+            "us_compact_median": round(statistics.median(us_k), 1),
+            "us_compact_min": round(min(us_k), 1), "us_compact_max": round(max(us_k), 1),
+            "us_compact_by_move": [round(statistics.median(us_k[m::moves]), 1) for m in range(moves)],
+            "nodes_used_before_mean_by_move": [round(statistics.mean(before[m::moves]), 1) for m in range(moves)],
+            "nodes_used_after_mean_by_move": [round(statistics.mean(after[m::moves]), 1) for m in range(moves)],
+            "nodes_used_before_mean": round(statistics.mean(before), 1),
+            "nodes_used_after_mean": round(statistics.mean(after), 1)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--games", default="4096,65536,262144")
@@ -87,14 +134,21 @@ def main():
     ap.add_argument("--sims", type=int, default=10)
     ap.add_argument("--rollouts", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--compact-games", default="")
+    ap.add_argument("--compact-rollouts", type=int, default=300)
+    ap.add_argument("--compact-reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     rows = []
-    for G in [int(x) for x in args.games.split(",")]:
+    for G in [int(x) for x in args.games.split(",") if x]:
         for mode in args.modes.split(","):
             row = run(G, mode, args.sims, args.rollouts, args.warmup)
             print(json.dumps(row), flush=True)
             rows.append(row)
+    for G in [int(x) for x in args.compact_games.split(",") if x]:
+        row = run_compact(G, args.sims, args.compact_rollouts, args.compact_reps)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
