@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""The reference's self_play.py main loop (self_play.py:176-242) with the games on the device: every run plays --games
+games of AlphaZero self-play under the current weights (qtttgym_amd.SelfPlay: the search trees, the moves and the
+training samples never leave the GPU), trains the policy/value network on the batch with ordinary torch autograd, packs
+the new weights for the search and repeats.
+
+    python examples/selfplay_train.py [--games 1024] [--rollouts 100] [--sims 10] [--epochs 50] [--runs 30]
+                                      [--dtype f32|bf16] [--out model.pt] [--model model.pt] [--value-targets 1,0]
+
+The network is nn.Model's (nn.py:7-28) under its own parameter names (qtttgym_amd.policy_value.SHAPES), so --out is a
+state dict that the reference, PolicyValueNet and examples/tree_tournament.py --model all load.  The loss is the
+reference's (self_play.py:226-236): 0.5 (v - v_target)^2 over every sample plus the KL divergence from the visit-count
+target to the network's policy over the legal actions of the samples that are not terminal; the optimiser is its Adam
+(lr 1e-3, weight decay 1e-3, amsgrad).  --value-targets 1,0 are the reference's targets, 1,-1 what it evidently meant
+(qtttgym_amd.SelfPlay).  --dtype is the precision of the search's network; training is f32.
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from qtttgym_amd import PolicyValueNet, SelfPlay  # noqa: E402
+from qtttgym_amd import recommended_env  # noqa: E402
+from qtttgym_amd.policy_value import HIDDEN, SHAPES  # noqa: E402
+recommended_env(apply=True)
+
+
+class Net(torch.nn.Module):
+    """nn.Model (nn.py:7-42): three ReLU layers of 256 units on the flattened 18 x 10 input, a value head and a policy
+    head, each a ReLU and a linear layer.  The parameter names are the reference's."""
+
+    def __init__(self):
+        super().__init__()
+        relu, lin = torch.nn.ReLU, torch.nn.Linear
+        self.fc = torch.nn.Sequential(lin(180, HIDDEN), relu(), lin(HIDDEN, HIDDEN), relu(), lin(HIDDEN, HIDDEN), relu())
+        self.V_head = torch.nn.Sequential(relu(), lin(HIDDEN, 1))
+        self.pi_head = torch.nn.Sequential(relu(), lin(HIDDEN, 36))
+        assert {k: tuple(p.shape) for k, p in self.state_dict().items()} == SHAPES
+
+    def forward(self, s):
+        z = self.fc(s.flatten(-2, -1).float())
+        return self.V_head(z).squeeze(-1), self.pi_head(z)
+
+
+def loss_terms(net, s, pi, mask, v_target, done):
+    """self_play.py:226-236: (L, J) = the value term per sample, the policy term per sample that is not terminal."""
+    v, logits = net(s)
+    keep = ~done
+    logp = torch.log_softmax(logits[keep].masked_fill(~mask[keep], -float("inf")), dim=-1)      # nn.py:41
+    p, legal = pi[keep], mask[keep]
+    J = torch.zeros_like(p)
+    J[legal] = p[legal] * (torch.log(p[legal] + 1e-7) - logp[legal])
+    return 0.5 * (v - v_target).pow(2), J.sum(-1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--games", type=int, default=1024, help="games per run (the reference's M = 50)")
+    ap.add_argument("--rollouts", type=int, default=100, help="rollouts before every move (the reference's n_rollouts)")
+    ap.add_argument("--sims", type=int, default=10, help="playouts per rollout (AlphaZero's num_simulations)")
+    ap.add_argument("--epochs", type=int, default=50)
+    ap.add_argument("--runs", type=int, default=30)
+    ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32")
+    ap.add_argument("--out", default="model.pt")
+    ap.add_argument("--model", default=None, help="state dict to start from (default: torch's initialisation)")
+    ap.add_argument("--value-targets", default="1,0", help="v of the first row when the first / second player wins")
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    torch.manual_seed(args.seed)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    model = Net().to(dev)
+    if args.model:
+        model.load_state_dict(torch.load(args.model, map_location=dev))
+    optim = torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-3, amsgrad=True)      # nn.py:27
+    net = PolicyValueNet(model, device=dev, dtype=torch.float32 if args.dtype == "f32" else torch.bfloat16)
+    targets = tuple(float(x) for x in args.value_targets.split(","))
+    sp = SelfPlay(args.games, n_rollouts=args.rollouts, num_simulations=args.sims, net=net, value_targets=targets,
+                  seed=args.seed)
+    for run in range(args.runs):
+        batch = sp.play()
+        s, pi, mask, v_target, done = batch.flat()
+        won = [int((batch.winner == w).sum()) for w in (1, 0, -1)]
+        for _ in range(args.epochs):
+            L, J = loss_terms(model, s, pi, mask, v_target, done)
+            loss = L.mean() + J.mean(0)
+            optim.zero_grad()
+            loss.backward()
+            optim.step()
+        print("run %d: %d samples of %d games (first player won %d, lost %d, drew %d); L: %.4f, J: %.4f"
+              % (run, len(s), args.games, won[0], won[1], won[2], L.mean().item(), J.mean().item()), flush=True)
+        net.load_state_dict(model)                           # the next run searches with the new weights
+        torch.save(model.state_dict(), args.out)
+
+
+if __name__ == "__main__":
+    main()

@@ -98,6 +98,12 @@ TREE_COMPACT_SIGNATURES = {
     "qttt_tree_compact_bytes": (_i64, [_i64, _i64]),
     "qttt_tree_compact": (_i32, [_vp, _i64, _i64, _vp, _vp]),
 }
+# every symbol include/qttt_selfplay.h declares (the self-play record; qttt.h includes it)
+SELFPLAY_ROWS = 10
+SELFPLAY_SIGNATURES = {
+    "qttt_selfplay_record": (_i32, [_vp, _i64, _i64, _i32, _u32, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp]),
+}
 
 _lib = None
 
@@ -161,7 +167,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(NN_SIGNATURES.items())
                                   + list(POLICY_ROLLOUT_SIGNATURES.items()) + list(TREE_SIGNATURES.items())
-                                  + list(TREE_COMPACT_SIGNATURES.items())):
+                                  + list(TREE_COMPACT_SIGNATURES.items()) + list(SELFPLAY_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

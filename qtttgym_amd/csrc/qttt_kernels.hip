@@ -49,16 +49,18 @@
 // tuple hash) -> qttt_search_core.h (the search rules several kernels share: counter draw, pair-action decode, expansion
 // of a pair, the uniform playout) -> qttt_aux_kernels.h (the cold kernels, the reset fills), qttt_mcts_kernels.h,
 // qttt_nn_kernels.h (the policy/value network) -> qttt_policy_rollout_kernels.h (network-guided playouts);
-// qttt_tree_kernels.h (the batched search trees).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
+// qttt_tree_kernels.h (the batched search trees) -> qttt_selfplay_kernels.h (the self-play record).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
 // qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include "qttt_step_kernels.h"
 #include "qttt_aux_kernels.h"
 #include "qttt_mcts_kernels.h"
 #include "qttt_nn_kernels.h"
 #include "qttt_policy_rollout_kernels.h"
 #include "qttt_tree_kernels.h"
+#include "qttt_selfplay_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -699,6 +701,21 @@ int qttt_tree_score(const double *W, const uint32_t *N, const double *prior, con
     if (misaligned(W, 8) || misaligned(prior, 8) || misaligned(out, 8) || misaligned(N, 4) || misaligned(Ntot, 4))
         return QTTT_ERR_ACTION;
     return launch(tree_score_kernel, ceil_div(n, 256), 256, stream, W, N, prior, Ntot, c_puct, n, out);
+}
+
+// ---------------------------------------------------------------- self-play (include/qttt_selfplay.h)
+int qttt_selfplay_record(const void *tree, int64_t games, int64_t capacity, int ply, uint32_t n_rollouts, double alpha,
+                         double v_first, double v_second, void *states, double *pi, uint8_t *mask, uint8_t *done,
+                         float *v, uint8_t *action36, uint8_t *length, int8_t *winner, uint8_t *actions, void *stream) {
+    if (tree_size_bad(games, capacity) || ply < 0 || ply >= QTTT_SELFPLAY_ROWS || n_rollouts == 0u || !std::isfinite(alpha) ||
+        !std::isfinite(v_first) || !std::isfinite(v_second) || alpha <= 0.0)
+        return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
+    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    return launch(selfplay_record_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity, ply,
+                  n_rollouts, alpha, (float)v_first, (float)v_second, o);
 }
 
 }  // extern "C"

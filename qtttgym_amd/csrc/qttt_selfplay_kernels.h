@@ -1,0 +1,96 @@
+// qttt_selfplay_kernels.h — the self-play record (include/qttt_selfplay.h): one root of every game of
+// the device search trees becomes one row of the trainer's batch, and the move to play comes back.
+//
+// Mapping: the tree kernels' (qttt_tree_kernels.h): ONE WAVEFRONT PER GAME, lane a = action a.  The root's 36 slots
+// are one coalesced 576-byte read, the pi row one coalesced 288-byte store, the mask row 36 bytes; the value back-fill
+// of a finished game is at most 10 lanes, one row each.  The tree is read only; a wave touches only its own game's
+// columns of the outputs, so there are no atomics, and nothing is handed from lane to lane through memory.  No LDS
+// (the winner and the terminal flag are the root's node flags, no line table is needed), no loop but the two six-step
+// butterflies (the sum, and choose's argmax).
+#ifndef QTTT_SELFPLAY_KERNELS_H
+#define QTTT_SELFPLAY_KERNELS_H
+#include "qttt_tree_kernels.h"
+#include "qttt_selfplay.h"
+
+namespace {
+
+struct SelfPlayOut {
+    u64 *states;                       // [ROWS][2][plane_stride(games)]
+    double *pi;                        // [ROWS][games][36]
+    uint8_t *mask;                     // [ROWS][games][36]
+    uint8_t *done;                     // [ROWS][games]
+    float *v;                          // [ROWS][games]
+    uint8_t *action36;                 // [ROWS][games]
+    uint8_t *length;                   // [games]
+    int8_t *winner;                    // [games]
+    uint8_t *actions;                  // [games][2]
+};
+
+// the sum of include/qttt_selfplay.h: 64 terms (lanes 36..63 hold 0), s[i] += s[i ^ m] for m = 1 .. 32; every lane ends
+// with the same double
+__device__ __forceinline__ double selfplay_wave_sum(double x) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) x = x + __shfl_xor(x, m);
+    return x;
+}
+
+__global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void *tree, int64_t games, int64_t capacity,
+                                                                     int ply, u32 n_rollouts, double alpha, float v_first,
+                                                                     float v_second, SelfPlayOut o) {
+    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
+    const u32 lane = threadIdx.x & 63u;
+    if (g >= games) return;
+    uint8_t *act = o.actions + 2 * g;
+    // live: the row before this one was recorded and was not the terminal one
+    if (ply != 0 && ((int)o.length[g] != ply || o.done[(int64_t)(ply - 1) * games + g] != 0)) {
+        if (lane == 0u) { act[0] = 255; act[1] = 255; }
+        return;
+    }
+    const TreeView v = tree_view(const_cast<void *>(tree), games, capacity);
+    const TreeRootLane r = tree_root_lane(v, g, lane);
+    const int64_t stride = plane_stride(games), row = (int64_t)ply * games + g;
+    const bool terminal = (r.h.flags & TN_TERMINAL) != 0u;
+    if (lane == 0u) {
+        u64 *planes_t = o.states + (int64_t)ply * 2 * stride;
+        planes_t[g] = r.h.P;
+        planes_t[stride + g] = r.h.Q;
+        o.done[row] = terminal ? 1 : 0;
+        o.length[g] = (uint8_t)(ply + 1);
+    }
+    if (terminal) {                                              // self_play.py:203-206 and the v of :195-216
+        if (lane < 36u) {
+            o.pi[row * 36 + lane] = 1.0 / 36.0;
+            o.mask[row * 36 + lane] = 1;
+        }
+        const int w = (int)((r.h.flags >> 8) & 3u) - 1;          // 1 / 0 / -1 = True / False / None
+        const float v0 = w > 0 ? v_first : (w == 0 ? v_second : 0.0f);
+        if ((int)lane <= ply) {
+            const float x = (lane & 1u) ? -v0 : v0;
+            o.v[(int64_t)lane * games + g] = x == 0.0f ? 0.0f : x;        // a zero is +0.0
+        }
+        if (lane == 0u) {
+            o.winner[g] = (int8_t)w;
+            o.action36[row] = 255;
+            act[0] = 255; act[1] = 255;
+        }
+        return;
+    }
+    // self_play.py:208-213: pi[a] = (N / n_rollouts) ** alpha on the legal actions, normalised
+    double x = r.legal ? (double)r.s.N / (double)n_rollouts : 0.0;
+    if (alpha != 1.0) x = r.legal ? pow(x, alpha) : 0.0;
+    const double sum = selfplay_wave_sum(x);
+    const int a = tree_choose(r, lane);
+    if (lane < 36u) {
+        o.pi[row * 36 + lane] = r.legal ? x / sum : 0.0;
+        o.mask[row * 36 + lane] = r.legal ? 1 : 0;
+    }
+    if (lane == 0u) {
+        const u32 pr = a < 0 ? 0xFFFFu : pair_action<false>(a < 0 ? 0 : a);      // lo | hi << 8
+        o.action36[row] = a < 0 ? (uint8_t)255 : (uint8_t)a;
+        act[0] = (uint8_t)pr; act[1] = (uint8_t)(pr >> 8);
+    }
+}
+
+}  // namespace
+
+#endif  // QTTT_SELFPLAY_KERNELS_H

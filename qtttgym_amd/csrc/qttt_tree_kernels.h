@@ -429,6 +429,28 @@ struct TreeRootOut {
     uint8_t *overflow;
 };
 
+// what lane a sees of game g's root: the node's header, whether action a is legal, and its slot (empty when it is not)
+struct TreeRootLane {
+    TreeNodeHdr h;
+    TreeSlot s;
+    bool legal;
+};
+__device__ __forceinline__ TreeRootLane tree_root_lane(const TreeView &v, int64_t g, u32 lane) {
+    TreeRootLane r;
+    const int32_t root = v.games[g].root;
+    r.h = *v.hdr(g, root);
+    r.legal = lane < 36u && ((r.h.legal >> lane) & 1ull);
+    r.s.W = 0.0; r.s.N = 0u; r.s.child = -1;
+    if (r.legal) r.s = v.slots(g, root)[lane];
+    return r;
+}
+// Q of a slot (mcts.py:181: W / N, 0 while unvisited) and MCTS.choose over the wave (mcts.py:308-315): -inf for
+// unvisited actions, ties to the lowest; -1 when no action is legal
+__device__ __forceinline__ double tree_slot_q(const TreeSlot &s) { return s.N ? s.W / (double)s.N : 0.0; }
+__device__ __forceinline__ int tree_choose(const TreeRootLane &r, u32 lane) {
+    return wave_argmax(r.legal, r.s.N ? tree_slot_q(r.s) : -__builtin_inf(), lane);
+}
+
 __global__ __launch_bounds__(TREE_BLOCK) void tree_root_kernel(const void *tree, int64_t games, int64_t capacity,
                                                                TreeRootOut o) {
     const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
@@ -436,24 +458,17 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_root_kernel(const void *tree,
     if (g >= games) return;
     const TreeView v = tree_view(const_cast<void *>(tree), games, capacity);
     const TreeGame *gh = &v.games[g];
-    const int32_t root = gh->root;
-    const TreeNodeHdr h = *v.hdr(g, root);
-    const bool legal = lane < 36u && ((h.legal >> lane) & 1ull);
-    TreeSlot s;
-    s.W = 0.0; s.N = 0u; s.child = -1;
-    if (legal) s = v.slots(g, root)[lane];
-    const double q = s.N ? s.W / (double)s.N : 0.0;
+    const TreeRootLane r = tree_root_lane(v, g, lane);
     if (lane < 36u) {
         const int64_t j = g * 36 + lane;
-        if (o.N) o.N[j] = (int32_t)s.N;
-        if (o.W) o.W[j] = s.W;
-        if (o.Q) o.Q[j] = q;
-        if (o.P) o.P[j] = (legal && (h.flags & TN_PRIORS)) ? tree_prior(v, g, root, h, lane) : 0.0;
+        if (o.N) o.N[j] = (int32_t)r.s.N;
+        if (o.W) o.W[j] = r.s.W;
+        if (o.Q) o.Q[j] = tree_slot_q(r.s);
+        if (o.P) o.P[j] = (r.legal && (r.h.flags & TN_PRIORS)) ? tree_prior(v, g, gh->root, r.h, lane) : 0.0;
     }
-    // choose (mcts.py:308-315): -inf for unvisited actions, ties to the lowest
-    const int a = wave_argmax(legal, s.N ? q : -__builtin_inf(), lane);
+    const int a = tree_choose(r, lane);
     if (lane == 0u) {
-        if (o.Ntot) o.Ntot[g] = (int32_t)h.Ntot;
+        if (o.Ntot) o.Ntot[g] = (int32_t)r.h.Ntot;
         if (o.choose) o.choose[g] = a < 0 ? (uint8_t)255 : (uint8_t)a;
         if (o.nodes_used) o.nodes_used[g] = gh->used;
         if (o.overflow) o.overflow[g] = (gh->flags & TG_OVERFLOW) ? 1 : 0;
