@@ -13,6 +13,10 @@
  * Each output is nullable, at least one must be given; only those given are written.  `state` is not modified.
  * precision QTTT_NN_F32: exact-f32 MFMA (the reference's numerics up to summation order); QTTT_NN_BF16: bf16
  * weights and activations (the input included: 1/3 becomes 0.333984375), f32 accumulation and biases.
+ * Non-finite numbers propagate as in torch: the trunk's ReLU keeps a NaN (relu(NaN) = NaN, not 0), 0 * inf = NaN, and an
+ * f32 accumulator that overflows gives +-inf, so a NaN or an infinity that torch's forward on the same weights produces
+ * appears in value and logits at the same positions; masked logits stay -inf.  probs of a row with a NaN or +inf
+ * legal logit are NaN at its legal actions and 0 at its masked ones.
  * Errors: QTTT_ERR_SIZE for n < 0 or an unknown precision, QTTT_ERR_NULL for a null state / weights or no
  * output, QTTT_ERR_ACTION for weights not 16-byte aligned or an output not 4-byte aligned.
  *

@@ -14,7 +14,8 @@
  *   collapse bit = h1 >> 31 (as qttt_rollout)
  *   u = (h2 >> 8) * 2^-24; over the legal actions a in ascending order, e_a = expf(logit_a - max) and S = sum of e_a
  *   (the expressions of qttt_evaluate's probs, f32); the action is the smallest legal a whose running sum of e_a
- *   exceeds u * S, or the largest legal a if rounding leaves none.
+ *   exceeds u * S, or the largest legal a if rounding leaves none.  With non-finite weights the same rule holds: where
+ *   a NaN or infinite logit makes every comparison fail, the move is the largest legal action, so every move is legal.
  * So simulation s equals a one-simulation call with step_idx0 + s * QTTT_SIM_STRIDE, and board_offset shifts the draws
  * as it does for qttt_rollout_many.
  *

@@ -61,7 +61,8 @@ __device__ __forceinline__ nn_f32x4 nn_mfma(nn_bf16x8 a, nn_bf16x8 b, nn_f32x4 c
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-// One hidden layer H <- relu(H[:, :K] . B + bias) on the tile, B = W^T in fragment order.  A fragment (k-step s, row
+// One hidden layer H <- relu(H[:, :K] . B + bias) on the tile, B = W^T in fragment order (relu as torch's: NaN
+// propagates, include/qttt_nn.h).  A fragment (k-step s, row
 // tile mt): lane l reads row mt*16 + (l & 15), k = s*KS + (l >> 4)*EPL .. +EPL-1; B fragment (s, column tile t) is the
 // blob's fragment s*16 + t, lane l's EPL elements at ((s*16 + t)*64 + l)*EPL.  The next k-step's B fragments are loaded
 // before this step's MFMAs (the L2 latency of the weights is the exposed part of the loop).
@@ -103,8 +104,10 @@ __device__ __forceinline__ void nn_hidden(const typename NNCfg<PREC>::T *__restr
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)                          // C/D: column = lane & 15, row = (lane >> 4)*4 + r
-                H[(mt * 16 + (lane >> 4) * 4 + r) * C::LD + col] = (T)fmaxf(acc[mt][j][r] + bv, 0.f);
+            for (int r = 0; r < 4; ++r) {                        // C/D: column = lane & 15, row = (lane >> 4)*4 + r
+                const float z = acc[mt][j][r] + bv;              // torch.relu: a NaN stays a NaN (fmaxf would return 0)
+                H[(mt * 16 + (lane >> 4) * 4 + r) * C::LD + col] = (T)(z < 0.f ? 0.f : z);
+            }
     }
     __syncthreads();
 }

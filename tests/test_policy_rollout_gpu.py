@@ -1,7 +1,9 @@
 """VecEnv.rollout_policy on the MI355X: every draw is the documented rule's draw (replayed ply by ply against the float64
 network), the leaf outputs equal evaluate() bit for bit, the simulation / board_offset layout, sizes and tile tails,
 the outcome frequencies of the reference's own AlphaZero._simulate (tests/golden/policy_playout_stats.npz), one kernel
-per call, weight refresh, and the AlphaZero example."""
+per call, weight refresh, and the AlphaZero example.  With the zero and the greedy network (tests/nn_reference64.py) the
+sampler is deterministic in f32 arithmetic, and a host model on the C oracle replays whole launches byte for byte; with
+non-finite weights every move stays legal and the fallback is the largest legal action."""
 import os
 import subprocess
 import sys
@@ -11,7 +13,9 @@ import pytest
 import torch
 
 from hip_graph_nodes import kernels_enqueued
-from nn_reference64 import forward64, golden_state_dict, load_golden, random_state_dict
+from nn_reference64 import (forward64, golden_state_dict, greedy_state_dict, load_golden, random_play_env,
+                            random_state_dict, zero_state_dict)
+from test_policy_rollout_cpu import draw
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -216,6 +220,147 @@ def test_weight_refresh_changes_the_next_call(golden):
     net.load_state_dict(golden_state_dict(golden))
     c = env.rollout_policy(net, n_sims=2, with_trace=True)
     assert torch.equal(a["trace"], c["trace"]) and torch.equal(a["result"], c["result"])
+
+
+# ---------------------------------------------------------------- whole launches replayed on the host
+MODEL_BOARDS, MODEL_SIMS, MODEL_T0 = 513, 3, 4321       # 1 539 lanes: tiles of 64 and of 128 lanes straddle boards
+
+
+def host_playout(env, S, t0, choose):
+    """The documented rule (include/qttt_policy_rollout.h) on the C oracle: lane (i, s) plays until its game is over,
+    ply p with (collapse bit, u) = draw(qttt_hash(seed, board_offset + i, t0 + 16 s + p)) and the action
+    choose(lane, p, legal mask, u), which must be legal.  Returns trace u8[n,S,9], result i8[n,S], plies u8[n,S] and
+    the boards' legal masks."""
+    import oracle
+    pair = [oracle.ind2move(a) for a in range(36)]
+    ex = {k: t.cpu().numpy() for k, t in env.export_boards().items()}
+    lanes = oracle.boards_from_arrays(ex["board"], ex["moves"], ex["n_moves"], ex["qmask"], ex["n_q"])
+    n, N = lanes.n, lanes.n * S
+    lanes.n, lanes.b = N, np.repeat(lanes.b, S)
+    trace, plies, legal0 = np.full((N, 9), 0xFF, np.uint8), np.zeros(N, np.uint8), None
+    for p in range(9):
+        _, terminal, legal, _ = oracle.node_info(lanes)
+        legal0 = legal[::S].copy() if p == 0 else legal0
+        live = np.flatnonzero((terminal == 0) & (legal != 0))
+        if not len(live):
+            break
+        acts, bits = np.zeros((len(live), 2), np.uint8), np.zeros(len(live), np.uint8)
+        for r, j in enumerate(live):
+            i, s = divmod(int(j), S)
+            bit, u = draw(oracle.hash64(env.seed, env.board_offset + i, t0 + 16 * s + p))
+            a = choose(int(j), p, int(legal[j]), u)
+            assert 0 <= a < 36 and int(legal[j]) >> a & 1, (j, p, a, hex(int(legal[j])))
+            acts[r], bits[r], trace[j, p] = pair[a], bit, a | bit << 6
+        sub = oracle.OracleBoards(len(live))
+        sub.b = lanes.b[live].copy()
+        sub.step(acts, bits)
+        lanes.b[live] = sub.b
+        plies[live] += 1
+    winner = oracle.node_info(lanes)[0]
+    result = np.where(winner < 0, 0, np.where(winner > 0, 1, -1)).astype(np.int8)
+    return trace.reshape(n, S, 9), result.reshape(n, S), plies.reshape(n, S), legal0
+
+
+def _legal_list(legal):
+    return [a for a in range(36) if legal >> a & 1]
+
+
+def uniform_choice(legal, u):
+    """The rule under equal logits, in f32 as the kernel computes it: every e_a = expf(0) = 1, S = k exactly, and the
+    action is the r-th legal one for the smallest r with float32(r + 1) > float32(u) * float32(k)."""
+    idx = _legal_list(legal)
+    target = np.float32(u) * np.float32(len(idx))
+    assert target.dtype == np.float32
+    for r, a in enumerate(idx):
+        if np.float32(r + 1) > target:
+            return a
+    return idx[-1]
+
+
+def _assert_launch_equals(out, model):
+    trace, result, plies, _ = model
+    assert np.array_equal(out["trace"].cpu().numpy(), trace)
+    assert np.array_equal(out["result"].cpu().numpy(), result)
+    assert np.array_equal(out["plies"].cpu().numpy(), plies)
+
+
+@pytest.fixture(scope="module")
+def model_env():
+    return random_play_env(MODEL_BOARDS, 41)
+
+
+def _launch(env, sd, dtype, leaf=()):
+    return env.rollout_policy(_net(sd, dtype), n_sims=MODEL_SIMS, step_idx0=MODEL_T0, with_plies=True, with_trace=True,
+                              leaf=leaf)
+
+
+def test_zero_network_samples_uniformly_and_replays_exactly(model_env):
+    model = host_playout(model_env, MODEL_SIMS, MODEL_T0, lambda j, p, legal, u: uniform_choice(legal, u))
+    assert (model[2] == 0).any() and model[2].max() >= 7 and len(np.unique(model[0] & 63)) == 37
+    outs = [_launch(model_env, zero_state_dict(), dtype) for dtype in DTYPES]
+    for out in outs:
+        _assert_launch_equals(out, model)
+    for k in ("trace", "result", "plies"):
+        assert torch.equal(outs[0][k], outs[1][k])
+    # the f32 rule is not the float64 interval's: u * k is rounded before the comparison.  31 u = 2 - 2^-24 is a tie in
+    # f32 and rounds to 2.0, so the third action is played where the float64 CDF interval names the second.
+    u, legal = 1082401 * 2.0 ** -24, (1 << 31) - 1
+    assert u * 31 < 2.0 and np.float32(u) * np.float32(31) == np.float32(2.0) and uniform_choice(legal, u) == 2
+    assert uniform_choice(legal, 1082400 * 2.0 ** -24) == 1
+
+
+def test_greedy_network_plays_the_largest_bias(model_env):
+    sd = greedy_state_dict()
+    bias = sd["pi_head.1.bias"].tolist()
+    model = host_playout(model_env, MODEL_SIMS, MODEL_T0, lambda j, p, legal, u: max(_legal_list(legal), key=bias.__getitem__))
+    legal0 = model[3]
+    for dtype in DTYPES:
+        out = _launch(model_env, sd, dtype, leaf=("probs",))
+        _assert_launch_equals(out, model)
+        probs = out["probs"].cpu()
+        want = torch.zeros((MODEL_BOARDS, 36))
+        for i, lm in enumerate(legal0):
+            if lm:
+                want[i, max(_legal_list(int(lm)), key=bias.__getitem__)] = 1.0
+        live = torch.from_numpy(legal0 != 0)
+        assert torch.equal(probs[live].view(torch.int32), want[live].view(torch.int32))
+        assert torch.isnan(probs[~live]).all() and (~live).any()
+
+
+def _nan_policy_head(sd):
+    sd["pi_head.1.bias"][:] = float("nan")
+
+
+def _nan_in_trunk(sd):
+    sd["fc.2.weight"][17, 200] = float("nan")
+
+
+def _inf_bias(sd):
+    sd["pi_head.1.bias"][8] = float("inf")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("mutate", [_nan_policy_head, _nan_in_trunk, _inf_bias], ids=lambda f: f.__name__.strip("_"))
+def test_non_finite_weights_keep_every_move_legal(model_env, mutate, dtype):
+    """include/qttt_policy_rollout.h: when no comparison of the running sum succeeds (a NaN or an infinite exp-sum), the
+    move is the largest legal action.  The host model takes each move from the trace (it asserts that the move is
+    legal on the replayed position) unless the rule fixes it: an all-NaN head or trunk, or +inf at a legal action,
+    makes the sum NaN."""
+    sd = {k: t.clone() for k, t in random_state_dict(7).items()}
+    mutate(sd)
+    out = _launch(model_env, sd, dtype)
+    trace = out["trace"].cpu().numpy().reshape(-1, 9)
+
+    def choose(j, p, legal, u):
+        if mutate is not _inf_bias or legal >> 8 & 1:
+            return legal.bit_length() - 1
+        return int(trace[j, p]) & 63 if trace[j, p] != 0xFF else -1
+
+    model = host_playout(model_env, MODEL_SIMS, MODEL_T0, choose)
+    _assert_launch_equals(out, model)
+    if mutate is _inf_bias:                               # both branches of the model were taken
+        first = model[3][np.repeat(np.arange(MODEL_BOARDS), MODEL_SIMS)].reshape(-1)
+        assert ((first >> np.uint64(8)) & np.uint64(1)).any() and (trace[:, 1:] != 0xFF).any()
 
 
 def test_alphazero_example_beats_random():

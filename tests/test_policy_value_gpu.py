@@ -20,6 +20,12 @@ ALL = ("value", "logits", "probs")
 # run measured f32 7.7e-7 / 6.2e-6 / 1.3e-6 and bf16 0.0071 / 0.022 / 0.0029 there: DESIGN.md §10)
 BOUNDS = {torch.float32: (1e-4, 1e-4, 1e-5), torch.bfloat16: (0.04, 0.1, 0.02)}
 FIXTURE_BOUNDS = {torch.float32: (5e-6, 2e-5, 5e-6), torch.bfloat16: (0.025, 0.06, 0.01)}
+# the default-init weights of random_state_dict give logits within a range of about 0.2, where BOUNDS' bf16 0.1 binds
+# nothing.  The CPU emulation of the bf16 contract (nn_reference64.forward_contract, 30 000 random-play positions, five
+# of the seeds below) differs from float64 by at most 2.9e-4 / 3.0e-4 / 6.7e-5; four times that allows for the larger
+# maximum over 1 M boards and is still below 1 % of the logit range.  tests/test_policy_value_numerics_gpu.py holds the
+# kernel to the contract itself.
+RANDOM_BOUNDS = {torch.float32: BOUNDS[torch.float32], torch.bfloat16: (1.2e-3, 1.2e-3, 3e-4)}
 ARGMAX_GAP = {torch.float32: 1e-3, torch.bfloat16: 0.2}
 DTYPES = [torch.float32, torch.bfloat16]
 
@@ -91,7 +97,7 @@ def test_sizes_against_float64(golden, n, dtype, weights):
     out = env.evaluate(_net(sd, dtype), rows=ALL)
     ref = forward64_chunked(sd, env.encode(with_mask=False))
     torch.cuda.synchronize()
-    _compare(out, ref, dtype)
+    _compare(out, ref, dtype, BOUNDS if weights == "fixture" else RANDOM_BOUNDS)
     _argmax_agrees(out["logits"], ref[1], dtype)
 
 
