@@ -95,11 +95,16 @@ class OracleBoards:
     def reset(self):
         lib().qo_reset_batch(_ptr(self.b), self.n)
 
-    def copy(self):
-        o = OracleBoards.__new__(OracleBoards)
-        o.n = self.n
-        o.b = self.b.copy()
+    @classmethod
+    def from_records(cls, recs):
+        """The boards `recs`, a sequence of BOARD_DTYPE records or an array of them, copied."""
+        o = cls.__new__(cls)
+        o.b = np.array(recs, dtype=BOARD_DTYPE).reshape(-1)
+        o.n = len(o.b)
         return o
+
+    def copy(self):
+        return OracleBoards.from_records(self.b)
 
     def step(self, actions, bits=None, seed=0, step_idx=0, board_offset=0, auto_reset=False):
         actions = np.ascontiguousarray(actions, dtype=np.uint8).reshape(self.n, 2)

@@ -86,21 +86,24 @@ class TreeSearch(LibCaller):
         if self._bound + 2 * r > self.capacity:
             raise ValueError("%d rollouts could use %d nodes, more than capacity %d"
                              % (r, self._bound + 2 * r, self.capacity))
-        G, cap, S = self.num_games, self.capacity, self.num_simulations
-        tree, leaf = self.tree.data_ptr(), self.leaf.state.data_ptr()
-        stride = S * _native.SIM_STRIDE
         for _ in range(r):
-            k = self.rollout_idx
-            self._call("qttt_tree_select", tree, G, cap, self.seed, k, self.board_offset, self.c_puct, leaf)
-            if self.net is None:
-                self.leaf.rollout_many(S, step_idx0=k * stride, out=self._out)
-                self._call("qttt_tree_backup", tree, G, cap, self._out.data_ptr(), S, None)
-            else:
-                self.leaf.rollout_policy(self.net, S, step_idx0=k * stride, out=self._out)
-                self._call("qttt_tree_backup", tree, G, cap, self._out["result"].data_ptr(), S,
-                           self._out["probs"].data_ptr())
-            self.rollout_idx = k + 1
+            self._rollout()
             self._bound += 2
+
+    def _rollout(self):
+        """One rollout, without contemplate's bounds: select, the playouts from the leaves, backup."""
+        G, cap, S, k = self.num_games, self.capacity, self.num_simulations, self.rollout_idx
+        tree, leaf = self.tree.data_ptr(), self.leaf.state.data_ptr()
+        step_idx0 = k * S * _native.SIM_STRIDE
+        self._call("qttt_tree_select", tree, G, cap, self.seed, k, self.board_offset, self.c_puct, leaf)
+        if self.net is None:
+            self.leaf.rollout_many(S, step_idx0=step_idx0, out=self._out)
+            self._call("qttt_tree_backup", tree, G, cap, self._out.data_ptr(), S, None)
+        else:
+            self.leaf.rollout_policy(self.net, S, step_idx0=step_idx0, out=self._out)
+            self._call("qttt_tree_backup", tree, G, cap, self._out["result"].data_ptr(), S,
+                       self._out["probs"].data_ptr())
+        self.rollout_idx = k + 1
 
     def root_stats(self):
         """The roots' statistics: N i32[G,36], W / Q / P f64[G,36], Ntot i32[G], choose u8[G], nodes_used i32[G],

@@ -7,14 +7,13 @@ import torch
 
 import selfplay_model
 import tree_layout
-from nn_reference64 import golden_state_dict, load_golden
-from test_tree_gpu import _env_from_arrays, _export, _random_positions
+from tree_harness import DEV, env_from_arrays, export, random_positions
+from tree_harness import net as _net
 
 from qtttgym_amd import SelfPlay, TreeSearch, VecEnv
 from qtttgym_amd.actions import action36_to_pairs, legal_mask_to_bool
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 ROWS = 10
 KEYS = ("pi", "mask", "done", "v", "action36", "length", "winner", "actions")
 
@@ -60,7 +59,7 @@ def test_whole_games_match_the_model_bit_for_bit(G):
             assert np.array_equal(words[t, 0, live], P) and np.array_equal(words[t, 1, live], Q), t
         rest = [g for g in range(G) if g not in live]
         assert not words[t][:, rest].any(), t
-    ex = _export(sp.env)
+    ex = export(sp.env)
     for key, val in (("board", ref_env.board), ("moves", ref_env.moves), ("n_moves", ref_env.n_moves),
                      ("qmask", ref_env.qmask), ("n_q", ref_env.n_q)):
         assert np.array_equal(ex[key], val.astype(ex[key].dtype)), key
@@ -132,9 +131,7 @@ def test_play_is_the_hand_loop_of_the_public_calls(played_130):
 
 
 def test_play_with_the_network_is_the_hand_loop_of_the_public_calls():
-    from qtttgym_amd import PolicyValueNet
-    net = PolicyValueNet(golden_state_dict(load_golden()), device=DEV, dtype=torch.float32)
-    _assert_play_is_the_hand_loop(65, 6, 2, net, 5)
+    _assert_play_is_the_hand_loop(65, 6, 2, _net(torch.float32), 5)
 
 
 # ---------------------------------------------------------------- invariants
@@ -246,7 +243,7 @@ def test_flat_is_the_reference_batch_in_game_major_order(played_130):
 def searched_positions():
     """130 positions 0..7 plies deep, searched with 40 rollouts: (tree, N i32[G,36], legal bool[G,36], terminal[G])."""
     G, R = 130, 40
-    env = _env_from_arrays(_random_positions(G, 130))
+    env = env_from_arrays(random_positions(G, 130))
     tree = TreeSearch(G, capacity=2 * R + 2, num_simulations=2, seed=9, device=DEV)
     tree.reset(env)
     tree.contemplate(R)

@@ -1,5 +1,5 @@
 """CPU tests of the search trees' compaction (include/qttt_tree_compact.h, TreeSearch.compact): the Python model of the
-stable renumbering (tests/tree_compact_model.py) against the node counts the reference's own MCTS leaves after its
+stable renumbering (TreeModel.compact, tests/tree_model.py) against the node counts the reference's own MCTS leaves after its
 sync has pruned (tests/golden/tree_traces.npz), a search that compacts after every move against one that never does,
 the header, the binding table and the argument errors.  No GPU."""
 import ctypes
@@ -18,26 +18,14 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "tree_traces.npz")
 HEADER = os.path.join(ROOT, "include", "qttt_tree_compact.h")
 
 
-def _positions(m):
-    import tree_model
-    return tree_model._batch([st["nodes"][st["root"]].rec for st in m.games], m.dtype)
-
-
-def _game_view(st):
-    """One game of the model as plain values that compare with ==, node by node."""
-    return [(n.rec.tobytes(), n.turn, n.terminal, n.winner, n.legal, n.Ntot, n.N, n.W, n.children, n.P,
-             None if n.probs is None else n.probs.tobytes()) for n in st["nodes"]]
-
-
 def test_model_compact_leaves_the_node_count_the_reference_has_after_its_sync_pruned():
     """The fixture's last record is taken `after` rollouts after the reference's sync, whose _prune (mcts.py:222-231,
     330-337) has dropped every node outside the new root's subtree: len(strat.nodes) there is the kept subtree plus
     what those rollouts added.  The model reaches that count only with compact() after its sync."""
-    import tree_compact_model
     import tree_model
     shrank = 0
     for grp in tree_model.golden_groups(GOLDEN):
-        m = tree_compact_model.TreeCompactModel(grp["n_sims"], seed=grp["seed"], board_offset=grp["offset"])
+        m = tree_model.TreeModel(grp["n_sims"], seed=grp["seed"], board_offset=grp["offset"])
         m.reset(grp["roots"])
         rec = grp["records"]
         done = 0
@@ -46,7 +34,7 @@ def test_model_compact_leaves_the_node_count_the_reference_has_after_its_sync_pr
                 m.rollout()
             done = c
             assert np.array_equal(m.root_stats()["nodes_used"], rec["n_nodes"][:, ci]), (ci, c)
-        new, _ = tree_model.after_move(_positions(m), grp["sync_action"], grp["sync_bit"])
+        new, _ = tree_model.after_move(m.root_positions(), grp["sync_action"], grp["sync_bit"])
         m.sync(new)
         moved = grp["sync_action"] != 255
         before = m.root_stats()
@@ -69,20 +57,19 @@ def test_model_compact_leaves_the_node_count_the_reference_has_after_its_sync_pr
 
 
 def test_compact_is_a_stable_renumbering_that_keeps_the_tree_invariants():
-    import tree_compact_model
     import tree_model
     grp = tree_model.golden_groups(GOLDEN)[0]
-    m = tree_compact_model.TreeCompactModel(grp["n_sims"], seed=grp["seed"], board_offset=grp["offset"])
+    m = tree_model.TreeModel(grp["n_sims"], seed=grp["seed"], board_offset=grp["offset"])
     m.reset(grp["roots"])
     for _ in range(40):
         m.rollout()
     # already compact (root 0, every node reachable): nothing changes, the recorded path included
-    snap = [(_game_view(st), st["root"], list(st["path"]), st["leaf"]) for st in m.games]
+    snap = [tree_model.game_view(d) for d in m.dump()]
     m.compact()
-    assert snap == [(_game_view(st), st["root"], list(st["path"]), st["leaf"]) for st in m.games]
-    new, _ = tree_model.after_move(_positions(m), grp["sync_action"], grp["sync_bit"])
+    assert snap == [tree_model.game_view(d) for d in m.dump()]
+    new, _ = tree_model.after_move(m.root_positions(), grp["sync_action"], grp["sync_bit"])
     m.sync(new)
-    old = [(tree_compact_model.reachable(st), list(st["nodes"])) for st in m.games]
+    old = [(tree_model.reachable(st), list(st["nodes"])) for st in m.games]
     stats = m.root_stats()
     m.compact()
     pairs = 0
@@ -101,20 +88,19 @@ def test_compact_is_a_stable_renumbering_that_keeps_the_tree_invariants():
     after = m.root_stats()
     for k in ("N", "W", "Q", "P", "Ntot", "choose"):
         assert np.array_equal(stats[k], after[k]), k
-    snap = [_game_view(st) for st in m.games]
+    snap = [tree_model.game_view(d) for d in m.dump()]
     m.compact()                                                                      # twice: nothing left to do
-    assert snap == [_game_view(st) for st in m.games]
+    assert snap == [tree_model.game_view(d) for d in m.dump()]
 
 
 def test_a_search_that_compacts_after_every_sync_goes_on_as_one_that_never_does():
     """Full games from the empty board, S = 4: model A never compacts, model B compacts after every sync.  Even games
     play choose(), odd games the least visited legal action (often a child never expanded: a fresh root, 1 node)."""
     import oracle
-    import tree_compact_model
     import tree_model
     G, R, S = 6, 24, 4
-    A = tree_compact_model.TreeCompactModel(S, seed=21, board_offset=3)
-    B = tree_compact_model.TreeCompactModel(S, seed=21, board_offset=3)
+    A = tree_model.TreeModel(S, seed=21, board_offset=3)
+    B = tree_model.TreeModel(S, seed=21, board_offset=3)
     A.reset(oracle.OracleBoards(G))
     B.reset(oracle.OracleBoards(G))
     fresh = moves = 0
@@ -134,7 +120,7 @@ def test_a_search_that_compacts_after_every_sync_goes_on_as_one_that_never_does(
         for g, n in enumerate(roots):
             if not frozen[g]:
                 act[g] = sa["choose"][g] if g % 2 == 0 else min(n.legal, key=lambda a: n.N[a])
-        new, _ = tree_model.after_move(_positions(A), act, ((np.arange(G) // 2 + moves) % 2).astype(np.uint8))
+        new, _ = tree_model.after_move(A.root_positions(), act, ((np.arange(G) // 2 + moves) % 2).astype(np.uint8))
         A.sync(new)
         B.sync(new)
         B.compact()
@@ -146,7 +132,7 @@ def test_a_search_that_compacts_after_every_sync_goes_on_as_one_that_never_does(
             assert np.array_equal(sa[k], sb[k]), (k, moves)
         # the kept subtrees are the same trees, node for node, up to the renumbering
         for a, b in zip(A.games, B.games):
-            keep = tree_compact_model.reachable(a)
+            keep = tree_model.reachable(a)
             fwd = {o: i for i, o in enumerate(keep)}
             for i, o in enumerate(keep):
                 na, nb = a["nodes"][o], b["nodes"][i]

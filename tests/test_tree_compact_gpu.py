@@ -1,49 +1,27 @@
 """qttt_tree_compact / TreeSearch.compact on the MI355X: the compacted buffer compared node by node with the Python
-model of the renumbering (tests/tree_compact_model.py), full games in which a tree that compacts after every move
-computes bit for bit what a tree eight times its size computes without compacting, and the edges (straight after reset,
-twice, a game that did not move, a fresh root, a set overflow flag, no games, a collapse pair, the host's bound).
+model of the renumbering (TreeModel.compact, tests/tree_model.py), full games in which a tree that compacts after
+every move computes bit for bit what a tree eight times its size computes without compacting, and the edges (straight
+after reset, twice, a game that did not move, a fresh root, a set overflow flag, no games, a collapse pair, the host's
+bound).
 
-Every test owns its tree buffer, filled with a sentinel byte before qttt_tree_reset; what lies at or beyond `used` is
-unspecified after a compaction and is not compared."""
+Every test owns its tree buffer (tree_harness.search), filled with a sentinel byte before qttt_tree_reset; what lies at
+or beyond `used` is unspecified after a compaction and is not compared, the headers' padding and the bytes after the
+tree are."""
 import numpy as np
 import pytest
 import torch
 
-import oracle
-import tree_compact_model
 import tree_layout
 import tree_model
-from test_tree_gpu import _env_from_arrays, _export, _stats
-from test_tree_whole_gpu import _boards, _net, _rollout
+from tree_harness import (DEV, SENTINEL, assert_stats_equal, boards, export, move, rollout, search, stats,
+                          two_plies_in)
+from tree_harness import net as _net
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SENTINEL = 0xA5
 STAT_KEYS = ("N", "W", "Q", "P", "Ntot", "choose")
 
 
 # ---------------------------------------------------------------- helpers
-def _two_plies_in(G, seed):
-    """G positions two uniform-random plies from the empty board (the oracle's draws), as import arrays."""
-    ob = oracle.OracleBoards(G)
-    for t in range(2):
-        ob.step(ob.sample_actions(seed, t), None, seed, t)
-    return {"board": ob.board, "moves": ob.moves, "n_moves": ob.n_moves, "qmask": ob.qmask, "n_q": ob.n_q}
-
-
-def _search(arrays, capacity, S, net=None, seed=5, offset=17, model_capacity=None):
-    """A TreeSearch over a sentinel-filled buffer, its env, and the model, both reset at the positions `arrays`."""
-    from qtttgym_amd import TreeSearch
-    env = _env_from_arrays(arrays)
-    G = env.num_envs
-    t = TreeSearch(G, capacity=capacity, num_simulations=S, net=net, seed=seed, board_offset=offset, device=DEV)
-    t.tree = torch.full((tree_layout.tree_bytes(G, capacity),), SENTINEL, dtype=torch.uint8, device=DEV)
-    t.reset(env)
-    m = tree_compact_model.TreeCompactModel(S, seed=seed, board_offset=offset, capacity=model_capacity)
-    m.reset(_boards(arrays))
-    return t, m, env
-
-
 def _plan_moves(m, stay=(), special=True):
     """One move per game from the model's trees: the action and collapse bit whose child holds the largest subtree,
     preferring one with a collapse pair in it.  With `special`, game 0 plays choose() instead and game 1 an action
@@ -64,7 +42,7 @@ def _plan_moves(m, stay=(), special=True):
         best = None
         for a in root.legal:
             for b, c in enumerate(root.children[a] or ()):
-                sub = tree_compact_model.reachable({"nodes": st["nodes"], "root": c})
+                sub = tree_model.reachable({"nodes": st["nodes"], "root": c})
                 pair = any(len(k or ()) == 2 for i in sub for k in st["nodes"][i].children)
                 if best is None or (pair, len(sub)) > best[0]:
                     best = ((pair, len(sub)), a, b)
@@ -73,19 +51,10 @@ def _plan_moves(m, stay=(), special=True):
     return act, bits
 
 
-def _move(t, m, env, act, bits):
-    """The games play `act` with collapse bits `bits`; the tree and the model sync."""
-    from qtttgym_amd.actions import action36_to_pairs
-    env.step_raw(action36_to_pairs(torch.as_tensor(act, device=DEV)).contiguous(), torch.as_tensor(bits, device=DEV))
-    t.sync(env)
-    m.sync(_boards(_export(env)))
-
-
 def _check(t, m):
-    n = tree_compact_model.assert_live_tree_equals_model(t.tree.cpu().numpy(), t.num_games, t.capacity, m, DEV)
-    st, ref = _stats(t), m.root_stats()
-    for k in STAT_KEYS + ("nodes_used", "overflow"):
-        assert np.array_equal(st[k], ref[k]), k
+    n = tree_layout.assert_tree_equals_model(t.tree.cpu().numpy(), t.num_games, t.capacity, m, SENTINEL, DEV,
+                                             compacted=True)
+    assert_stats_equal(stats(t), m.root_stats(), STAT_KEYS + ("nodes_used", "overflow"))
     return n
 
 
@@ -102,11 +71,11 @@ def _live_bytes(t):
 @pytest.mark.parametrize("network", [False, True])
 def test_every_node_of_the_compacted_trees_equals_the_model(network):
     G, capacity, S, R = 5, 96, 4, 24
-    t, m, env = _search(_two_plies_in(G, 31), capacity, S, net=_net(torch.float32) if network else None)
+    t, m, env = search(two_plies_in(G, 31), capacity, S, net=_net(torch.float32) if network else None)
     for _ in range(R):
-        _rollout(t, m)
+        rollout(t, m)
     act, bits = _plan_moves(m, stay=(4,))
-    _move(t, m, env, act, bits)
+    move(t, m, env, act, bits)
     before = m.root_stats()
     kept = m.reachable_counts()
     t.compact()
@@ -114,7 +83,7 @@ def test_every_node_of_the_compacted_trees_equals_the_model(network):
     assert t._bound == int(kept.max())
     network_rows = _check(t, m)
     assert (network_rows > 0) == network
-    st = _stats(t)
+    st = stats(t)
     assert np.array_equal(st["nodes_used"], kept)
     assert kept[4] == before["nodes_used"][4] and act[4] == 255     # the game that did not move keeps every node
     assert (kept[:4] < before["nodes_used"][:4]).all()              # the others give nodes back
@@ -124,10 +93,10 @@ def test_every_node_of_the_compacted_trees_equals_the_model(network):
     # the search goes on, in lockstep with the model, on the compacted trees: another move's rollouts, a move, a
     # compaction of trees that hold carried nodes and new ones
     for _ in range(R):
-        _rollout(t, m)
+        rollout(t, m)
     _check(t, m)
     act, bits = _plan_moves(m)
-    _move(t, m, env, act, bits)
+    move(t, m, env, act, bits)
     t.compact()
     m.compact()
     _check(t, m)
@@ -190,19 +159,19 @@ def test_full_games_compacting_after_every_move_equal_full_games_that_never_comp
 # ---------------------------------------------------------------- (3) edges
 def test_compact_straight_after_reset_and_twice():
     G, S = 5, 4
-    t, m, env = _search(_two_plies_in(G, 32), 96, S)
+    t, m, env = search(two_plies_in(G, 32), 96, S)
     snap = t.tree.cpu().numpy().copy()
     t.compact()
     assert np.array_equal(t.tree.cpu().numpy(), snap)               # 1 node per game: not a byte changes
-    assert (_stats(t)["nodes_used"] == 1).all() and t._bound == 1
+    assert (stats(t)["nodes_used"] == 1).all() and t._bound == 1
     for _ in range(24):
-        _rollout(t, m)
+        rollout(t, m)
     snap = t.tree.cpu().numpy().copy()
     t.compact()                                                     # no game moved: compact already, the path stays
     assert np.array_equal(t.tree.cpu().numpy(), snap)
     _check(t, m)
     act, bits = _plan_moves(m)
-    _move(t, m, env, act, bits)
+    move(t, m, env, act, bits)
     t.compact()
     m.compact()
     _check(t, m)
@@ -214,11 +183,11 @@ def test_compact_straight_after_reset_and_twice():
 
 def test_a_kept_subtree_with_a_collapse_pair_keeps_it_adjacent_with_bit_30():
     G, S = 5, 4
-    t, m, env = _search(_two_plies_in(G, 33), 96, S, seed=9, offset=4)
+    t, m, env = search(two_plies_in(G, 33), 96, S, seed=9, offset=4)
     for _ in range(40):
-        _rollout(t, m)
+        rollout(t, m)
     act, bits = _plan_moves(m, special=False)
-    _move(t, m, env, act, bits)
+    move(t, m, env, act, bits)
     t.compact()
     m.compact()
     _check(t, m)
@@ -239,20 +208,20 @@ def test_a_kept_subtree_with_a_collapse_pair_keeps_it_adjacent_with_bit_30():
 
 def test_a_set_overflow_flag_outlives_the_compaction():
     G, S, capacity = 5, 2, 8
-    t, m, env = _search(_two_plies_in(G, 34), capacity, S, seed=8, offset=1, model_capacity=capacity)
+    t, m, env = search(two_plies_in(G, 34), capacity, S, seed=8, offset=1, model_capacity=capacity)
     for _ in range(16):
-        _rollout(t, m, bounded=False)               # the pool is too small: the well-defined overflow flag is set
-    flagged = _stats(t)["overflow"].copy()
+        rollout(t, m, bounded=False)               # the pool is too small: the well-defined overflow flag is set
+    flagged = stats(t)["overflow"].copy()
     assert flagged.any()
     act, bits = _plan_moves(m, special=False)       # onto expanded children: a full pool could not hold a fresh root
     from qtttgym_amd.actions import action36_to_pairs
     env.step_raw(action36_to_pairs(torch.as_tensor(act, device=DEV)).contiguous(), torch.as_tensor(bits, device=DEV))
     t._call("qttt_tree_sync", t.tree.data_ptr(), G, capacity, env.state.data_ptr())        # TreeSearch.sync less its bound
-    m.sync(_boards(_export(env)))
+    m.sync(boards(export(env)))
     t.compact()
     m.compact()
     _check(t, m)
-    st = _stats(t)
+    st = stats(t)
     assert np.array_equal(st["overflow"], flagged)
     assert (st["nodes_used"] < capacity).all()
 
@@ -264,7 +233,7 @@ def test_no_games_and_the_bound_without_a_read_back(monkeypatch):
     t.compact()
     assert t._bound == 1
     assert t._lib.qttt_tree_compact(None, 0, 8, None, None) == 0
-    t, m, env = _search(_two_plies_in(5, 35), 96, 4)
+    t, m, env = search(two_plies_in(5, 35), 96, 4)
     t.contemplate(10)
     bound = t._bound
     monkeypatch.setattr(t, "_root", lambda **kw: pytest.fail("update_bound=False must not read anything back"))

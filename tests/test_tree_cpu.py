@@ -41,18 +41,13 @@ def test_model_reproduces_the_reference_mcts_traces():
             assert np.array_equal(st["nodes_used"], rec["n_nodes"][:, ci])
         assert np.array_equal(m.root_stats()["choose"][grp["sync_action"] != 255],
                               grp["sync_action"][grp["sync_action"] != 255])
-        new, _ = tree_model.after_move(_positions(m), grp["sync_action"], grp["sync_bit"])
+        new, _ = tree_model.after_move(m.root_positions(), grp["sync_action"], grp["sync_bit"])
         m.sync(new)
         for _ in range(grp["after"]):
             m.rollout()
         st = m.root_stats()
         for k in ("N", "W", "Q", "Ntot", "choose"):
             assert np.array_equal(st[k], rec[k][:, -1]), k
-
-
-def _positions(m):
-    import tree_model
-    return tree_model._batch([st["nodes"][st["root"]].rec for st in m.games], m.dtype)
 
 
 def test_header_is_plain_c99_and_included_by_qttt_h():
@@ -187,21 +182,15 @@ def test_uniform_prior_and_sqrt_rounding_on_the_host_side():
     assert math.sqrt(2) == float(np.sqrt(np.float64(2)))
 
 
-def _game_view(d):
-    """One game of TreeModel.dump() as plain values that compare with == (the records as bytes)."""
-    return (d["used"], d["root"], d["path"], d["leaf"],
-            [(n["rec"].tobytes(), n["turn"], n["terminal"], n["winner"], n["legal"], n["Ntot"], n["N"], n["W"],
-              n["children"], n["P"]) for n in d["nodes"]])
-
-
 @pytest.mark.parametrize("capacity", [1, 2, 3, 8])
 def test_model_with_capacity_diverges_exactly_at_the_first_expansion_that_does_not_fit(capacity):
     """include/qttt_tree.h's overflow rule in the model: TreeModel(capacity=c) is TreeModel() until, per game, the first
     expansion whose nodes do not fit; that select ends on the node it stood on, without the edge, nothing is allocated,
     and the flag stays."""
+    import oracle
     import tree_model
     grp = tree_model.golden_groups(GOLDEN)[0]
-    roots = tree_model._batch(list(grp["roots"].b[:12]), grp["roots"].b.dtype)
+    roots = oracle.OracleBoards.from_records(grp["roots"].b[:12])
     kw = dict(seed=grp["seed"], board_offset=grp["offset"])
     free, capped = tree_model.TreeModel(grp["n_sims"], **kw), tree_model.TreeModel(grp["n_sims"], capacity=capacity, **kw)
     free.reset(roots)
@@ -217,7 +206,7 @@ def test_model_with_capacity_diverges_exactly_at_the_first_expansion_that_does_n
                 assert b[g]["overflow"] and b[g]["used"] <= capacity          # sticky, and never past the pool
                 continue
             if a[g]["used"] <= capacity:                                      # the expansion (if any) fits
-                assert not b[g]["overflow"] and _game_view(a[g]) == _game_view(b[g]), (k, g)
+                assert not b[g]["overflow"] and tree_model.game_view(a[g]) == tree_model.game_view(b[g]), (k, g)
                 assert lf.b[g].tobytes() == lc.b[g].tobytes()
                 continue
             # the first expansion that does not fit: the path loses its last edge, the leaf is that edge's node
@@ -226,7 +215,7 @@ def test_model_with_capacity_diverges_exactly_at_the_first_expansion_that_does_n
             assert b[g]["path"] == a[g]["path"][:-1] and b[g]["leaf"] == a[g]["path"][-1][0], (k, g)
             assert b[g]["nodes"][b[g]["leaf"]]["P"] is not None
             # nothing but the path and the flag changed in that game
-            assert _game_view(b[g])[4] == _game_view(before[g])[4], (k, g)
+            assert tree_model.game_view(b[g])[4] == tree_model.game_view(before[g])[4], (k, g)
         free.backup(free.playouts(lf))
         capped.backup(capped.playouts(lc))
     assert any(diverged) and capped.root_stats()["overflow"].tolist() == diverged
@@ -236,7 +225,7 @@ def test_model_with_capacity_diverges_exactly_at_the_first_expansion_that_does_n
     lmask = [[a for a in range(36) if st0["N"][g, a] == 0 and a in capped.games[g]["nodes"][capped.games[g]["root"]].legal]
              for g in range(roots.n)]
     act = np.array([lm[-1] if lm else 255 for lm in lmask], dtype=np.uint8)      # a never-visited action: no child
-    new, _ = tree_model.after_move(_positions(capped), act, np.zeros(roots.n, np.uint8))
+    new, _ = tree_model.after_move(capped.root_positions(), act, np.zeros(roots.n, np.uint8))
     roots_before = [st["root"] for st in capped.games]
     capped.sync(new)
     d = capped.dump()
@@ -245,3 +234,96 @@ def test_model_with_capacity_diverges_exactly_at_the_first_expansion_that_does_n
             assert d[g]["overflow"] and d[g]["root"] == roots_before[g] and d[g]["used"] == capacity, g
     capped.reset(roots)
     assert not capped.root_stats()["overflow"].any()
+
+
+# ---------------------------------------------------------------- the whole-tree comparison itself (tests/tree_layout.py)
+def _stub_pack(ob):
+    """Stands in for the device's packed planes: two words per position that depend on every byte of its record."""
+    import zlib
+    return (np.array([zlib.crc32(r.tobytes()) for r in ob.b], dtype=np.uint64),
+            np.array([zlib.adler32(r.tobytes()) for r in ob.b], dtype=np.uint64))
+
+
+def _encode(model, capacity, sentinel, tail):
+    """The model's trees written node by node, as include/qttt_tree.h lays them out, into a buffer filled with
+    `sentinel` that ends `tail` bytes after the tree."""
+    import oracle
+    import tree_layout as tl
+    dump = model.dump()
+    buf = np.full(tl.tree_bytes(len(dump), capacity) + tail, sentinel, dtype=np.uint8)
+    games, nodes, priors, _ = tl.decode(buf, len(dump), capacity)
+    for g, d in enumerate(dump):
+        leaf = d["nodes"][d["leaf"]]
+        games["used"][g], games["root"][g] = d["used"], d["root"]
+        games["depth"][g], games["leaf"][g] = len(d["path"]), d["leaf"]
+        games["flags"][g] = (tl.GAME_OVERFLOW * d["overflow"] + tl.GAME_LEAF_TURN * leaf["turn"]
+                             + tl.GAME_LEAF_TERMINAL * leaf["terminal"])
+        for k, (i, a) in enumerate(d["path"]):
+            games["path_node"][g, k], games["path_action"][g, k] = i, a
+        for i, n in enumerate(d["nodes"]):
+            P, Q = _stub_pack(oracle.OracleBoards.from_records([n["rec"]]))
+            rec = nodes[g, i]
+            rec["P"], rec["Q"], rec["legal"], rec["Ntot"] = P[0], Q[0], n["legal"], n["Ntot"]
+            rec["flags"] = (tl.NODE_PRIORS * (n["P"] is not None) + tl.NODE_UNIFORM * isinstance(n["P"], str)
+                            + tl.NODE_TERMINAL * n["terminal"] + tl.NODE_TURN * n["turn"] + ((n["winner"] + 1) << 8))
+            for a in range(36):
+                kids = n["children"][a]
+                rec["slots"][a] = (n["W"][a], n["N"][a], -1 if not kids else kids[0] + tl.CHILD_PAIR * (len(kids) == 2))
+            if isinstance(n["P"], np.ndarray):
+                priors[g, i] = n["P"]
+    return buf
+
+
+def test_the_whole_tree_comparison_passes_on_the_model_and_fails_on_every_single_change():
+    """tree_layout.assert_tree_equals_model on a buffer encoded from the model (uniform and network priors, a sync):
+    it passes, and each single change of the buffer fails it; with compacted=True only the changes where a compaction
+    leaves the bytes unspecified pass."""
+    import oracle
+    import tree_layout as tl
+    import tree_model
+    G, capacity, sentinel, tail = 2, 40, 0xA5, 64
+    grp = tree_model.golden_groups(GOLDEN)[0]
+    m = tree_model.TreeModel(grp["n_sims"], seed=grp["seed"], board_offset=grp["offset"])
+    m.reset(oracle.OracleBoards.from_records(grp["roots"].b[:G]))
+    rng = np.random.default_rng(3)
+    for k in range(12):                              # uniform priors first, then rows a network could have written
+        m.backup(m.playouts(m.select()), None if k < 6 else rng.random((G, 36)).astype(np.float32))
+    new, _ = tree_model.after_move(m.root_positions(), m.root_stats()["choose"], np.zeros(G, np.uint8))
+    m.sync(new)
+    buf = _encode(m, capacity, sentinel, tail)
+    dump = m.dump()
+    used, kinds = dump[0]["used"], [type(n["P"]) for n in dump[0]["nodes"]]
+    assert used < capacity and dump[0]["path"] and {np.ndarray, str, type(None)} <= set(kinds)
+    i, bare = kinds.index(np.ndarray), kinds.index(type(None))       # game 0: a node with network priors, one without
+
+    def check(b, compacted):
+        return tl.assert_tree_equals_model(b, G, capacity, m, sentinel, compacted=compacted, pack=_stub_pack)
+
+    def views(b):
+        games, nodes, priors, rest = tl.decode(b, G, capacity)
+        return {"games": games, "nodes": nodes, "slots": nodes["slots"], "W": nodes["slots"]["W"].view(np.int64),
+                "priors": priors.view(np.uint32), "node bytes": nodes.view(np.uint8).reshape(G, capacity, -1),
+                "priors bytes": priors.view(np.uint8).reshape(G, capacity, -1), "tail": rest}
+
+    rows = sum(isinstance(n["P"], np.ndarray) for d in dump for n in d["nodes"])
+    assert check(buf, False) == rows and check(buf, True) == rows
+    # one bit at a time: (view, field, index, whether compacted=True must still see it)
+    changes = [("games", f, 1, True) for f in ("used", "root", "depth", "leaf", "flags")]
+    changes += [("games", f, (0, 0), True) for f in ("path_node", "path_action", "pad")] + [("games", "pad2", (1, 45), True)]
+    changes += [("nodes", f, (0, i), True) for f in ("P", "Q", "legal", "Ntot", "flags")]
+    changes += [("slots", "N", (0, i, 7), True), ("W", None, (0, i, 7), True), ("slots", "child", (0, i, 7), True)]
+    changes += [("priors", None, (0, i, 35), True), ("tail", None, tail - 1, True)]
+    changes += [("node bytes", None, (0, used, 0), False), ("priors bytes", None, (0, capacity - 1, -1), False),
+                ("priors bytes", None, (0, bare, 0), False)]
+    for view, field, index, seen_when_compacted in changes:
+        b = buf.copy()
+        target = views(b)[view] if field is None else views(b)[view][field]
+        target[index] ^= 1
+        assert (b != buf).sum() == 1, (view, field)
+        with pytest.raises(AssertionError):
+            check(b, False)
+        if seen_when_compacted:
+            with pytest.raises(AssertionError):
+                check(b, True)
+        else:
+            check(b, True)

@@ -1,6 +1,6 @@
 """qtttgym_amd.TreeSearch on the MI355X: the reference MCTS's own traces (tests/golden/tree_traces.npz), lockstep with
-the float64 model (tests/tree_model.py) in both playout modes, ragged batches, invariants at 65 536 games, sync, the
-select kernel's sqrt, and playing strength against a random opponent."""
+the float64 model (tests/tree_model.py, driven by tests/tree_harness.py) in both playout modes, ragged batches,
+invariants at 65 536 games, sync, the select kernel's sqrt, and playing strength against a random opponent."""
 import math
 import os
 import subprocess
@@ -12,46 +12,13 @@ import torch
 
 import oracle
 import tree_model
-from nn_reference64 import golden_state_dict, load_golden
+from tree_harness import (DEV, assert_stats_equal, boards, env_from_arrays, export, random_positions, rollout, search,
+                          stats)
+from tree_harness import net as _net
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
 GOLDEN = os.path.join(ROOT, "tests", "golden", "tree_traces.npz")
-
-
-def _env_from_arrays(arrays, seed=0):
-    from qtttgym_amd import VecEnv
-    env = VecEnv(len(arrays["n_moves"]), device=DEV, seed=seed)
-    env.import_boards(arrays["moves"], arrays["n_moves"], arrays["board"], np.asarray(arrays["qmask"]).astype(np.int16),
-                      arrays["n_q"])
-    return env
-
-
-def _export(env):
-    ex = env.export_boards()
-    return {k: v.cpu().numpy() for k, v in ex.items()}
-
-
-def _random_positions(G, seed):
-    """G positions 0..7 random plies deep (step_random_many), as import arrays."""
-    from qtttgym_amd import VecEnv
-    env = VecEnv(G, device=DEV, seed=seed)
-    snaps = [_export(env)]
-    for _ in range(7):
-        env.step_random_many(1)
-        snaps.append(_export(env))
-    depth = np.random.default_rng(seed).integers(0, len(snaps), G)
-    return {k: np.stack([snaps[d][k][g] for g, d in enumerate(depth)]) for k in snaps[0]}
-
-
-def _stats(t):
-    return {k: v.cpu().numpy() for k, v in t.root_stats().items()}
-
-
-def _model_stats_equal(dev, ref, keys=("N", "W", "Q", "Ntot", "choose")):
-    for k in keys:
-        assert np.array_equal(dev[k], ref[k]), (k, np.nonzero(np.any((dev[k] != ref[k]).reshape(len(dev[k]), -1), 1))[0][:8])
 
 
 # ---------------------------------------------------------------- (a) the reference's own traces
@@ -59,7 +26,7 @@ def test_device_reproduces_the_reference_mcts_traces():
     from qtttgym_amd import TreeSearch
     from qtttgym_amd.actions import action36_to_pairs
     for grp in tree_model.golden_groups(GOLDEN):
-        env = _env_from_arrays(grp["arrays"])
+        env = env_from_arrays(grp["arrays"])
         G = env.num_envs
         total = grp["checkpoints"][-1] + grp["after"]
         t = TreeSearch(G, capacity=1 + 2 * total + 1, num_simulations=grp["n_sims"], seed=grp["seed"],
@@ -70,7 +37,7 @@ def test_device_reproduces_the_reference_mcts_traces():
         for ci, c in enumerate(grp["checkpoints"]):
             t.contemplate(c - done)
             done = c
-            st = _stats(t)
+            st = stats(t)
             for k, r in (("N", "N"), ("W", "W"), ("Q", "Q"), ("Ntot", "Ntot"), ("choose", "choose"),
                          ("nodes_used", "n_nodes")):
                 assert np.array_equal(st[k], rec[r][:, ci]), (k, c)
@@ -80,35 +47,17 @@ def test_device_reproduces_the_reference_mcts_traces():
         env.step_raw(action36_to_pairs(a).contiguous(), bits)
         t.sync(env)
         t.contemplate(grp["after"])
-        st = _stats(t)
+        st = stats(t)
         for k in ("N", "W", "Q", "Ntot", "choose"):
             assert np.array_equal(st[k], rec[k][:, -1]), k
 
 
 # ---------------------------------------------------------------- (b, c) lockstep with the model
 def _lockstep(G, rollouts, S, net=None, seed=5, offset=17):
-    from qtttgym_amd import TreeSearch
-    arrays = _random_positions(G, seed)
-    env = _env_from_arrays(arrays)
-    t = TreeSearch(G, capacity=3 + 2 * rollouts, num_simulations=S, net=net, seed=seed, board_offset=offset,
-                   device=DEV)
-    t.reset(env)
-    m = tree_model.TreeModel(S, seed=seed, board_offset=offset)
-    m.reset(oracle.boards_from_arrays(arrays["board"], arrays["moves"], arrays["n_moves"], arrays["qmask"],
-                                      arrays["n_q"]))
+    t, m, _ = search(random_positions(G, seed), 3 + 2 * rollouts, S, net=net, seed=seed, offset=offset)
     for _ in range(rollouts):
-        k = t.rollout_idx
-        leaves = m.select()
-        t.contemplate(1)          # select -> playouts -> backup on the device
-        # the leaf of this rollout (the leaf buffer is only rewritten by the next select)
-        ex = _export(t.leaf)
-        for key, val in (("board", leaves.board), ("moves", leaves.moves), ("n_moves", leaves.n_moves)):
-            assert np.array_equal(ex[key], val), (key, k)
-        out = t._out if net is None else t._out["result"]
-        probs = None if net is None else t._out["probs"].cpu().numpy()
-        m.backup(out.cpu().numpy(), probs)
-    st, ref = _stats(t), m.root_stats()
-    _model_stats_equal(st, ref, ("N", "W", "Q", "P", "Ntot", "choose", "nodes_used"))
+        rollout(t, m)             # select -> playouts -> backup on the device, the leaves compared
+    assert_stats_equal(stats(t), m.root_stats(), ("N", "W", "Q", "P", "Ntot", "choose", "nodes_used"))
     return t, m
 
 
@@ -117,20 +66,17 @@ def test_lockstep_with_the_model_uniform_playouts():
     # the device's playouts are qttt_rollout_many's, checked here on a sample against the oracle
     leaves = m.select()
     sample = np.arange(0, 4096, 37)
-    sub = tree_model._batch([leaves.b[g] for g in sample], leaves.b.dtype)
     t.contemplate(1)
     dev = t._out.cpu().numpy()[sample]
     for s in range(4):
-        ref = np.array([oracle.rollout(tree_model._one(sub.b[i]), 5, 64 * 4 * 16 + s * 16, 17 + int(g))[0][0]
-                        for i, g in enumerate(sample)])
+        ref = np.array([oracle.rollout(oracle.OracleBoards.from_records(leaves.b[g:g + 1]), 5, 64 * 4 * 16 + s * 16,
+                                       17 + int(g))[0][0] for g in sample])
         assert np.array_equal(dev[:, s], ref), s
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_lockstep_with_the_model_network_playouts(dtype):
-    from qtttgym_amd import PolicyValueNet
-    net = PolicyValueNet(golden_state_dict(load_golden()), device=DEV, dtype=dtype)
-    _lockstep(1024, 24, 4, net=net, seed=9)
+    _lockstep(1024, 24, 4, net=_net(dtype), seed=9)
 
 
 # ---------------------------------------------------------------- (d) ragged batches
@@ -143,12 +89,12 @@ def test_ragged_batches(G):
 def test_invariants_at_65536_games():
     from qtttgym_amd import TreeSearch
     G, R = 65536, 16
-    arrays = _random_positions(G, 21)
-    env = _env_from_arrays(arrays)
+    arrays = random_positions(G, 21)
+    env = env_from_arrays(arrays)
     t = TreeSearch(G, capacity=1 + 2 * R + 1, num_simulations=10, seed=1, device=DEV)
     t.reset(env)
     t.contemplate(R)
-    st = _stats(t)
+    st = stats(t)
     info = env.node_info(python_key=False)
     term = info["terminal"].cpu().numpy().astype(bool)
     legal = info["legal"].cpu().numpy().astype(np.uint64)
@@ -172,17 +118,16 @@ def test_sync_keeps_the_chosen_subtree_and_starts_fresh_otherwise():
     from qtttgym_amd import TreeSearch
     from qtttgym_amd.actions import action36_to_pairs
     G, R = 1024, 40
-    arrays = _random_positions(G, 33)
-    env = _env_from_arrays(arrays)
+    arrays = random_positions(G, 33)
+    env = env_from_arrays(arrays)
     t = TreeSearch(G, capacity=1 + 2 * R + 2, num_simulations=4, seed=3, device=DEV)
     t.reset(env)
     t.contemplate(R)
     m = tree_model.TreeModel(4, seed=3)
-    m.reset(oracle.boards_from_arrays(arrays["board"], arrays["moves"], arrays["n_moves"], arrays["qmask"],
-                                      arrays["n_q"]))
+    m.reset(boards(arrays))
     for _ in range(R):
         m.rollout()
-    before = _stats(t)
+    before = stats(t)
     # half the games play the chosen (visited) action, half the least visited legal one (often never expanded)
     legal = env.node_info(python_key=False)["legal"].cpu().numpy().astype(np.uint64)
     lmask = ((legal[:, None] >> np.arange(36, dtype=np.uint64)) & 1) == 1
@@ -192,12 +137,10 @@ def test_sync_keeps_the_chosen_subtree_and_starts_fresh_otherwise():
     bits = (np.arange(G) // 2 % 2).astype(np.uint8)
     env.step_raw(action36_to_pairs(torch.as_tensor(act, device=DEV)).contiguous(), torch.as_tensor(bits, device=DEV))
     t.sync(env)
-    ex = _export(env)
-    new = oracle.boards_from_arrays(ex["board"], ex["moves"], ex["n_moves"], ex["qmask"], ex["n_q"])
-    m.sync(new)
-    after = _stats(t)
+    m.sync(boards(export(env)))
+    after = stats(t)
     ref = m.root_stats()
-    _model_stats_equal(after, ref, ("N", "W", "Q", "P", "Ntot", "choose"))
+    assert_stats_equal(after, ref, ("N", "W", "Q", "P", "Ntot", "choose"))
     fresh = after["nodes_used"] > before["nodes_used"]
     assert fresh.any() and (~fresh).any()
     assert (after["Ntot"][fresh] == 0).all()

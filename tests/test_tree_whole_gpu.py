@@ -1,10 +1,11 @@
 """The device search trees (include/qttt_tree.h) compared whole with the float64 model (tests/tree_model.py) on the
 MI355X: the selection score bit for bit at c_puct values where a fused multiply-add would show, every node of every
-game after lockstep rollouts (tests/tree_layout.py), wide simulation counts and draw indices at the top of their
-range, full games through up to nine syncs, and the overflow branches of select and sync.
+game after lockstep rollouts (tests/tree_harness.py, tests/tree_layout.py), wide simulation counts and draw indices at
+the top of their range, full games through up to nine syncs, and the overflow branches of select and sync.
 
-Every test owns its tree buffer: it is filled with a sentinel byte before qttt_tree_reset and ends in a tail of four
-node records, so a write outside what the header allows shows as a failed comparison inside the allocation."""
+Every test owns its tree buffer (tree_harness.search): it is filled with a sentinel byte before qttt_tree_reset and ends
+in a tail of four node records, so a write outside what the header allows shows as a failed comparison inside the
+allocation."""
 import fractions
 import math
 
@@ -14,83 +15,23 @@ import torch
 
 import oracle
 import tree_layout
-import tree_model
-from nn_reference64 import golden_state_dict, load_golden
-from test_tree_gpu import _env_from_arrays, _export, _random_positions, _stats
+from tree_harness import (DEV, SENTINEL, assert_stats_equal, boards, export, random_positions, rollout, search, stats)
+from tree_harness import net as _net
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SENTINEL = 0xA5
-TAIL = 4 * tree_layout.NODE_BYTES
 SQRT2 = math.sqrt(2.0)
 STAT_KEYS = ("N", "W", "Q", "P", "Ntot", "choose", "nodes_used", "overflow")
 
 
 # ---------------------------------------------------------------- helpers
-def _boards(arrays):
-    return oracle.boards_from_arrays(arrays["board"], arrays["moves"], arrays["n_moves"], arrays["qmask"], arrays["n_q"])
-
-
-def _search(env, boards, capacity, S, c_puct=1.0, net=None, seed=5, offset=17, model_capacity=None):
-    """A TreeSearch over a sentinel-filled buffer of the test's own (with a tail) and the model, both reset."""
-    from qtttgym_amd import TreeSearch
-    G = env.num_envs
-    t = TreeSearch(G, capacity=capacity, num_simulations=S, c_puct=c_puct, net=net, seed=seed, board_offset=offset,
-                   device=DEV)
-    nbytes = int(t._lib.qttt_tree_bytes(G, capacity))
-    assert nbytes == tree_layout.tree_bytes(G, capacity)
-    t.tree = torch.full((nbytes + TAIL,), SENTINEL, dtype=torch.uint8, device=DEV)
-    t.reset(env)
-    m = tree_model.TreeModel(S, seed=seed, board_offset=offset, c_puct=c_puct, capacity=model_capacity)
-    m.reset(boards)
-    return t, m
-
-
-def _contemplate_unbounded(t):
-    """TreeSearch.contemplate(1) without the host-side bounds: the same entries, the same arguments."""
-    from qtttgym_amd import _native
-    G, cap, S, k = t.num_games, t.capacity, t.num_simulations, t.rollout_idx
-    tree, leaf = t.tree.data_ptr(), t.leaf.state.data_ptr()
-    t._call("qttt_tree_select", tree, G, cap, t.seed, k, t.board_offset, t.c_puct, leaf)
-    if t.net is None:
-        t.leaf.rollout_many(S, step_idx0=k * S * _native.SIM_STRIDE, out=t._out)
-        t._call("qttt_tree_backup", tree, G, cap, t._out.data_ptr(), S, None)
-    else:
-        t.leaf.rollout_policy(t.net, S, step_idx0=k * S * _native.SIM_STRIDE, out=t._out)
-        t._call("qttt_tree_backup", tree, G, cap, t._out["result"].data_ptr(), S, t._out["probs"].data_ptr())
-    t.rollout_idx = k + 1
-
-
-def _rollout(t, m, bounded=True):
-    """One rollout in lockstep: the model selects, the device does a whole rollout, the model backs up from the
-    device's playouts (and network priors).  Returns (the model's leaves, the device's result)."""
-    leaves = m.select()
-    if bounded:
-        t.contemplate(1)
-    else:
-        _contemplate_unbounded(t)
-    ex = _export(t.leaf)              # the leaf buffer is only rewritten by the next select
-    for key, val in (("board", leaves.board), ("moves", leaves.moves), ("n_moves", leaves.n_moves)):
-        assert np.array_equal(ex[key], val), (key, m.k)
-    result = (t._out if t.net is None else t._out["result"]).cpu().numpy()
-    m.backup(result, None if t.net is None else t._out["probs"].cpu().numpy())
-    return leaves, result
-
-
 def _check_tree(t, m):
     tree_layout.assert_tree_equals_model(t.tree.cpu().numpy(), t.num_games, t.capacity, m, SENTINEL, DEV)
 
 
 def _check_stats(t, m):
-    st, ref = _stats(t), m.root_stats()
-    for k in STAT_KEYS:
-        assert np.array_equal(st[k], ref[k]), (k, np.nonzero(np.any((st[k] != ref[k]).reshape(len(ref[k]), -1), 1))[0][:8])
+    st = stats(t)
+    assert_stats_equal(st, m.root_stats(), STAT_KEYS)
     return st
-
-
-def _net(dtype):
-    from qtttgym_amd import PolicyValueNet
-    return PolicyValueNet(golden_state_dict(load_golden()), device=DEV, dtype=dtype)
 
 
 # ---------------------------------------------------------------- (a) the score, bit for bit
@@ -152,15 +93,14 @@ def test_select_score_is_the_reference_score_bit_for_bit(score_tuples, c_puct):
 # ---------------------------------------------------------------- (b) whole-tree lockstep
 @pytest.fixture(scope="module")
 def positions_257():
-    return _random_positions(257, 5)
+    return random_positions(257, 5)
 
 
 def _whole_tree_lockstep(arrays, c_puct, net=None, rollouts=48, S=3, checks=(1, 2, 7)):
-    env, boards = _env_from_arrays(arrays), _boards(arrays)
-    t, m = _search(env, boards, 3 + 2 * rollouts, S, c_puct=c_puct, net=net)
+    t, m, _ = search(arrays, 3 + 2 * rollouts, S, c_puct=c_puct, net=net)
     _check_tree(t, m)
     for r in range(1, rollouts + 1):
-        _rollout(t, m)
+        rollout(t, m)
         if r in checks or r == rollouts:
             _check_tree(t, m)
     _check_stats(t, m)
@@ -183,25 +123,24 @@ def test_whole_tree_lockstep_network_playouts(positions_257, dtype):
 # ---------------------------------------------------------------- (c) wide simulations and high indices
 @pytest.fixture(scope="module")
 def positions_65():
-    return _random_positions(65, 65)
+    return random_positions(65, 65)
 
 
 @pytest.mark.parametrize("S,high", [(64, False), (65, False), (128, False), (64, True), (65, True), (128, True), (1, True)])
 def test_wide_simulations_and_draw_indices_at_the_top_of_their_range(positions_65, S, high):
     from qtttgym_amd import _native
     G, R, seed, offset = 65, 6, 11, 3
-    env, boards = _env_from_arrays(positions_65), _boards(positions_65)
-    t, m = _search(env, boards, 3 + 2 * R, S, seed=seed, offset=offset)
+    t, m, _ = search(positions_65, 3 + 2 * R, S, seed=seed, offset=offset)
     if high:
         t.rollout_idx = m.k = t.max_rollouts - R
         assert t.max_rollouts == min(1 << 24, (1 << 31) // (16 * S))
     for _ in range(R):
         k = m.k
-        leaves, result = _rollout(t, m)
+        leaves, result = rollout(t, m)
     # the last rollout's playouts are qttt_rollout_many's at step_idx0 = k * S * 16: a sample against the oracle
     assert not high or (k + 2) * S * _native.SIM_STRIDE > (1 << 31) or k + 1 == (1 << 24)
     for g in (0, 31, 64):
-        leaf = tree_model._one(leaves.b[g])
+        leaf = oracle.OracleBoards.from_records(leaves.b[g:g + 1])
         ref = [oracle.rollout(leaf, seed, k * S * 16 + s * 16, offset + g)[0][0] for s in range(S)]
         assert np.array_equal(result[g], np.array(ref, dtype=np.int8)), g
     _check_tree(t, m)
@@ -218,9 +157,9 @@ def test_full_games_through_every_sync(network):
     from qtttgym_amd.actions import action36_to_pairs
     G, R, S = 257, 12, 3
     capacity = 1 + 9 * (2 * R + 1) + 1
-    env = VecEnv(G, device=DEV, seed=4)
-    t, m = _search(env, oracle.OracleBoards(G), capacity, S, net=_net(torch.float32) if network else None, seed=13,
-                   offset=2)
+    t, m, env = search(export(VecEnv(G, device=DEV)), capacity, S, net=_net(torch.float32) if network else None,
+                       seed=13, offset=2)
+    env.seed = 4                        # (never drawn from: every step_raw below is given its bits)
     done = torch.zeros(G, dtype=torch.bool, device=DEV)
     onto_child = fresh_root = 0
     moves = 0
@@ -231,7 +170,7 @@ def test_full_games_through_every_sync(network):
             break
         assert moves < 9
         for _ in range(R):
-            _rollout(t, m)
+            rollout(t, m)
         st = _check_stats(t, m)
         assert np.array_equal(t.choose().cpu().numpy(), st["choose"])
         # even games play the chosen action, odd games the least visited legal one (often a child never expanded)
@@ -245,7 +184,7 @@ def test_full_games_through_every_sync(network):
         done |= term
         t.sync(env)
         before = [(st_["root"], len(st_["nodes"])) for st_ in m.games]
-        m.sync(_boards(_export(env)))
+        m.sync(boards(export(env)))
         for g, st_ in enumerate(m.games):
             if not frozen[g]:
                 assert st_["root"] != before[g][0], g
@@ -257,11 +196,11 @@ def test_full_games_through_every_sync(network):
             _check_tree(t, m)
     _check_tree(t, m)
     assert onto_child > 0 and fresh_root > 0, (onto_child, fresh_root)
-    assert not _stats(t)["overflow"].any()
+    assert not stats(t)["overflow"].any()
     # every game is over: one more rollout selects nothing, expands nothing and backs nothing up (launched without the
     # host-side bound, which nine moves may have used up: it counts two nodes per rollout whatever the games do)
     snap = t.tree.cpu().numpy().copy()
-    _rollout(t, m, bounded=False)
+    rollout(t, m, bounded=False)
     o = G * tree_layout.GAME_BYTES
     assert np.array_equal(t.tree.cpu().numpy()[o:], snap[o:])
     _check_tree(t, m)
@@ -270,17 +209,16 @@ def test_full_games_through_every_sync(network):
 # ---------------------------------------------------------------- (e) overflow
 @pytest.fixture(scope="module")
 def positions_130():
-    return _random_positions(130, 130)
+    return random_positions(130, 130)
 
 
 @pytest.mark.parametrize("capacity", [1, 2, 3, 8])
 def test_overflow_in_select_and_sync(positions_130, capacity):
     from qtttgym_amd.actions import action36_to_pairs
     G, S, R = 130, 2, 16
-    env, boards = _env_from_arrays(positions_130), _boards(positions_130)
-    t, m = _search(env, boards, capacity, S, seed=8, offset=1, model_capacity=capacity)
+    t, m, env = search(positions_130, capacity, S, seed=8, offset=1, model_capacity=capacity)
     for _ in range(R):
-        _rollout(t, m, bounded=False)
+        rollout(t, m, bounded=False)
         st = _check_stats(t, m)                     # overflow and nodes_used among them
         assert (st["nodes_used"] <= capacity).all()
         _check_tree(t, m)
@@ -299,7 +237,7 @@ def test_overflow_in_select_and_sync(positions_130, capacity):
     env.step_raw(action36_to_pairs(torch.as_tensor(act, device=DEV)).contiguous(), torch.as_tensor(bits, device=DEV))
     before = m.dump()
     t._call("qttt_tree_sync", t.tree.data_ptr(), G, capacity, env.state.data_ptr())       # TreeSearch.sync less its bound
-    m.sync(_boards(_export(env)))
+    m.sync(boards(export(env)))
     st = _check_stats(t, m)
     _check_tree(t, m)
     after = m.dump()
@@ -320,6 +258,6 @@ def test_overflow_in_select_and_sync(positions_130, capacity):
     # ---- the flag outlives later selects (above) and a sync; qttt_tree_reset clears it
     t.tree.fill_(SENTINEL)
     t.reset(env)
-    m.reset(_boards(_export(env)))
+    m.reset(boards(export(env)))
     assert not _check_stats(t, m)["overflow"].any()
     _check_tree(t, m)

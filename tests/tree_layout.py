@@ -1,7 +1,8 @@
 """A tree buffer of include/qttt_tree.h, copied to the host and read as numpy arrays — by the layout written in that
 header alone (game headers, node headers, 36 action slots, priors), not by the kernels' structs — and the comparison
-of every byte of it that the header gives a meaning with the float64 model (tests/tree_model.py).  Test
-infrastructure for tests/test_tree_whole_gpu.py; a plain helper module."""
+of every byte of it that the header gives a meaning with the float64 model (tests/tree_model.py), before or after a
+compaction.  Test infrastructure for tests/test_tree_whole_gpu.py, tests/test_tree_compact_gpu.py and
+tests/test_selfplay_gpu.py; tests/test_tree_cpu.py checks the comparison itself.  A plain helper module."""
 import numpy as np
 
 GAME_BYTES, NODE_BYTES, PRIOR_BYTES = 128, 608, 144
@@ -39,17 +40,18 @@ def decode(buf, G, capacity):
     return games, nodes, priors, buf[o3:]
 
 
-def pack_positions(recs, device):
-    """The packed planes (P, Q) u64[n] of positions given as oracle board records: one import_boards of all of them."""
+def pack_positions(recs, device="cuda:0", pack=None):
+    """The packed planes (P, Q) u64[n] of positions given as oracle board records: one import_boards of all of them on
+    `device`, or pack(the records as OracleBoards) where a test stands in for the device."""
     import oracle
+    ob = oracle.OracleBoards.from_records(recs)
+    if pack is not None:
+        return pack(ob)
     import torch
     from qtttgym_amd import VecEnv
-    n = len(recs)
-    ob = oracle.OracleBoards.__new__(oracle.OracleBoards)
-    ob.n, ob.b = n, np.array(recs, dtype=oracle.BOARD_DTYPE)
-    env = VecEnv(n, device=device)
+    env = VecEnv(ob.n, device=device)
     env.import_boards(ob.moves, ob.n_moves, ob.board, ob.qmask.astype(np.int16), ob.n_q)
-    planes = env.state.view(torch.int64).view(2, -1)[:, :n].cpu().numpy().view(np.uint64)
+    planes = env.state.view(torch.int64).view(2, -1)[:, :ob.n].cpu().numpy().view(np.uint64)
     return planes[0].copy(), planes[1].copy()
 
 
@@ -57,67 +59,61 @@ def _rows(mask):
     return np.argwhere(mask)[:8].tolist()
 
 
-def assert_tree_equals_model(buf, G, capacity, model, sentinel, device="cuda:0"):
-    """Every game header, every node < used and every priors row of the tree buffer `buf` (host bytes) against the
-    model; what the header leaves unwritten — the headers' padding, the node records at or beyond `used`, the priors
-    rows of nodes without network priors, whatever follows the tree in buf — must still hold the byte `sentinel` that
-    the test filled the buffer with before qttt_tree_reset."""
+def assert_tree_equals_model(buf, G, capacity, model, sentinel, device="cuda:0", compacted=False, pack=None):
+    """Every game header, every node < used and every network priors row of the tree buffer `buf` (host bytes) against
+    the model; what the header leaves unwritten must still hold the byte `sentinel` that the test filled the buffer
+    with before qttt_tree_reset: the headers' padding, whatever follows the tree in buf and, unless `compacted`, the
+    node records and priors rows at or beyond `used` and the priors rows of nodes without network priors (a compaction
+    leaves those unspecified).  Returns the number of network priors rows compared."""
     games, nodes, priors, tail = decode(buf, G, capacity)
     dump = model.dump()
     assert len(dump) == G
     used = np.array([d["used"] for d in dump], dtype=np.int32)
     assert (used <= capacity).all()
-    # ---- game headers
-    assert np.array_equal(games["used"], used), _rows(games["used"] != used)
-    root = np.array([d["root"] for d in dump], dtype=np.int32)
-    assert np.array_equal(games["root"], root), _rows(games["root"] != root)
-    depth = np.array([len(d["path"]) for d in dump], dtype=np.int32)
-    assert np.array_equal(games["depth"], depth), _rows(games["depth"] != depth)
-    leaf = np.array([d["leaf"] for d in dump], dtype=np.int32)
-    assert np.array_equal(games["leaf"], leaf), _rows(games["leaf"] != leaf)
-    gflags = np.array([(GAME_OVERFLOW if d["overflow"] else 0)
-                       | (GAME_LEAF_TURN if d["nodes"][d["leaf"]]["turn"] else 0)
-                       | (GAME_LEAF_TERMINAL if d["nodes"][d["leaf"]]["terminal"] else 0) for d in dump], dtype=np.uint32)
-    assert np.array_equal(games["flags"], gflags), _rows(games["flags"] != gflags)
-    for g, d in enumerate(dump):
-        for k, (i, a) in enumerate(d["path"]):
-            assert games["path_node"][g, k] == i and games["path_action"][g, k] == a, (g, k)
-    assert (games["pad"] == sentinel).all() and (games["pad2"] == sentinel).all()      # the padding is never written
-    # ---- nodes < used, flattened over the games in (game, node) order
     live = np.arange(capacity)[None, :] < used[:, None]
-    dev = nodes[live]
+    dev, pri = nodes[live], priors[live]                  # nodes < used, flattened over the games in (game, node) order
     flat = [n for d in dump for n in d["nodes"]]
     assert len(flat) == len(dev)
-    P, Q = pack_positions([n["rec"] for n in flat], device)
-    assert np.array_equal(dev["P"], P), _rows(dev["P"] != P)
-    assert np.array_equal(dev["Q"], Q), _rows(dev["Q"] != Q)
-    legal = np.array([n["legal"] for n in flat], dtype=np.uint64)
-    assert np.array_equal(dev["legal"], legal), _rows(dev["legal"] != legal)
-    ntot = np.array([n["Ntot"] for n in flat], dtype=np.uint32)
-    assert np.array_equal(dev["Ntot"], ntot), _rows(dev["Ntot"] != ntot)
-    network = np.array([isinstance(n["P"], np.ndarray) for n in flat], dtype=bool)
-    flags = np.array([(0 if n["P"] is None else NODE_PRIORS) | (NODE_UNIFORM if isinstance(n["P"], str) else 0)
-                      | (NODE_TERMINAL if n["terminal"] else 0) | (NODE_TURN if n["turn"] else 0)
-                      | ((n["winner"] + 1) << 8) for n in flat], dtype=np.uint32)
-    assert np.array_equal(dev["flags"], flags), _rows(dev["flags"] != flags)
-    N = np.array([n["N"] for n in flat], dtype=np.uint32).reshape(-1, 36)
-    assert np.array_equal(dev["slots"]["N"], N), _rows(dev["slots"]["N"] != N)
-    W = np.array([n["W"] for n in flat], dtype=np.float64).reshape(-1, 36)
-    assert np.array_equal(dev["slots"]["W"].view(np.int64), W.view(np.int64)), \
-        _rows(dev["slots"]["W"].view(np.int64) != W.view(np.int64))
-    child = np.array([[-1 if not c else (c[0] | (CHILD_PAIR if len(c) == 2 else 0)) for c in n["children"]] for n in flat],
-                     dtype=np.int32).reshape(-1, 36)
     assert all(len(c) < 2 or c[1] == c[0] + 1 for n in flat for c in n["children"])
-    assert np.array_equal(dev["slots"]["child"], child), _rows(dev["slots"]["child"] != child)
-    # ---- priors: the network's rows bit for bit; every other row is never written
-    pri = priors[live]
-    if network.any():
-        ref = np.stack([n["P"] for n in flat if isinstance(n["P"], np.ndarray)]).astype(np.float32)
-        assert np.array_equal(pri[network].view(np.uint32), ref.view(np.uint32)), \
-            _rows(pri[network].view(np.uint32) != ref.view(np.uint32))
-    assert (pri[~network].view(np.uint8) == sentinel).all()
-    assert (priors[~live].view(np.uint8) == sentinel).all()
-    # ---- node records at or beyond `used`, and what follows the tree
-    rest = nodes[~live]
-    assert (rest.view(np.uint8) == sentinel).all(), "a node record at or beyond `used` was written"
-    assert (tail == sentinel).all(), "bytes after the tree were written"
+    leaves = [d["nodes"][d["leaf"]] for d in dump]
+    P, Q = pack_positions([n["rec"] for n in flat], device, pack)
+    network = np.array([isinstance(n["P"], np.ndarray) for n in flat], dtype=bool)
+    expected = (
+        ("used", games["used"], used),
+        ("root", games["root"], np.array([d["root"] for d in dump], dtype=np.int32)),
+        ("depth", games["depth"], np.array([len(d["path"]) for d in dump], dtype=np.int32)),
+        ("leaf", games["leaf"], np.array([d["leaf"] for d in dump], dtype=np.int32)),
+        ("game flags", games["flags"],
+         np.array([(GAME_OVERFLOW if d["overflow"] else 0) | (GAME_LEAF_TURN if n["turn"] else 0)
+                   | (GAME_LEAF_TERMINAL if n["terminal"] else 0) for d, n in zip(dump, leaves)], dtype=np.uint32)),
+        ("P", dev["P"], P),
+        ("Q", dev["Q"], Q),
+        ("legal", dev["legal"], np.array([n["legal"] for n in flat], dtype=np.uint64)),
+        ("Ntot", dev["Ntot"], np.array([n["Ntot"] for n in flat], dtype=np.uint32)),
+        ("flags", dev["flags"],
+         np.array([(0 if n["P"] is None else NODE_PRIORS) | (NODE_UNIFORM if isinstance(n["P"], str) else 0)
+                   | (NODE_TERMINAL if n["terminal"] else 0) | (NODE_TURN if n["turn"] else 0)
+                   | ((n["winner"] + 1) << 8) for n in flat], dtype=np.uint32)),
+        ("N", dev["slots"]["N"], np.array([n["N"] for n in flat], dtype=np.uint32).reshape(-1, 36)),
+        ("W", dev["slots"]["W"].view(np.int64),                                                     # bit for bit
+         np.array([n["W"] for n in flat], dtype=np.float64).reshape(-1, 36).view(np.int64)),
+        ("child", dev["slots"]["child"],
+         np.array([[-1 if not c else (c[0] | (CHILD_PAIR if len(c) == 2 else 0)) for c in n["children"]] for n in flat],
+                  dtype=np.int32).reshape(-1, 36)),
+        ("network priors", pri[network].view(np.uint32),                                            # bit for bit
+         np.array([n["P"] for n in flat if isinstance(n["P"], np.ndarray)], dtype=np.float32).reshape(-1, 36)
+         .view(np.uint32)))
+    for name, got, ref in expected:
+        assert np.array_equal(got, ref), (name, _rows(got != ref))
+    for g, d in enumerate(dump):
+        for k, (i, a) in enumerate(d["path"]):
+            assert games["path_node"][g, k] == i and games["path_action"][g, k] == a, ("path", g, k)
+    unwritten = [("the game headers' padding", games["pad"]), ("the game headers' padding", games["pad2"]),
+                 ("bytes after the tree", tail)]
+    if not compacted:
+        unwritten += [("a priors row of a node without network priors", pri[~network]),
+                      ("a priors row at or beyond `used`", priors[~live]),
+                      ("a node record at or beyond `used`", nodes[~live])]
+    for name, region in unwritten:
+        assert (region.view(np.uint8) == sentinel).all(), name + ": written"
+    return int(network.sum())

@@ -1,7 +1,7 @@
 """A float64 Python restatement of the batched search tree of include/qttt_tree.h (qtttgym_amd.TreeSearch), built on the
-C oracle's expand / rollout / counter hash.  Test infrastructure: tests/test_tree_cpu.py ties it to the reference's own
-MCTS class (tests/golden/tree_traces.npz), tests/test_tree_gpu.py and tests/test_tree_whole_gpu.py run the device in
-lockstep with it.
+C oracle's expand / rollout / counter hash.  Test infrastructure: tests/test_tree_cpu.py and
+tests/test_tree_compact_cpu.py tie it to the reference's own MCTS class (tests/golden/tree_traces.npz); the GPU tests
+run the device in lockstep with it (tests/tree_harness.py) and compare whole trees with it (tests/tree_layout.py).
 
 Per game a plain list of nodes (the reference's node dict never merges two paths: its keys hold the full move
 history).  The arithmetic is the reference's, in Python floats: score = Q + c_puct * (P * sqrt(Ntot) / (1 + N)),
@@ -10,6 +10,11 @@ W += r, Q = W / N.
 TreeModel(capacity=c) also restates the header's overflow rule: an expansion (in select) or a fresh root (in sync) that
 does not fit c nodes sets the game's sticky overflow flag and allocates nothing.  Node indices equal the device's: child
 0 at `used`, child 1 at `used + 1`, a fresh root appended.
+
+compact() is qttt_tree_compact (the reference's _prune as MCTS.sync does it), a stable renumbering: per game the nodes
+reachable from the root keep their relative order, the root becomes node 0, every child list is rewritten, and the
+recorded path is cleared as by reset.  A game that is compact already (root 0, every node reachable) is left as it is,
+its recorded path included.
 """
 import math
 
@@ -22,17 +27,7 @@ SELECT_BASE = 1 << 31
 
 
 def _one(rec):
-    ob = oracle.OracleBoards.__new__(oracle.OracleBoards)
-    ob.n = 1
-    ob.b = np.array([rec], dtype=rec.dtype)
-    return ob
-
-
-def _batch(recs, dtype):
-    ob = oracle.OracleBoards.__new__(oracle.OracleBoards)
-    ob.n = len(recs)
-    ob.b = np.array(recs, dtype=dtype)
-    return ob
+    return oracle.OracleBoards.from_records([rec])
 
 
 def position_key(rec):
@@ -68,7 +63,6 @@ class TreeModel:
 
     # ---- MCTS.reset
     def reset(self, ob):
-        self.dtype = ob.b.dtype
         self.games = []
         for g in range(ob.n):
             rec = ob.b[g].copy()
@@ -107,7 +101,7 @@ class TreeModel:
                 i = kids[(bits >> (len(path) - 1)) & 1] if len(kids) == 2 else kids[0]
             st["path"], st["leaf"] = path, i
             leaves.append(nodes[i].rec)
-        return _batch(leaves, self.dtype)
+        return oracle.OracleBoards.from_records(leaves)
 
     def playouts(self, leaves):
         """result i8[G, n_sims] of the uniform playouts of rollout k (oracle.rollout, the draws of qttt_rollout_many)."""
@@ -166,6 +160,25 @@ class TreeModel:
                 found = len(nodes) - 1
             st["root"] = found
 
+    # ---- qttt_tree_compact
+    def reachable_counts(self):
+        return np.array([len(reachable(st)) for st in self.games], dtype=np.int32)
+
+    def compact(self):
+        for st in self.games:
+            keep = reachable(st)
+            if st["root"] == 0 and len(keep) == len(st["nodes"]):
+                continue
+            fwd = {old: new for new, old in enumerate(keep)}
+            nodes = [st["nodes"][i] for i in keep]
+            for n in nodes:
+                n.children = [None if kids is None else [fwd[c] for c in kids] for kids in n.children]
+            st["nodes"], st["root"], st["path"], st["leaf"] = nodes, 0, [], 0
+
+    def root_positions(self):
+        """The roots' records, as OracleBoards."""
+        return oracle.OracleBoards.from_records([st["nodes"][st["root"]].rec for st in self.games])
+
     # ---- the roots' statistics, as qttt_tree_root
     def root_stats(self):
         G = len(self.games)
@@ -201,6 +214,28 @@ class TreeModel:
             out.append({"used": len(nodes), "root": st["root"], "overflow": st["overflow"], "path": list(st["path"]),
                         "leaf": st["leaf"], "nodes": nodes})
         return out
+
+
+def reachable(st):
+    """The indices of the nodes of one game that can be reached from its root, ascending."""
+    nodes = st["nodes"]
+    seen = {st["root"]}
+    stack = [st["root"]]
+    while stack:
+        for kids in nodes[stack.pop()].children:
+            for c in (kids or ()):
+                assert c not in seen, "a node with two parents"
+                seen.add(c)
+                stack.append(c)
+    return sorted(seen)
+
+
+def game_view(d):
+    """One game of TreeModel.dump() as plain values that compare with == (records and network priors as bytes): (used,
+    root, path, leaf, nodes)."""
+    return (d["used"], d["root"], d["path"], d["leaf"],
+            [(n["rec"].tobytes(), n["turn"], n["terminal"], n["winner"], n["legal"], n["Ntot"], n["N"], n["W"],
+              n["children"], n["P"].tobytes() if isinstance(n["P"], np.ndarray) else n["P"]) for n in d["nodes"]])
 
 
 def choose(n):
