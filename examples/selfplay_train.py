@@ -6,13 +6,16 @@ the new weights for the search and repeats.
 
     python examples/selfplay_train.py [--games 1024] [--rollouts 100] [--sims 10] [--epochs 50] [--runs 30]
                                       [--dtype f32|bf16] [--out model.pt] [--model model.pt] [--value-targets 1,0]
+                                      [--symmetries]
 
 The network is nn.Model's (nn.py:7-28) under its own parameter names (qtttgym_amd.policy_value.SHAPES), so --out is a
 state dict that the reference, PolicyValueNet and examples/tree_tournament.py --model all load.  The loss is the
 reference's (self_play.py:226-236): 0.5 (v - v_target)^2 over every sample plus the KL divergence from the visit-count
 target to the network's policy over the legal actions of the samples that are not terminal; the optimiser is its Adam
 (lr 1e-3, weight decay 1e-3, amsgrad).  --value-targets 1,0 are the reference's targets, 1,-1 what it evidently meant
-(qtttgym_amd.SelfPlay).  --dtype is the precision of the search's network; training is f32.
+(qtttgym_amd.SelfPlay).  --dtype is the precision of the search's network; training is f32.  --symmetries trains on
+every game's eight images under the board's symmetries (SelfPlayBatch.augment: eight times the samples for the same
+search), which the reference left as a stub (self_play.py expand_symetries).
 """
 import argparse
 import os
@@ -66,6 +69,7 @@ def main():
     ap.add_argument("--out", default="model.pt")
     ap.add_argument("--model", default=None, help="state dict to start from (default: torch's initialisation)")
     ap.add_argument("--value-targets", default="1,0", help="v of the first row when the first / second player wins")
+    ap.add_argument("--symmetries", action="store_true", help="train on the eight images of every game")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     torch.manual_seed(args.seed)
@@ -80,7 +84,7 @@ def main():
                   seed=args.seed)
     for run in range(args.runs):
         batch = sp.play()
-        s, pi, mask, v_target, done = batch.flat()
+        s, pi, mask, v_target, done = (batch.augment() if args.symmetries else batch).flat()
         won = [int((batch.winner == w).sum()) for w in (1, 0, -1)]
         for _ in range(args.epochs):
             L, J = loss_terms(model, s, pi, mask, v_target, done)

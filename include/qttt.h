@@ -329,11 +329,13 @@ uint64_t qttt_hash(uint64_t seed, uint64_t board_id, uint32_t step_idx);
 #endif
 
 /* The policy/value network entry points (ABI 6) are declared in qttt_nn.h, the network-guided playouts in
- * qttt_policy_rollout.h, the batched search trees in qttt_tree.h, their compaction in qttt_tree_compact.h and the
- * self-play record in qttt_selfplay.h, included here so that this one header gives a C caller the whole library. */
+ * qttt_policy_rollout.h, the batched search trees in qttt_tree.h, their compaction in qttt_tree_compact.h, the
+ * self-play record in qttt_selfplay.h and the board's symmetries in qttt_symmetry.h, included here so that this one
+ * header gives a C caller the whole library. */
 #include "qttt_nn.h"
 #include "qttt_policy_rollout.h"
 #include "qttt_tree.h"
 #include "qttt_tree_compact.h"
 #include "qttt_selfplay.h"
+#include "qttt_symmetry.h"
 #endif

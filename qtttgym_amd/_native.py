@@ -104,6 +104,14 @@ SELFPLAY_SIGNATURES = {
     "qttt_selfplay_record": (_i32, [_vp, _i64, _i64, _i32, _u32, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp]),
 }
+# every symbol include/qttt_symmetry.h declares (the board's symmetries; qttt.h includes it)
+SYMMETRIES = 8
+_u8p = ctypes.POINTER(ctypes.c_uint8)
+SYMMETRY_SIGNATURES = {
+    "qttt_symmetry_tables": (_i32, [_u8p, _u8p, _u8p, _u8p]),
+    "qttt_transform": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp]),
+    "qttt_selfplay_augment": (_i32, [_i64, _u8p, _i32] + [_vp] * 18 + [_vp]),
+}
 
 _lib = None
 
@@ -167,7 +175,8 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(NN_SIGNATURES.items())
                                   + list(POLICY_ROLLOUT_SIGNATURES.items()) + list(TREE_SIGNATURES.items())
-                                  + list(TREE_COMPACT_SIGNATURES.items()) + list(SELFPLAY_SIGNATURES.items())):
+                                  + list(TREE_COMPACT_SIGNATURES.items()) + list(SELFPLAY_SIGNATURES.items())
+                                  + list(SYMMETRY_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

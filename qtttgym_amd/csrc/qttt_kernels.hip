@@ -49,7 +49,8 @@
 // tuple hash) -> qttt_search_core.h (the search rules several kernels share: counter draw, pair-action decode, expansion
 // of a pair, the uniform playout) -> qttt_aux_kernels.h (the cold kernels, the reset fills), qttt_mcts_kernels.h,
 // qttt_nn_kernels.h (the policy/value network) -> qttt_policy_rollout_kernels.h (network-guided playouts);
-// qttt_tree_kernels.h (the batched search trees) -> qttt_selfplay_kernels.h (the self-play record).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
+// qttt_tree_kernels.h (the batched search trees) -> qttt_selfplay_kernels.h (the self-play record) ->
+// qttt_symmetry_kernels.h (the board's symmetries: images of states, the augmented self-play batch).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
 // qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
@@ -61,6 +62,7 @@
 #include "qttt_policy_rollout_kernels.h"
 #include "qttt_tree_kernels.h"
 #include "qttt_selfplay_kernels.h"
+#include "qttt_symmetry_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -716,6 +718,55 @@ int qttt_selfplay_record(const void *tree, int64_t games, int64_t capacity, int 
     const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
     return launch(selfplay_record_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity, ply,
                   n_rollouts, alpha, (float)v_first, (float)v_second, o);
+}
+
+// ---------------------------------------------------------------- symmetries (include/qttt_symmetry.h)
+int qttt_symmetry_tables(uint8_t *cells, uint8_t *actions, uint8_t *inverse, uint8_t *compose) {
+    for (u32 k = 0; k < (u32)QTTT_SYMMETRIES; ++k) {
+        for (u32 v = 0; v < 9u && cells; ++v) cells[k * 9u + v] = (uint8_t)sym_cell(SYM_TABLES.cells[k], v);
+        for (u32 i = 0, a = 0; i < 9u && actions; ++i)
+            for (u32 j = i + 1u; j < 9u; ++j, ++a) actions[k * 36u + a] = (uint8_t)sym_action_of_pair(SYM_TABLES.cells[k], i | (j << 4));
+        if (inverse) inverse[k] = SYM_TABLES.inverse[k];
+        for (u32 b = 0; b < (u32)QTTT_SYMMETRIES && compose; ++b) compose[k * QTTT_SYMMETRIES + b] = SYM_TABLES.compose[k][b];
+    }
+    return 0;
+}
+
+int qttt_transform(const void *state_in, void *state_out, const uint8_t *sym, int k, int64_t n, void *stream) {
+    if (n < 0 || k < 0 || k >= QTTT_SYMMETRIES) return QTTT_ERR_SIZE;
+    if (n == 0) return 0;
+    if (any_null(state_in, state_out)) return QTTT_ERR_NULL;
+    if (misaligned(state_in, 16) || misaligned(state_out, 16)) return QTTT_ERR_ACTION;
+    const Planes i = planes(const_cast<void *>(state_in), n), o = planes(state_out, n);
+    return launch(transform_kernel, ceil_div(n, QTTT_COLD_BLOCK), QTTT_COLD_BLOCK, stream, i.P, i.Q, o.P, o.Q, sym, (u32)k, n);
+}
+
+int qttt_selfplay_augment(int64_t games, const uint8_t *symmetries, int n_sym, const void *states, const double *pi,
+                          const uint8_t *mask, const uint8_t *done, const float *v, const uint8_t *action36,
+                          const uint8_t *length, const int8_t *winner, const uint8_t *actions, void *states_out,
+                          double *pi_out, uint8_t *mask_out, uint8_t *done_out, float *v_out, uint8_t *action36_out,
+                          uint8_t *length_out, int8_t *winner_out, uint8_t *actions_out, void *stream) {
+    if (games < 0 || n_sym < 1 || n_sym > QTTT_SYMMETRIES || games > INT64_MAX / (36 * QTTT_SELFPLAY_ROWS * QTTT_SYMMETRIES))
+        return QTTT_ERR_SIZE;
+    u32 syms = 0;
+    for (int s = 0; s < n_sym && symmetries; ++s) {
+        if (symmetries[s] >= QTTT_SYMMETRIES) return QTTT_ERR_SIZE;
+        syms |= (u32)symmetries[s] << (4 * s);
+    }
+    if (games == 0) return 0;
+    if (!symmetries || any_null(states, pi, mask, done, v, action36, length, winner, actions) ||
+        any_null(states_out, pi_out, mask_out, done_out, v_out, action36_out, length_out, winner_out, actions_out))
+        return QTTT_ERR_NULL;
+    if (misaligned(states, 16) || misaligned(states_out, 16) || misaligned(pi, 8) || misaligned(pi_out, 8) ||
+        misaligned(v, 4) || misaligned(v_out, 4))
+        return QTTT_ERR_ACTION;
+    const SelfPlayOut in = {static_cast<u64 *>(const_cast<void *>(states)), const_cast<double *>(pi), const_cast<uint8_t *>(mask),
+                            const_cast<uint8_t *>(done), const_cast<float *>(v), const_cast<uint8_t *>(action36),
+                            const_cast<uint8_t *>(length), const_cast<int8_t *>(winner), const_cast<uint8_t *>(actions)};
+    const SelfPlayOut out = {static_cast<u64 *>(states_out), pi_out, mask_out, done_out, v_out, action36_out, length_out,
+                             winner_out, actions_out};
+    return launch(selfplay_augment_kernel, ceil_div(games * n_sym, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, games, (u32)n_sym,
+                  syms, in, out);
 }
 
 }  // extern "C"

@@ -6,12 +6,17 @@ root turned into a training sample (self_play.py:193-216) by one kernel per ply.
     s, pi, mask, v, done = sp.play().flat()         # the reference's s_batch, pi_batch, mask_batch, v_batch, done
 
 Training on the batch is ordinary torch autograd (examples/selfplay_train.py); there is no loss, gradient or optimiser
-here.  The move played is MCTS.choose, as in the reference: no temperature, no Dirichlet noise, no symmetries.
+here.  The move played is MCTS.choose, as in the reference: no temperature, no Dirichlet noise.  The board's eight
+symmetries, which the reference left as a stub (self_play.py expand_symetries), are SelfPlayBatch.augment (DESIGN.md
+§14): one launch turns the batch of G games into the batch of 8 G games it stands for.
 """
+import ctypes
+
 import torch
 
 from . import _native
-from ._host import LibCaller, check_net, check_tensor, resolve_device
+from ._host import LibCaller, _raw_stream, check_net, check_tensor, resolve_device
+from .symmetry import check_symmetries
 from .tree import TreeSearch
 from .vec_env import VecEnv
 
@@ -41,6 +46,24 @@ class SelfPlayBatch:
     def row_env(self, t):
         """Row t's states as a VecEnv (a view: encode(), evaluate(), export_boards() ... of the t-th roots)."""
         return VecEnv.from_state(self.states[t], self.num_games)
+
+    _FIELDS = ("states", "pi", "mask", "done", "v", "action36", "length", "winner", "actions")
+
+    def augment(self, symmetries=None):
+        """The batch of K * G games this one stands for under the board's symmetries (include/qttt_symmetry.h
+        qttt_selfplay_augment, one launch): `symmetries` = 1..8 of 0..7 (qtttgym_amd.symmetry), default all eight in
+        order.  Game s * G + g of the result is game g under symmetries[s]: its states are the states of the mirrored
+        game, pi / mask / action36 are permuted, v / done / length / winner are the game's own.  A new SelfPlayBatch."""
+        sym = check_symmetries(symmetries)
+        G, K, lib = self.num_games, len(sym), _native.lib()
+        out = SelfPlayBatch(K * G, self.device, lib.qttt_state_bytes(K * G))
+        with torch.cuda.device(self.device):
+            rc = lib.qttt_selfplay_augment(G, (ctypes.c_uint8 * K)(*sym), K,
+                                           *[getattr(self, f).data_ptr() for f in self._FIELDS],
+                                           *[getattr(out, f).data_ptr() for f in self._FIELDS],
+                                           _raw_stream(self.device.index))
+        _native.check(rc, "qttt_selfplay_augment")
+        return out
 
     def flat(self):
         """The reference's batch, game-major and in the order self_play.py:200-216 appends: s f32[n, 18, 10]

@@ -552,6 +552,23 @@ class VecEnv(LibCaller):
                                  auto_reset=self.auto_reset if auto_reset is None else auto_reset,
                                  board_offset=self.board_offset if board_offset is None else board_offset)
 
+    def transformed(self, k, out=None):
+        """The boards' images under a symmetry (include/qttt_symmetry.h qttt_transform; qtttgym_amd.symmetry numbers
+        the eight): a VecEnv over the states that stepping reaches when the mirrored games are played, bit for bit.
+        k = an int 0..7 for every board, or a uint8 tensor [N] with one per board (an entry past 7 leaves that board as
+        it is).  out = a VecEnv of N boards on this device to overwrite — `self` for in place; default: a new one with
+        this one's seed and board_offset."""
+        n = self.num_envs
+        if torch.is_tensor(k):
+            sym, k = check_tensor(k, torch.uint8, (n,), self.device, "k"), 0
+        else:
+            sym, k = None, int(k)
+            if not 0 <= k < _native.SYMMETRIES:
+                raise ValueError("a symmetry is 0..%d, got %d" % (_native.SYMMETRIES - 1, k))
+        out = self._like(out, "out")
+        self._call("qttt_transform", self.state.data_ptr(), out.state.data_ptr(), _ptr(sym), k, n)
+        return out
+
     def node_info(self, out=None, python_key=True):
         """GameState bookkeeping per board (mcts.py:20-27,52-65,93-94): winner i8 (1/0/-1 = True/
         False/None), terminal bool, legal int64 (bit a = action a legal), state_key int64 (the native 64-bit
