@@ -3,8 +3,9 @@ PolicyValueNet / VecEnv.evaluate.  tests/test_policy_value_cpu.py pins it to the
 (tests/golden/model_eval.npz); the GPU tests compare the kernel with it.
 
 forward_contract restates the precision contract of include/qttt_nn.h (bf16 weights, input and activations, f32 biases,
-accumulation in a chosen dtype), and zero / greedy / counting_state_dict are three networks whose outputs are exact in
-every precision and summation order; tests/test_policy_value_numerics_cpu.py checks both without a device."""
+accumulation in a chosen dtype), and zero / greedy / counting / sharp_counting_state_dict are networks whose outputs are
+exact in every precision and summation order; tests/test_policy_value_numerics_cpu.py checks both without a device.
+forward_reference32 is the reference's own chain of torch f32 operations (nn.py:30-42, alphazero.py:296-298)."""
 import os
 
 import numpy as np
@@ -190,6 +191,50 @@ def counting_state_dict(seed=0):
     sd["pi_head.1.bias"] = ri(-8, 8, (36,))
     sd["V_head.1.bias"] = ri(-8, 8, (1,))
     return sd
+
+
+SHARP_FACTOR = 128.0
+SHARP_TIED = 12
+
+
+def sharp_counting_state_dict(seed=0):
+    """counting_state_dict with the policy head (weight and bias) times 128 and its rows tied in threes (row a is row
+    a mod 12): the logits are integer multiples of 128 below 2^17 (exact in f32 and bf16 under any accumulation order),
+    two legal logits are equal or at least 128 apart, so every expf(logit - max) is exactly 1 or exactly 0 in f32 and
+    the probabilities are float32(1) / float32(m) on the m largest legal logits and 0 elsewhere, a set that depends on
+    the position: on the network's outputs for which triple is largest, on the board for which of its three actions
+    are legal.  The factor alone leaves the counting network's 36 distinct rows tied at the maximum on 2 % of the
+    positions of random play; with the tied rows about a sixth of them have m = 1 and the rest m = 2, 3 or 6
+    (tests/test_policy_value_numerics_cpu.py asserts the shares)."""
+    sd = counting_state_dict(seed)
+    rows = torch.arange(36) % SHARP_TIED
+    sd["pi_head.1.weight"] = sd["pi_head.1.weight"][rows] * SHARP_FACTOR
+    sd["pi_head.1.bias"] = sd["pi_head.1.bias"][rows] * SHARP_FACTOR
+    return sd
+
+
+EXACT_NETS = {"zero": zero_state_dict, "greedy": greedy_state_dict, "sharp": sharp_counting_state_dict}
+
+
+def forward_reference32(sd, vec):
+    """The reference's own operations in torch f32 on the CPU: Model.forward (nn.py:30-42: get_mask, .float(), the
+    Sequentials with the heads' leading ReLU, `logits[mask] -= inf`) and Categorical(logits=logits).probs
+    (alphazero.py:297-298) row by row as the reference calls it.  vec [N,18,10] -> (value f32[N], logits f32[N,36],
+    probs f32[N,36]; a row with no legal action, which the reference never evaluates, is NaN)."""
+    from torch.distributions import Categorical
+    from torch.nn.functional import linear
+    w = {k: sd[k].to(torch.float32) for k in KEYS}
+    mask = _mask(vec)
+    z = vec.to(torch.float64).flatten(-2, -1).float()
+    for i in (0, 2, 4):
+        z = torch.relu(linear(z, w["fc.%d.weight" % i], w["fc.%d.bias" % i]))
+    v = linear(torch.relu(z), w["V_head.1.weight"], w["V_head.1.bias"]).squeeze(-1)
+    logits = linear(torch.relu(z), w["pi_head.1.weight"], w["pi_head.1.bias"])
+    logits[mask] -= torch.inf
+    probs = torch.full_like(logits, float("nan"))
+    for i in torch.nonzero(~mask.all(1)).flatten().tolist():
+        probs[i] = Categorical(logits=logits[i]).probs
+    return v, logits, probs
 
 
 def random_play_vectors(n, seed):

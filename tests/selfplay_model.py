@@ -1,6 +1,7 @@
 """A plain-Python restatement of the self-play record of include/qttt_selfplay.h (qtttgym_amd.SelfPlay) over the
 float64 tree model (tests/tree_model.py) and the C oracle.  Test infrastructure: tests/test_selfplay_cpu.py ties it to
-the numpy expressions the reference runs, tests/test_selfplay_gpu.py runs the device against it.
+the numpy expressions the reference runs and tests/test_az_reference_cpu.py to whole games of the reference's own
+play_game (tests/golden/selfplay_traces.npz); tests/test_selfplay_gpu.py runs the device against it.
 
 What it restates, by line of the reference's self_play.py:
   :43-76   play_game: until the root is terminal, n_rollouts x do_rollout, choose, make_move; the visited roots and the
@@ -90,11 +91,12 @@ def record(tree, ply, n_rollouts, alpha, v_first, v_second, out):
     return out["actions"]
 
 
-def play(G, n_rollouts, n_sims, seed=0, alpha=1.0, c_puct=1.0, v_first=1.0, v_second=0.0):
-    """SelfPlay.play(seed) with net=None: (the batch, the final OracleBoards).  The environment's collapse bits are the
-    counter hash of (seed, game, ply); the trees draw with 2 * seed + 1."""
+def play(G, n_rollouts, n_sims, seed=0, alpha=1.0, c_puct=1.0, v_first=1.0, v_second=0.0, net=None):
+    """SelfPlay.play(seed): (the batch, the final OracleBoards); net = None (MCTS) or the state dict of an exact network
+    (TreeModel(net=...)).  The environment's collapse bits are the counter hash of (seed, game, ply); the trees draw
+    with 2 * seed + 1."""
     env = oracle.OracleBoards(G)
-    tree = tree_model.TreeModel(n_sims, seed=2 * seed + 1, board_offset=0, c_puct=c_puct)
+    tree = tree_model.TreeModel(n_sims, seed=2 * seed + 1, board_offset=0, c_puct=c_puct, net=net)
     tree.reset(env)
     out = new_batch(G)
     for ply in range(ROWS):
@@ -105,3 +107,44 @@ def play(G, n_rollouts, n_sims, seed=0, alpha=1.0, c_puct=1.0, v_first=1.0, v_se
         env.step(actions.copy(), None, seed, ply, 0, False)          # self_play.py:69; (255, 255) is a noop
         tree.sync(env)
     return out, env
+
+
+# ---------------------------------------------------------------- tests/golden/selfplay_traces.npz
+def golden_games(path):
+    """Per network of the fixture: dict(net, seed, n_rollouts, n_sims, G, and the reference's own s f32[n,18,10],
+    pi f64[n,36], mask bool[n,36], v i8[n], done bool[n] in game-major order, length u8[G], winner i8[G],
+    actions u8[G,9] (255 past the game's end) and bits u8[G,9])."""
+    z = np.load(path)
+    out = []
+    for name in (str(x) for x in z["nets"]):
+        d = {k: z["%s_%s" % (name, k)] for k in ("s", "pi", "mask", "v", "done", "length", "winner", "actions", "bits")}
+        d.update(net=name, seed=int(z["seed"]), n_rollouts=int(z["n_rollouts"]), n_sims=int(z["n_sims"]), G=len(d["length"]))
+        out.append(d)
+    return out
+
+
+def assert_rows_equal_reference(fx, s, pi, mask, v, done):
+    """The batch rows (game-major, as SelfPlayBatch.flat() and the reference's lists) against one network of the
+    fixture: everything exact but pi, whose sum the device takes in wave order and numpy in its own: two orders of 36
+    non-negative doubles differ by less than 2 * 35 * 2^-53 relative, so rtol = 1e-14 and atol = 0; the illegal
+    entries are exactly 0 and the terminal row exactly 1 / 36 under a full mask."""
+    assert s.dtype == np.float32 and np.array_equal(s, fx["s"])
+    assert np.array_equal(np.asarray(mask, dtype=bool), fx["mask"])
+    assert np.array_equal(np.asarray(done, dtype=bool), fx["done"])
+    v = np.asarray(v, dtype=np.float32)
+    assert np.array_equal(v.view(np.uint32), fx["v"].astype(np.float32).view(np.uint32))
+    assert pi.dtype == np.float64 and pi.shape == fx["pi"].shape
+    np.testing.assert_allclose(pi, fx["pi"], rtol=1e-14, atol=0.0)
+    assert (pi[~fx["mask"]] == 0).all()
+    last = fx["done"]
+    assert last.sum() == fx["G"] and (pi[last] == 1.0 / 36.0).all() and fx["mask"][last].all()
+    assert np.array_equal(np.flatnonzero(last), np.cumsum(fx["length"].astype(np.int64)) - 1)
+
+
+def assert_games_equal_reference(fx, action36, length, winner):
+    """action36 u8[10, G], length[G] and winner[G] of a batch against the games the reference played."""
+    assert np.array_equal(length, fx["length"]) and np.array_equal(winner, fx["winner"])
+    for g in range(fx["G"]):
+        n = int(fx["length"][g])
+        assert np.array_equal(action36[:n - 1, g], fx["actions"][g, :n - 1]) and action36[n - 1, g] == 255, g
+        assert (fx["actions"][g, n - 1:] == 255).all() and not action36[n:, g].any(), g

@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from policy_playout_model import draw
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "qttt_policy_rollout.h")
 
@@ -24,12 +26,6 @@ def _declared():
 
 
 # ---------------------------------------------------------------- the draw rule (include/qttt_policy_rollout.h)
-def draw(h64):
-    """(collapse bit, u) of one ply from qttt_hash's 64 bits."""
-    h1, h2 = h64 & 0xFFFFFFFF, h64 >> 32
-    return h1 >> 31, (h2 >> 8) * 2.0 ** -24
-
-
 def pick(logits, legal, u):
     """The smallest legal a whose running sum of exp(logit - max) exceeds u * S, in float64; the largest legal a if none."""
     idx = [a for a in range(36) if legal >> a & 1]

@@ -12,10 +12,12 @@ import numpy as np
 import pytest
 import torch
 
+import policy_playout_model
 from hip_graph_nodes import kernels_enqueued
 from nn_reference64 import (forward64, golden_state_dict, greedy_state_dict, load_golden, random_play_env,
                             random_state_dict, zero_state_dict)
-from test_policy_rollout_cpu import draw
+from policy_playout_model import legal_list as _legal_list
+from policy_playout_model import uniform_choice
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -227,54 +229,11 @@ MODEL_BOARDS, MODEL_SIMS, MODEL_T0 = 513, 3, 4321       # 1 539 lanes: tiles of 
 
 
 def host_playout(env, S, t0, choose):
-    """The documented rule (include/qttt_policy_rollout.h) on the C oracle: lane (i, s) plays until its game is over,
-    ply p with (collapse bit, u) = draw(qttt_hash(seed, board_offset + i, t0 + 16 s + p)) and the action
-    choose(lane, p, legal mask, u), which must be legal.  Returns trace u8[n,S,9], result i8[n,S], plies u8[n,S] and
-    the boards' legal masks."""
+    """policy_playout_model.host_playout on the boards of `env`, with its seed and board_offset."""
     import oracle
-    pair = [oracle.ind2move(a) for a in range(36)]
     ex = {k: t.cpu().numpy() for k, t in env.export_boards().items()}
-    lanes = oracle.boards_from_arrays(ex["board"], ex["moves"], ex["n_moves"], ex["qmask"], ex["n_q"])
-    n, N = lanes.n, lanes.n * S
-    lanes.n, lanes.b = N, np.repeat(lanes.b, S)
-    trace, plies, legal0 = np.full((N, 9), 0xFF, np.uint8), np.zeros(N, np.uint8), None
-    for p in range(9):
-        _, terminal, legal, _ = oracle.node_info(lanes)
-        legal0 = legal[::S].copy() if p == 0 else legal0
-        live = np.flatnonzero((terminal == 0) & (legal != 0))
-        if not len(live):
-            break
-        acts, bits = np.zeros((len(live), 2), np.uint8), np.zeros(len(live), np.uint8)
-        for r, j in enumerate(live):
-            i, s = divmod(int(j), S)
-            bit, u = draw(oracle.hash64(env.seed, env.board_offset + i, t0 + 16 * s + p))
-            a = choose(int(j), p, int(legal[j]), u)
-            assert 0 <= a < 36 and int(legal[j]) >> a & 1, (j, p, a, hex(int(legal[j])))
-            acts[r], bits[r], trace[j, p] = pair[a], bit, a | bit << 6
-        sub = oracle.OracleBoards(len(live))
-        sub.b = lanes.b[live].copy()
-        sub.step(acts, bits)
-        lanes.b[live] = sub.b
-        plies[live] += 1
-    winner = oracle.node_info(lanes)[0]
-    result = np.where(winner < 0, 0, np.where(winner > 0, 1, -1)).astype(np.int8)
-    return trace.reshape(n, S, 9), result.reshape(n, S), plies.reshape(n, S), legal0
-
-
-def _legal_list(legal):
-    return [a for a in range(36) if legal >> a & 1]
-
-
-def uniform_choice(legal, u):
-    """The rule under equal logits, in f32 as the kernel computes it: every e_a = expf(0) = 1, S = k exactly, and the
-    action is the r-th legal one for the smallest r with float32(r + 1) > float32(u) * float32(k)."""
-    idx = _legal_list(legal)
-    target = np.float32(u) * np.float32(len(idx))
-    assert target.dtype == np.float32
-    for r, a in enumerate(idx):
-        if np.float32(r + 1) > target:
-            return a
-    return idx[-1]
+    ob = oracle.boards_from_arrays(ex["board"], ex["moves"], ex["n_moves"], ex["qmask"], ex["n_q"])
+    return policy_playout_model.host_playout(ob, env.seed, env.board_offset, S, t0, choose)
 
 
 def _assert_launch_equals(out, model):

@@ -1,13 +1,14 @@
 """The references of tests/test_policy_value_numerics_gpu.py, checked without a device: forward_contract (the precision
 contract of include/qttt_nn.h on the CPU) against the device run on record in DESIGN.md §10 and against the fixture, and
-the conditions that make the zero / greedy / counting networks exact."""
+the conditions that make the zero / greedy / counting / sharp counting networks exact."""
 import numpy as np
 import pytest
 import torch
 
-from nn_reference64 import (BINARY_COLUMNS, COUNTING_MAX, GREEDY_GAP, contract_hidden, counting_state_dict, forward64,
-                            forward_contract, golden_state_dict, greedy_state_dict, load_golden, random_play_vectors,
-                            scaled_state_dict, zero_state_dict)
+from nn_reference64 import (BINARY_COLUMNS, COUNTING_MAX, EXACT_NETS, GREEDY_GAP, SHARP_FACTOR, SHARP_TIED,
+                            contract_hidden, counting_state_dict, forward64, forward_contract, forward_reference32,
+                            golden_state_dict, greedy_state_dict, load_golden, random_play_vectors, scaled_state_dict,
+                            sharp_counting_state_dict, zero_state_dict)
 
 F64, F32, BF16 = torch.float64, torch.float32, torch.bfloat16
 
@@ -160,3 +161,63 @@ def test_zero_network_is_uniform_in_float32(positions):
     assert k.min() == 0 and k.max() == 36
     for row, kk in zip(p[k > 0][:50], k[k > 0][:50]):
         assert torch.equal(row[row > 0], torch.full((int(kk),), 1.0) / float(kk))
+
+
+def test_sharp_counting_network_gives_exact_uniform_probabilities_over_the_largest_logits():
+    """On random play: the logits are integer multiples of 128 below 2^17, every expf(logit - max) is exactly 1 or 0 in
+    f32, the probabilities are float32(1) / float32(m) on the m largest legal logits, and a fair share of the positions
+    has m = 1 and a fair share m > 1."""
+    sd, base = sharp_counting_state_dict(), counting_state_dict()
+    rows = torch.arange(36) % SHARP_TIED
+    assert SHARP_FACTOR == 128.0 and np.exp(np.float32(-SHARP_FACTOR)) == np.float32(0.0)
+    for k in sd:
+        head = k.startswith("pi_head")
+        assert torch.equal(sd[k], base[k][rows] * SHARP_FACTOR if head else base[k]), k
+        assert torch.equal(sd[k].to(BF16).to(F32), sd[k]) or k.endswith(".bias"), k      # biases stay f32
+    vec = random_play_vectors(2000, 77)
+    v, lg, p = forward64(sd, vec)
+    fin = torch.isfinite(lg)
+    live = fin.any(1)
+    assert torch.equal(lg[fin], (lg[fin] / 128).round() * 128) and lg[fin].abs().max() < 2 ** 17
+    top = torch.where(fin, lg, torch.tensor(-float("inf"), dtype=F64)).max(1, keepdim=True).values
+    e = np.exp((lg[live] - top[live]).to(F32).numpy())
+    assert e.dtype == np.float32 and set(np.unique(e).tolist()) == {0.0, 1.0}
+    tied = torch.from_numpy(e == 1)
+    m = tied.sum(1)
+    want = torch.where(tied, (torch.ones(len(m), dtype=F32) / m.to(F32))[:, None], torch.zeros((), dtype=F32))
+    share_one, share_more = (m == 1).float().mean().item(), (m > 1).float().mean().item()
+    print("sharp counting network on %d positions: m = 1 on %.3f, m > 1 on %.3f, m in %s; %d distinct largest actions"
+          % (len(m), share_one, share_more, sorted(m.unique().tolist()), len(lg[live].argmax(1).unique())))
+    assert share_one >= 0.15 and share_more >= 0.15 and len(m.unique()) >= 3
+    assert len(lg[live].argmax(1).unique()) >= 12                                        # the set moves with the position
+    # the float64 forward, the contract in both dtypes and accumulations, and the reference's own f32 operations
+    # (the f32-accumulated contract on a part of them: it sums term by term in Python)
+    n = 300
+    outs = [((v, lg, p), len(vec)), (forward_reference32(sd, vec), len(vec))]
+    outs += [(forward_contract(sd, vec[:n], dtype, acc), n) for dtype in (F32, BF16) for acc in (F64, F32)]
+    for o, n in outs:
+        assert torch.equal(o[0].to(F32).view(torch.int32), v[:n].to(F32).view(torch.int32))
+        assert torch.equal(o[1].to(F32).view(torch.int32), lg[:n].to(F32).view(torch.int32))
+        assert torch.equal(o[2][live[:n]].to(F32).view(torch.int32), want[:int(live[:n].sum())].view(torch.int32))
+        assert torch.isnan(o[2][~live[:n]]).all()
+
+
+@pytest.mark.parametrize("name", sorted(EXACT_NETS))
+def test_exact_networks_agree_bit_for_bit_in_every_forward(name):
+    """What lets a tree searched by the reference's own class be reproduced without a tolerance: the float64 forward
+    rounded to f32, the contract in f32 and bf16, and the reference's chain of torch f32 operations give the same value,
+    logits and probabilities bit for bit, and every expf(logit - max) the sampling rule forms is exactly 0 or 1."""
+    sd = EXACT_NETS[name]()
+    vec = random_play_vectors(240, 5)
+    ref = forward64(sd, vec)
+    live = torch.isfinite(ref[1]).any(1)
+    assert live.any() and not live.all() and torch.isnan(ref[2][~live]).all() and not torch.isnan(ref[2][live]).any()
+    outs = [forward_reference32(sd, vec)] + [forward_contract(sd, vec, dtype, F32) for dtype in (F32, BF16)]
+    for o in outs:
+        for a, b in zip(o, ref):
+            a, b = a.to(F32), b.to(F32)
+            assert torch.equal(torch.isnan(a), torch.isnan(b))
+            assert torch.equal(a.nan_to_num(7.0).view(torch.int32), b.nan_to_num(7.0).view(torch.int32))
+    top = ref[1][live].max(1, keepdim=True).values
+    e = np.exp((ref[1][live] - top).to(F32).numpy())
+    assert set(np.unique(e).tolist()) <= {0.0, 1.0}

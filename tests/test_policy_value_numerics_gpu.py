@@ -1,5 +1,5 @@
-"""The numerics of evaluate_kernel on the MI355X, pinned without a bound taken from the kernel: three networks whose
-outputs are exact (zero, greedy, counting: bit for bit in both precisions), the precision contract of include/qttt_nn.h
+"""The numerics of evaluate_kernel on the MI355X, pinned without a bound taken from the kernel: four networks whose
+outputs are exact (zero, greedy, counting, sharp counting: bit for bit in both precisions), the precision contract of include/qttt_nn.h
 (within 8 x the disagreement of two CPU accumulation dtypes, at weight scales 2^-20, 1 and 4), argmax / masks / row sums
 at scale, and non-finite weights (torch's propagation).  Positions: the fixture's 800 and 257 of random play; every
 network runs on the whole pool and on batches of 1, 63, 64, 65, 127, 128, 129 and 257 of it (the tile tails of M = 64
@@ -9,7 +9,7 @@ import torch
 
 from nn_reference64 import (GREEDY_VALUE, KEYS, concat_envs, contract_hidden, counting_state_dict, forward64,
                             forward_contract, golden_state_dict, greedy_state_dict, load_golden, random_play_env,
-                            random_state_dict, scaled_state_dict, zero_state_dict)
+                            random_state_dict, scaled_state_dict, sharp_counting_state_dict, zero_state_dict)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -135,6 +135,24 @@ def test_counting_network_equals_float64_bit_for_bit(pool):
     for a, b in zip(outs[torch.float32], outs[torch.bfloat16]):
         assert torch.equal(_bits(a), _bits(b))
     assert len(r64[1][torch.isfinite(r64[1])].unique()) >= 50
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_sharp_counting_network_is_exactly_uniform_over_the_largest_logits(pool, dtype):
+    """Value and logits are the float64 forward's bit for bit, and the probabilities exactly float32(1) / float32(m) on
+    the m largest legal logits and +0.0 elsewhere (tests/test_policy_value_numerics_cpu.py proves that the float64
+    forward gives exactly these)."""
+    sd = sharp_counting_state_dict()
+    r64 = forward64(sd, pool.vec)
+    v, lg, p = _triple(pool.evaluate(sd, dtype))
+    assert torch.equal(_bits(v), _bits(r64[0].to(F32))) and torch.equal(_bits(lg), _bits(r64[1].to(F32)))
+    live = pool.legal.any(1)
+    tied = r64[1] == r64[1].max(1, keepdim=True).values
+    m = tied.sum(1)
+    want = torch.where(tied, (torch.ones(pool.n, dtype=F32) / m.to(F32))[:, None], torch.zeros((), dtype=F32))
+    assert torch.equal(_bits(p[live]), _bits(want[live])) and torch.equal(_bits(p[live]), _bits(r64[2][live].to(F32)))
+    assert torch.isnan(p[~live]).all()
+    assert len(m[live].unique()) >= 3 and int((m[live] == 1).sum()) >= 50 and int((m[live] > 1).sum()) >= 50
 
 
 # ---------------------------------------------------------------- the precision contract, at three weight scales

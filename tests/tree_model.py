@@ -11,6 +11,11 @@ TreeModel(capacity=c) also restates the header's overflow rule: an expansion (in
 does not fit c nodes sets the game's sticky overflow flag and allocates nothing.  Node indices equal the device's: child
 0 at `used`, child 1 at `used + 1`, a fresh root appended.
 
+TreeModel(net=sd) searches as AlphaZero does (alphazero.py:192-205, 294-303) under an exact network of
+tests/nn_reference64.py: the playouts are the host network playout of tests/policy_playout_model.py and the leaf's priors
+the float64 forward's probabilities rounded to f32; tests/test_az_reference_cpu.py ties that to the reference's own
+AlphaZero class (tests/golden/az_tree_traces.npz) and QTTTGame (tests/golden/selfplay_traces.npz).
+
 compact() is qttt_tree_compact (the reference's _prune as MCTS.sync does it), a stable renumbering: per game the nodes
 reachable from the root keep their relative order, the root becomes node 0, every child list is rewritten, and the
 recorded path is cleared as by reset.  A game that is compact already (root 0, every node reachable) is left as it is,
@@ -55,8 +60,9 @@ class Node:
 
 
 class TreeModel:
-    def __init__(self, n_sims, seed=0, board_offset=0, c_puct=1.0, capacity=None):
+    def __init__(self, n_sims, seed=0, board_offset=0, c_puct=1.0, capacity=None, net=None):
         self.n_sims, self.seed, self.board_offset, self.c_puct = int(n_sims), int(seed), int(board_offset), float(c_puct)
+        self.net = net                                                    # None: MCTS; a state dict: AlphaZero
         self.capacity = None if capacity is None else int(capacity)       # None: the pool always fits
         self.games = []
         self.k = 0
@@ -104,8 +110,13 @@ class TreeModel:
         return oracle.OracleBoards.from_records(leaves)
 
     def playouts(self, leaves):
-        """result i8[G, n_sims] of the uniform playouts of rollout k (oracle.rollout, the draws of qttt_rollout_many)."""
+        """result i8[G, n_sims] of the playouts of rollout k: uniform (oracle.rollout, the draws of qttt_rollout_many),
+        or under the network (policy_playout_model.host_playout, the draws of qttt_rollout_policy)."""
         S = self.n_sims
+        if self.net is not None:
+            import policy_playout_model
+            return policy_playout_model.host_playout(leaves, self.seed, self.board_offset, S, self.k * S * SIM_STRIDE,
+                                                     net=self.net)[1]
         out = np.empty((leaves.n, S), dtype=np.int8)
         for s in range(S):
             out[:, s] = oracle.rollout(leaves, self.seed, self.k * S * SIM_STRIDE + s * SIM_STRIDE, self.board_offset)[0]
@@ -136,8 +147,16 @@ class TreeModel:
                     leaf.probs = np.array(probs[g], dtype=np.float32)
         self.k += 1
 
+    def priors(self, leaves):
+        """What backup takes as probs: None (uniform), or the network's f32[G, 36] rows of the leaves."""
+        if self.net is None:
+            return None
+        import policy_playout_model
+        return policy_playout_model.probs32(self.net, leaves)
+
     def rollout(self):
-        self.backup(self.playouts(self.select()))
+        leaves = self.select()
+        self.backup(self.playouts(leaves), self.priors(leaves))
 
     # ---- MCTS.sync: ob = the games' positions after the move
     def sync(self, ob):
@@ -197,6 +216,15 @@ class TreeModel:
             o["nodes_used"][g] = len(st["nodes"])
             o["overflow"][g] = st["overflow"]
         return o
+
+    def root_children_ntot(self):
+        """i32[G, 36, 2]: Ntot of the root's children per action and child index, -1 where there is none."""
+        out = np.full((len(self.games), 36, 2), -1, dtype=np.int32)
+        for g, st in enumerate(self.games):
+            for a, kids in enumerate(st["nodes"][st["root"]].children):
+                for c, i in enumerate(kids or ()):
+                    out[g, a, c] = st["nodes"][i].Ntot
+        return out
 
     # ---- the whole trees, node by node in allocation order (= the device's node indices)
     def dump(self):
@@ -265,6 +293,38 @@ def golden_groups(path):
                     "arrays": {k: z["r_" + k][sel] for k in ("board", "moves", "n_moves", "qmask", "n_q")},
                     "sync_action": z["r_sync_action"][sel], "sync_bit": z["r_sync_bit"][sel], "records": rows})
     return out
+
+
+def az_golden_groups(path):
+    """tests/golden/az_tree_traces.npz: a list of golden_groups-shaped dicts, one per (network, group), with "net" (the
+    name in nn_reference64.EXACT_NETS) and "n_synced" (the reference's len(nodes) right after its sync) besides; the
+    records hold P and child_Ntot too."""
+    z = np.load(path)
+    out = []
+    for ni, name in enumerate(str(x) for x in z["nets"]):
+        rec0 = 0
+        for gi in range(len(z["g_seed"])):
+            sel = np.nonzero(z["r_group"] == gi)[0]
+            nr = int(z["g_records"][gi])
+            rows = {k[2:]: z[k][ni, rec0:rec0 + len(sel) * nr].reshape((len(sel), nr) + z[k].shape[2:])
+                    for k in z.files if k.startswith("c_")}
+            rec0 += len(sel) * nr
+            out.append({"net": name, "group": gi, "seed": int(z["g_seed"][gi]), "offset": int(z["g_offset"][gi]),
+                        "n_sims": int(z["g_n_sims"][gi]), "after": int(z["g_after"][gi]),
+                        "checkpoints": [int(c) for c in z["g%d_checkpoints" % gi]],
+                        "roots": oracle.boards_from_arrays(z["r_board"][sel], z["r_moves"][sel], z["r_n_moves"][sel],
+                                                           z["r_qmask"][sel], z["r_n_q"][sel]),
+                        "arrays": {k: z["r_" + k][sel] for k in ("board", "moves", "n_moves", "qmask", "n_q")},
+                        "sync_action": z["n_sync_action"][ni][sel], "sync_bit": z["r_sync_bit"][sel],
+                        "n_synced": z["n_synced"][ni][sel], "records": rows})
+    return out
+
+
+def az_tight_capacity(grp):
+    """The smallest pool in which a search of the group that compacts after its sync never overflows: the largest
+    node count the reference has before the move (and one node for a fresh root) or at its last record."""
+    n = grp["records"]["n_nodes"]
+    return max(int(n[:, -2].max()) + 1, int(n[:, -1].max()))
 
 
 def after_move(ob, action36, bits):
