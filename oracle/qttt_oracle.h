@@ -5,8 +5,9 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library; the product
  * (qtttgym_amd + libqttt_hip.so) never does.
  *
- * Parity pin: checked bit-for-bit against tests/golden/step_traces.npz, which was produced by
- * running the unmodified reference here (tests/golden/make_golden.py), and fuzzed live against
+ * Parity pin: checked bit-for-bit against tests/golden/step_traces.npz and step_forest_traces.npz (forced
+ * forest shapes, re-root walks of 0..8 edges), which were produced by running the unmodified reference here
+ * (tests/golden/make_golden.py, make_golden_forest.py), and fuzzed live against
  * the imported reference in the build container (tests/test_oracle_vs_reference.py).
  */
 #ifndef QTTT_ORACLE_H

@@ -43,7 +43,11 @@ def tuning():
     assert L.qttt_set_tuning(0, 0) == 0
 
 
-@pytest.mark.parametrize("bpl,blk", [(1, 0), (2, 0), (4, 0), (1, 256), (2, 256), (1, 1024), (2, 1024), (0, 0)])
+# (boards per lane, workgroup size) as qttt_set_tuning takes them; 0 = chosen by batch size
+LAUNCH_SHAPES = [(1, 0), (2, 0), (4, 0), (1, 256), (2, 256), (1, 1024), (2, 1024), (0, 0)]
+
+
+@pytest.mark.parametrize("bpl,blk", LAUNCH_SHAPES)
 @pytest.mark.parametrize("n", [1, 3, 64, 65, 257, 4099, 262144])
 def test_every_launch_shape_vs_oracle(tuning, bpl, blk, n):
     """qttt_set_tuning(boards per lane 1|2|4, workgroup size 256|512|1024; 0 = by batch size) is exported

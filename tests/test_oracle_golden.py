@@ -1,6 +1,8 @@
 """T1: the C oracle (oracle/qttt_oracle.c) against the golden traces recorded from the
 unmodified reference (tests/golden/make_golden.py).  Bit-exact on every reference-visible
-quantity, reward compared as IEEE bits so that -0.0 (env.py:49) is pinned."""
+quantity, reward compared as IEEE bits so that -0.0 (env.py:49) is pinned.
+The check_* functions take any fixture of step_traces.npz's arrays (tests/test_forest_golden_cpu.py calls them on
+step_forest_traces.npz)."""
 import numpy as np
 
 import oracle
@@ -15,7 +17,7 @@ def replay(golden):
         yield t, ob, reward, term
 
 
-def test_oracle_matches_golden_state_and_outputs(golden):
+def check_oracle_state_and_outputs(golden):
     for t, ob, reward, term in replay(golden):
         assert np.array_equal(ob.board, golden["board"][:, t]), t
         assert np.array_equal(ob.n_moves, golden["n_moves"][:, t]), t
@@ -30,7 +32,7 @@ def test_oracle_matches_golden_state_and_outputs(golden):
         assert np.array_equal(p2, golden["p2_round"][:, t]), t
 
 
-def test_oracle_matches_golden_observation(golden):
+def check_oracle_observation(golden):
     for t, ob, _, _ in replay(golden):
         classical, q1, l1, q2, l2, turn = ob.observe()
         assert np.array_equal(classical, golden["board"][:, t])
@@ -41,12 +43,24 @@ def test_oracle_matches_golden_observation(golden):
         assert np.array_equal(turn, golden["turn"][:, t])
 
 
-def test_reward_is_negative_zero_or_minus_one(golden):
+def check_reward_is_negative_zero_or_minus_one(golden):
     r = golden["reward"]
     assert np.signbit(r).all()
     assert set(np.unique(np.abs(r))) <= {0.0, 1.0}
     bits = r.astype(np.float32).view(np.uint32)
     assert set(np.unique(bits)) <= {0x80000000, 0xBF800000}
+
+
+def test_oracle_matches_golden_state_and_outputs(golden):
+    check_oracle_state_and_outputs(golden)
+
+
+def test_oracle_matches_golden_observation(golden):
+    check_oracle_observation(golden)
+
+
+def test_reward_is_negative_zero_or_minus_one(golden):
+    check_reward_is_negative_zero_or_minus_one(golden)
 
 
 def test_known_answer_traces(golden):
@@ -101,10 +115,11 @@ def test_oracle_state_invariants_under_random_play():
                     assert j == 8 and int(board[i][lo]) == 8       # autofill is always round 8
 
 
-def test_pure_python_restatement_matches_golden(golden):
+def check_pure_python_restatement(golden, every=3, every_full=7):
+    """PyEnv.step on every `every`-th episode from 0, PyEnv.step_full on every `every_full`-th from 1."""
     from oracle.py_env import PyEnv
     acts, bits = golden["actions"], golden["bits"]
-    for e in range(0, acts.shape[0], 3):
+    for e in range(0, acts.shape[0], every):
         env = PyEnv()
         for t in range(acts.shape[1]):
             r, term = env.step(int(acts[e, t, 0]), int(acts[e, t, 1]), int(bits[e, t]))
@@ -113,7 +128,7 @@ def test_pure_python_restatement_matches_golden(golden):
             assert np.float64(r).view(np.uint64) == golden["reward"][e, t].view(np.uint64)
             assert term == bool(golden["terminated"][e, t])
     # ... and the form that returns what the reference's Env.step returns, observation included (env.py:46,68-85)
-    for e in range(1, acts.shape[0], 7):
+    for e in range(1, acts.shape[0], every_full):
         env = PyEnv()
         for t in range(acts.shape[1]):
             obs, r, term, trunc, info = env.step_full(int(acts[e, t, 0]), int(acts[e, t, 1]), int(bits[e, t]))
@@ -123,3 +138,7 @@ def test_pure_python_restatement_matches_golden(golden):
             for key, g, ln in (("q_states_p1", "q_p1", "q_p1_len"), ("q_states_p2", "q_p2", "q_p2_len")):
                 k = int(golden[ln][e, t])
                 assert [list(p) for p in obs[key]] == golden[g][e, t, :k].tolist(), (e, t, key)
+
+
+def test_pure_python_restatement_matches_golden(golden):
+    check_pure_python_restatement(golden)

@@ -37,7 +37,9 @@ def _same(got, want, what, t):
         None if bad is None or not len(bad) else want[tuple(bad[0])]))
 
 
-def test_golden_traces_through_hip(golden):
+def check_traces_through_hip(golden):
+    """A fixture of step_traces.npz's arrays through VecEnv.step: every field of every step (tests/test_forest_parity_gpu.py
+    calls it on step_forest_traces.npz)."""
     from qtttgym_amd import VecEnv
     acts, bits = golden["actions"], golden["bits"]
     E, T = bits.shape
@@ -64,6 +66,10 @@ def test_golden_traces_through_hip(golden):
         p1, p2 = env.check_win()
         _same(_np(p1), golden["p1_round"][:, t], "p1_round", t)
         _same(_np(p2), golden["p2_round"][:, t], "p2_round", t)
+
+
+def test_golden_traces_through_hip(golden):
+    check_traces_through_hip(golden)
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 4096, 262144])
