@@ -6,7 +6,7 @@ the new weights for the search and repeats.
 
     python examples/selfplay_train.py [--games 1024] [--rollouts 100] [--sims 10] [--epochs 50] [--runs 30]
                                       [--dtype f32|bf16] [--out model.pt] [--model model.pt] [--value-targets 1,0]
-                                      [--symmetries]
+                                      [--symmetries] [--leaf-eval playouts|value]
 
 The network is nn.Model's (nn.py:7-28) under its own parameter names (qtttgym_amd.policy_value.SHAPES), so --out is a
 state dict that the reference, PolicyValueNet and examples/tree_tournament.py --model all load.  The loss is the
@@ -15,7 +15,9 @@ target to the network's policy over the legal actions of the samples that are no
 (lr 1e-3, weight decay 1e-3, amsgrad).  --value-targets 1,0 are the reference's targets, 1,-1 what it evidently meant
 (qtttgym_amd.SelfPlay).  --dtype is the precision of the search's network; training is f32.  --symmetries trains on
 every game's eight images under the board's symmetries (SelfPlayBatch.augment: eight times the samples for the same
-search), which the reference left as a stub (self_play.py expand_symetries).
+search), which the reference left as a stub (self_play.py expand_symetries).  --leaf-eval value searches with the
+network's value head at the leaves instead of --sims playouts (TreeSearch(leaf_eval="value")): the value head that every
+run trains is then what the next run searches with; use --value-targets 1,-1 with it, the scale of a terminal leaf.
 """
 import argparse
 import os
@@ -70,6 +72,8 @@ def main():
     ap.add_argument("--model", default=None, help="state dict to start from (default: torch's initialisation)")
     ap.add_argument("--value-targets", default="1,0", help="v of the first row when the first / second player wins")
     ap.add_argument("--symmetries", action="store_true", help="train on the eight images of every game")
+    ap.add_argument("--leaf-eval", choices=("playouts", "value"), default="playouts",
+                    help="what scores a leaf of the search: --sims playouts, or the network's value head")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     torch.manual_seed(args.seed)
@@ -81,7 +85,7 @@ def main():
     net = PolicyValueNet(model, device=dev, dtype=torch.float32 if args.dtype == "f32" else torch.bfloat16)
     targets = tuple(float(x) for x in args.value_targets.split(","))
     sp = SelfPlay(args.games, n_rollouts=args.rollouts, num_simulations=args.sims, net=net, value_targets=targets,
-                  seed=args.seed)
+                  seed=args.seed, leaf_eval=args.leaf_eval)
     for run in range(args.runs):
         batch = sp.play()
         s, pi, mask, v_target, done = (batch.augment() if args.symmetries else batch).flat()

@@ -8,8 +8,9 @@ syncs after every move (strat_eval.play_game).  Finished games are frozen: their
                                        [--weights tests/golden/model_eval.npz | --model model.pt]
                                        [--compact [--carry N]]
 
-A player is mcts:R (uniform playouts and priors, MCTS(R)), az:R (the network's playouts and priors, AlphaZero(R)) or
-random (the uniform-legal policy).  Prints player 1's win, loss and draw counts and rates.
+A player is mcts:R (uniform playouts and priors, MCTS(R)), az:R (the network's playouts and priors, AlphaZero(R)),
+azv:R (the network's value head at the leaf and its priors, TreeSearch(leaf_eval="value"): no playouts) or random (the
+uniform-legal policy).  Prints player 1's win, loss and draw counts and rates.
 
 --compact: every tree gives the nodes outside its new root's subtree back after each sync (TreeSearch.compact, the
 reference's _prune), so its pool holds 2 * R + carry nodes instead of every node of the game.
@@ -33,8 +34,8 @@ def parse_player(spec):
     kind, _, n = spec.partition(":")
     if kind == "random":
         return ("random", 0)
-    if kind not in ("mcts", "az") or not n.isdigit() or int(n) < 1:
-        raise SystemExit("a player is mcts:R, az:R or random, not %r" % spec)
+    if kind not in ("mcts", "az", "azv") or not n.isdigit() or int(n) < 1:
+        raise SystemExit("a player is mcts:R, az:R, azv:R or random, not %r" % spec)
     return (kind, int(n))
 
 
@@ -57,8 +58,8 @@ def play(players, G, sims, net, seed, carry=None):
             continue
         own_moves = 5 if i == 0 else 4
         capacity = 1 + 2 * R * own_moves + 9 if carry is None else 2 * R + (carry if carry >= 0 else 2 * R + 2)
-        t = TreeSearch(G, capacity=capacity, num_simulations=sims, net=net if kind == "az" else None,
-                       seed=seed * 2 + 1 + i, device=env.device)
+        t = TreeSearch(G, capacity=capacity, num_simulations=sims, net=net if kind in ("az", "azv") else None,
+                       seed=seed * 2 + 1 + i, device=env.device, leaf_eval="value" if kind == "azv" else "playouts")
         t.reset(env)
         trees.append(t)
     finished = torch.zeros(G, dtype=torch.bool, device=env.device)
@@ -106,7 +107,7 @@ def main():
     if half < 1:
         raise SystemExit("--games must be at least 2")
     net = None
-    if "az" in (p1[0], p2[0]):
+    if {"az", "azv"} & {p1[0], p2[0]}:
         net = PolicyValueNet(load_state_dict(args), device="cuda",
                              dtype=torch.float32 if args.dtype == "f32" else torch.bfloat16)
     if args.carry is not None and not args.compact:

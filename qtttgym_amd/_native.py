@@ -112,6 +112,10 @@ SYMMETRY_SIGNATURES = {
     "qttt_transform": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp]),
     "qttt_selfplay_augment": (_i32, [_i64, _u8p, _i32] + [_vp] * 18 + [_vp]),
 }
+# every symbol include/qttt_tree_value.h declares (the value rollout of the search trees; qttt.h includes it)
+TREE_VALUE_SIGNATURES = {
+    "qttt_tree_value_rollout": (_i32, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
+}
 
 _lib = None
 
@@ -176,7 +180,7 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(NN_SIGNATURES.items())
                                   + list(POLICY_ROLLOUT_SIGNATURES.items()) + list(TREE_SIGNATURES.items())
                                   + list(TREE_COMPACT_SIGNATURES.items()) + list(SELFPLAY_SIGNATURES.items())
-                                  + list(SYMMETRY_SIGNATURES.items())):
+                                  + list(SYMMETRY_SIGNATURES.items()) + list(TREE_VALUE_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -50,7 +50,8 @@
 // of a pair, the uniform playout) -> qttt_aux_kernels.h (the cold kernels, the reset fills), qttt_mcts_kernels.h,
 // qttt_nn_kernels.h (the policy/value network) -> qttt_policy_rollout_kernels.h (network-guided playouts);
 // qttt_tree_kernels.h (the batched search trees) -> qttt_selfplay_kernels.h (the self-play record) ->
-// qttt_symmetry_kernels.h (the board's symmetries: images of states, the augmented self-play batch).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
+// qttt_symmetry_kernels.h (the board's symmetries: images of states, the augmented self-play batch);
+// qttt_tree_value_kernels.h (the value rollout: network evaluation of the leaves and backup in one launch).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
 // qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
@@ -63,6 +64,7 @@
 #include "qttt_tree_kernels.h"
 #include "qttt_selfplay_kernels.h"
 #include "qttt_symmetry_kernels.h"
+#include "qttt_tree_value_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -767,6 +769,21 @@ int qttt_selfplay_augment(int64_t games, const uint8_t *symmetries, int n_sym, c
                              winner_out, actions_out};
     return launch(selfplay_augment_kernel, ceil_div(games * n_sym, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, games, (u32)n_sym,
                   syms, in, out);
+}
+
+// ---------------------------------------------------------------- the value rollout (include/qttt_tree_value.h)
+int qttt_tree_value_rollout(void *tree, int64_t games, int64_t capacity, const void *leaf_state, const void *weights,
+                            int precision, float *leaf_value, float *leaf_probs, void *stream) {
+    if (tree_size_bad(games, capacity) || (precision != QTTT_NN_F32 && precision != QTTT_NN_BF16)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, leaf_state, weights)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(weights, 16) || misaligned(leaf_value, 4) || misaligned(leaf_probs, 4))
+        return QTTT_ERR_ACTION;                                  // 16-byte node vectors and fragment loads / f32 stores
+    const Planes l = planes(const_cast<void *>(leaf_state), games);
+    return with_int<QTTT_NN_F32, QTTT_NN_BF16>(precision, [&](auto P) {
+        return launch(tree_value_rollout_kernel<P>, ceil_div(games, NNCfg<P>::M), QTTT_NN_BLOCK, stream, tree, games, capacity,
+                      l.P, l.Q, weights, leaf_value, leaf_probs);
+    });
 }
 
 }  // extern "C"

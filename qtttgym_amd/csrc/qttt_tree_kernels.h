@@ -230,6 +230,54 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_select_kernel(void *tree, int
     }
 }
 
+// _backpropogate (mcts.py:175-183), shared by tree_backup_kernel and tree_value_rollout_kernel
+// (qttt_tree_value_kernels.h).  Lane d < depth owns the d-th edge of the recorded path: tree_edge_load reads its
+// statistics, tree_edge_store writes them back with a value `val` seen by the player to move at the leaf: the deepest
+// edge gets -val (r = -r, mcts.py:179), the one above +val, ...  Two halves, so that a kernel with several games per
+// wave can have the loads of all of them in flight before the first store.
+struct TreeEdge {
+    TreeSlot *slot;
+    TreeNodeHdr *hdr;
+    double W;
+    u32 N, Ntot;
+    bool on;
+};
+__device__ __forceinline__ TreeEdge tree_edge_load(const TreeView &v, int64_t g, const TreeGame *gh, int32_t depth, u32 lane) {
+    TreeEdge e;
+    e.on = (int32_t)lane < depth;
+    e.slot = nullptr; e.hdr = nullptr;
+    e.W = 0.0; e.N = 0u; e.Ntot = 0u;
+    if (e.on) {
+        const int32_t node = gh->path_node[lane];
+        const u32 a = gh->path_action[lane];
+        e.slot = &v.slots(g, node)[a];
+        e.hdr = v.hdr(g, node);
+        e.W = e.slot->W;
+        e.N = e.slot->N;
+        e.Ntot = e.hdr->Ntot;
+    }
+    return e;
+}
+__device__ __forceinline__ void tree_edge_store(const TreeEdge &e, int32_t depth, u32 lane, double val) {
+#pragma clang fp contract(off)
+    if (e.on) {
+        const double rv = ((depth - (int32_t)lane) & 1) ? -val : val;
+        e.slot->W = e.W + rv;
+        e.slot->N = e.N + 1u;
+        e.hdr->Ntot = e.Ntot + 1u;
+    }
+}
+// _simulate's priors (mcts.py:188-191): a leaf with flags lf that is not terminal and has no priors gets them, lane
+// a < 36 writing prob(a) of the network's row, or (network = false) the uniform flag alone; any other leaf is left alone
+template <typename F>
+__device__ __forceinline__ void tree_leaf_priors(const TreeView &v, int64_t g, int32_t leaf, u32 lf, u32 lane, bool network,
+                                                 F &&prob) {
+    if ((lf & (TN_PRIORS | TN_TERMINAL)) == 0u) {
+        if (network && lane < 36u) v.prior(g, leaf)[lane] = prob(lane);
+        if (lane == 0u) v.hdr(g, leaf)->flags = lf | TN_PRIORS | (network ? 0u : TN_UNIFORM);
+    }
+}
+
 // lane d < depth updates the d-th edge of the path; the leaf's priors go in with it
 __global__ __launch_bounds__(TREE_BLOCK) void tree_backup_kernel(void *tree, int64_t games, int64_t capacity,
                                                                  const int8_t *result, u32 n_sims,
@@ -246,23 +294,9 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_backup_kernel(void *tree, int
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) r += __shfl_xor(r, m);
     if (!(gflags & TG_LEAF_TURN)) r = -r;                        // r if leaf.turn else -r (mcts.py:171)
-    const double val = (double)r / (double)n_sims;               // mcts.py:173
-    if ((int32_t)lane < depth) {
-        const int32_t node = gh->path_node[lane];
-        const u32 a = gh->path_action[lane];
-        const double rv = ((depth - (int32_t)lane) & 1) ? -val : val;     // deepest edge first: r = -r (mcts.py:179)
-        TreeSlot *s = &v.slots(g, node)[a];
-        s->W = s->W + rv;
-        s->N = s->N + 1u;
-        TreeNodeHdr *h = v.hdr(g, node);
-        h->Ntot = h->Ntot + 1u;
-    }
-    TreeNodeHdr *lh = v.hdr(g, leaf);
-    const u32 lf = lh->flags;
-    if ((lf & (TN_PRIORS | TN_TERMINAL)) == 0u) {                // _simulate (mcts.py:188-191)
-        if (leaf_probs && lane < 36u) v.prior(g, leaf)[lane] = leaf_probs[g * 36 + lane];
-        if (lane == 0u) lh->flags = lf | TN_PRIORS | (leaf_probs ? 0u : TN_UNIFORM);
-    }
+    tree_edge_store(tree_edge_load(v, g, gh, depth, lane), depth, lane, (double)r / (double)n_sims);      // mcts.py:173
+    tree_leaf_priors(v, g, leaf, v.hdr(g, leaf)->flags, lane, leaf_probs != nullptr,
+                     [&](u32 a) { return leaf_probs[g * 36 + a]; });
 }
 
 __global__ __launch_bounds__(TREE_BLOCK) void tree_sync_kernel(void *tree, int64_t games, int64_t capacity,

@@ -84,10 +84,16 @@ class SelfPlay(LibCaller):
     compact=True compacts the trees after every move: their pool then holds 2 * n_rollouts + carry nodes (carry
     defaults to 2 * n_rollouts + 2; a carry that turns out too small raises ValueError before a node is lost) instead
     of 1 + 10 * (2 * n_rollouts + 1), at the price of one host read-back per move.  Without it play() never waits
-    for the device."""
+    for the device.
+    leaf_eval is TreeSearch's: "playouts" (the reference's rollout) or "value" (the leaf scored by net's value head)."""
 
     def __init__(self, num_games, n_rollouts=100, num_simulations=10, net=None, alpha=1.0, c_puct=1.0,
-                 value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None):
+                 value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts"):
+        if leaf_eval not in TreeSearch.LEAF_EVALS:
+            raise ValueError("leaf_eval must be one of %s" % (TreeSearch.LEAF_EVALS,))
+        if leaf_eval == "value" and net is None:
+            raise ValueError('leaf_eval="value" needs a net')
+        self.leaf_eval = leaf_eval
         self.num_games, self.n_rollouts = int(num_games), int(n_rollouts)
         self.num_simulations, self.net = int(num_simulations), net
         self.alpha, self.c_puct, self.seed, self.compact = float(alpha), float(c_puct), int(seed), bool(compact)
@@ -148,7 +154,8 @@ class SelfPlay(LibCaller):
         G, R = self.num_games, self.n_rollouts
         env = self.env = VecEnv(G, device=self.device, seed=s)
         tree = self.tree = TreeSearch(G, capacity=self.capacity, num_simulations=self.num_simulations,
-                                      c_puct=self.c_puct, net=self.net, seed=2 * s + 1, device=self.device)
+                                      c_puct=self.c_puct, net=self.net, seed=2 * s + 1, device=self.device,
+                                      leaf_eval=self.leaf_eval)
         tree.reset(env)
         batch = self.new_batch()
         for ply in range(ROWS):

@@ -2,7 +2,10 @@
 G independent games, kept on the device (include/qttt_tree.h).
 
 A rollout is select -> playouts from the leaf (VecEnv.rollout_many, or VecEnv.rollout_policy under a network) ->
-backup, three launches on the current stream with no host synchronisation.  Nodes that sync leaves behind stay
+backup, three launches on the current stream with no host synchronisation.  leaf_eval="value" is the standard AlphaZero
+search instead (include/qttt_tree_value.h): the leaf's value is the network's value head and its priors
+the policy head, one evaluation fused with the backup, so a rollout is select -> value rollout, two launches and no
+playout.  Nodes that sync leaves behind stay
 allocated until compact() (the reference's _prune) gives them back: with a compact() after every sync, `capacity` has
 to hold the kept subtree and one move's rollouts; without it, every rollout and sync since the last reset.  The host
 keeps an upper bound on the nodes used (+2 per rollout, +1 per sync; compact() replaces it by the real maximum) and
@@ -21,15 +24,26 @@ class TreeSearch(LibCaller):
                   "P": (torch.float64, (36,)), "Ntot": (torch.int32, ()), "choose": (torch.uint8, ()),
                   "nodes_used": (torch.int32, ()), "overflow": (torch.uint8, ())}
 
+    LEAF_EVALS = ("playouts", "value")
+    leaf_eval = "playouts"
+
     def __init__(self, num_games, capacity, num_simulations=10, c_puct=1.0, net=None, seed=0, board_offset=0,
-                 device=None):
+                 device=None, leaf_eval="playouts"):
+        """leaf_eval="playouts": the reference's rollout, num_simulations playouts from the leaf (uniform, or guided by
+        `net`).  leaf_eval="value" (needs `net`): the leaf is scored by the value head, seen by the player to move
+        there; a terminal leaf by its reward.  num_simulations is then ignored: no playout draw is taken."""
+        if leaf_eval not in self.LEAF_EVALS:
+            raise ValueError("leaf_eval must be one of %s" % (self.LEAF_EVALS,))
+        if leaf_eval == "value" and net is None:
+            raise ValueError('leaf_eval="value" needs a net')
+        self.leaf_eval = leaf_eval
         self.num_games, self.capacity = int(num_games), int(capacity)
         self.num_simulations, self.c_puct = int(num_simulations), float(c_puct)
         self.net, self.seed, self.board_offset = net, int(seed), int(board_offset)
         if self.num_games < 0 or not 1 <= self.capacity <= _native.TREE_MAX_CAPACITY:
             raise ValueError("num_games must be >= 0 and capacity in 1..%d" % _native.TREE_MAX_CAPACITY)
         limit = _native.POLICY_ROLLOUT_MAX_SIMS if net is not None else _native.TREE_MAX_SIMS
-        if not 1 <= self.num_simulations <= limit:
+        if leaf_eval != "value" and not 1 <= self.num_simulations <= limit:
             raise ValueError("num_simulations must be in 1..%d" % limit)
         if self.board_offset < 0:
             raise ValueError("board_offset must be >= 0")
@@ -45,8 +59,10 @@ class TreeSearch(LibCaller):
         self.tree = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
         leaf_state = torch.zeros(int(self._lib.qttt_state_bytes(G)), dtype=torch.uint8, device=dev)
         self.leaf = VecEnv.from_state(leaf_state, G, seed=self.seed, board_offset=self.board_offset)
-        # what the playouts write and the backup reads
-        if net is None:
+        # what the playouts write and the backup reads (a value rollout has neither)
+        if leaf_eval == "value":
+            self._out = None
+        elif net is None:
             self._out = out_tensor(torch.int8, (S,), G, dev)
         else:
             self._out = out_rows(VecEnv._policy_rows(S), G, dev, keys=("result", "probs"))
@@ -62,7 +78,9 @@ class TreeSearch(LibCaller):
     @property
     def max_rollouts(self):
         """Rollouts allowed between two resets: Ntot stays below QTTT_TREE_MAX_ROLLOUTS and the playouts' step indices
-        below QTTT_TREE_SELECT_BASE."""
+        below QTTT_TREE_SELECT_BASE (value rollouts draw nothing but select's bits, addressed by the rollout index)."""
+        if self.leaf_eval == "value":
+            return _native.TREE_MAX_ROLLOUTS
         return min(_native.TREE_MAX_ROLLOUTS, _native.TREE_SELECT_BASE // (self.num_simulations * _native.SIM_STRIDE))
 
     # ------------------------------------------------------------------ the reference's interface, batched
@@ -91,12 +109,16 @@ class TreeSearch(LibCaller):
             self._bound += 2
 
     def _rollout(self):
-        """One rollout, without contemplate's bounds: select, the playouts from the leaves, backup."""
+        """One rollout, without contemplate's bounds: select, the playouts from the leaves, backup; or select and the
+        value rollout."""
         G, cap, S, k = self.num_games, self.capacity, self.num_simulations, self.rollout_idx
         tree, leaf = self.tree.data_ptr(), self.leaf.state.data_ptr()
         step_idx0 = k * S * _native.SIM_STRIDE
         self._call("qttt_tree_select", tree, G, cap, self.seed, k, self.board_offset, self.c_puct, leaf)
-        if self.net is None:
+        if self.leaf_eval == "value":
+            self._call("qttt_tree_value_rollout", tree, G, cap, leaf, self.net.blob.data_ptr(), self.net.precision,
+                       None, None)
+        elif self.net is None:
             self.leaf.rollout_many(S, step_idx0=step_idx0, out=self._out)
             self._call("qttt_tree_backup", tree, G, cap, self._out.data_ptr(), S, None)
         else:

@@ -6,6 +6,11 @@ over the measured rollouts), the playouts alone re-run on the same leaves as the
     python tools/treebench.py [--games 4096,65536,262144] [--modes uniform,f32,bf16] [--sims 10] [--rollouts 32]
                               [--warmup 4] [--out profiles/tree/treebench.jsonl]
 
+--value-games 4096,65536,262144 adds the value-rollout leg (TreeSearch(leaf_eval="value")) per dtype of
+--value-modes f32,bf16: medians over --value-reps repetitions, the legs interleaved within each repetition, of a value
+rollout (select + the fused launch), a playout rollout at --sims, the fused launch alone, and qttt_evaluate (value +
+probs) and qttt_tree_backup alone on the same leaves.
+
 --compact-games 4096,65536 adds the compaction leg (uniform playouts): per move contemplate(R) -> choose -> step ->
 sync -> compact(), timed with HIP events around contemplate and around compact (its launch alone; the read-back of the
 bound comes after the second event), medians over the moves of --compact-reps games from the empty board, with the
@@ -87,6 +92,53 @@ def run(G, mode, sims, rollouts, warmup):
             "nodes_used_mean": round(float(used.mean()), 2), "nodes_used_max": int(used.max())}
 
 
+def run_value(G, mode, sims, reps, rollouts=6, warmup=4):
+    """One JSON row: medians over `reps` interleaved repetitions of `rollouts` launches per leg."""
+    import statistics
+    net = _net(torch.float32 if mode == "f32" else torch.bfloat16)
+    env = VecEnv(G, seed=1)
+    env.step_random_many(2)
+    cap = 1 + 2 * (warmup + (reps + 1) * rollouts * 2)
+    tv = TreeSearch(G, capacity=cap, net=net, seed=2, leaf_eval="value")
+    tp = TreeSearch(G, capacity=1 + 2 * (warmup + (reps + 1) * rollouts), num_simulations=sims, net=net, seed=2)
+    for t in (tv, tp):
+        t.reset(env)
+        t.contemplate(warmup)
+    stream = torch.cuda.current_stream()
+    ev_out = tv.leaf.evaluate(net, rows=("value", "probs"))
+    res = torch.zeros((G, sims), dtype=torch.int8, device=env.device)
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        for _ in range(rollouts):
+            fn()
+        b.record(stream)
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e3 / rollouts
+
+    def fused():                                 # the leaves of the last select again: the tree keeps its shape
+        tv._call("qttt_tree_value_rollout", tv.tree.data_ptr(), G, tv.capacity, tv.leaf.state.data_ptr(),
+                 net.blob.data_ptr(), net.precision, None, None)
+
+    legs = {"value_rollout": lambda: tv.contemplate(1), "playout_rollout": lambda: tp.contemplate(1), "fused": fused,
+            "evaluate": lambda: tv.leaf.evaluate(net, out=ev_out),
+            "backup": lambda: tv._call("qttt_tree_backup", tv.tree.data_ptr(), G, tv.capacity, res.data_ptr(), sims,
+                                       ev_out["probs"].data_ptr())}
+    us = {k: [] for k in legs}
+    for rep in range(reps + 1):
+        for k, fn in legs.items():
+            x = timed(fn)
+            if rep:                              # the first repetition warms every leg up
+                us[k].append(x)
+    row = {"games": G, "mode": mode, "leg": "value", "n_sims": sims, "reps": reps, "launches_per_rep": rollouts}
+    for k, xs in us.items():
+        row["us_%s_median" % k] = round(statistics.median(xs), 2)
+        row["us_%s_min_max" % k] = [round(min(xs), 2), round(max(xs), 2)]
+    row["us_evaluate_plus_backup_median"] = round(row["us_evaluate_median"] + row["us_backup_median"], 2)
+    return row
+
+
 def run_compact(G, sims, R, reps, moves=4):
     """contemplate(R) + a move + sync + compact(), `moves` times per game from the empty board, `reps` games (the
     first one more as warm-up).  One JSON row: medians over every timed (game, move)."""
@@ -134,6 +186,9 @@ def main():
     ap.add_argument("--sims", type=int, default=10)
     ap.add_argument("--rollouts", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--value-games", default="")
+    ap.add_argument("--value-modes", default="f32,bf16")
+    ap.add_argument("--value-reps", type=int, default=7)
     ap.add_argument("--compact-games", default="")
     ap.add_argument("--compact-rollouts", type=int, default=300)
     ap.add_argument("--compact-reps", type=int, default=3)
@@ -143,6 +198,11 @@ def main():
     for G in [int(x) for x in args.games.split(",") if x]:
         for mode in args.modes.split(","):
             row = run(G, mode, args.sims, args.rollouts, args.warmup)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    for G in [int(x) for x in args.value_games.split(",") if x]:
+        for mode in args.value_modes.split(","):
+            row = run_value(G, mode, args.sims, args.value_reps)
             print(json.dumps(row), flush=True)
             rows.append(row)
     for G in [int(x) for x in args.compact_games.split(",") if x]:
