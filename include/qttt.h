@@ -92,7 +92,12 @@ int qttt_step_observe(void *state, const uint8_t *actions, const uint8_t *bits, 
  * bits + t*n (when bits != NULL), uses step_idx0 + t, and writes reward + t*out_stride and
  * terminated + t*out_stride (out_stride 0: only the LAST step's outputs are written, to the
  * first n elements: the earlier steps would be overwritten and store none — with and without
- * QTTT_FLAG_FUSED; reward and terminated are still required and checked for every step). */
+ * QTTT_FLAG_FUSED; reward and terminated are still required and checked for every step).
+ * Same results, not always n_steps launches: with out_stride 0, 448 K < n <= 1536 K boards (a batch that is one
+ * occupancy round of the step kernel), n_steps >= 16 and no launch shape named (QTTT_FLAG_SHAPE, qttt_set_tuning,
+ * QTTT_STEP_BPL / QTTT_STEP_BLOCK) the steps run with the boards held in registers, one launch per 64 steps, as with
+ * QTTT_FLAG_FUSED — only the state after the last step and that step's outputs can be read.  Every other call is one
+ * launch per step. */
 int qttt_step_many(void *state, const uint8_t *actions, const uint8_t *bits, uint64_t seed,
                    uint32_t step_idx0, int64_t board_offset, uint32_t flags, float *reward,
                    uint8_t *terminated, int64_t out_stride, int64_t n, int32_t n_steps,

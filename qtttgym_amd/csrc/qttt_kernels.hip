@@ -251,7 +251,9 @@ int qttt_step_many(void *state, const uint8_t *actions, const uint8_t *bits, uin
     if (n_steps < 0 || out_stride < 0) return QTTT_ERR_SIZE;
     const u64 first = (u64)(board_offset < 0 ? 0 : board_offset);
     const bool one_hi = n > 0 && (first >> 32) == ((first + (u64)n - 1u) >> 32);
-    if ((flags & QTTT_FLAG_FUSED) && n > 0 && n_steps > 0 && one_hi) {
+    // the boards in registers: asked for (QTTT_FLAG_FUSED), or the route of the one-round rows (resident_route, qttt_launch.h)
+    const bool fused = (flags & QTTT_FLAG_FUSED) != 0 || resident_route(n, flags, out_stride, n_steps);
+    if (fused && n > 0 && n_steps > 0 && one_hi) {
         if (board_offset < 0) return QTTT_ERR_SIZE;
         if (any_null(state, actions, reward, terminated)) return QTTT_ERR_NULL;
         if (misaligned(actions, 2)) return QTTT_ERR_ACTION;
@@ -260,12 +262,18 @@ int qttt_step_many(void *state, const uint8_t *actions, const uint8_t *bits, uin
         const u32 hi_fold = (u32)(first >> 32) * 0x9E3779B9u;
         const uint16_t *a16 = reinterpret_cast<const uint16_t *>(actions);
         u32 *rb = reinterpret_cast<u32 *>(reward);
-        // With out_stride == 0 every launch writes its last ply's outputs to the same place; the run's last wins.
+        // With out_stride == 0 only the run's last launch stores outputs (its last ply's, once, after the loop); the earlier
+        // launches are handed no output pointers.
         return fused_runs(seed, step_idx0, n_steps, [&](int64_t done, int32_t plies, const FusedKeys &keys) {
+            const int out = out_stride != 0 ? FUSED_OUT_EVERY : done + plies == n_steps ? FUSED_OUT_LAST : FUSED_OUT_NONE;
             return with_bools([&](auto HB, auto AR) {
-                return launch(step_fused_kernel<HB, AR>, ceil_div(n, QTTT_BLOCK), QTTT_BLOCK, stream, p.P, p.Q, a16 + done * n,
-                              bits ? bits + done * n : nullptr, keys, hi_fold, (u32)first, rb + done * out_stride,
-                              terminated + done * out_stride, out_stride, n, plies);
+                return with_int<FUSED_OUT_EVERY, FUSED_OUT_LAST, FUSED_OUT_NONE>(out, [&](auto OUT) {
+                    u32 *r_c = OUT == FUSED_OUT_NONE ? nullptr : rb + done * out_stride;
+                    uint8_t *t_c = OUT == FUSED_OUT_NONE ? nullptr : terminated + done * out_stride;
+                    return launch(step_fused_kernel<HB, AR, OUT>, ceil_div(n, QTTT_BLOCK), QTTT_BLOCK, stream, p.P, p.Q,
+                                  a16 + done * n, bits ? bits + done * n : nullptr, keys, hi_fold, (u32)first, r_c, t_c,
+                                  out_stride, n, plies);
+                });
             }, bits != nullptr, (flags & QTTT_FLAG_AUTO_RESET) != 0);
         });
     }

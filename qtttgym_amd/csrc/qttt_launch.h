@@ -32,6 +32,23 @@ inline void auto_tuning(int64_t n, int &bpl, int &blk) {
     else if (n <= 1536 * 1024) { bpl = 2; blk = 1024; }
     else { bpl = 2; blk = 256; }
 }
+// qttt_step_many's register-resident route: the rows of the table above where a batch is ONE occupancy round of the step
+// kernel — (1, 1024), (2, 512), (2, 1024): every board of the batch is on the chip at once and the whole working set sits in
+// the Infinity Cache.  There a run of steps whose per-step outputs nobody keeps (out_stride == 0) goes through
+// step_fused_kernel, one launch per FUSED_MAX_PLIES steps with the boards in registers, instead of one launch per step:
+// only the state after the last step and that step's reward / terminated can ever be read.  Not below and not above these
+// rows: there qttt_step_many is one launch per step, which is what bench.py's 4 096-, 262 144- and 16 M-board replay legs
+// are defined and accounted as.  Not for a caller who names a launch shape (the call's QTTT_FLAG_SHAPE bits
+// or the process tuning word): they are asking for the per-step kernel.  Not for runs shorter than RESIDENT_MIN_STEPS: a
+// short run at a chip-filling size is the form launch-level measurements are taken in (the mailbox's "launches 2 .. 9 after
+// a Board call"), and it stays what they measure; from 16 plies on the launch's own state round trip is under a tenth of
+// the run.  QTTT_FLAG_FUSED asks for the same kernel at any size and any length.
+constexpr int32_t RESIDENT_MIN_STEPS = 16;
+inline bool one_round_rows(int64_t n) { return n > 448 * 1024 && n <= 1536 * 1024; }
+inline bool shape_named(uint32_t flags);
+inline bool resident_route(int64_t n, uint32_t flags, int64_t out_stride, int32_t n_steps) {
+    return one_round_rows(n) && out_stride == 0 && n_steps >= RESIDENT_MIN_STEPS && !shape_named(flags);
+}
 // Process-wide DEFAULT launch shape (bench / profiling): boards per lane 1|2|4 and workgroup size
 // 256|512|1024, 0 = by batch size.  Initialised from QTTT_STEP_BPL / QTTT_STEP_BLOCK, changeable through
 // qttt_set_tuning(); one relaxed atomic word (bpl | block << 8), so concurrent callers never race on it.
@@ -44,6 +61,9 @@ inline std::atomic<int> &tuning_word() {
         return bpl | (blk << 8);
     }());
     return v;
+}
+inline bool shape_named(uint32_t flags) {
+    return (flags & ((7u << 8) | (3u << 12))) != 0 || tuning_word().load(std::memory_order_relaxed) != 0;
 }
 // the shape one call is launched with: the call's own QTTT_FLAG_SHAPE bits, else the process default,
 // else the table; `observe`: the observation tiles are sized for <= 2 boards per lane

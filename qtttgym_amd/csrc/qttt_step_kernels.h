@@ -240,7 +240,21 @@ __global__ __launch_bounds__(BLOCK) void step_quiet_kernel(
 // 3.57 -> 3.44 us per ply at 1 M boards, 1.19 -> 1.10 at 262 144 (profiles/r05/fused_kernarg_keys_check.txt).
 constexpr int FUSED_MAX_PLIES = 64;
 struct FusedKeys { u64 k[FUSED_MAX_PLIES]; };
-template <bool HAS_BITS, bool AUTO_RESET>
+// OUT — which plies' reward / terminated a launch stores:
+//   FUSED_OUT_EVERY  every ply's (out_stride != 0), from inside the loop;
+//   FUSED_OUT_LAST   its last ply's only (out_stride == 0, the last launch of a run): formed from `win` and P1 AFTER the
+//                    loop and stored once, beside the two planes;
+//   FUSED_OUT_NONE   none (out_stride == 0, the earlier launches of a run longer than FUSED_MAX_PLIES: the run's last
+//                    launch overwrites whatever they would store; they are handed no output pointers).
+// Without per-ply outputs the loop holds no store, no output pointer and no test of what to keep, and nothing couples the
+// action stream to a store queue: the actions are then requested FUSED_PREFETCH plies ahead instead of one (the stream of a
+// long replay comes from HBM, not from the Infinity Cache), and the state is consumed in front of the loop (as in
+// step_random_fused_kernel below) so that the wait for its loads does not land inside.
+constexpr int FUSED_OUT_NONE = 0, FUSED_OUT_LAST = 1, FUSED_OUT_EVERY = 2;
+// (tools/stepbench, interleaved, 1 M boards, us per step with 1 / 2 / 4 plies ahead: 3.29 / 3.27 / 3.29 at K = 200,
+// 3.46 / 3.43 / 3.47 at K = 20 — within the spread of the repeats; profiles/resident/stepbench_1M_k*.txt)
+constexpr int FUSED_PREFETCH = 2;
+template <bool HAS_BITS, bool AUTO_RESET, int OUT>
 __global__ __launch_bounds__(QTTT_BLOCK) void step_fused_kernel(
     u64 *__restrict__ pP, u64 *__restrict__ pQ, const uint16_t *__restrict__ actions,
     const uint8_t *__restrict__ bits, FusedKeys keys, u32 id_hi_fold, u32 id_base,
@@ -258,31 +272,69 @@ __global__ __launch_bounds__(QTTT_BLOCK) void step_fused_kernel(
     // per-ply streams: a block-uniform 64-bit base (scalar unit, advanced by the stride every ply) plus the lane's offset
     const uint16_t *a_blk = actions + ib;
     const uint8_t *b_blk = HAS_BITS ? bits + ib : nullptr;
-    u32 *r_blk = reward_bits + ib;
-    uint8_t *t_blk = terminated + ib;
     const u32 lane = threadIdx.x;
     u32 win = 0;
     u64 key = keys.k[0];
-    u32 act = load_stream(&a_blk[lane]), bit_in = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
-    for (int32_t t = 0; t < n_steps; ++t) {
-        const u64 key_next = keys.k[(t + 1) & (FUSED_MAX_PLIES - 1)];   // one scalar load, requested a ply ahead
-        // the next ply's action (and bit) are requested before this ply's step: their latency hides behind it
-        const bool more = t + 1 < n_steps;
-        a_blk += more ? n : 0;
-        if (HAS_BITS) b_blk += more ? n : 0;
-        const u32 act_next = load_stream(&a_blk[lane]), bit_next = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
-        const u32 bit = HAS_BITS ? (bit_in & 1u) : collapse_bit_of(id ^ (u32)key);
-        win = step_core<AUTO_RESET>(P0, P1, Q0, Q1, act, bit, lut);
-        if (out_stride != 0 || t == n_steps - 1) {
-            // (the compiler's own stores here: it counts them when it waits for the action requested a ply ahead)
-            store_stream(&r_blk[lane], 0x80000000u | (win << 23));
-            store_stream(&t_blk[lane], (uint8_t)(P1 >> 31));
+    if constexpr (OUT == FUSED_OUT_EVERY) {
+        u32 *r_blk = reward_bits + ib;
+        uint8_t *t_blk = terminated + ib;
+        u32 act = load_stream(&a_blk[lane]), bit_in = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
+        for (int32_t t = 0; t < n_steps; ++t) {
+            const u64 key_next = keys.k[(t + 1) & (FUSED_MAX_PLIES - 1)];   // one scalar load, requested a ply ahead
+            // the next ply's action (and bit) are requested before this ply's step: their latency hides behind it
+            const bool more = t + 1 < n_steps;
+            a_blk += more ? n : 0;
+            if (HAS_BITS) b_blk += more ? n : 0;
+            const u32 act_next = load_stream(&a_blk[lane]), bit_next = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
+            const u32 bit = HAS_BITS ? (bit_in & 1u) : collapse_bit_of(id ^ (u32)key);
+            win = step_core<AUTO_RESET>(P0, P1, Q0, Q1, act, bit, lut);
+            if (out_stride != 0 || t == n_steps - 1) {
+                // (the compiler's own stores here: it counts them when it waits for the action requested a ply ahead)
+                store_stream(&r_blk[lane], 0x80000000u | (win << 23));
+                store_stream(&t_blk[lane], (uint8_t)(P1 >> 31));
+            }
+            r_blk += out_stride;
+            t_blk += out_stride;
+            key = key_next;
+            act = act_next;
+            bit_in = bit_next;
         }
-        r_blk += out_stride;
-        t_blk += out_stride;
-        key = key_next;
-        act = act_next;
-        bit_in = bit_next;
+    } else {
+        // the actions (and bits) of plies 0 .. FUSED_PREFETCH - 1 are in flight before the first step; a ply past the
+        // launch's last re-reads the last one's (the base stops advancing), so every address stays inside the run
+        u32 act[FUSED_PREFETCH], bit_in[FUSED_PREFETCH];
+#pragma unroll
+        for (int k = 0; k < FUSED_PREFETCH; ++k) {
+            if (k > 0) {
+                const bool more = k < n_steps;
+                a_blk += more ? n : 0;
+                if (HAS_BITS) b_blk += more ? n : 0;
+            }
+            act[k] = load_stream(&a_blk[lane]);
+            bit_in[k] = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
+        }
+        asm volatile("" : "+v"(P0), "+v"(P1), "+v"(Q0), "+v"(Q1));
+        for (int32_t t = 0; t < n_steps; ++t) {
+            const u64 key_next = keys.k[(t + 1) & (FUSED_MAX_PLIES - 1)];   // one scalar load, requested a ply ahead
+            const bool more = t + FUSED_PREFETCH < n_steps;
+            a_blk += more ? n : 0;
+            if (HAS_BITS) b_blk += more ? n : 0;
+            const u32 act_far = load_stream(&a_blk[lane]), bit_far = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
+            const u32 bit = HAS_BITS ? (bit_in[0] & 1u) : collapse_bit_of(id ^ (u32)key);
+            win = step_core<AUTO_RESET>(P0, P1, Q0, Q1, act[0], bit, lut);
+            key = key_next;
+#pragma unroll
+            for (int k = 0; k + 1 < FUSED_PREFETCH; ++k) {
+                act[k] = act[k + 1];
+                bit_in[k] = bit_in[k + 1];
+            }
+            act[FUSED_PREFETCH - 1] = act_far;
+            bit_in[FUSED_PREFETCH - 1] = bit_far;
+        }
+        if constexpr (OUT == FUSED_OUT_LAST) {
+            store_stream(&reward_bits[i], 0x80000000u | (win << 23));   // env.py:49: -1.0f / -0.0f
+            store_stream(&terminated[i], (uint8_t)(P1 >> 31));          // env.py:51
+        }
     }
     store_stream(&pP[i], (u64)P0 | ((u64)P1 << 32));
     store_stream(&pQ[i], (u64)Q0 | ((u64)Q1 << 32));

@@ -5,7 +5,10 @@
 // device differences cancel.  Also times a "traffic floor" kernel that moves the same bytes per
 // board with no game logic.
 //   hipcc --offload-arch=gfx950 -O3 -Iinclude tools/stepbench.cpp -ldl -o tools/stepbench
-//   tools/stepbench N K REPS  lib.so[:boards_per_lane[:workgroup_size]] ...   (0 = the library's own choice)
+//   tools/stepbench N K REPS  lib.so[:boards_per_lane[:workgroup_size[:fused]]] ...   (0 = the library's own choice)
+// fused = 1: the replay with QTTT_FLAG_FUSED — the boards in registers, no outputs per ply (step_fused_kernel's output-free
+// loop), at any size.  With nothing named, a library takes that route itself in the one-round rows of its launch-shape
+// table (448 K < N <= 1536 K boards); naming a shape there (e.g. lib.so:2:1024) times the launch-per-step quiet kernel.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <cstdio>
@@ -104,7 +107,7 @@ __global__ __launch_bounds__(BLK) void floor16_kernel(u64 *pA, u64 *pB, const ui
 
 struct Lib {
     std::string spec, path;
-    int bpl, pipe;
+    int bpl, pipe, fused;
     void *h;
     int64_t (*state_bytes)(int64_t);
     int (*reset)(void *, int64_t, void *);
@@ -128,9 +131,9 @@ int main(int argc, char **argv) {
     std::vector<Lib> libs;
     for (int i = 4; i < argc; ++i) {
         Lib L; L.spec = argv[i];
-        char path[512]; int bpl = 0, pipe = 0;      // lib.so:boards_per_lane:workgroup_size, 0 = the library's choice
-        if (sscanf(argv[i], "%511[^:]:%d:%d", path, &bpl, &pipe) < 1) return 2;
-        L.path = path; L.bpl = bpl; L.pipe = pipe;
+        char path[512]; int bpl = 0, pipe = 0, fused = 0;      // lib.so:boards_per_lane:workgroup_size:fused, 0 = the library's choice
+        if (sscanf(argv[i], "%511[^:]:%d:%d:%d", path, &bpl, &pipe, &fused) < 1) return 2;
+        L.path = path; L.bpl = bpl; L.pipe = pipe; L.fused = fused;
         L.h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
         if (!L.h) { fprintf(stderr, "dlopen %s: %s\n", path, dlerror()); return 1; }
 #define SYM(f, name) *(void **)(&L.f) = dlsym(L.h, name); if (!L.f) { fprintf(stderr, "missing %s\n", name); return 1; }
@@ -185,7 +188,7 @@ int main(int argc, char **argv) {
                 for (int t = 0; t < K && !rc; ++t)
                     rc = L.step_random(state, seed, W + t, 0, 1, actions + (size_t)(W + t) * 2 * n, reward, term, n, s);
             } else {
-                rc = L.step_many(state, actions + (size_t)W * 2 * n, nullptr, seed, W, 0, 1, reward, term, 0, n, K, s);
+                rc = L.step_many(state, actions + (size_t)W * 2 * n, nullptr, seed, W, 0, 1u | (L.fused ? 2u : 0u), reward, term, 0, n, K, s);
             }
             CK(hipEventRecord(e1, s));
             CK(hipStreamSynchronize(s));

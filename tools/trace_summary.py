@@ -18,6 +18,12 @@ bench.py line's us per launch, printed beside the profiled period.
 With the default substring the dispatches of step_quiet_kernel (qttt_step_many's steps that store no reward /
 terminated: every timed step of a replay region but its last) count as step dispatches too, and the timed average is
 also printed for the two kernels separately.
+
+Where step_many takes the register-resident route (no output buffers, 448 K < boards <= 1536 K, K >= 16) the timed
+region is ceil(K / 64) dispatches of step_fused_kernel and nothing else: pass `step_fused_kernel` as the substring and
+PLIES = the plies per timed region as K's meaning changes — K = ceil(steps / 64), W = the warm-up's dispatches of that
+kernel (0 when the warm-up is shorter than 16 steps: it then runs launch per step) — and read "per step" as the timed
+span divided by the steps, printed when STEPS_PER_REGION is set in the environment.
 """
 import csv
 import glob
@@ -65,6 +71,10 @@ def main():
             v = by_kernel[k]
             print("timed, %-5s dispatches only : %d x avg %.1f ns  min %d  max %d" % (k, len(v), sum(v) / len(v), min(v), max(v)))
     print("timed span / K per region  : median %.1f ns  min %.1f  max %.1f" % (spans[len(spans) // 2], spans[0], spans[-1]))
+    if os.environ.get("STEPS_PER_REGION"):
+        f_ = K / float(os.environ["STEPS_PER_REGION"])
+        print("timed span / step          : median %.1f ns  min %.1f  max %.1f  (%s steps in %d dispatches per region)"
+              % (spans[len(spans) // 2] * f_, spans[0] * f_, spans[-1] * f_, os.environ["STEPS_PER_REGION"], K))
     gaps = [b[k + 1] - e[k] for b, e in regs for k in range(K - 1)]
     periods = [b[k + 1] - b[k] for b, e in regs for k in range(K - 1)]
     gaps.sort()
