@@ -7,6 +7,7 @@ the new weights for the search and repeats.
     python examples/selfplay_train.py [--games 1024] [--rollouts 100] [--sims 10] [--epochs 50] [--runs 30]
                                       [--dtype f32|bf16] [--out model.pt] [--model model.pt] [--value-targets 1,0]
                                       [--symmetries] [--leaf-eval playouts|value]
+                                      [--root-noise EPS,ALPHA] [--temperature T] [--sample-plies K]
 
 The network is nn.Model's (nn.py:7-28) under its own parameter names (qtttgym_amd.policy_value.SHAPES), so --out is a
 state dict that the reference, PolicyValueNet and examples/tree_tournament.py --model all load.  The loss is the
@@ -18,6 +19,10 @@ every game's eight images under the board's symmetries (SelfPlayBatch.augment: e
 search), which the reference left as a stub (self_play.py expand_symetries).  --leaf-eval value searches with the
 network's value head at the leaves instead of --sims playouts (TreeSearch(leaf_eval="value")): the value head that every
 run trains is then what the next run searches with; use --value-targets 1,-1 with it, the scale of a terminal leaf.
+--root-noise 0.25,0.3 mixes Dirichlet(0.3) noise into the roots' priors before every searched move, and --sample-plies K
+draws the move of the first K plies from the visit counts (N ** (1 / --temperature)) instead of playing the best one:
+AlphaZero's root exploration (SelfPlay(root_noise=, temperature=, sample_plies=)), without which the games of a run under
+--leaf-eval value all open alike.
 """
 import argparse
 import os
@@ -74,6 +79,10 @@ def main():
     ap.add_argument("--symmetries", action="store_true", help="train on the eight images of every game")
     ap.add_argument("--leaf-eval", choices=("playouts", "value"), default="playouts",
                     help="what scores a leaf of the search: --sims playouts, or the network's value head")
+    ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA",
+                    help="Dirichlet(ALPHA) noise with weight EPS on the roots' priors before every searched move")
+    ap.add_argument("--temperature", type=float, default=1.0, help="the sampled moves follow N ** (1 / temperature)")
+    ap.add_argument("--sample-plies", type=int, default=0, help="plies whose move is drawn from the visit counts")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     torch.manual_seed(args.seed)
@@ -85,7 +94,9 @@ def main():
     net = PolicyValueNet(model, device=dev, dtype=torch.float32 if args.dtype == "f32" else torch.bfloat16)
     targets = tuple(float(x) for x in args.value_targets.split(","))
     sp = SelfPlay(args.games, n_rollouts=args.rollouts, num_simulations=args.sims, net=net, value_targets=targets,
-                  seed=args.seed, leaf_eval=args.leaf_eval)
+                  seed=args.seed, leaf_eval=args.leaf_eval,
+                  root_noise=None if args.root_noise is None else tuple(float(x) for x in args.root_noise.split(",")),
+                  temperature=args.temperature, sample_plies=args.sample_plies)
     for run in range(args.runs):
         batch = sp.play()
         s, pi, mask, v_target, done = (batch.augment() if args.symmetries else batch).flat()

@@ -116,6 +116,18 @@ SYMMETRY_SIGNATURES = {
 TREE_VALUE_SIGNATURES = {
     "qttt_tree_value_rollout": (_i32, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
 }
+# every symbol include/qttt_tree_explore.h declares (root exploration: Dirichlet noise, the sampled move; qttt.h
+# includes it)
+TREE_NOISE_BASE = 0xC0000000
+TREE_NOISE_TRIES = 16
+TREE_NOISE_DRAWS = 2 * TREE_NOISE_TRIES + 1
+SELFPLAY_MOVE_BASE = 0xE0000000
+TREE_MAX_NOISE = (SELFPLAY_MOVE_BASE - TREE_NOISE_BASE) // (36 * TREE_NOISE_DRAWS)
+TREE_EXPLORE_SIGNATURES = {
+    "qttt_tree_root_noise": (_i32, [_vp, _i64, _i64, _u64, _u32, _i64, _f64, _f64, _vp, _vp, _vp]),
+    "qttt_selfplay_record_sampled": (_i32, SELFPLAY_SIGNATURES["qttt_selfplay_record"][1][:-1]
+                                     + [_u64, _i64, _f64, _i32, _vp]),
+}
 
 _lib = None
 
@@ -180,7 +192,8 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(NN_SIGNATURES.items())
                                   + list(POLICY_ROLLOUT_SIGNATURES.items()) + list(TREE_SIGNATURES.items())
                                   + list(TREE_COMPACT_SIGNATURES.items()) + list(SELFPLAY_SIGNATURES.items())
-                                  + list(SYMMETRY_SIGNATURES.items()) + list(TREE_VALUE_SIGNATURES.items())):
+                                  + list(SYMMETRY_SIGNATURES.items()) + list(TREE_VALUE_SIGNATURES.items())
+                                  + list(TREE_EXPLORE_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -51,7 +51,8 @@
 // qttt_nn_kernels.h (the policy/value network) -> qttt_policy_rollout_kernels.h (network-guided playouts);
 // qttt_tree_kernels.h (the batched search trees) -> qttt_selfplay_kernels.h (the self-play record) ->
 // qttt_symmetry_kernels.h (the board's symmetries: images of states, the augmented self-play batch);
-// qttt_tree_value_kernels.h (the value rollout: network evaluation of the leaves and backup in one launch).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
+// qttt_tree_value_kernels.h (the value rollout: network evaluation of the leaves and backup in one launch);
+// qttt_tree_explore_kernels.h (root exploration: Dirichlet noise on the roots' priors, the sampled move).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
 // qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
@@ -62,6 +63,7 @@
 #include "qttt_nn_kernels.h"
 #include "qttt_policy_rollout_kernels.h"
 #include "qttt_tree_kernels.h"
+#include "qttt_tree_explore_kernels.h"
 #include "qttt_selfplay_kernels.h"
 #include "qttt_symmetry_kernels.h"
 #include "qttt_tree_value_kernels.h"
@@ -726,8 +728,8 @@ int qttt_selfplay_record(const void *tree, int64_t games, int64_t capacity, int 
     if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions)) return QTTT_ERR_NULL;
     if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
     const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
-    return launch(selfplay_record_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity, ply,
-                  n_rollouts, alpha, (float)v_first, (float)v_second, o);
+    return launch(selfplay_record_kernel<false>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, SelfPlaySampling<false>{});
 }
 
 // ---------------------------------------------------------------- symmetries (include/qttt_symmetry.h)
@@ -792,6 +794,38 @@ int qttt_tree_value_rollout(void *tree, int64_t games, int64_t capacity, const v
         return launch(tree_value_rollout_kernel<P>, ceil_div(games, NNCfg<P>::M), QTTT_NN_BLOCK, stream, tree, games, capacity,
                       l.P, l.Q, weights, leaf_value, leaf_probs);
     });
+}
+
+// ---------------------------------------------------------------- root exploration (include/qttt_tree_explore.h)
+int qttt_tree_root_noise(void *tree, int64_t games, int64_t capacity, uint64_t seed, uint32_t noise_idx,
+                         int64_t board_offset, double epsilon, double alpha, double *noise, uint8_t *applied,
+                         void *stream) {
+    if (tree_size_bad(games, capacity) || board_offset < 0 || noise_idx >= QTTT_TREE_MAX_NOISE || !(epsilon >= 0.0 && epsilon <= 1.0) ||
+        !std::isfinite(alpha) || alpha <= 0.0)
+        return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (!tree) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(noise, 8)) return QTTT_ERR_ACTION;
+    return launch(tree_root_noise_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (u64)seed, noise_idx, (u64)board_offset, epsilon, alpha, noise, applied);
+}
+
+int qttt_selfplay_record_sampled(const void *tree, int64_t games, int64_t capacity, int ply, uint32_t n_rollouts,
+                                 double alpha, double v_first, double v_second, void *states, double *pi, uint8_t *mask,
+                                 uint8_t *done, float *v, uint8_t *action36, uint8_t *length, int8_t *winner,
+                                 uint8_t *actions, uint64_t seed, int64_t board_offset, double temperature,
+                                 int sample_plies, void *stream) {
+    if (tree_size_bad(games, capacity) || ply < 0 || ply >= QTTT_SELFPLAY_ROWS || n_rollouts == 0u || !std::isfinite(alpha) ||
+        !std::isfinite(v_first) || !std::isfinite(v_second) || alpha <= 0.0 || board_offset < 0 || !std::isfinite(temperature) ||
+        temperature <= 0.0 || sample_plies < 0 || sample_plies > QTTT_SELFPLAY_ROWS)
+        return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
+    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    const SelfPlaySampling<true> s = {(u64)seed, (u64)board_offset, temperature, sample_plies};
+    return launch(selfplay_record_kernel<true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
 }
 
 }  // extern "C"

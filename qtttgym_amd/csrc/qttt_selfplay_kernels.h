@@ -7,9 +7,13 @@
 // columns of the outputs, so there are no atomics, and nothing is handed from lane to lane through memory.  No LDS
 // (the winner and the terminal flag are the root's node flags, no line table is needed), no loop but the two six-step
 // butterflies (the sum, and choose's argmax).
+// selfplay_record_kernel<true> is the sampled record of include/qttt_tree_explore.h: the same kernel with the move of
+// the first plies drawn from the visit counts (explore_sample_move); <false> is qttt_selfplay_record's, whose code the
+// flag does not touch.
 #ifndef QTTT_SELFPLAY_KERNELS_H
 #define QTTT_SELFPLAY_KERNELS_H
 #include "qttt_tree_kernels.h"
+#include "qttt_tree_explore_kernels.h"
 #include "qttt_selfplay.h"
 
 namespace {
@@ -26,17 +30,21 @@ struct SelfPlayOut {
     uint8_t *actions;                  // [games][2]
 };
 
-// the sum of include/qttt_selfplay.h: 64 terms (lanes 36..63 hold 0), s[i] += s[i ^ m] for m = 1 .. 32; every lane ends
-// with the same double
-__device__ __forceinline__ double selfplay_wave_sum(double x) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) x = x + __shfl_xor(x, m);
-    return x;
-}
+// what the sampled record takes besides: nothing at all in the plain one
+template <bool SAMPLED>
+struct SelfPlaySampling {};
+template <>
+struct SelfPlaySampling<true> {
+    u64 seed, board_offset;
+    double temperature;
+    int sample_plies;
+};
 
+template <bool SAMPLED>
 __global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void *tree, int64_t games, int64_t capacity,
                                                                      int ply, u32 n_rollouts, double alpha, float v_first,
-                                                                     float v_second, SelfPlayOut o) {
+                                                                     float v_second, SelfPlayOut o,
+                                                                     SelfPlaySampling<SAMPLED> sampling) {
     const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
     const u32 lane = threadIdx.x & 63u;
     if (g >= games) return;
@@ -79,7 +87,14 @@ __global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void 
     double x = r.legal ? (double)r.s.N / (double)n_rollouts : 0.0;
     if (alpha != 1.0) x = r.legal ? pow(x, alpha) : 0.0;
     const double sum = selfplay_wave_sum(x);
-    const int a = tree_choose(r, lane);
+    int a = tree_choose(r, lane);
+    if constexpr (SAMPLED) {
+        if (ply < sampling.sample_plies) {                       // wave-uniform
+            const int drawn = explore_sample_move(r.s.N, lane, sampling.seed, sampling.board_offset + (u64)g, ply,
+                                                  sampling.temperature);
+            a = drawn < 0 ? a : drawn;
+        }
+    }
     if (lane < 36u) {
         o.pi[row * 36 + lane] = r.legal ? x / sum : 0.0;
         o.mask[row * 36 + lane] = r.legal ? 1 : 0;

@@ -122,6 +122,14 @@ __device__ __forceinline__ int wave_argmax(bool valid, double score, u32 lane) {
     return idx;
 }
 
+// the sum of include/qttt_selfplay.h (the record's pi, and the noise of qttt_tree_explore.h): 64 terms (lanes 36..63
+// hold 0), s[i] += s[i ^ m] for m = 1 .. 32; every lane ends with the same double
+__device__ __forceinline__ double selfplay_wave_sum(double x) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) x = x + __shfl_xor(x, m);
+    return x;
+}
+
 __device__ __forceinline__ double tree_prior(const TreeView &v, int64_t g, int32_t node, const TreeNodeHdr &h, u32 a) {
     if (h.flags & TN_UNIFORM) return g_uniform_priors.p[__builtin_popcountll(h.legal)];
     return (double)v.prior(g, node)[a];

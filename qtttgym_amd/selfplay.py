@@ -6,8 +6,10 @@ root turned into a training sample (self_play.py:193-216) by one kernel per ply.
     s, pi, mask, v, done = sp.play().flat()         # the reference's s_batch, pi_batch, mask_batch, v_batch, done
 
 Training on the batch is ordinary torch autograd (examples/selfplay_train.py); there is no loss, gradient or optimiser
-here.  The move played is MCTS.choose, as in the reference: no temperature, no Dirichlet noise.  The board's eight
-symmetries, which the reference left as a stub (self_play.py expand_symetries), are SelfPlayBatch.augment (DESIGN.md
+here.  By default the move played is MCTS.choose, as in the reference.  AlphaZero's root exploration is optional
+(include/qttt_tree_explore.h): root_noise=(epsilon, alpha) mixes Dirichlet noise into the roots' priors
+before every searched move, and sample_plies / temperature draw the move of the first plies from the visit counts.  The
+board's eight symmetries, which the reference left as a stub (self_play.py expand_symetries), are SelfPlayBatch.augment (DESIGN.md
 §14): one launch turns the batch of G games into the batch of 8 G games it stands for.
 """
 import ctypes
@@ -85,10 +87,16 @@ class SelfPlay(LibCaller):
     defaults to 2 * n_rollouts + 2; a carry that turns out too small raises ValueError before a node is lost) instead
     of 1 + 10 * (2 * n_rollouts + 1), at the price of one host read-back per move.  Without it play() never waits
     for the device.
-    leaf_eval is TreeSearch's: "playouts" (the reference's rollout) or "value" (the leaf scored by net's value head)."""
+    leaf_eval is TreeSearch's: "playouts" (the reference's rollout) or "value" (the leaf scored by net's value head).
+    root_noise=(epsilon, alpha): every searched ply runs one rollout (so that every live root has priors), then
+    TreeSearch.add_root_noise(epsilon, alpha), then the other n_rollouts - 1.  sample_plies=k > 0: the move of plies
+    0..k-1 is drawn with probability proportional to N ** (1 / temperature) (qttt_selfplay_record_sampled, with the
+    trees' seed); later plies play MCTS.choose.  pi stays the visit-count target either way.  With the defaults play()
+    issues the calls it always did."""
 
     def __init__(self, num_games, n_rollouts=100, num_simulations=10, net=None, alpha=1.0, c_puct=1.0,
-                 value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts"):
+                 value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts",
+                 root_noise=None, temperature=1.0, sample_plies=0):
         if leaf_eval not in TreeSearch.LEAF_EVALS:
             raise ValueError("leaf_eval must be one of %s" % (TreeSearch.LEAF_EVALS,))
         if leaf_eval == "value" and net is None:
@@ -104,6 +112,16 @@ class SelfPlay(LibCaller):
             raise ValueError("alpha must be positive and finite")
         if not all(abs(x) < float("inf") for x in (self.v_first, self.v_second)):
             raise ValueError("value_targets must be finite")
+        self.root_noise = None if root_noise is None else tuple(float(x) for x in root_noise)
+        self.temperature, self.sample_plies = float(temperature), int(sample_plies)
+        if self.root_noise is not None:
+            if len(self.root_noise) != 2 or not 0.0 <= self.root_noise[0] <= 1.0 \
+                    or not 0.0 < self.root_noise[1] < float("inf"):
+                raise ValueError("root_noise must be None or (epsilon in [0, 1], alpha positive and finite)")
+        if not 0.0 < self.temperature < float("inf"):
+            raise ValueError("temperature must be positive and finite")
+        if not 0 <= self.sample_plies <= ROWS:
+            raise ValueError("sample_plies must be in 0..%d" % ROWS)
         R = self.n_rollouts
         if self.compact:
             self.carry = 2 * R + 2 if carry is None else int(carry)
@@ -128,7 +146,8 @@ class SelfPlay(LibCaller):
 
     def record(self, tree, ply, batch):
         """One qttt_selfplay_record: the roots of `tree` become row `ply` of `batch`; returns batch.actions, the move
-        to step with."""
+        to step with.  With sample_plies > 0 it is qttt_selfplay_record_sampled, drawing with the tree's seed and
+        board_offset."""
         G, dev = self.num_games, self.device
         if tree.num_games != G or tree.device != dev or batch.num_games != G:
             raise ValueError("tree and batch must hold %d games on %s" % (G, dev))
@@ -138,10 +157,15 @@ class SelfPlay(LibCaller):
         check_tensor(batch.length, torch.uint8, (G,), dev, "batch.length")
         check_tensor(batch.winner, torch.int8, (G,), dev, "batch.winner")
         check_tensor(batch.actions, torch.uint8, (G, 2), dev, "batch.actions")
-        self._call("qttt_selfplay_record", tree.tree.data_ptr(), G, tree.capacity, int(ply), self.n_rollouts, self.alpha,
-                   self.v_first, self.v_second, batch.states.data_ptr(), batch.pi.data_ptr(), batch.mask.data_ptr(),
-                   batch.done.data_ptr(), batch.v.data_ptr(), batch.action36.data_ptr(), batch.length.data_ptr(),
-                   batch.winner.data_ptr(), batch.actions.data_ptr())
+        args = (tree.tree.data_ptr(), G, tree.capacity, int(ply), self.n_rollouts, self.alpha, self.v_first, self.v_second,
+                batch.states.data_ptr(), batch.pi.data_ptr(), batch.mask.data_ptr(), batch.done.data_ptr(),
+                batch.v.data_ptr(), batch.action36.data_ptr(), batch.length.data_ptr(), batch.winner.data_ptr(),
+                batch.actions.data_ptr())
+        if self.sample_plies > 0:
+            self._call("qttt_selfplay_record_sampled", *args, tree.seed, tree.board_offset, self.temperature,
+                       self.sample_plies)
+        else:
+            self._call("qttt_selfplay_record", *args)
         return batch.actions
 
     def play(self, seed=None):
@@ -160,7 +184,12 @@ class SelfPlay(LibCaller):
         batch = self.new_batch()
         for ply in range(ROWS):
             if ply < ROWS - 1:                  # at ply 9 every game is over: nine moves fill the board
-                tree.contemplate(R)
+                if self.root_noise is None:
+                    tree.contemplate(R)
+                else:                           # the same R rollouts, the noise after the one that gives the priors
+                    tree.contemplate(1)
+                    tree.add_root_noise(*self.root_noise)
+                    tree.contemplate(R - 1)
             env.step_raw(self.record(tree, ply, batch))
             tree.sync(env)
             if self.compact:

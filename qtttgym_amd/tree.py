@@ -10,11 +10,14 @@ allocated until compact() (the reference's _prune) gives them back: with a compa
 to hold the kept subtree and one move's rollouts; without it, every rollout and sync since the last reset.  The host
 keeps an upper bound on the nodes used (+2 per rollout, +1 per sync; compact() replaces it by the real maximum) and
 raises ValueError before launching work that could pass it.
+
+add_root_noise() is AlphaZero's root exploration (include/qttt_tree_explore.h): Dirichlet noise mixed into
+the priors of every root that has them, one launch.
 """
 import torch
 
 from . import _native
-from ._host import LibCaller, _ptr, check_net, out_rows, out_tensor, resolve_device
+from ._host import LibCaller, _ptr, check_net, check_tensor, out_rows, out_tensor, resolve_device
 from .vec_env import VecEnv
 
 
@@ -67,6 +70,7 @@ class TreeSearch(LibCaller):
         else:
             self._out = out_rows(VecEnv._policy_rows(S), G, dev, keys=("result", "probs"))
         self.rollout_idx = 0          # k of include/qttt_tree.h: rollouts since the last reset
+        self.noise_idx = 0            # add_root_noise() calls since the last reset: what addresses their draws
         self._bound = None            # upper bound on the nodes used (None: not reset yet)
         self._scratch = None          # compact()'s forwarding table, allocated by its first call
 
@@ -89,7 +93,7 @@ class TreeSearch(LibCaller):
         included)."""
         self._check_env(env)
         self._call("qttt_tree_reset", self.tree.data_ptr(), self.num_games, self.capacity, env.state.data_ptr())
-        self.rollout_idx, self._bound = 0, 1
+        self.rollout_idx, self.noise_idx, self._bound = 0, 0, 1
 
     def contemplate(self, rollouts):
         """`rollouts` x MCTS._rollout (mcts.py:166-176) in every game."""
@@ -126,6 +130,31 @@ class TreeSearch(LibCaller):
             self._call("qttt_tree_backup", tree, G, cap, self._out["result"].data_ptr(), S,
                        self._out["probs"].data_ptr())
         self.rollout_idx = k + 1
+
+    def add_root_noise(self, epsilon=0.25, alpha=0.3, noise=None, applied=None):
+        """P <- (1 - epsilon) P + epsilon Dirichlet(alpha) at every root that has priors, is not terminal and has a
+        legal action (qttt_tree_root_noise); a root that has no priors yet is left alone, so run one rollout first.
+        The draws are addressed by (seed, board_offset + g, noise_idx), and noise_idx counts these calls since reset():
+        a call never repeats an earlier one's noise, and a second call on the same root mixes again.  noise f64[G, 36]
+        and applied u8[G], both optional, receive the normalised noise and whether the game was noised."""
+        eps, alpha = float(epsilon), float(alpha)
+        if not 0.0 <= eps <= 1.0:
+            raise ValueError("epsilon must be in [0, 1]")
+        if not 0.0 < alpha < float("inf"):
+            raise ValueError("alpha must be positive and finite")
+        if self._bound is None:
+            raise RuntimeError("reset() first")
+        if self.noise_idx >= _native.TREE_MAX_NOISE:
+            raise ValueError("%d noise calls since reset: the bound is %d (draw indices)"
+                             % (self.noise_idx, _native.TREE_MAX_NOISE))
+        G, dev = self.num_games, self.device
+        if noise is not None:
+            check_tensor(noise, torch.float64, (G, 36), dev, "noise")
+        if applied is not None:
+            check_tensor(applied, torch.uint8, (G,), dev, "applied")
+        self._call("qttt_tree_root_noise", self.tree.data_ptr(), G, self.capacity, self.seed, self.noise_idx,
+                   self.board_offset, eps, alpha, _ptr(noise), _ptr(applied))
+        self.noise_idx += 1
 
     def root_stats(self):
         """The roots' statistics: N i32[G,36], W / Q / P f64[G,36], Ntot i32[G], choose u8[G], nodes_used i32[G],

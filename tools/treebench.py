@@ -17,6 +17,13 @@ bound comes after the second event), medians over the moves of --compact-reps ga
 mean nodes used before and after each compaction.
 
     python tools/treebench.py --games "" --compact-games 4096,65536 [--compact-rollouts 300] [--compact-reps 3]
+
+--explore adds the root-exploration leg at --explore-games 4096,65536: microseconds per launch of
+qttt_tree_root_noise, of qttt_selfplay_record_sampled and, beside them in the same process, of qttt_selfplay_record and
+qttt_tree_root, on searched uniform trees two plies in; HIP events around --explore-launches back-to-back launches, the
+legs interleaved, medians of --explore-reps repetitions after one that warms up.
+
+    python tools/treebench.py --games "" --explore [--out profiles/explore/treebench_explore.jsonl]
 """
 import argparse
 import json
@@ -139,6 +146,55 @@ def run_value(G, mode, sims, reps, rollouts=6, warmup=4):
     return row
 
 
+def run_explore(G, reps, launches, rollouts=8):
+    """One JSON row: medians over `reps` interleaved repetitions of `launches` launches per leg."""
+    import statistics
+    from qtttgym_amd import SelfPlay
+    from qtttgym_amd._host import out_rows
+    env = VecEnv(G, seed=1)
+    env.step_random_many(2)
+    t = TreeSearch(G, capacity=1 + 2 * rollouts, num_simulations=2, seed=2)
+    t.reset(env)
+    t.contemplate(rollouts)                      # every root has priors and visits
+    sp = SelfPlay(G, n_rollouts=rollouts, num_simulations=2)
+    batch = sp.new_batch()
+    root = out_rows(TreeSearch._ROOT_ROWS, G, t.device)
+    noise = torch.empty((G, 36), dtype=torch.float64, device=t.device)
+    applied = torch.empty(G, dtype=torch.uint8, device=t.device)
+    rec = (t.tree.data_ptr(), G, t.capacity, 0, sp.n_rollouts, sp.alpha, sp.v_first, sp.v_second, batch.states.data_ptr(),
+           batch.pi.data_ptr(), batch.mask.data_ptr(), batch.done.data_ptr(), batch.v.data_ptr(), batch.action36.data_ptr(),
+           batch.length.data_ptr(), batch.winner.data_ptr(), batch.actions.data_ptr())
+    stream = torch.cuda.current_stream()
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        for _ in range(launches):
+            fn()
+        b.record(stream)
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e3 / launches
+
+    legs = {"root_noise": lambda: t.add_root_noise(0.25, 0.3, noise=noise, applied=applied),      # mixes again each time
+            "root_noise_alpha_2.5": lambda: t.add_root_noise(0.25, 2.5, noise=noise, applied=applied),
+            "record_sampled": lambda: sp._call("qttt_selfplay_record_sampled", *rec, t.seed, t.board_offset, 1.0, 10),
+            "record_sampled_temperature_0.5": lambda: sp._call("qttt_selfplay_record_sampled", *rec, t.seed,
+                                                                t.board_offset, 0.5, 10),
+            "record": lambda: sp._call("qttt_selfplay_record", *rec),
+            "tree_root": lambda: t._root(**root)}
+    us = {k: [] for k in legs}
+    for rep in range(reps + 1):
+        for k, fn in legs.items():
+            x = timed(fn)
+            if rep:
+                us[k].append(x)
+    row = {"games": G, "leg": "explore", "reps": reps, "launches_per_rep": launches, "applied": int(applied.sum())}
+    for k, xs in us.items():
+        row["us_%s_median" % k] = round(statistics.median(xs), 2)
+        row["us_%s_min_max" % k] = [round(min(xs), 2), round(max(xs), 2)]
+    return row
+
+
 def run_compact(G, sims, R, reps, moves=4):
     """contemplate(R) + a move + sync + compact(), `moves` times per game from the empty board, `reps` games (the
     first one more as warm-up).  One JSON row: medians over every timed (game, move)."""
@@ -192,6 +248,10 @@ def main():
     ap.add_argument("--compact-games", default="")
     ap.add_argument("--compact-rollouts", type=int, default=300)
     ap.add_argument("--compact-reps", type=int, default=3)
+    ap.add_argument("--explore", action="store_true")
+    ap.add_argument("--explore-games", default="4096,65536")
+    ap.add_argument("--explore-reps", type=int, default=5)
+    ap.add_argument("--explore-launches", type=int, default=20)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     rows = []
@@ -207,6 +267,10 @@ def main():
             rows.append(row)
     for G in [int(x) for x in args.compact_games.split(",") if x]:
         row = run_compact(G, args.sims, args.compact_rollouts, args.compact_reps)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    for G in [int(x) for x in args.explore_games.split(",") if x and args.explore]:
+        row = run_explore(G, args.explore_reps, args.explore_launches)
         print(json.dumps(row), flush=True)
         rows.append(row)
     if args.out:
