@@ -46,9 +46,10 @@ extern "C" {
     ((((uint32_t)(boards_per_lane) & 7u) << 8) |                                                  \
      ((workgroup_size) == 256 ? 1u << 12 : (workgroup_size) == 512 ? 2u << 12 : (workgroup_size) == 1024 ? 3u << 12 : 0u))
 
-#define QTTT_FLAG_FUSED 2u        /* qttt_step_many only: run the n_steps steps in ONE launch per 64 steps with
-                                     the boards held in registers (same results; for replay / evaluation
-                                     where all actions are known up front) */
+#define QTTT_FLAG_FUSED 2u        /* qttt_step_many only: run the n_steps steps with the boards held in registers,
+                                     ONE launch per 256 steps without per-step outputs (out_stride 0), per 64
+                                     with them (same results; for replay / evaluation where all actions are
+                                     known up front) */
 
 int     qttt_abi_version(void);
 /* bytes of device memory needed for n boards */
@@ -95,7 +96,7 @@ int qttt_step_observe(void *state, const uint8_t *actions, const uint8_t *bits, 
  * QTTT_FLAG_FUSED; reward and terminated are still required and checked for every step).
  * Same results, not always n_steps launches: with out_stride 0, 448 K < n <= 1536 K boards (a batch that is one
  * occupancy round of the step kernel), n_steps >= 16 and no launch shape named (QTTT_FLAG_SHAPE, qttt_set_tuning,
- * QTTT_STEP_BPL / QTTT_STEP_BLOCK) the steps run with the boards held in registers, one launch per 64 steps, as with
+ * QTTT_STEP_BPL / QTTT_STEP_BLOCK) the steps run with the boards held in registers, one launch per 256 steps, as with
  * QTTT_FLAG_FUSED — only the state after the last step and that step's outputs can be read.  Every other call is one
  * launch per step. */
 int qttt_step_many(void *state, const uint8_t *actions, const uint8_t *bits, uint64_t seed,

@@ -264,19 +264,25 @@ int qttt_step_many(void *state, const uint8_t *actions, const uint8_t *bits, uin
         const u32 hi_fold = (u32)(first >> 32) * 0x9E3779B9u;
         const uint16_t *a16 = reinterpret_cast<const uint16_t *>(actions);
         u32 *rb = reinterpret_cast<u32 *>(reward);
+        const bool has_bits = bits != nullptr, auto_reset = (flags & QTTT_FLAG_AUTO_RESET) != 0;
+        if (out_stride != 0)
+            return fused_runs<FUSED_MAX_PLIES, FusedKeys>(seed, step_idx0, n_steps, [&](int64_t done, int32_t plies, const FusedKeys &keys) {
+                return with_bools([&](auto HB, auto AR) {
+                    return launch(step_fused_kernel<HB, AR, FUSED_OUT_EVERY>, ceil_div(n, QTTT_BLOCK), QTTT_BLOCK, stream, p.P, p.Q,
+                                  a16 + done * n, bits ? bits + done * n : nullptr, keys, hi_fold, (u32)first,
+                                  rb + done * out_stride, terminated + done * out_stride, out_stride, n, plies);
+                }, has_bits, auto_reset);
+            });
         // With out_stride == 0 only the run's last launch stores outputs (its last ply's, once, after the loop); the earlier
-        // launches are handed no output pointers.
-        return fused_runs(seed, step_idx0, n_steps, [&](int64_t done, int32_t plies, const FusedKeys &keys) {
-            const int out = out_stride != 0 ? FUSED_OUT_EVERY : done + plies == n_steps ? FUSED_OUT_LAST : FUSED_OUT_NONE;
-            return with_bools([&](auto HB, auto AR) {
-                return with_int<FUSED_OUT_EVERY, FUSED_OUT_LAST, FUSED_OUT_NONE>(out, [&](auto OUT) {
-                    u32 *r_c = OUT == FUSED_OUT_NONE ? nullptr : rb + done * out_stride;
-                    uint8_t *t_c = OUT == FUSED_OUT_NONE ? nullptr : terminated + done * out_stride;
-                    return launch(step_fused_kernel<HB, AR, OUT>, ceil_div(n, QTTT_BLOCK), QTTT_BLOCK, stream, p.P, p.Q,
-                                  a16 + done * n, bits ? bits + done * n : nullptr, keys, hi_fold, (u32)first, r_c, t_c,
-                                  out_stride, n, plies);
-                });
-            }, bits != nullptr, (flags & QTTT_FLAG_AUTO_RESET) != 0);
+        // launches are handed no output pointers.  RESIDENT_MAX_PLIES per launch: nothing but the keys argument bounds it.
+        typedef ResidentKeys<RESIDENT_MAX_PLIES> Keys;
+        return fused_runs<RESIDENT_MAX_PLIES, Keys>(seed, step_idx0, n_steps, [&](int64_t done, int32_t plies, const Keys &keys) {
+            return with_bools([&](auto HB, auto AR, auto LAST) {
+                constexpr int OUT = LAST ? FUSED_OUT_LAST : FUSED_OUT_NONE;
+                return launch(step_fused_kernel<HB, AR, OUT, RESIDENT_MAX_PLIES, RESIDENT_BLOCK>, ceil_div(n, RESIDENT_BLOCK),
+                              RESIDENT_BLOCK, stream, p.P, p.Q, a16 + done * n, bits ? bits + done * n : nullptr, keys, hi_fold,
+                              (u32)first, LAST ? rb : nullptr, LAST ? terminated : nullptr, n, plies);
+            }, has_bits, auto_reset, done + plies == n_steps);
         });
     }
     // With out_stride == 0 every step writes the same n outputs and only the last step's can ever be read: the earlier
@@ -311,7 +317,7 @@ int qttt_step_random_many(void *state, uint64_t seed, uint32_t step_idx0, int64_
     // test-free loop is no faster and at 1 M boards 2 % slower (profiles/r05/fused_keep_instantiation_ab.txt, same box,
     // alternating)
     const bool keep_all = out_stride != 0 && a16 && rb && n < 262144;
-    return fused_runs(seed, step_idx0, n_steps, [&](int64_t done, int32_t plies, const FusedKeys &keys) {
+    return fused_runs<FUSED_MAX_PLIES, FusedKeys>(seed, step_idx0, n_steps, [&](int64_t done, int32_t plies, const FusedKeys &keys) {
         const bool writes = out_stride != 0 || done + plies == n_steps;
         uint16_t *a_c = (a16 && writes) ? a16 + done * out_stride : nullptr;
         u32 *r_c = (rb && writes) ? rb + done * out_stride : nullptr;

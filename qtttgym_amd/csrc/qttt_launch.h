@@ -35,7 +35,7 @@ inline void auto_tuning(int64_t n, int &bpl, int &blk) {
 // qttt_step_many's register-resident route: the rows of the table above where a batch is ONE occupancy round of the step
 // kernel — (1, 1024), (2, 512), (2, 1024): every board of the batch is on the chip at once and the whole working set sits in
 // the Infinity Cache.  There a run of steps whose per-step outputs nobody keeps (out_stride == 0) goes through
-// step_fused_kernel, one launch per FUSED_MAX_PLIES steps with the boards in registers, instead of one launch per step:
+// step_fused_kernel, one launch per RESIDENT_MAX_PLIES steps with the boards in registers, instead of one launch per step:
 // only the state after the last step and that step's reward / terminated can ever be read.  Not below and not above these
 // rows: there qttt_step_many is one launch per step, which is what bench.py's 4 096-, 262 144- and 16 M-board replay legs
 // are defined and accounted as.  Not for a caller who names a launch shape (the call's QTTT_FLAG_SHAPE bits
@@ -110,14 +110,16 @@ inline int launch(void (*kernel)(P...), int64_t groups, int block, void *stream,
     return e == hipSuccess ? 0 : (int)e;
 }
 
-// Runs of at most FUSED_MAX_PLIES plies from step_idx0 on, one launch each (the plies' launch keys travel as a kernel
-// argument): launch_run(done, plies, keys) for every run, in order; stops at the first launch that fails.
-template <typename F>
+// Runs of at most CAP plies from step_idx0 on, one launch each (the plies' launch keys travel as a kernel argument, KEYS:
+// FusedKeys with FUSED_MAX_PLIES, ResidentKeys<CAP> for the output-free kernel): launch_run(done, plies, keys) for every
+// run, in order; stops at the first launch that fails.  A slot past the run's last ply holds the first ply's key.
+template <int CAP, typename KEYS, typename F>
 inline int fused_runs(uint64_t seed, uint32_t step_idx0, int32_t n_steps, F &&launch_run) {
-    for (int64_t done = 0; done < n_steps; done += FUSED_MAX_PLIES) {
-        const int32_t plies = (int32_t)(n_steps - done < FUSED_MAX_PLIES ? n_steps - done : FUSED_MAX_PLIES);
-        FusedKeys keys;
-        for (int32_t t = 0; t < FUSED_MAX_PLIES; ++t) keys.k[t] = launch_key(seed, step_idx0 + (u32)done + (u32)(t < plies ? t : 0));
+    static_assert(sizeof(KEYS) == CAP * sizeof(u64), "one key per ply");
+    for (int64_t done = 0; done < n_steps; done += CAP) {
+        const int32_t plies = (int32_t)(n_steps - done < CAP ? n_steps - done : CAP);
+        KEYS keys;
+        for (int32_t t = 0; t < CAP; ++t) keys.k[t] = launch_key(seed, step_idx0 + (u32)done + (u32)(t < plies ? t : 0));
         if (const int rc = launch_run(done, plies, keys)) return rc;
     }
     return 0;

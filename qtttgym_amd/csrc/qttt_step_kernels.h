@@ -241,25 +241,20 @@ __global__ __launch_bounds__(BLOCK) void step_quiet_kernel(
 constexpr int FUSED_MAX_PLIES = 64;
 struct FusedKeys { u64 k[FUSED_MAX_PLIES]; };
 // OUT — which plies' reward / terminated a launch stores:
-//   FUSED_OUT_EVERY  every ply's (out_stride != 0), from inside the loop;
+//   FUSED_OUT_EVERY  every ply's (out_stride != 0), from inside the loop: the kernel below, FUSED_MAX_PLIES per launch;
 //   FUSED_OUT_LAST   its last ply's only (out_stride == 0, the last launch of a run): formed from `win` and P1 AFTER the
 //                    loop and stored once, beside the two planes;
-//   FUSED_OUT_NONE   none (out_stride == 0, the earlier launches of a run longer than FUSED_MAX_PLIES: the run's last
+//   FUSED_OUT_NONE   none (out_stride == 0, the earlier launches of a run longer than one launch: the run's last
 //                    launch overwrites whatever they would store; they are handed no output pointers).
-// Without per-ply outputs the loop holds no store, no output pointer and no test of what to keep, and nothing couples the
-// action stream to a store queue: the actions are then requested FUSED_PREFETCH plies ahead instead of one (the stream of a
-// long replay comes from HBM, not from the Infinity Cache), and the state is consumed in front of the loop (as in
-// step_random_fused_kernel below) so that the wait for its loads does not land inside.
+// LAST and NONE are the output-free kernel further down (the overload with a ply cap and a workgroup size of its own).
 constexpr int FUSED_OUT_NONE = 0, FUSED_OUT_LAST = 1, FUSED_OUT_EVERY = 2;
-// (tools/stepbench, interleaved, 1 M boards, us per step with 1 / 2 / 4 plies ahead: 3.29 / 3.27 / 3.29 at K = 200,
-// 3.46 / 3.43 / 3.47 at K = 20 — within the spread of the repeats; profiles/resident/stepbench_1M_k*.txt)
-constexpr int FUSED_PREFETCH = 2;
 template <bool HAS_BITS, bool AUTO_RESET, int OUT>
 __global__ __launch_bounds__(QTTT_BLOCK) void step_fused_kernel(
     u64 *__restrict__ pP, u64 *__restrict__ pQ, const uint16_t *__restrict__ actions,
     const uint8_t *__restrict__ bits, FusedKeys keys, u32 id_hi_fold, u32 id_base,
     u32 *__restrict__ reward_bits, uint8_t *__restrict__ terminated, int64_t out_stride, int64_t n,
     int32_t n_steps) {
+    static_assert(OUT == FUSED_OUT_EVERY, "the output-free forms are the overload below");
     __shared__ __attribute__((aligned(16))) uint8_t lut[LINE_LUT_BYTES];
     const int64_t ib = (int64_t)blockIdx.x * QTTT_BLOCK;            // first board of the workgroup (block-uniform)
     const int64_t i = ib + threadIdx.x;
@@ -275,66 +270,121 @@ __global__ __launch_bounds__(QTTT_BLOCK) void step_fused_kernel(
     const u32 lane = threadIdx.x;
     u32 win = 0;
     u64 key = keys.k[0];
-    if constexpr (OUT == FUSED_OUT_EVERY) {
-        u32 *r_blk = reward_bits + ib;
-        uint8_t *t_blk = terminated + ib;
-        u32 act = load_stream(&a_blk[lane]), bit_in = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
-        for (int32_t t = 0; t < n_steps; ++t) {
-            const u64 key_next = keys.k[(t + 1) & (FUSED_MAX_PLIES - 1)];   // one scalar load, requested a ply ahead
-            // the next ply's action (and bit) are requested before this ply's step: their latency hides behind it
-            const bool more = t + 1 < n_steps;
+    u32 *r_blk = reward_bits + ib;
+    uint8_t *t_blk = terminated + ib;
+    u32 act = load_stream(&a_blk[lane]), bit_in = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
+    for (int32_t t = 0; t < n_steps; ++t) {
+        const u64 key_next = keys.k[(t + 1) & (FUSED_MAX_PLIES - 1)];   // one scalar load, requested a ply ahead
+        // the next ply's action (and bit) are requested before this ply's step: their latency hides behind it
+        const bool more = t + 1 < n_steps;
+        a_blk += more ? n : 0;
+        if (HAS_BITS) b_blk += more ? n : 0;
+        const u32 act_next = load_stream(&a_blk[lane]), bit_next = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
+        const u32 bit = HAS_BITS ? (bit_in & 1u) : collapse_bit_of(id ^ (u32)key);
+        win = step_core<AUTO_RESET>(P0, P1, Q0, Q1, act, bit, lut);
+        if (out_stride != 0 || t == n_steps - 1) {
+            // (the compiler's own stores here: it counts them when it waits for the action requested a ply ahead)
+            store_stream(&r_blk[lane], 0x80000000u | (win << 23));
+            store_stream(&t_blk[lane], (uint8_t)(P1 >> 31));
+        }
+        r_blk += out_stride;
+        t_blk += out_stride;
+        key = key_next;
+        act = act_next;
+        bit_in = bit_next;
+    }
+    store_stream(&pP[i], (u64)P0 | ((u64)P1 << 32));
+    store_stream(&pQ[i], (u64)Q0 | ((u64)Q1 << 32));
+}
+
+// The output-free forms (FUSED_OUT_LAST / FUSED_OUT_NONE: qttt_step_many with out_stride == 0, asked for or by the route of
+// the one-round rows).  Without per-ply outputs the loop holds no store, no output pointer and no test of what to keep, and
+// nothing couples the action stream to a store queue: the actions are requested FUSED_PREFETCH plies ahead instead of one
+// (the stream of a long replay comes from HBM, not from the Infinity Cache), and the state is consumed in front of the loop
+// (as in step_random_fused_kernel below) so that the wait for its loads does not land inside.
+// (tools/stepbench, interleaved, 1 M boards, us per step with 1 / 2 / 4 plies ahead: 3.29 / 3.27 / 3.29 at K = 200,
+// 3.46 / 3.43 / 3.47 at K = 20 — within the spread of the repeats; profiles/resident/stepbench_1M_k*.txt)
+constexpr int FUSED_PREFETCH = 2;
+// CAP — the plies one launch takes, the size of its keys argument (ResidentKeys<CAP>, 8 B per ply; the kernel arguments
+// stay within 4 KB).  A launch costs the kernel boundary, the wave ramp, the table fill behind the workgroup's barrier, the
+// state's round trip and the drain of the second occupancy round, and nothing in the result needs any of it; with no
+// per-ply outputs only the keys argument bounds a launch.  RESIDENT_MAX_PLIES is the product's CAP: the smallest within
+// the spread of the best.  tools/stepbench 1048576 K 15 parent.so this.so resident:CAP:512 ..., interleaved, us per step,
+// median (min) (profiles/resident_long/stepbench_cap_and_block.txt):
+//   plies per launch      64            128           256           448
+//   K = 1000              3.14 (3.09)   3.07 (3.06)   3.04 (3.03)   3.05 (3.04)     a launch costs (3.14 - 3.04) x 1000 / 12 = 8 us
+//   K = 200               3.26 (3.22)   3.20 (3.13)   3.18 (3.11)   3.18 (3.14)
+//   K = 20                3.47 (3.42)   -             3.48 (3.41)   -               one launch either way
+// BLOCK — threads per workgroup (RESIDENT_BLOCK in the product).  The same tool, K = 200, CAP = 256, median (min):
+//   boards        256           512           1024
+//   458 816       1.68 (1.66)   1.74 (1.70)   1.72 (1.70)
+//   786 432       2.47 (2.43)   2.48 (2.43)   2.47 (2.45)
+//   1 048 576     3.18 (3.15)   3.20 (3.14)   3.20 (3.14)
+//   1 572 864     4.67 (4.62)   4.67 (4.60)   4.68 (4.60)
+// 512 stays: from 786 432 boards on the three are within the spread of the repeats (0.03 - 0.07 between a variant's min and
+// median); 256 threads are 0.04 - 0.06 ahead at the window's first size only, one spread, and a second instantiation for
+// that edge was not taken.
+constexpr int RESIDENT_MAX_PLIES = 256;
+constexpr int RESIDENT_BLOCK = QTTT_BLOCK;
+template <int CAP>
+struct ResidentKeys { u64 k[CAP]; };
+template <bool HAS_BITS, bool AUTO_RESET, int OUT, int CAP, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void step_fused_kernel(
+    u64 *__restrict__ pP, u64 *__restrict__ pQ, const uint16_t *__restrict__ actions,
+    const uint8_t *__restrict__ bits, ResidentKeys<CAP> keys, u32 id_hi_fold, u32 id_base,
+    u32 *__restrict__ reward_bits, uint8_t *__restrict__ terminated, int64_t n, int32_t n_steps) {
+    static_assert(OUT == FUSED_OUT_LAST || OUT == FUSED_OUT_NONE, "every ply's outputs: the kernel above");
+    static_assert(sizeof(ResidentKeys<CAP>) + 64 + 256 <= 4096, "4 KB of kernel arguments, the hidden ones included");
+    __shared__ __attribute__((aligned(16))) uint8_t lut[LINE_LUT_BYTES];
+    const int64_t ib = (int64_t)blockIdx.x * BLOCK;                 // first board of the workgroup (block-uniform)
+    const int64_t i = ib + threadIdx.x;
+    const int64_t il = i < n ? i : 0;                               // idle lanes re-read board 0, store nothing
+    const u64 P = load_stream(&pP[il]), Q = load_stream(&pQ[il]);   // requested before the table fills
+    fill_line_lut<BLOCK>(lut);
+    if (i >= n) return;
+    u32 P0 = (u32)P, P1 = (u32)(P >> 32), Q0 = (u32)Q, Q1 = (u32)(Q >> 32);
+    const u32 id = (id_base + (u32)i) ^ id_hi_fold;
+    // per-ply streams: a block-uniform 64-bit base (scalar unit, advanced by the stride every ply) plus the lane's offset
+    const uint16_t *a_blk = actions + ib;
+    const uint8_t *b_blk = HAS_BITS ? bits + ib : nullptr;
+    const u32 lane = threadIdx.x;
+    u32 win = 0;
+    u64 key = keys.k[0];
+    // the actions (and bits) of plies 0 .. FUSED_PREFETCH - 1 are in flight before the first step; a ply past the
+    // launch's last re-reads the last one's (the base stops advancing), so every address stays inside the run
+    u32 act[FUSED_PREFETCH], bit_in[FUSED_PREFETCH];
+#pragma unroll
+    for (int k = 0; k < FUSED_PREFETCH; ++k) {
+        if (k > 0) {
+            const bool more = k < n_steps;
             a_blk += more ? n : 0;
             if (HAS_BITS) b_blk += more ? n : 0;
-            const u32 act_next = load_stream(&a_blk[lane]), bit_next = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
-            const u32 bit = HAS_BITS ? (bit_in & 1u) : collapse_bit_of(id ^ (u32)key);
-            win = step_core<AUTO_RESET>(P0, P1, Q0, Q1, act, bit, lut);
-            if (out_stride != 0 || t == n_steps - 1) {
-                // (the compiler's own stores here: it counts them when it waits for the action requested a ply ahead)
-                store_stream(&r_blk[lane], 0x80000000u | (win << 23));
-                store_stream(&t_blk[lane], (uint8_t)(P1 >> 31));
-            }
-            r_blk += out_stride;
-            t_blk += out_stride;
-            key = key_next;
-            act = act_next;
-            bit_in = bit_next;
         }
-    } else {
-        // the actions (and bits) of plies 0 .. FUSED_PREFETCH - 1 are in flight before the first step; a ply past the
-        // launch's last re-reads the last one's (the base stops advancing), so every address stays inside the run
-        u32 act[FUSED_PREFETCH], bit_in[FUSED_PREFETCH];
+        act[k] = load_stream(&a_blk[lane]);
+        bit_in[k] = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
+    }
+    asm volatile("" : "+v"(P0), "+v"(P1), "+v"(Q0), "+v"(Q1));
+    for (int32_t t = 0; t < n_steps; ++t) {
+        // one scalar load, requested a ply ahead; the index wraps at CAP (a mask where CAP is a power of two)
+        const u64 key_next = keys.k[(CAP & (CAP - 1)) == 0 ? (t + 1) & (CAP - 1) : t + 1 < CAP ? t + 1 : 0];
+        const bool more = t + FUSED_PREFETCH < n_steps;
+        a_blk += more ? n : 0;
+        if (HAS_BITS) b_blk += more ? n : 0;
+        const u32 act_far = load_stream(&a_blk[lane]), bit_far = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
+        const u32 bit = HAS_BITS ? (bit_in[0] & 1u) : collapse_bit_of(id ^ (u32)key);
+        win = step_core<AUTO_RESET>(P0, P1, Q0, Q1, act[0], bit, lut);
+        key = key_next;
 #pragma unroll
-        for (int k = 0; k < FUSED_PREFETCH; ++k) {
-            if (k > 0) {
-                const bool more = k < n_steps;
-                a_blk += more ? n : 0;
-                if (HAS_BITS) b_blk += more ? n : 0;
-            }
-            act[k] = load_stream(&a_blk[lane]);
-            bit_in[k] = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
+        for (int k = 0; k + 1 < FUSED_PREFETCH; ++k) {
+            act[k] = act[k + 1];
+            bit_in[k] = bit_in[k + 1];
         }
-        asm volatile("" : "+v"(P0), "+v"(P1), "+v"(Q0), "+v"(Q1));
-        for (int32_t t = 0; t < n_steps; ++t) {
-            const u64 key_next = keys.k[(t + 1) & (FUSED_MAX_PLIES - 1)];   // one scalar load, requested a ply ahead
-            const bool more = t + FUSED_PREFETCH < n_steps;
-            a_blk += more ? n : 0;
-            if (HAS_BITS) b_blk += more ? n : 0;
-            const u32 act_far = load_stream(&a_blk[lane]), bit_far = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
-            const u32 bit = HAS_BITS ? (bit_in[0] & 1u) : collapse_bit_of(id ^ (u32)key);
-            win = step_core<AUTO_RESET>(P0, P1, Q0, Q1, act[0], bit, lut);
-            key = key_next;
-#pragma unroll
-            for (int k = 0; k + 1 < FUSED_PREFETCH; ++k) {
-                act[k] = act[k + 1];
-                bit_in[k] = bit_in[k + 1];
-            }
-            act[FUSED_PREFETCH - 1] = act_far;
-            bit_in[FUSED_PREFETCH - 1] = bit_far;
-        }
-        if constexpr (OUT == FUSED_OUT_LAST) {
-            store_stream(&reward_bits[i], 0x80000000u | (win << 23));   // env.py:49: -1.0f / -0.0f
-            store_stream(&terminated[i], (uint8_t)(P1 >> 31));          // env.py:51
-        }
+        act[FUSED_PREFETCH - 1] = act_far;
+        bit_in[FUSED_PREFETCH - 1] = bit_far;
+    }
+    if constexpr (OUT == FUSED_OUT_LAST) {
+        store_stream(&reward_bits[i], 0x80000000u | (win << 23));   // env.py:49: -1.0f / -0.0f
+        store_stream(&terminated[i], (uint8_t)(P1 >> 31));          // env.py:51
     }
     store_stream(&pP[i], (u64)P0 | ((u64)P1 << 32));
     store_stream(&pQ[i], (u64)Q0 | ((u64)Q1 << 32));

@@ -348,7 +348,8 @@ class VecEnv(LibCaller):
         """T consecutive steps from pre-recorded device tensors actions u8[T,N,2] (bits u8[T,N]),
         enqueued from C with no per-step host work.  With `reward`/`terminated` of shape [T,N]
         every step's outputs are kept; otherwise only the last step's (returned).
-        fused=True runs the T steps with the boards in registers, one launch per 64 steps (same results); without
+        fused=True runs the T steps with the boards in registers, one launch per 256 steps (per 64 when every step's
+        outputs are kept; same results); without
         output buffers the library does so by itself for 448 K < N <= 1536 K boards, T >= 16 and no launch shape named
         (one launch per step otherwise)."""
         n, dev = self.num_envs, self.device

@@ -18,7 +18,7 @@ count (K - 1 quiet + 1 full per region), with the two kinds listed beside it.  W
 either kind is averaged (the recording pass and the warm-up passes included).
 
 Where step_many takes the register-resident route (no output buffers, 448 K < boards <= 1536 K, K >= 16) the timed region
-is ceil(K / 64) dispatches of step_fused_kernel: with PMC_KERNEL_FILTER=step_fused_kernel and PMC_STEPS=K every dispatch of
+is ceil(K / 256) dispatches of step_fused_kernel (RESIDENT_MAX_PLIES, csrc/qttt_step_kernels.h): with PMC_KERNEL_FILTER=step_fused_kernel and PMC_STEPS=K every dispatch of
 that kernel is a timed one (the warm-up of fewer than 16 steps runs launch per step), their bytes are summed per region and
 divided by K, so that the entry stays "bytes per step" like the quiet / full one; its algorithmic figure is the action
 stream's 2 B per board-step plus one state round trip (2 x state bytes) and the last ply's 5 B per region."""
@@ -35,6 +35,7 @@ KERNEL_FILTER = os.environ.get("PMC_KERNEL_FILTER", "step_kernel")
 
 QUIET_FILTER = "step_quiet_kernel"
 STEPS = int(os.environ.get("PMC_STEPS", "0"))
+RESIDENT_MAX_PLIES = 256                     # csrc/qttt_step_kernels.h: the plies of one output-free launch
 REGION = tuple(int(x) for x in os.environ["PMC_REGION"].split(",")) if os.environ.get("PMC_REGION") else None
 
 
@@ -48,7 +49,7 @@ def mean_counter(d, name):
                 rows.append((int(r["Dispatch_Id"]), "quiet" if quiet else "full", float(r["Counter_Value"])))
     rows.sort()
     if STEPS:
-        per_region = -(-STEPS // 64)
+        per_region = -(-STEPS // RESIDENT_MAX_PLIES)
         n_regions = len(rows) // per_region
         total = sum(x[2] for x in rows[-n_regions * per_region:])
         return total / (n_regions * STEPS), n_regions * per_region, {}
@@ -111,7 +112,7 @@ def main():
     if STEPS:
         entry["resident_route_steps_per_region"] = STEPS
         entry["algorithmic_bytes_per_launch"] = (2 + (2 * state_bytes + 5) / STEPS) * int(boards)
-        entry["note"] += "; step_fused_kernel: bytes per STEP of a region of %d steps in %d dispatches" % (STEPS, -(-STEPS // 64))
+        entry["note"] += "; step_fused_kernel: bytes per STEP of a region of %d steps in %d dispatches" % (STEPS, -(-STEPS // RESIDENT_MAX_PLIES))
     if REGION:
         entry["timed_region_steps_warmup_regions"] = list(REGION)
     path = os.path.join(ROOT, "profiles", "pmc_traffic.json")

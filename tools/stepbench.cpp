@@ -4,12 +4,16 @@
 // hipEvents), and times the variants INTERLEAVED in one process on one device, so that clock and
 // device differences cancel.  Also times a "traffic floor" kernel that moves the same bytes per
 // board with no game logic.
-//   hipcc --offload-arch=gfx950 -O3 -Iinclude tools/stepbench.cpp -ldl -o tools/stepbench
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Iqtttgym_amd/csrc tools/stepbench.cpp -ldl -o tools/stepbench
 //   tools/stepbench N K REPS  lib.so[:boards_per_lane[:workgroup_size[:fused]]] ...   (0 = the library's own choice)
 // fused = 1: the replay with QTTT_FLAG_FUSED — the boards in registers, no outputs per ply (step_fused_kernel's output-free
 // loop), at any size.  With nothing named, a library takes that route itself in the one-round rows of its launch-shape
 // table (448 K < N <= 1536 K boards); naming a shape there (e.g. lib.so:2:1024) times the launch-per-step quiet kernel.
-#include <hip/hip_runtime.h>
+// resident:CAP:BLOCK in place of a library (after at least one): the output-free step_fused_kernel compiled HERE from the
+// product's headers with CAP plies per launch (64 | 128 | 256 | 448) and BLOCK threads per workgroup (256 | 512 | 1024),
+// launched as qttt_step_many launches it — how RESIDENT_MAX_PLIES and RESIDENT_BLOCK were chosen; the product library
+// carries one instantiation only.
+#include "qttt_launch.h"
 #include <dlfcn.h>
 #include <cstdio>
 #include <cstdlib>
@@ -21,13 +25,8 @@
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e)); exit(1); } } while (0)
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
+namespace floors {            // the traffic-floor kernels and their own vector types
 template <typename T, int N> struct alignas(sizeof(T) * N) Vec { T v[N]; };
-
-typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 template <int B> struct RawOf;
 template <> struct RawOf<1> { typedef uint8_t type; };
 template <> struct RawOf<2> { typedef uint16_t type; };
@@ -105,9 +104,40 @@ __global__ __launch_bounds__(BLK) void floor16_kernel(u64 *pA, u64 *pB, const ui
     }
 }
 
+}  // namespace floors
+using floors::floor_kernel;
+using floors::floor16_kernel;
+
+// K plies of the output-free kernel with CAP plies per launch and BLOCK threads per workgroup: hashed collapse bits,
+// auto-reset, board ids from 0 — qttt_step_many(flags = AUTO_RESET, out_stride = 0) with those two constants
+template <int CAP, int BLOCK>
+int resident_many(void *state, const uint8_t *actions, uint64_t seed, uint32_t step_idx0, float *reward, uint8_t *term,
+                  int64_t n, int32_t K, void *stream) {
+    const Planes p = planes(state, n);
+    const uint16_t *a16 = reinterpret_cast<const uint16_t *>(actions);
+    typedef ResidentKeys<CAP> Keys;
+    return fused_runs<CAP, Keys>(seed, step_idx0, K, [&](int64_t done, int32_t plies, const Keys &keys) {
+        return with_bools([&](auto LAST) {
+            return launch(step_fused_kernel<false, true, LAST ? FUSED_OUT_LAST : FUSED_OUT_NONE, CAP, BLOCK>, ceil_div(n, BLOCK),
+                          BLOCK, stream, p.P, p.Q, a16 + done * n, (const uint8_t *)nullptr, keys, 0u, 0u,
+                          LAST ? (u32 *)reward : nullptr, LAST ? term : nullptr, n, plies);
+        }, done + plies == K);
+    });
+}
+typedef int (*resident_fn)(void *, const uint8_t *, uint64_t, uint32_t, float *, uint8_t *, int64_t, int32_t, void *);
+static resident_fn resident_variant(int cap, int block) {
+    return with_int<64, 128, 256, 448, 0>(cap, [&](auto CAP) -> resident_fn {
+        return with_int<256, 512, 1024, 0>(block, [&](auto BLOCK) -> resident_fn {
+            if constexpr (CAP == 0 || BLOCK == 0) return nullptr;
+            else return resident_many<CAP, BLOCK>;
+        });
+    });
+}
+
 struct Lib {
     std::string spec, path;
     int bpl, pipe, fused;
+    resident_fn resident;
     void *h;
     int64_t (*state_bytes)(int64_t);
     int (*reset)(void *, int64_t, void *);
@@ -134,6 +164,14 @@ int main(int argc, char **argv) {
         char path[512]; int bpl = 0, pipe = 0, fused = 0;      // lib.so:boards_per_lane:workgroup_size:fused, 0 = the library's choice
         if (sscanf(argv[i], "%511[^:]:%d:%d:%d", path, &bpl, &pipe, &fused) < 1) return 2;
         L.path = path; L.bpl = bpl; L.pipe = pipe; L.fused = fused;
+        L.resident = nullptr;
+        if (L.path == "resident") {                            // resident:CAP:BLOCK — the first library's entries around it
+            if (libs.empty() || !(L.resident = resident_variant(bpl, pipe))) { fprintf(stderr, "%s: after a library; CAP 64|128|256|448, BLOCK 256|512|1024\n", argv[i]); return 2; }
+            const resident_fn r = L.resident;
+            L = libs[0]; L.spec = argv[i]; L.resident = r; L.bpl = L.pipe = L.fused = 0; L.step_wpb = nullptr;
+            libs.push_back(L);
+            continue;
+        }
         L.h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
         if (!L.h) { fprintf(stderr, "dlopen %s: %s\n", path, dlerror()); return 1; }
 #define SYM(f, name) *(void **)(&L.f) = dlsym(L.h, name); if (!L.f) { fprintf(stderr, "missing %s\n", name); return 1; }
@@ -187,6 +225,8 @@ int main(int argc, char **argv) {
             } else if (random_mode && L.step_random) {
                 for (int t = 0; t < K && !rc; ++t)
                     rc = L.step_random(state, seed, W + t, 0, 1, actions + (size_t)(W + t) * 2 * n, reward, term, n, s);
+            } else if (L.resident) {
+                rc = L.resident(state, actions + (size_t)W * 2 * n, seed, W, reward, term, n, K, s);
             } else {
                 rc = L.step_many(state, actions + (size_t)W * 2 * n, nullptr, seed, W, 0, 1u | (L.fused ? 2u : 0u), reward, term, 0, n, K, s);
             }

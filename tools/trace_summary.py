@@ -20,8 +20,8 @@ terminated: every timed step of a replay region but its last) count as step disp
 also printed for the two kernels separately.
 
 Where step_many takes the register-resident route (no output buffers, 448 K < boards <= 1536 K, K >= 16) the timed
-region is ceil(K / 64) dispatches of step_fused_kernel and nothing else: pass `step_fused_kernel` as the substring and
-PLIES = the plies per timed region as K's meaning changes — K = ceil(steps / 64), W = the warm-up's dispatches of that
+region is ceil(K / 256) dispatches of step_fused_kernel (RESIDENT_MAX_PLIES, csrc/qttt_step_kernels.h) and nothing else: pass `step_fused_kernel` as the substring and
+PLIES = the plies per timed region as K's meaning changes — K = ceil(steps / 256), W = the warm-up's dispatches of that
 kernel (0 when the warm-up is shorter than 16 steps: it then runs launch per step) — and read "per step" as the timed
 span divided by the steps, printed when STEPS_PER_REGION is set in the environment.
 """
