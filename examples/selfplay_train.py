@@ -7,7 +7,7 @@ the new weights for the search and repeats.
     python examples/selfplay_train.py [--games 1024] [--rollouts 100] [--sims 10] [--epochs 50] [--runs 30]
                                       [--dtype f32|bf16] [--out model.pt] [--model model.pt] [--value-targets 1,0]
                                       [--symmetries] [--leaf-eval playouts|value]
-                                      [--root-noise EPS,ALPHA] [--temperature T] [--sample-plies K]
+                                      [--root-noise EPS,ALPHA] [--temperature T] [--sample-plies K] [--leaves K]
 
 The network is nn.Model's (nn.py:7-28) under its own parameter names (qtttgym_amd.policy_value.SHAPES), so --out is a
 state dict that the reference, PolicyValueNet and examples/tree_tournament.py --model all load.  The loss is the
@@ -22,7 +22,8 @@ run trains is then what the next run searches with; use --value-targets 1,-1 wit
 --root-noise 0.25,0.3 mixes Dirichlet(0.3) noise into the roots' priors before every searched move, and --sample-plies K
 draws the move of the first K plies from the visit counts (N ** (1 / --temperature)) instead of playing the best one:
 AlphaZero's root exploration (SelfPlay(root_noise=, temperature=, sample_plies=)), without which the games of a run under
---leaf-eval value all open alike.
+--leaf-eval value all open alike.  --leaves K (with --leaf-eval value) searches K leaves per game per round, kept apart
+by virtual loss (SelfPlay(leaves=K)): one network launch per round evaluates games * K leaves.
 """
 import argparse
 import os
@@ -79,6 +80,8 @@ def main():
     ap.add_argument("--symmetries", action="store_true", help="train on the eight images of every game")
     ap.add_argument("--leaf-eval", choices=("playouts", "value"), default="playouts",
                     help="what scores a leaf of the search: --sims playouts, or the network's value head")
+    ap.add_argument("--leaves", type=int, default=1,
+                    help="leaves per game per round of the search (SelfPlay(leaves=K): virtual loss; needs --leaf-eval value)")
     ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA",
                     help="Dirichlet(ALPHA) noise with weight EPS on the roots' priors before every searched move")
     ap.add_argument("--temperature", type=float, default=1.0, help="the sampled moves follow N ** (1 / temperature)")
@@ -94,7 +97,7 @@ def main():
     net = PolicyValueNet(model, device=dev, dtype=torch.float32 if args.dtype == "f32" else torch.bfloat16)
     targets = tuple(float(x) for x in args.value_targets.split(","))
     sp = SelfPlay(args.games, n_rollouts=args.rollouts, num_simulations=args.sims, net=net, value_targets=targets,
-                  seed=args.seed, leaf_eval=args.leaf_eval,
+                  seed=args.seed, leaf_eval=args.leaf_eval, leaves=args.leaves,
                   root_noise=None if args.root_noise is None else tuple(float(x) for x in args.root_noise.split(",")),
                   temperature=args.temperature, sample_plies=args.sample_plies)
     for run in range(args.runs):

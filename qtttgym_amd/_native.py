@@ -116,6 +116,14 @@ SYMMETRY_SIGNATURES = {
 TREE_VALUE_SIGNATURES = {
     "qttt_tree_value_rollout": (_i32, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
 }
+# every symbol include/qttt_tree_leaves.h declares (leaf-parallel rounds of the search trees; qttt.h includes it)
+TREE_MAX_LEAVES = 64
+TREE_PATH_BYTES = 64
+TREE_LEAVES_SIGNATURES = {
+    "qttt_tree_paths_bytes": (_i64, [_i64, _i32]),
+    "qttt_tree_select_batch": (_i32, [_vp, _i64, _i64, _u64, _u32, _i32, _i64, _f64, _f64, _vp, _vp, _vp]),
+    "qttt_tree_backup_batch": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+}
 # every symbol include/qttt_tree_explore.h declares (root exploration: Dirichlet noise, the sampled move; qttt.h
 # includes it)
 TREE_NOISE_BASE = 0xC0000000
@@ -193,7 +201,7 @@ def lib():
                                   + list(POLICY_ROLLOUT_SIGNATURES.items()) + list(TREE_SIGNATURES.items())
                                   + list(TREE_COMPACT_SIGNATURES.items()) + list(SELFPLAY_SIGNATURES.items())
                                   + list(SYMMETRY_SIGNATURES.items()) + list(TREE_VALUE_SIGNATURES.items())
-                                  + list(TREE_EXPLORE_SIGNATURES.items())):
+                                  + list(TREE_EXPLORE_SIGNATURES.items()) + list(TREE_LEAVES_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

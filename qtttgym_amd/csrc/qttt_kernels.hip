@@ -52,6 +52,7 @@
 // qttt_tree_kernels.h (the batched search trees) -> qttt_selfplay_kernels.h (the self-play record) ->
 // qttt_symmetry_kernels.h (the board's symmetries: images of states, the augmented self-play batch);
 // qttt_tree_value_kernels.h (the value rollout: network evaluation of the leaves and backup in one launch);
+// qttt_tree_leaves_kernels.h (leaf-parallel rounds: K descents per game under virtual loss, and their backup);
 // qttt_tree_explore_kernels.h (root exploration: Dirichlet noise on the roots' priors, the sampled move).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
 // qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
@@ -67,6 +68,7 @@
 #include "qttt_selfplay_kernels.h"
 #include "qttt_symmetry_kernels.h"
 #include "qttt_tree_value_kernels.h"
+#include "qttt_tree_leaves_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -189,6 +191,10 @@ bool expand_rows_misaligned(const int8_t *winner, const uint8_t *terminal, const
 }
 
 bool tree_size_bad(int64_t games, int64_t capacity) { return games < 0 || capacity < 1 || capacity > QTTT_TREE_MAX_CAPACITY; }
+// the sizes of a leaf-parallel round: K in range, and games * K boards, records and priors rows addressable
+bool tree_leaves_bad(int64_t games, int leaves) {
+    return games < 0 || leaves < 1 || leaves > QTTT_TREE_MAX_LEAVES || games > INT64_MAX / (256 * (int64_t)QTTT_TREE_MAX_LEAVES);
+}
 
 }  // namespace
 
@@ -800,6 +806,38 @@ int qttt_tree_value_rollout(void *tree, int64_t games, int64_t capacity, const v
         return launch(tree_value_rollout_kernel<P>, ceil_div(games, NNCfg<P>::M), QTTT_NN_BLOCK, stream, tree, games, capacity,
                       l.P, l.Q, weights, leaf_value, leaf_probs);
     });
+}
+
+// ---------------------------------------------------------------- leaf-parallel rounds (include/qttt_tree_leaves.h)
+int64_t qttt_tree_paths_bytes(int64_t games, int leaves) {
+    if (tree_leaves_bad(games, leaves)) return QTTT_ERR_SIZE;
+    return games * leaves * (int64_t)QTTT_TREE_PATH_BYTES;
+}
+
+int qttt_tree_select_batch(void *tree, int64_t games, int64_t capacity, uint64_t seed, uint32_t rollout_idx0, int leaves,
+                           int64_t board_offset, double c_puct, double virtual_loss, void *paths, void *leaf_state,
+                           void *stream) {
+    if (tree_size_bad(games, capacity) || board_offset < 0 || tree_leaves_bad(games, leaves) ||
+        (uint64_t)rollout_idx0 + (uint64_t)leaves > QTTT_TREE_MAX_ROLLOUTS || !std::isfinite(virtual_loss) || virtual_loss < 0.0)
+        return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, paths, leaf_state)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(paths, 16)) return QTTT_ERR_ACTION;
+    const Planes l = planes(leaf_state, games * leaves);
+    return launch(tree_select_batch_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (u64)seed, rollout_idx0, (u32)leaves, (u64)board_offset, c_puct, virtual_loss, static_cast<TreePathRec *>(paths),
+                  l.P, l.Q);
+}
+
+int qttt_tree_backup_batch(void *tree, int64_t games, int64_t capacity, int leaves, const void *paths,
+                           const float *leaf_value, const float *leaf_probs, void *stream) {
+    if (tree_size_bad(games, capacity) || tree_leaves_bad(games, leaves)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, paths, leaf_value, leaf_probs)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(paths, 16) || misaligned(leaf_value, 4) || misaligned(leaf_probs, 4))
+        return QTTT_ERR_ACTION;
+    return launch(tree_backup_batch_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (u32)leaves, static_cast<const TreePathRec *>(paths), leaf_value, leaf_probs);
 }
 
 // ---------------------------------------------------------------- root exploration (include/qttt_tree_explore.h)

@@ -88,6 +88,7 @@ class SelfPlay(LibCaller):
     of 1 + 10 * (2 * n_rollouts + 1), at the price of one host read-back per move.  Without it play() never waits
     for the device.
     leaf_eval is TreeSearch's: "playouts" (the reference's rollout) or "value" (the leaf scored by net's value head).
+    leaves and virtual_loss are TreeSearch's too: leaves=K > 1 searches K leaves per game per round (value leaves only).
     root_noise=(epsilon, alpha): every searched ply runs one rollout (so that every live root has priors), then
     TreeSearch.add_root_noise(epsilon, alpha), then the other n_rollouts - 1.  sample_plies=k > 0: the move of plies
     0..k-1 is drawn with probability proportional to N ** (1 / temperature) (qttt_selfplay_record_sampled, with the
@@ -96,12 +97,19 @@ class SelfPlay(LibCaller):
 
     def __init__(self, num_games, n_rollouts=100, num_simulations=10, net=None, alpha=1.0, c_puct=1.0,
                  value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts",
-                 root_noise=None, temperature=1.0, sample_plies=0):
+                 root_noise=None, temperature=1.0, sample_plies=0, leaves=1, virtual_loss=1.0):
         if leaf_eval not in TreeSearch.LEAF_EVALS:
             raise ValueError("leaf_eval must be one of %s" % (TreeSearch.LEAF_EVALS,))
         if leaf_eval == "value" and net is None:
             raise ValueError('leaf_eval="value" needs a net')
         self.leaf_eval = leaf_eval
+        self.leaves, self.virtual_loss = int(leaves), float(virtual_loss)
+        if not 1 <= self.leaves <= _native.TREE_MAX_LEAVES:
+            raise ValueError("leaves must be in 1..%d" % _native.TREE_MAX_LEAVES)
+        if self.leaves > 1 and leaf_eval != "value":
+            raise ValueError('leaves > 1 needs leaf_eval="value"')
+        if not 0.0 <= self.virtual_loss < float("inf"):
+            raise ValueError("virtual_loss must be finite and >= 0")
         self.num_games, self.n_rollouts = int(num_games), int(n_rollouts)
         self.num_simulations, self.net = int(num_simulations), net
         self.alpha, self.c_puct, self.seed, self.compact = float(alpha), float(c_puct), int(seed), bool(compact)
@@ -179,7 +187,7 @@ class SelfPlay(LibCaller):
         env = self.env = VecEnv(G, device=self.device, seed=s)
         tree = self.tree = TreeSearch(G, capacity=self.capacity, num_simulations=self.num_simulations,
                                       c_puct=self.c_puct, net=self.net, seed=2 * s + 1, device=self.device,
-                                      leaf_eval=self.leaf_eval)
+                                      leaf_eval=self.leaf_eval, leaves=self.leaves, virtual_loss=self.virtual_loss)
         tree.reset(env)
         batch = self.new_batch()
         for ply in range(ROWS):

@@ -11,6 +11,11 @@ to hold the kept subtree and one move's rollouts; without it, every rollout and 
 keeps an upper bound on the nodes used (+2 per rollout, +1 per sync; compact() replaces it by the real maximum) and
 raises ValueError before launching work that could pass it.
 
+leaves=K > 1 (value leaves only) is the leaf-parallel search (include/qttt_tree_leaves.h): a round of K
+rollouts is select_batch -> VecEnv.evaluate on the G * K leaves -> backup_batch, three launches; the K descents of a game
+are kept apart by `virtual_loss`, which lives in spare bits of the visit counts between the two tree launches of a round
+and never touches W.
+
 add_root_noise() is AlphaZero's root exploration (include/qttt_tree_explore.h): Dirichlet noise mixed into
 the priors of every root that has them, one launch.
 """
@@ -31,15 +36,25 @@ class TreeSearch(LibCaller):
     leaf_eval = "playouts"
 
     def __init__(self, num_games, capacity, num_simulations=10, c_puct=1.0, net=None, seed=0, board_offset=0,
-                 device=None, leaf_eval="playouts"):
+                 device=None, leaf_eval="playouts", leaves=1, virtual_loss=1.0):
         """leaf_eval="playouts": the reference's rollout, num_simulations playouts from the leaf (uniform, or guided by
         `net`).  leaf_eval="value" (needs `net`): the leaf is scored by the value head, seen by the player to move
-        there; a terminal leaf by its reward.  num_simulations is then ignored: no playout draw is taken."""
+        there; a terminal leaf by its reward.  num_simulations is then ignored: no playout draw is taken.
+        leaves=K > 1 (needs leaf_eval="value"): contemplate() searches K leaves per game per round, each descent counted
+        as a loss of `virtual_loss` by the ones after it until the round is backed up.  leaves=1 is the search as it
+        always was."""
         if leaf_eval not in self.LEAF_EVALS:
             raise ValueError("leaf_eval must be one of %s" % (self.LEAF_EVALS,))
         if leaf_eval == "value" and net is None:
             raise ValueError('leaf_eval="value" needs a net')
         self.leaf_eval = leaf_eval
+        self.leaves, self.virtual_loss = int(leaves), float(virtual_loss)
+        if not 1 <= self.leaves <= _native.TREE_MAX_LEAVES:
+            raise ValueError("leaves must be in 1..%d" % _native.TREE_MAX_LEAVES)
+        if self.leaves > 1 and leaf_eval != "value":
+            raise ValueError('leaves > 1 needs leaf_eval="value"')
+        if not 0.0 <= self.virtual_loss < float("inf"):
+            raise ValueError("virtual_loss must be finite and >= 0")
         self.num_games, self.capacity = int(num_games), int(capacity)
         self.num_simulations, self.c_puct = int(num_simulations), float(c_puct)
         self.net, self.seed, self.board_offset = net, int(seed), int(board_offset)
@@ -73,6 +88,8 @@ class TreeSearch(LibCaller):
         self.noise_idx = 0            # add_root_noise() calls since the last reset: what addresses their draws
         self._bound = None            # upper bound on the nodes used (None: not reset yet)
         self._scratch = None          # compact()'s forwarding table, allocated by its first call
+        self._rounds = {}             # k -> the buffers of a round of k leaves per game, allocated by its first round
+        self._fresh = True            # no contemplate since the last reset() or sync(): the root may lack priors
 
     # ------------------------------------------------------------------ helpers
     def _check_env(self, env):
@@ -93,10 +110,12 @@ class TreeSearch(LibCaller):
         included)."""
         self._check_env(env)
         self._call("qttt_tree_reset", self.tree.data_ptr(), self.num_games, self.capacity, env.state.data_ptr())
-        self.rollout_idx, self.noise_idx, self._bound = 0, 0, 1
+        self.rollout_idx, self.noise_idx, self._bound, self._fresh = 0, 0, 1, True
 
     def contemplate(self, rollouts):
-        """`rollouts` x MCTS._rollout (mcts.py:166-176) in every game."""
+        """`rollouts` x MCTS._rollout (mcts.py:166-176) in every game.  With leaves = K > 1 they are taken K at a time:
+        after a reset() or sync() one single rollout first (K descents would all end on a root without priors), then
+        rounds of K and one shorter round for what is left."""
         r = int(rollouts)
         if r < 0:
             raise ValueError("rollouts must be >= 0")
@@ -108,9 +127,52 @@ class TreeSearch(LibCaller):
         if self._bound + 2 * r > self.capacity:
             raise ValueError("%d rollouts could use %d nodes, more than capacity %d"
                              % (r, self._bound + 2 * r, self.capacity))
-        for _ in range(r):
+        if self.leaves == 1:
+            for _ in range(r):
+                self._rollout()
+                self._bound += 2
+            return
+        if r and self._fresh:
             self._rollout()
             self._bound += 2
+            r -= 1
+            self._fresh = False
+        K = self.leaves
+        for k in [K] * (r // K) + [r % K] * (r % K > 0):
+            self._round(k)
+            self._bound += 2 * k
+
+    def _round_buffers(self, k):
+        """The buffers of a round of k leaves per game: the G * k leaves as a VecEnv, the path records, and the rows that
+        the network writes and the backup reads."""
+        b = self._rounds.get(k)
+        if b is None:
+            n, dev = self.num_games * k, self.device
+            nbytes = int(self._lib.qttt_tree_paths_bytes(self.num_games, k))
+            if nbytes < 0:
+                raise ValueError("qttt_tree_paths_bytes(%d, %d) failed" % (self.num_games, k))
+            state = torch.zeros(int(self._lib.qttt_state_bytes(n)), dtype=torch.uint8, device=dev)
+            b = self._rounds[k] = {"leaf": VecEnv.from_state(state, n, seed=self.seed, board_offset=self.board_offset),
+                                   "paths": torch.zeros(max(nbytes, 16), dtype=torch.uint8, device=dev),
+                                   "out": out_rows(VecEnv._EVAL_ROWS, n, dev, keys=("value", "probs"))}
+        return b
+
+    def _round(self, k):
+        """One round of k rollouts (1..TREE_MAX_LEAVES) through the leaf-parallel entries, without contemplate's bounds:
+        k descents per game under virtual loss, one evaluation of the G * k leaves, their backup."""
+        k = int(k)
+        if not 1 <= k <= _native.TREE_MAX_LEAVES:
+            raise ValueError("a round holds 1..%d leaves" % _native.TREE_MAX_LEAVES)
+        if self.leaf_eval != "value":
+            raise ValueError('a leaf-parallel round needs leaf_eval="value"')
+        b = self._round_buffers(k)
+        G, cap, tree = self.num_games, self.capacity, self.tree.data_ptr()
+        self._call("qttt_tree_select_batch", tree, G, cap, self.seed, self.rollout_idx, k, self.board_offset, self.c_puct,
+                   self.virtual_loss, b["paths"].data_ptr(), b["leaf"].state.data_ptr())
+        b["leaf"].evaluate(self.net, out=b["out"])
+        self._call("qttt_tree_backup_batch", tree, G, cap, k, b["paths"].data_ptr(), b["out"]["value"].data_ptr(),
+                   b["out"]["probs"].data_ptr())
+        self.rollout_idx += k
 
     def _rollout(self):
         """One rollout, without contemplate's bounds: select, the playouts from the leaves, backup; or select and the
@@ -192,6 +254,7 @@ class TreeSearch(LibCaller):
             raise ValueError("a sync could use %d nodes, more than capacity %d" % (self._bound + 1, self.capacity))
         self._call("qttt_tree_sync", self.tree.data_ptr(), self.num_games, self.capacity, env.state.data_ptr())
         self._bound += 1
+        self._fresh = True
 
     def compact(self, update_bound=True):
         """MCTS._prune as sync does it (mcts.py:222-231, 330-337): every game keeps the nodes reachable from its root,

@@ -11,6 +11,16 @@ over the measured rollouts), the playouts alone re-run on the same leaves as the
 rollout (select + the fused launch), a playout rollout at --sims, the fused launch alone, and qttt_evaluate (value +
 probs) and qttt_tree_backup alone on the same leaves.
 
+--leaves 1,8,32 turns the --value-games legs into the leaf-parallel comparison (TreeSearch(leaves=K)) per
+dtype of --value-modes: one value search per K on the same positions, the legs interleaved within each of --value-reps
+repetitions after one that warms up.  Every repetition resets each tree, contemplates 8 rollouts and then times 32
+rollouts back to back (K = 1: today's select + fused launch; K > 1: rounds of K through select_batch / evaluate /
+backup_batch), HIP events around the lot, and once more with events between the launches for the breakdown.  A row per K:
+microseconds per rollout (= round time / K), median, min and max, its parts, and the factor over the K = 1 leg of the
+same run with that leg's own max - min spread beside it.
+
+    python tools/treebench.py --games "" --value-games 256,4096,65536 --leaves 1,8,32 [--out profiles/tree_leaves/treebench_leaves.jsonl]
+
 --compact-games 4096,65536 adds the compaction leg (uniform playouts): per move contemplate(R) -> choose -> step ->
 sync -> compact(), timed with HIP events around contemplate and around compact (its launch alone; the read-back of the
 bound comes after the second event), medians over the moves of --compact-reps games from the empty board, with the
@@ -146,6 +156,77 @@ def run_value(G, mode, sims, reps, rollouts=6, warmup=4):
     return row
 
 
+def run_leaves(G, mode, Ks, reps, rollouts=32, warmup=8):
+    """One JSON row per K: medians over `reps` interleaved repetitions of `rollouts` rollouts per leg."""
+    import statistics
+    net = _net(torch.float32 if mode == "f32" else torch.bfloat16)
+    env = VecEnv(G, seed=1)
+    env.step_random_many(2)
+    stream = torch.cuda.current_stream()
+    cap = 1 + 2 * (warmup + 2 * rollouts + 2 * max(Ks))
+    trees = {K: TreeSearch(G, capacity=cap, net=net, seed=2, leaf_eval="value", leaves=K) for K in Ks}
+    event = lambda: torch.cuda.Event(enable_timing=True)
+
+    def launches(t, K):
+        """The launches of one round of K (one rollout at K = 1), as callables in order."""
+        tree = t.tree.data_ptr()
+        if K == 1:
+            leaf = t.leaf.state.data_ptr()
+            return (lambda: t._call("qttt_tree_select", tree, G, cap, t.seed, t.rollout_idx, t.board_offset, t.c_puct, leaf),
+                    lambda: t._call("qttt_tree_value_rollout", tree, G, cap, leaf, net.blob.data_ptr(), net.precision, None, None))
+        b = t._round_buffers(K)
+        paths, out = b["paths"].data_ptr(), b["out"]
+        return (lambda: t._call("qttt_tree_select_batch", tree, G, cap, t.seed, t.rollout_idx, K, t.board_offset, t.c_puct,
+                                t.virtual_loss, paths, b["leaf"].state.data_ptr()),
+                lambda: b["leaf"].evaluate(net, out=out),
+                lambda: t._call("qttt_tree_backup_batch", tree, G, cap, K, paths, out["value"].data_ptr(), out["probs"].data_ptr()))
+
+    us = {K: {"total": [], "parts": []} for K in Ks}
+    for rep in range(reps + 1):
+        for K in Ks:
+            t = trees[K]
+            t.reset(env)
+            t.contemplate(warmup)
+            rounds = max(1, rollouts // K)
+            torch.cuda.synchronize()
+            a, b = event(), event()
+            a.record(stream)
+            for _ in range(rounds):
+                t._rollout() if K == 1 else t._round(K)
+            b.record(stream)
+            torch.cuda.synchronize()
+            total = a.elapsed_time(b) * 1e3 / (rounds * K)
+            fns = launches(t, K)
+            ev = [[event() for _ in range(len(fns) + 1)] for _ in range(rounds)]
+            for e in ev:
+                e[0].record(stream)
+                for i, fn in enumerate(fns):
+                    fn()
+                    e[i + 1].record(stream)
+                t.rollout_idx += K
+            torch.cuda.synchronize()
+            parts = [sum(e[i].elapsed_time(e[i + 1]) for e in ev) * 1e3 / (rounds * K) for i in range(len(fns))]
+            if rep:                              # the first repetition warms every leg up
+                us[K]["total"].append(total)
+                us[K]["parts"].append(parts)
+    rows = []
+    for K in Ks:
+        xs = us[K]["total"]
+        row = {"games": G, "mode": mode, "leg": "leaves", "leaves": K, "reps": reps, "rollouts_per_rep": max(1, rollouts // K) * K,
+               "us_per_rollout_median": round(statistics.median(xs), 2), "us_per_rollout_min_max": [round(min(xs), 2), round(max(xs), 2)]}
+        names = ("select", "fused") if K == 1 else ("select_batch", "evaluate", "backup_batch")
+        for i, name in enumerate(names):
+            row["us_%s_per_rollout_median" % name] = round(statistics.median(p[i] for p in us[K]["parts"]), 2)
+        rows.append(row)
+    base = next((r for r in rows if r["leaves"] == 1), None)
+    for row in rows:
+        if base is not None and row is not base:
+            row["k1_us_per_rollout_median"] = base["us_per_rollout_median"]
+            row["k1_spread_us"] = round(base["us_per_rollout_min_max"][1] - base["us_per_rollout_min_max"][0], 2)
+            row["factor_over_k1"] = round(base["us_per_rollout_median"] / row["us_per_rollout_median"], 3)
+    return rows
+
+
 def run_explore(G, reps, launches, rollouts=8):
     """One JSON row: medians over `reps` interleaved repetitions of `launches` launches per leg."""
     import statistics
@@ -245,6 +326,7 @@ def main():
     ap.add_argument("--value-games", default="")
     ap.add_argument("--value-modes", default="f32,bf16")
     ap.add_argument("--value-reps", type=int, default=7)
+    ap.add_argument("--leaves", default="", help="e.g. 1,8,32: the --value-games legs compare leaves per round")
     ap.add_argument("--compact-games", default="")
     ap.add_argument("--compact-rollouts", type=int, default=300)
     ap.add_argument("--compact-reps", type=int, default=3)
@@ -262,9 +344,10 @@ def main():
             rows.append(row)
     for G in [int(x) for x in args.value_games.split(",") if x]:
         for mode in args.value_modes.split(","):
-            row = run_value(G, mode, args.sims, args.value_reps)
-            print(json.dumps(row), flush=True)
-            rows.append(row)
+            Ks = [int(x) for x in args.leaves.split(",") if x]
+            for row in (run_leaves(G, mode, Ks, args.value_reps) if Ks else [run_value(G, mode, args.sims, args.value_reps)]):
+                print(json.dumps(row), flush=True)
+                rows.append(row)
     for G in [int(x) for x in args.compact_games.split(",") if x]:
         row = run_compact(G, args.sims, args.compact_rollouts, args.compact_reps)
         print(json.dumps(row), flush=True)
