@@ -209,6 +209,121 @@ __device__ __forceinline__ u32 step_core(u32 &P0, u32 &P1, u32 &Q0, u32 &Q1, u32
 }
 
 //@isa other
+// ====================================================================== the resident ply
+// The ply of the output-free step_fused_kernel (qttt_step_kernels.h), which touches the packed words twice per launch and
+// not twice per ply: the board lives in a form of its own between unpack() and pack().
+//   gone   "done" as a lane mask (all ones / zero) instead of P1's bit 31: the line test's answer IS the next ply's reset mask
+//   H, CL  the high nibble of comps (at bit 0) and the classical mask (at its place in P1), each in a register of its own: no
+//          extract in front of the 64-bit shifts, no mask in front of the line test, no clear-and-merge of P1 behind the move
+//   P1     square 8's nibble, n and `last x` only (bits 20,21 pass through); the other fields are zero
+//   wx, wo the last ply's two lookups: the reward is formed from them once, behind the loop
+// The walk and the rooting rule are step_core's own functions.  The slots, the qstructs and the lookups are written out again,
+// operand for operand: as shared pieces (tried) they reorder the instruction streams of every other kernel that steps.
+// What each part is worth is listed above the kernel.
+template <bool AUTO_RESET>
+struct ResidentBoard {
+    u32 P0, P1, Q0, Q1, H, CL, gone, wx, wo;
+
+    __device__ __forceinline__ void unpack(u32 p0, u32 p1, u32 q0, u32 q1) {
+        P0 = p0, Q0 = q0, Q1 = q1;
+        wx = wo = 0u;
+        gone = (u32)((int)p1 >> 31);
+        H = (p1 >> P1_CHI_SHIFT) & 0xFu;
+        CL = p1 & (0x1FFu << P1_CL_SHIFT);
+        P1 = p1 & ~((0xFu << P1_CHI_SHIFT) | (0x1FFu << P1_CL_SHIFT) | P1_DONE);
+        asm volatile("" : "+v"(P0), "+v"(P1), "+v"(Q0), "+v"(Q1), "+v"(H), "+v"(CL), "+v"(gone));
+    }
+
+    // the exact packed state, and win = 0x7F iff the last ply left a completed line (step_core's return value)
+    __device__ __forceinline__ void pack(u32 &p0, u32 &p1, u32 &q0, u32 &q1, u32 &win) const {
+        p0 = P0, q0 = Q0, q1 = Q1;
+        p1 = P1 | (H << P1_CHI_SHIFT) | CL | (gone & P1_DONE);
+        win = wx | wo;
+    }
+
+    // act: the action's two bytes in bits 0..15 (the bits above are not looked at)
+    __device__ __forceinline__ void ply(u32 act, u32 bit, const uint8_t *lut) {
+//@isa reset
+        if (AUTO_RESET) {                                   // finished boards restart: empty = all zero
+            u32 g = gone;
+            asm("" : "+v"(g));                              // (as step_auto_reset: ANDs, not a compare and selects)
+            P0 &= ~g;
+            P1 &= ~g;
+            Q0 &= ~g;
+            Q1 &= ~g;
+            H &= ~g;
+            CL &= ~g;
+        }
+//@isa decode
+        StepPrep s;
+        // SDWA reads the two bytes where they lie; x lands at `last x`'s place in the same instruction
+        asm("v_min_u32_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_1" : "=v"(s.lo) : "v"(act));
+        asm("v_max_u32_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_1" : "=v"(s.hi) : "v"(act));
+        asm("v_xor_b32_sdwa %0, %1, %1 dst_sel:WORD_1 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_1" : "=v"(s.x16) : "v"(act));
+        // the two squares as a mask at the classical mask's place (only looked at when hi < 9)
+        const u32 cl_bit0 = 1u << P1_CL_SHIFT;
+        u32 pmS;
+        asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(pmS) : "v"(cl_bit0), "v"(s.lo), "v"(cl_bit0 << (s.hi & 31u)));
+        const u32 z = CL & pmS;
+        s.pm = pmS >> P1_CL_SHIFT;
+        // board.py:10-15.  With hi < 9, x16 is 0 (lo == hi) or lies in [1 << 16, 0xF0000], and z is 0 or at least 1 << 22 (one
+        // of the squares is classical): ONE compare answers "lo != hi and neither square is classical"
+        s.legal = s.hi < 9u && s.x16 > z;
+//@isa comps
+        s.n6 = P1 >> (P1_N_SHIFT - 2u);
+        s.comps = (u64)Q1 | ((u64)H << 32);
+        s.mlo = (u32)(s.comps >> (s.lo & 63u)) & SLOT_LSB;  // as step_prep
+        s.mhi = (u32)(s.comps >> (s.hi & 63u)) & SLOT_LSB;
+        asm("" : "+v"(s.mlo), "+v"(s.mhi));
+        s.has_lo = s.mlo != 0u;
+        s.cyc = (s.mlo & s.mhi) != 0u;
+//@isa glue
+        if (s.legal) {
+            const u64 P = step_reroot((u64)P0 | ((u64)P1 << 32), Q0, step_child_end4(s.lo, s.hi, s.has_lo, s.cyc, bit), s.n6);
+            P0 = (u32)P;
+            P1 = (u32)(P >> 32);
+//@isa append
+            Q0 ^= rotr32(s.x16, s.n6 + 18u);
+//@isa qstructs
+            // as step_fields, line for line: c1 = component of hi, sT = the slot the move goes to, pop on a cycle or a union
+            const u32 c1 = (u32)(s.comps >> (ffbl_raw(s.mhi) & 63u)) & 0x1FFu;
+            const u32 tsel = s.has_lo ? s.mlo : s.mhi;
+            const u32 c32 = (u32)s.comps;
+            const u32 y8 = (((c32 & 0x03FDFEFFu) + 0x03FDFEFFu) | c32) >> 8;
+            const u32 sT = ffbl_raw(BITOP3(tsel, y8, SLOT_LSB, A | (~B & C)));
+            const u64 ins = (u64)(s.pm | c1) << sT;
+            const u32 q1 = c32 | (u32)ins;
+            const u32 chi2 = (u32)(s.comps >> 32) | (u32)(ins >> 32);
+            const u32 mpop = s.has_lo ? s.mhi : 0u;
+            const u32 low = mpop - 1u;
+            Q1 = BITOP3(q1, low, __builtin_amdgcn_alignbit(chi2, q1, 9u), (A & B) | (C & ~B));
+//@isa fields
+            // after a pop the high nibble is empty; on a cycle the component goes classical; `last x` replaced, n += 1
+            H = mpop ? 0u : chi2;
+            CL = lshl_or<P1_CL_SHIFT>(s.cyc ? c1 : 0u, CL);
+            P1 = BITOP3(P1, ~(0xFu << P1_LX_SHIFT), s.x16, (A & B) | C) + (1u << P1_N_SHIFT);
+        }
+//@isa line
+        // as step_line up to the two lookups; their results are kept apart
+        const u32 par4 = P0 & 0x44444444u;
+        const u32 even4 = lshl_or<8>(P1 & 4u, __builtin_amdgcn_udot8(par4, 0x00008421u, 0u, false) |
+                                              (__builtin_amdgcn_udot8(par4, 0x84210000u, 0u, false) << 4));
+        u32 cl4 = CL >> (P1_CL_SHIFT - 2u);
+        asm("" : "+v"(cl4));
+        const u32 pc = (u32)__builtin_popcount(cl4);
+        u32 O4 = cl4 & ~even4;
+        asm("" : "+v"(O4));
+        const u32 X4 = pc >= 8u ? (O4 ^ 0x7FCu) : (cl4 & even4);
+        wx = *reinterpret_cast<const u32 *>(lut + X4);
+        wo = *reinterpret_cast<const u32 *>(lut + O4);
+        // env.py:51 as in step_line: bit 3 of (win | pc), spread over the lane's word by the sign-extending extract
+        u32 nw = (u32)__builtin_amdgcn_sbfe(BITOP3(wx, wo, pc, A | B | C), 3u, 1u);
+        asm("" : "+v"(nw));
+        gone = AUTO_RESET ? nw : (gone | nw);              // only ever set: after the reset above nothing is left to keep
+    }
+};
+
+//@isa other
 // Both values of the collapse bit at once (MCTS._step, mcts.py:233-267): child a = the closing move on lo (bit 0),
 // child b = on hi (bit 1).  Everything but the path reversal and the line test is shared; without a cycle the
 // children are the same board.  Returns n_children: 0 = make_move raises, 1 = no collapse, 2 = collapse.

@@ -324,6 +324,21 @@ constexpr int FUSED_PREFETCH = 2;
 // 512 stays: from 786 432 boards on the three are within the spread of the repeats (0.03 - 0.07 between a variant's min and
 // median); 256 threads are 0.04 - 0.06 ahead at the window's first size only, one spread, and a second instantiation for
 // that edge was not taken.
+// The ply — ResidentBoard (qttt_step_core.h): the loop runs on a form of the board of its own, unpacked in front of it and
+// packed behind it.  tools/isa_budget.py '<this kernel>' 1 --loop: 118.8 -> 113.8 VALU, 164.2 -> 157.6 ns of issue per
+// wave-ply; SQ_INSTS_VALU per board-ply 121.7 -> 116.8.  tools/stepbench 1048576 K 15, every variant its own library,
+// interleaved, us per step, median (min), the parent 3.06 (3.04) at K = 1000 and 3.46 (3.37) at K = 20
+// (profiles/resident_diet/stepbench_candidates.txt):
+//   kept     "done" as a lane mask, the lookups kept apart, the reward formed behind the loop: alone 3.06 (3.04) / 3.48 (3.38)
+//   kept     SDWA byte selects in the decode, one compare for "lo != hi and neither is classical": alone 3.05 (3.01) / 3.43 (3.34)
+//   kept     comps' high nibble and the classical mask in registers of their own, `last x` by one v_bitop3: alone 3.02 (2.99) / 3.46 (3.38)
+//            the three together 2.89 (2.88) / 3.32 (3.23): more than their sum (the body without any of them: 3.04 / 3.49)
+//   dropped  SLOT_LSB, the `last x` mask and the classical mask's bit pinned in VGPRs (their v_bitop3 fast-class, -0.7 ns in the
+//            model): alone 3.06 (3.04) / 3.47 (3.43), on top of the three 2.92 (2.91) / 3.34 (3.24): not faster
+//   dropped  the action as a 16-bit operand (no v_and 0xffff): the compiler packs two plies' actions into one register and
+//            pays a v_alignbit to rotate them; by the model +0.7 ns, not run
+//   dropped  the slots / qstructs / lookups as pieces shared with step_core: the other kernels' instruction streams reorder
+//   not tried: the walk's cost per node, the classical mask "times four" (the one compare above needs it above x16)
 constexpr int RESIDENT_MAX_PLIES = 256;
 constexpr int RESIDENT_BLOCK = QTTT_BLOCK;
 template <int CAP>
@@ -363,7 +378,8 @@ __global__ __launch_bounds__(BLOCK) void step_fused_kernel(
         act[k] = load_stream(&a_blk[lane]);
         bit_in[k] = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
     }
-    asm volatile("" : "+v"(P0), "+v"(P1), "+v"(Q0), "+v"(Q1));
+    ResidentBoard<AUTO_RESET> board;
+    board.unpack(P0, P1, Q0, Q1);                                   // (consumes the state in front of the loop)
     for (int32_t t = 0; t < n_steps; ++t) {
         // one scalar load, requested a ply ahead; the index wraps at CAP (a mask where CAP is a power of two)
         const u64 key_next = keys.k[(CAP & (CAP - 1)) == 0 ? (t + 1) & (CAP - 1) : t + 1 < CAP ? t + 1 : 0];
@@ -372,7 +388,7 @@ __global__ __launch_bounds__(BLOCK) void step_fused_kernel(
         if (HAS_BITS) b_blk += more ? n : 0;
         const u32 act_far = load_stream(&a_blk[lane]), bit_far = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
         const u32 bit = HAS_BITS ? (bit_in[0] & 1u) : collapse_bit_of(id ^ (u32)key);
-        win = step_core<AUTO_RESET>(P0, P1, Q0, Q1, act[0], bit, lut);
+        board.ply(act[0], bit, lut);
         key = key_next;
 #pragma unroll
         for (int k = 0; k + 1 < FUSED_PREFETCH; ++k) {
@@ -382,6 +398,7 @@ __global__ __launch_bounds__(BLOCK) void step_fused_kernel(
         act[FUSED_PREFETCH - 1] = act_far;
         bit_in[FUSED_PREFETCH - 1] = bit_far;
     }
+    board.pack(P0, P1, Q0, Q1, win);
     if constexpr (OUT == FUSED_OUT_LAST) {
         store_stream(&reward_bits[i], 0x80000000u | (win << 23));   // env.py:49: -1.0f / -0.0f
         store_stream(&terminated[i], (uint8_t)(P1 >> 31));          // env.py:51
