@@ -4,9 +4,11 @@
 // slots are read as one coalesced 576-byte load (16 B per lane), every lane scores its action in f64, and a butterfly
 // over the wave picks the argmax.  The one-lane-per-board mapping of the step kernels fits a state that
 // lives in registers; a tree node is 36-wide and lives in HBM, so here a lane per action is the natural unit.
-// A wave owns its game: node allocation needs no atomics, and no kernel re-reads what it wrote itself (a freshly
-// expanded child has no priors, so select ends on it; the child's header is still in registers).  The one exception
-// is tree_compact_kernel, whose lanes hand each other marks through memory, with tree_wave_sync() in between.
+// A wave owns its game: node allocation needs no atomics, and no kernel here re-reads what it wrote itself.  The one
+// descent, tree_descend (called by tree_select_kernel, and K times per game by tree_select_batch_kernel of
+// qttt_tree_leaves_kernels.h), reads nothing that it stored: a freshly expanded child has no priors, so the descent ends
+// on it with the child's header still in registers, and the path stays in lane registers until the caller stores it.  The
+// one exception is tree_compact_kernel, whose lanes hand each other marks through memory, with tree_wave_sync() in between.
 // Buffer layout: include/qttt_tree.h.
 #ifndef QTTT_TREE_KERNELS_H
 #define QTTT_TREE_KERNELS_H
@@ -21,7 +23,7 @@ namespace {
 constexpr int TREE_BLOCK = 256;                                 // 4 games per workgroup
 constexpr int TREE_GAMES_PER_BLOCK = TREE_BLOCK / 64;
 constexpr u32 TN_PRIORS = 1u, TN_UNIFORM = 2u, TN_TERMINAL = 4u, TN_TURN = 8u;      // node flags
-constexpr u32 TG_OVERFLOW = 1u, TG_LEAF_TURN = 2u, TG_LEAF_TERMINAL = 4u;          // game-header flags
+constexpr u32 TG_OVERFLOW = 1u, TG_LEAF_TURN = 2u, TG_LEAF_TERMINAL = 4u;          // game-header and path-record flags
 constexpr int TREE_CHILD_PAIR = 1 << 30;
 
 struct TreeGame {                      // 128 B, include/qttt_tree.h
@@ -97,6 +99,11 @@ __device__ __forceinline__ TreeNodeHdr tree_node_of(u64 P, u64 Q, bool turn, con
     return tree_node(P, Q, turn, w, t, legal_mask_of(s.cl));
 }
 
+// what the game header and a path record say of a leaf with these node flags
+__device__ __forceinline__ u32 tree_leaf_flags(u32 node_flags) {
+    return (node_flags & TN_TURN ? TG_LEAF_TURN : 0u) | (node_flags & TN_TERMINAL ? TG_LEAF_TERMINAL : 0u);
+}
+
 // a fresh node: header (by lane `writer`) and 36 empty slots (lanes 0..35)
 __device__ __forceinline__ void tree_write_node(const TreeView &v, int64_t g, int32_t i, const TreeNodeHdr &h, u32 lane,
                                                 u32 writer) {
@@ -157,8 +164,93 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_reset_kernel(void *tree, int6
     if (lane == 0u) {
         TreeGame *gh = &v.games[g];
         gh->used = 1; gh->root = 0; gh->depth = 0; gh->leaf = 0;
-        gh->flags = (h.flags & TN_TURN ? TG_LEAF_TURN : 0u) | (h.flags & TN_TERMINAL ? TG_LEAF_TERMINAL : 0u);
+        gh->flags = tree_leaf_flags(h.flags);
     }
+}
+
+// _expand_child (mcts.py:210-221) of action a of `node` (header h): both collapse children at once, as qttt_expand
+// (expand_pair: one step_core_both() for the two), in the records `used` and `used + 1`, and the one that `bit` picks becomes (node, h): a fresh node has no priors, so it is
+// the leaf and its header stays in registers.  False when nothing was allocated: the action is not legal (cannot happen
+// for one that the descent chose), or the children do not fit the pool (`overflow`).
+__device__ __forceinline__ bool tree_expand_child(const TreeView &v, int64_t g, int32_t &node, TreeNodeHdr &h, int a, u32 bit,
+                                                  int32_t &used, const uint8_t *lut, u32 lane, bool &overflow) {
+    const Expansion e = expand_pair(h.P, h.Q, pair_action<false>(a), lut);
+    if (e.kids == 0u || (int64_t)used + e.kids > v.capacity) {
+        overflow = e.kids != 0u;
+        return false;
+    }
+    const bool turn = !(h.flags & TN_TURN);
+    TreeNodeHdr c[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        int w, t;
+        update_winner_from_step(e.P[k], e.xo[k], lut, w, t);
+        c[k] = tree_node(e.P[k], e.Q, turn, w, t, legal_mask_of(classical_with_autofill(e.P[k])));
+    }
+    tree_write_node(v, g, used, c[0], lane, 0u);
+    if (e.kids == 2u) tree_write_node(v, g, used + 1, c[1], lane, 1u);
+    if (lane == 0u) v.slots(g, node)[a].child = used | (e.kids == 2u ? TREE_CHILD_PAIR : 0);
+    const u32 pick = e.kids == 2u ? bit : 0u;
+    node = used + (int32_t)pick;
+    h = pick ? c[1] : c[0];
+    used += (int32_t)e.kids;
+    return true;
+}
+
+// _select (mcts.py:269-280): one path of game g from `root` to a leaf, the only descent of the device trees.  bits = the
+// collapse choices, bit d = the child at path depth d; score(W, N word, prior, Ntot word, c_puct) = the selection score
+// of a legal action, tree_score or its in-flight form.  The path lives in lane registers: lane d < depth holds edge d as
+// (edge_node, edge_action), and the caller stores it where it belongs.  An expansion that does not fit ends the descent
+// on the node it stands on, and that edge is not on the path.
+// The winner is lane 0's for the whole wave: under NaN scores the lanes of wave_argmax disagree, and the path, the
+// expansion and whatever the caller marks must be one path (with ordinary scores every lane holds the same a).
+// Against the two copies of the loop that this replaced (profiles/tree_descent/treebench_parent_vs_change.txt: one
+// MI355X, the two libraries alternating, medians of three processes, us; [the old code's max - min]):
+//   qttt_tree_select per launch   4 096 games uniform 14.03 -> 13.94 [0.10], bf16 15.10 -> 14.82 [0.31]; 65 536 games
+//                                 93.46 -> 92.58 [1.69], 113.89 -> 112.44 [0.93]; 262 144 games 375.16 -> 370.31 [2.12],
+//                                 446.22 -> 442.11 [2.09]
+//   a value rollout, bf16         4 096 games K = 1 / 8 / 32: 78.36 -> 78.22 [0.13], 14.28 -> 14.17 [0.02], 9.78 -> 9.68 [0.12];
+//                                 65 536 games 180.88 -> 179.43 [0.66], 152.55 -> 150.76 [0.37], 124.93 -> 123.63 [0.29]
+//   a value rollout, f32          4 096 games 102.36 -> 102.19 [0.37], 26.87 -> 26.65 [0.16], 23.66 -> 23.50 [0.03];
+//                                 65 536 games 393.57 -> 392.25 [1.84], 361.64 -> 360.06 [0.85], 331.05 -> 330.09 [0.17]
+// Both kernels keep their registers, their 2 048 B of LDS and no scratch (device_code_parent_vs_change.txt there).
+struct TreeDescent {
+    int32_t leaf, depth;
+    TreeNodeHdr h;                     // the leaf's header
+    bool overflow;                     // the expansion did not fit
+    int32_t edge_node;                 // lane d < depth: edge d
+    u32 edge_action;
+};
+template <typename Score>
+__device__ __forceinline__ TreeDescent tree_descend(const TreeView &v, int64_t g, int32_t root, u32 bits, int32_t &used,
+                                                    const uint8_t *lut, u32 lane, double c_puct, Score &&score) {
+    TreeDescent d;
+    d.leaf = root; d.depth = 0;
+    d.overflow = false;
+    d.edge_node = 0; d.edge_action = 0u;
+    d.h = *v.hdr(g, root);
+    while ((d.h.flags & TN_PRIORS) && !(d.h.flags & TN_TERMINAL) && d.h.legal != 0ull && d.depth < QTTT_TREE_MAX_DEPTH) {
+        const bool legal = lane < 36u && ((d.h.legal >> lane) & 1ull);
+        TreeSlot s;
+        s.W = 0.0; s.N = 0u; s.child = -1;
+        if (lane < 36u) s = v.slots(g, d.leaf)[lane];
+        double sc = 0.0;
+        if (legal) sc = score(s.W, s.N, tree_prior(v, g, d.leaf, d.h, lane), d.h.Ntot, c_puct);
+        const int a = __builtin_amdgcn_readfirstlane(wave_argmax(legal, sc, lane));
+        const int32_t child = __shfl(s.child, a);
+        const u32 bit = (bits >> d.depth) & 1u;
+        const int32_t parent = d.leaf;
+        if (child >= 0) {                                        // descend (mcts.py:275-276)
+            d.leaf = (child & (TREE_CHILD_PAIR - 1)) + ((child & TREE_CHILD_PAIR) ? (int32_t)bit : 0);
+            d.h = *v.hdr(g, d.leaf);
+        } else if (!tree_expand_child(v, g, d.leaf, d.h, a, bit, used, lut, lane, d.overflow)) {
+            break;
+        }
+        if ((int32_t)lane == d.depth) { d.edge_node = parent; d.edge_action = (u32)a; }
+        ++d.depth;
+        if (child < 0) break;                                    // a fresh node has no priors: it is the leaf
+    }
+    return d;
 }
 
 __global__ __launch_bounds__(TREE_BLOCK) void tree_select_kernel(void *tree, int64_t games, int64_t capacity, u64 seed,
@@ -171,70 +263,25 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_select_kernel(void *tree, int
     if (g >= games) return;
     const TreeView v = tree_view(tree, games, capacity);
     TreeGame *gh = &v.games[g];
-    int32_t node = gh->root, used = gh->used;
+    int32_t used = gh->used;
     // the collapse choices of this rollout: bit d = the child at path depth d (qttt_hash's low word)
     const u64 key = launch_key(seed, QTTT_TREE_SELECT_BASE + rollout_idx);
     const u32 bits = lowbias32(fold_id(board_offset + (u64)g) ^ (u32)key);
-    u32 overflow = 0u;
-    int32_t depth = 0;
-    TreeNodeHdr h = *v.hdr(g, node);
-    while ((h.flags & TN_PRIORS) && !(h.flags & TN_TERMINAL) && h.legal != 0ull && depth < QTTT_TREE_MAX_DEPTH) {
-        const bool legal = lane < 36u && ((h.legal >> lane) & 1ull);
-        TreeSlot s;
-        s.W = 0.0; s.N = 0u; s.child = -1;
-        if (lane < 36u) s = v.slots(g, node)[lane];
-        double score = 0.0;
-        if (legal) score = tree_score(s.W, s.N, tree_prior(v, g, node, h, lane), tree_sqrt(h.Ntot), c_puct);
-        const int a = wave_argmax(legal, score, lane);
-        const int32_t child = __shfl(s.child, a);
-        const u32 bit = (bits >> depth) & 1u;
-        if (child >= 0) {                                        // descend (mcts.py:275-276)
-            if (lane == 0u) { gh->path_node[depth] = node; gh->path_action[depth] = (uint8_t)a; }
-            ++depth;
-            node = (child & (TREE_CHILD_PAIR - 1)) + ((child & TREE_CHILD_PAIR) ? (int32_t)bit : 0);
-            h = *v.hdr(g, node);
-            continue;
-        }
-        // _expand_child (mcts.py:210-221): both collapse children at once, as qttt_expand
-        // expand_pair(), spelled out: through the helper this kernel's instruction stream changes
-        u32 Q0 = (u32)h.Q, Q1 = (u32)(h.Q >> 32), P0a, P1a, P0b, P1b, xo0, xo1;
-        const u32 kids = step_core_both((u32)h.P, (u32)(h.P >> 32), Q0, Q1, pair_action<false>(a), lut, P0a, P1a, P0b, P1b, xo0, xo1);
-        if (kids == 0u || (int64_t)used + kids > capacity) {     // cannot happen for a legal action / does not fit
-            overflow = kids == 0u ? 0u : TG_OVERFLOW;
-            break;
-        }
-        const bool turn = !(h.flags & TN_TURN);
-        TreeNodeHdr c[2];
-        const u64 kidP[2] = {(u64)P0a | ((u64)P1a << 32), (u64)P0b | ((u64)P1b << 32)};
-        const u32 xo[2] = {xo0, xo1};
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            int w, t;
-            update_winner_from_step(kidP[k], xo[k], lut, w, t);
-            c[k] = tree_node(kidP[k], (u64)Q0 | ((u64)Q1 << 32), turn, w, t, legal_mask_of(classical_with_autofill(kidP[k])));
-        }
-        tree_write_node(v, g, used, c[0], lane, 0u);
-        if (kids == 2u) tree_write_node(v, g, used + 1, c[1], lane, 1u);
-        if (lane == 0u) {
-            v.slots(g, node)[a].child = used | (kids == 2u ? TREE_CHILD_PAIR : 0);
-            gh->path_node[depth] = node;
-            gh->path_action[depth] = (uint8_t)a;
-        }
-        ++depth;
-        const u32 pick = kids == 2u ? bit : 0u;
-        node = used + (int32_t)pick;
-        h = pick ? c[1] : c[0];
-        used += (int32_t)kids;
-        break;                                                   // a fresh node has no priors: it is the leaf
+    const TreeDescent d = tree_descend(v, g, gh->root, bits, used, lut, lane, c_puct,
+                                       [](double W, u32 N, double prior, u32 Ntot, double c) {
+                                           return tree_score(W, N, prior, tree_sqrt(Ntot), c);
+                                       });
+    if ((int32_t)lane < d.depth) {                               // entries at and past depth stay as they were
+        gh->path_node[lane] = d.edge_node;
+        gh->path_action[lane] = (uint8_t)d.edge_action;
     }
     if (lane == 0u) {
         gh->used = used;
-        gh->depth = depth;
-        gh->leaf = node;
-        gh->flags = (gh->flags & TG_OVERFLOW) | overflow | (h.flags & TN_TURN ? TG_LEAF_TURN : 0u) |
-                    (h.flags & TN_TERMINAL ? TG_LEAF_TERMINAL : 0u);
-        leafP[g] = h.P;
-        leafQ[g] = h.Q;
+        gh->depth = d.depth;
+        gh->leaf = d.leaf;
+        gh->flags = (gh->flags & TG_OVERFLOW) | (d.overflow ? TG_OVERFLOW : 0u) | tree_leaf_flags(d.h.flags);
+        leafP[g] = d.h.P;
+        leafQ[g] = d.h.Q;
     }
 }
 
@@ -266,11 +313,14 @@ __device__ __forceinline__ TreeEdge tree_edge_load(const TreeView &v, int64_t g,
     }
     return e;
 }
+// what edge `lane` of a path of `depth` edges gets of the leaf's value: r = -r per level, deepest first (mcts.py:179)
+__device__ __forceinline__ double tree_edge_value(int32_t depth, u32 lane, double val) {
+    return ((depth - (int32_t)lane) & 1) ? -val : val;
+}
 __device__ __forceinline__ void tree_edge_store(const TreeEdge &e, int32_t depth, u32 lane, double val) {
 #pragma clang fp contract(off)
     if (e.on) {
-        const double rv = ((depth - (int32_t)lane) & 1) ? -val : val;
-        e.slot->W = e.W + rv;
+        e.slot->W = e.W + tree_edge_value(depth, lane, val);
         e.slot->N = e.N + 1u;
         e.hdr->Ntot = e.Ntot + 1u;
     }
@@ -458,7 +508,7 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_compact_kernel(void *tree, in
     }
     if (lane == 0u) {                                            // as tree_reset_kernel's, for this root
         gh->used = count; gh->root = 0; gh->depth = 0; gh->leaf = 0;
-        gh->flags = (gflags & TG_OVERFLOW) | (rflags & TN_TURN ? TG_LEAF_TURN : 0u) | (rflags & TN_TERMINAL ? TG_LEAF_TERMINAL : 0u);
+        gh->flags = (gflags & TG_OVERFLOW) | tree_leaf_flags(rflags);
     }
 }
 

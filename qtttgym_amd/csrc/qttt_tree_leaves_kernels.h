@@ -6,13 +6,14 @@
 // line table for the expansions.  The K descents of a game are sequential by construction (descent j + 1 scores what
 // descent j left in flight); the parallelism is across games and in the games * K-row network launch.
 //
+// A descent is qttt_tree_kernels.h's tree_descend, the one tree_select_kernel makes, scored by tree_score_in_flight.
 // Unlike tree_select_kernel, a wave here re-reads what its own lanes wrote earlier in the launch: the in-flight bits of N
 // and Ntot (written by lane d for edge d, read by lane a for action a), a child word written by lane 0, a fresh child's
 // header and slots, Ntot of the root that all K paths share, and, in the backup, the leaf's priors flag.  Every such
 // store is separated from its loads by tree_wave_sync(), as in tree_compact_kernel: one at the top of every descent and
-// one after every backed-up record.  WITHIN a descent nothing written is read again: a fresh child is the leaf and its
-// header stays in registers, and the in-flight marks touch the N and Ntot words only, which the descent's expansion
-// (child word, fresh records) does not write.
+// one after every backed-up record.  WITHIN a descent nothing written is read again (tree_descend keeps the fresh child's
+// header and the path in registers), and the in-flight marks, made after it, touch the N and Ntot words only, which the
+// descent's expansion (child word, fresh records) does not write.
 //
 // In flight: bits 24-31 of a slot's N word and of a node's Ntot word count the round's descents through them; N and Ntot
 // proper stay below 2^24 (QTTT_TREE_MAX_ROLLOUTS), K <= 64 < 256, and W is never touched by select.  Every loop is
@@ -25,7 +26,6 @@
 namespace {
 
 constexpr u32 TREE_FLIGHT_SHIFT = 24u, TREE_FLIGHT_ONE = 1u << TREE_FLIGHT_SHIFT, TREE_COUNT_MASK = TREE_FLIGHT_ONE - 1u;
-constexpr u32 TP_OVERFLOW = 1u, TP_LEAF_TURN = 2u, TP_LEAF_TERMINAL = 4u;        // path-record flags: the TG_ bits
 
 struct TreePathRec {                   // 64 B, include/qttt_tree_leaves.h
     int32_t leaf;
@@ -36,7 +36,6 @@ struct TreePathRec {                   // 64 B, include/qttt_tree_leaves.h
 };
 static_assert(sizeof(TreePathRec) == QTTT_TREE_PATH_BYTES && offsetof(TreePathRec, action) == 8 &&
               offsetof(TreePathRec, node) == 24, "path record");
-static_assert(TP_OVERFLOW == TG_OVERFLOW && TP_LEAF_TURN == TG_LEAF_TURN && TP_LEAF_TERMINAL == TG_LEAF_TERMINAL, "flag bits");
 
 // a statistics word with its in-flight visits counted in: n + f
 __device__ __forceinline__ u32 tree_effective(u32 word) { return (word & TREE_COUNT_MASK) + (word >> TREE_FLIGHT_SHIFT); }
@@ -70,84 +69,35 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_select_batch_kernel(void *tre
     for (u32 j = 0; j < leaves; ++j) {
         tree_wave_sync();                                        // what the earlier descents stored
         const u32 bits = lowbias32(id ^ (u32)launch_key(seed, QTTT_TREE_SELECT_BASE + rollout_idx0 + j));
-        int32_t node = root, depth = 0;
-        int32_t my_node = 0;                                     // lane d: edge d of this descent's path
-        u32 my_action = 0u, over = 0u;
-        TreeNodeHdr h = *v.hdr(g, node);
-        while ((h.flags & TN_PRIORS) && !(h.flags & TN_TERMINAL) && h.legal != 0ull && depth < QTTT_TREE_MAX_DEPTH) {
-            const bool legal = lane < 36u && ((h.legal >> lane) & 1ull);
-            TreeSlot s;
-            s.W = 0.0; s.N = 0u; s.child = -1;
-            if (lane < 36u) s = v.slots(g, node)[lane];
-            double score = 0.0;
-            if (legal)
-                score = tree_score_in_flight(s.W, s.N, tree_prior(v, g, node, h, lane), tree_sqrt(tree_effective(h.Ntot)), c_puct, vloss);
-            // lane 0's winner for the whole wave: under NaN scores the lanes of wave_argmax disagree, and the marks, the
-            // record and the expansion of a descent must be one path (with ordinary scores every lane holds the same a)
-            const int a = __builtin_amdgcn_readfirstlane(wave_argmax(legal, score, lane));
-            const int32_t child = __shfl(s.child, a);
-            const u32 bit = (bits >> depth) & 1u;
-            if (child >= 0) {                                    // descend
-                if ((int32_t)lane == depth) { my_node = node; my_action = (u32)a; }
-                ++depth;
-                node = (child & (TREE_CHILD_PAIR - 1)) + ((child & TREE_CHILD_PAIR) ? (int32_t)bit : 0);
-                h = *v.hdr(g, node);
-                continue;
-            }
-            // the expansion of tree_select_kernel: both collapse children at once
-            u32 Q0 = (u32)h.Q, Q1 = (u32)(h.Q >> 32), P0a, P1a, P0b, P1b, xo0, xo1;
-            const u32 kids = step_core_both((u32)h.P, (u32)(h.P >> 32), Q0, Q1, pair_action<false>(a), lut, P0a, P1a, P0b, P1b, xo0, xo1);
-            if (kids == 0u || (int64_t)used + kids > capacity) { // cannot happen for a legal action / does not fit
-                over = kids == 0u ? 0u : TP_OVERFLOW;
-                break;
-            }
-            const bool turn = !(h.flags & TN_TURN);
-            TreeNodeHdr c[2];
-            const u64 kidP[2] = {(u64)P0a | ((u64)P1a << 32), (u64)P0b | ((u64)P1b << 32)};
-            const u32 xo[2] = {xo0, xo1};
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                int w, t;
-                update_winner_from_step(kidP[k], xo[k], lut, w, t);
-                c[k] = tree_node(kidP[k], (u64)Q0 | ((u64)Q1 << 32), turn, w, t, legal_mask_of(classical_with_autofill(kidP[k])));
-            }
-            tree_write_node(v, g, used, c[0], lane, 0u);
-            if (kids == 2u) tree_write_node(v, g, used + 1, c[1], lane, 1u);
-            if (lane == 0u) v.slots(g, node)[a].child = used | (kids == 2u ? TREE_CHILD_PAIR : 0);
-            if ((int32_t)lane == depth) { my_node = node; my_action = (u32)a; }
-            ++depth;
-            const u32 pick = kids == 2u ? bit : 0u;
-            node = used + (int32_t)pick;
-            h = pick ? c[1] : c[0];
-            used += (int32_t)kids;
-            break;                                               // a fresh node has no priors: it is the leaf
-        }
+        const TreeDescent d = tree_descend(v, g, root, bits, used, lut, lane, c_puct,
+                                           [vloss](double W, u32 N, double prior, u32 Ntot, double c) {
+                                               return tree_score_in_flight(W, N, prior, tree_sqrt(tree_effective(Ntot)), c, vloss);
+                                           });
+        const u32 over = d.overflow ? TG_OVERFLOW : 0u;
         overflow |= over;
         // one in-flight visit on every edge of the path: lane d owns edge d, and the edges lie in different nodes
         TreePathRec *rec = paths + (g * (int64_t)leaves + j);
-        if ((int32_t)lane < depth) {
-            TreeSlot *slot = &v.slots(g, my_node)[my_action];
-            TreeNodeHdr *nh = v.hdr(g, my_node);
+        if ((int32_t)lane < d.depth) {
+            TreeSlot *slot = &v.slots(g, d.edge_node)[d.edge_action];
+            TreeNodeHdr *nh = v.hdr(g, d.edge_node);
             slot->N = slot->N + TREE_FLIGHT_ONE;
             nh->Ntot = nh->Ntot + TREE_FLIGHT_ONE;
-            rec->node[lane] = my_node;
-            rec->action[lane] = (uint8_t)my_action;
+            rec->node[lane] = d.edge_node;
+            rec->action[lane] = (uint8_t)d.edge_action;
         }
         if (lane == 0u) {
-            rec->leaf = node;
-            rec->depth = (uint8_t)depth;
-            rec->flags = (uint8_t)(over | (h.flags & TN_TURN ? TP_LEAF_TURN : 0u) | (h.flags & TN_TERMINAL ? TP_LEAF_TERMINAL : 0u));
-            leafP[g * (int64_t)leaves + j] = h.P;
-            leafQ[g * (int64_t)leaves + j] = h.Q;
+            rec->leaf = d.leaf;
+            rec->depth = (uint8_t)d.depth;
+            rec->flags = (uint8_t)(over | tree_leaf_flags(d.h.flags));
+            leafP[g * (int64_t)leaves + j] = d.h.P;
+            leafQ[g * (int64_t)leaves + j] = d.h.Q;
         }
     }
     if (lane == 0u) {                                            // the recorded path as tree_compact_kernel leaves it
-        const u32 rflags = v.hdr(g, root)->flags;                // (select never writes a node's flags)
-        gh->used = used;
+        gh->used = used;                                         // (select never writes a node's flags)
         gh->depth = 0;
         gh->leaf = root;
-        gh->flags = (gh->flags & TG_OVERFLOW) | overflow | (rflags & TN_TURN ? TG_LEAF_TURN : 0u) |
-                    (rflags & TN_TERMINAL ? TG_LEAF_TERMINAL : 0u);
+        gh->flags = (gh->flags & TG_OVERFLOW) | overflow | tree_leaf_flags(v.hdr(g, root)->flags);
     }
 }
 
@@ -187,11 +137,10 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_backup_batch_kernel(void *tre
         if (p.depth > (u32)QTTT_TREE_MAX_DEPTH || p.leaf < 0 || (int64_t)p.leaf >= capacity || __ballot(bad_edge) != 0ull) continue;
         const u32 lf = v.hdr(g, p.leaf)->flags;
         const double val = (lf & TN_TERMINAL) ? tree_terminal_value(lf) : (double)p.value;
-        if (edge) {                                              // tree_edge_store's signs: the deepest edge gets -val
+        if (edge) {
             TreeSlot *slot = &v.slots(g, p.node)[p.action];
             TreeNodeHdr *nh = v.hdr(g, p.node);
-            const double rv = ((p.depth - lane) & 1u) ? -val : val;
-            slot->W = slot->W + rv;
+            slot->W = slot->W + tree_edge_value((int32_t)p.depth, lane, val);
             slot->N = slot->N + 1u - TREE_FLIGHT_ONE;
             nh->Ntot = nh->Ntot + 1u - TREE_FLIGHT_ONE;
         }

@@ -98,18 +98,8 @@ class SelfPlay(LibCaller):
     def __init__(self, num_games, n_rollouts=100, num_simulations=10, net=None, alpha=1.0, c_puct=1.0,
                  value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts",
                  root_noise=None, temperature=1.0, sample_plies=0, leaves=1, virtual_loss=1.0):
-        if leaf_eval not in TreeSearch.LEAF_EVALS:
-            raise ValueError("leaf_eval must be one of %s" % (TreeSearch.LEAF_EVALS,))
-        if leaf_eval == "value" and net is None:
-            raise ValueError('leaf_eval="value" needs a net')
+        self.leaves, self.virtual_loss = TreeSearch.check_search_args(leaf_eval, net, leaves, virtual_loss)
         self.leaf_eval = leaf_eval
-        self.leaves, self.virtual_loss = int(leaves), float(virtual_loss)
-        if not 1 <= self.leaves <= _native.TREE_MAX_LEAVES:
-            raise ValueError("leaves must be in 1..%d" % _native.TREE_MAX_LEAVES)
-        if self.leaves > 1 and leaf_eval != "value":
-            raise ValueError('leaves > 1 needs leaf_eval="value"')
-        if not 0.0 <= self.virtual_loss < float("inf"):
-            raise ValueError("virtual_loss must be finite and >= 0")
         self.num_games, self.n_rollouts = int(num_games), int(n_rollouts)
         self.num_simulations, self.net = int(num_simulations), net
         self.alpha, self.c_puct, self.seed, self.compact = float(alpha), float(c_puct), int(seed), bool(compact)

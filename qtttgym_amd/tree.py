@@ -43,18 +43,8 @@ class TreeSearch(LibCaller):
         leaves=K > 1 (needs leaf_eval="value"): contemplate() searches K leaves per game per round, each descent counted
         as a loss of `virtual_loss` by the ones after it until the round is backed up.  leaves=1 is the search as it
         always was."""
-        if leaf_eval not in self.LEAF_EVALS:
-            raise ValueError("leaf_eval must be one of %s" % (self.LEAF_EVALS,))
-        if leaf_eval == "value" and net is None:
-            raise ValueError('leaf_eval="value" needs a net')
+        self.leaves, self.virtual_loss = self.check_search_args(leaf_eval, net, leaves, virtual_loss)
         self.leaf_eval = leaf_eval
-        self.leaves, self.virtual_loss = int(leaves), float(virtual_loss)
-        if not 1 <= self.leaves <= _native.TREE_MAX_LEAVES:
-            raise ValueError("leaves must be in 1..%d" % _native.TREE_MAX_LEAVES)
-        if self.leaves > 1 and leaf_eval != "value":
-            raise ValueError('leaves > 1 needs leaf_eval="value"')
-        if not 0.0 <= self.virtual_loss < float("inf"):
-            raise ValueError("virtual_loss must be finite and >= 0")
         self.num_games, self.capacity = int(num_games), int(capacity)
         self.num_simulations, self.c_puct = int(num_simulations), float(c_puct)
         self.net, self.seed, self.board_offset = net, int(seed), int(board_offset)
@@ -92,6 +82,27 @@ class TreeSearch(LibCaller):
         self._fresh = True            # no contemplate since the last reset() or sync(): the root may lack priors
 
     # ------------------------------------------------------------------ helpers
+    @staticmethod
+    def check_search_args(leaf_eval, net, leaves, virtual_loss):
+        """What the constructors of TreeSearch and SelfPlay check of the search's form, before anything is opened;
+        returns (leaves, virtual_loss) as int and float."""
+        if leaf_eval not in TreeSearch.LEAF_EVALS:
+            raise ValueError("leaf_eval must be one of %s" % (TreeSearch.LEAF_EVALS,))
+        if leaf_eval == "value" and net is None:
+            raise ValueError('leaf_eval="value" needs a net')
+        leaves, virtual_loss = int(leaves), float(virtual_loss)
+        if not 1 <= leaves <= _native.TREE_MAX_LEAVES:
+            raise ValueError("leaves must be in 1..%d" % _native.TREE_MAX_LEAVES)
+        if leaves > 1 and leaf_eval != "value":
+            raise ValueError('leaves > 1 needs leaf_eval="value"')
+        if not 0.0 <= virtual_loss < float("inf"):
+            raise ValueError("virtual_loss must be finite and >= 0")
+        return leaves, virtual_loss
+
+    def _need_reset(self):
+        if self._bound is None:
+            raise RuntimeError("reset() first")
+
     def _check_env(self, env):
         if env.num_envs != self.num_games or env.state.device != self.device:
             raise ValueError("env must hold %d boards on %s" % (self.num_games, self.device))
@@ -119,8 +130,7 @@ class TreeSearch(LibCaller):
         r = int(rollouts)
         if r < 0:
             raise ValueError("rollouts must be >= 0")
-        if self._bound is None:
-            raise RuntimeError("reset() first")
+        self._need_reset()
         if self.rollout_idx + r > self.max_rollouts:
             raise ValueError("%d rollouts since reset would pass the bound of %d (draw indices)"
                              % (self.rollout_idx + r, self.max_rollouts))
@@ -204,8 +214,7 @@ class TreeSearch(LibCaller):
             raise ValueError("epsilon must be in [0, 1]")
         if not 0.0 < alpha < float("inf"):
             raise ValueError("alpha must be positive and finite")
-        if self._bound is None:
-            raise RuntimeError("reset() first")
+        self._need_reset()
         if self.noise_idx >= _native.TREE_MAX_NOISE:
             raise ValueError("%d noise calls since reset: the bound is %d (draw indices)"
                              % (self.noise_idx, _native.TREE_MAX_NOISE))
@@ -227,8 +236,7 @@ class TreeSearch(LibCaller):
         return o
 
     def _root(self, N=None, W=None, Q=None, P=None, Ntot=None, choose=None, nodes_used=None, overflow=None):
-        if self._bound is None:
-            raise RuntimeError("reset() first")
+        self._need_reset()
         self._call("qttt_tree_root", self.tree.data_ptr(), self.num_games, self.capacity, _ptr(N), _ptr(W), _ptr(Q),
                    _ptr(P), _ptr(Ntot), _ptr(choose), _ptr(nodes_used), _ptr(overflow))
 
@@ -248,8 +256,7 @@ class TreeSearch(LibCaller):
         (keeping its statistics), or onto a fresh root when that child was never expanded; a game whose position did
         not change keeps its root."""
         self._check_env(env)
-        if self._bound is None:
-            raise RuntimeError("reset() first")
+        self._need_reset()
         if self._bound + 1 > self.capacity:
             raise ValueError("a sync could use %d nodes, more than capacity %d" % (self._bound + 1, self.capacity))
         self._call("qttt_tree_sync", self.tree.data_ptr(), self.num_games, self.capacity, env.state.data_ptr())
@@ -263,8 +270,7 @@ class TreeSearch(LibCaller):
         back and makes its maximum the host's bound, which is what lets contemplate() accept the next move's rollouts
         in a small `capacity`: one host read-back (a device synchronisation) per call, so call it once per move,
         never per rollout.  update_bound=False reads nothing back; the old bound stays, still valid."""
-        if self._bound is None:
-            raise RuntimeError("reset() first")
+        self._need_reset()
         if self._scratch is None:
             nbytes = int(self._lib.qttt_tree_compact_bytes(self.num_games, self.capacity))
             if nbytes < 0:

@@ -19,7 +19,7 @@ import numpy as np
 
 import oracle
 import value_tree_model
-from tree_model import SELECT_BASE, Node, _one
+from tree_model import SELECT_BASE
 from value_tree_model import OVERFLOW_CAPACITY, POOL_SEED, ValueTreeModel, terminal_value  # noqa: F401
 
 MAX_LEAVES = 64
@@ -105,31 +105,19 @@ class LeafParallelModel(ValueTreeModel):
         for g, st in enumerate(games):
             nodes = st["nodes"]
             fN, fNtot = st["fN"], st["fNtot"] = Counter(), Counter()
+
+            def score(node, i):
+                key = lambda x: self._score_in_flight(node, x, fN[i, x], fNtot[i], vloss)
+                if fNtot[i]:
+                    plain = max(node.legal, key=lambda x: self._score(node, x))
+                    self.met["diverted"] += plain != max(node.legal, key=key)
+                return key
+
             recs = []
             overflowed_before = False
             for j in range(K):
                 bits = oracle.hash64(self.seed, self.board_offset + g, SELECT_BASE + self.k + j) & 0xFFFFFFFF
-                i = st["root"]
-                path, over, expanded = [], False, None
-                while nodes[i].P is not None and not nodes[i].terminal and nodes[i].legal and len(path) < 10:
-                    node = nodes[i]
-                    a = max(node.legal, key=lambda x: self._score_in_flight(node, x, fN[i, x], fNtot[i], vloss))
-                    if fNtot[i]:
-                        plain = max(node.legal, key=lambda x: self._score(node, x))
-                        self.met["diverted"] += plain != a
-                    if node.children[a] is None:
-                        nch, kids, _, _, _, _ = oracle.expand(_one(node.rec), np.array([a], dtype=np.uint8))
-                        if self.capacity is not None and len(nodes) + int(nch[0]) > self.capacity:
-                            st["overflow"] = over = True
-                            break
-                        node.children[a] = []
-                        for c in range(int(nch[0])):
-                            nodes.append(Node(kids[c].b[0].copy(), not node.turn))
-                            node.children[a].append(len(nodes) - 1)
-                        expanded = node.children[a]
-                    kids = node.children[a]
-                    path.append((i, a))
-                    i = kids[(bits >> (len(path) - 1)) & 1] if len(kids) == 2 else kids[0]
+                path, i, over, expanded = self._descend(st, bits, score)
                 for n, a in path:
                     fN[n, a] += 1
                     fNtot[n] += 1
@@ -172,12 +160,8 @@ class LeafParallelModel(ValueTreeModel):
                     r = float(np.float32(values[row]))
                     if rec["flags"] & REC_OVERFLOW:
                         self.ends["overflowed"] += 1
-                for i, a in reversed(rec["path"]):
-                    r = -r
-                    node = nodes[i]
-                    node.W[a] += r
-                    node.N[a] += 1
-                    node.Ntot += 1
+                self._back_up(st, rec["path"], r)
+                for i, a in rec["path"]:
                     st["fN"][i, a] -= 1
                     st["fNtot"][i] -= 1
                 if not leaf.terminal and leaf.P is None:

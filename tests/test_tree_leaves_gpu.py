@@ -2,7 +2,8 @@
 bit for bit against tests/leaf_parallel_model.py under the exact networks, in both precisions, at G = 1, 3 and 65 and
 K = 1, 2, 5 and 8, through a move, a sync and a compaction, and in a pool small enough to overflow; rounds in lockstep
 with the model under general weights (the path records, the leaf rows, the in-flight bits in the middle of a round and
-their absence after it); rounds of one against today's rollout, byte for byte; a NaN weight; the argument errors;
+their absence after it); rounds of one against today's rollout, byte for byte; the path that qttt_tree_select leaves
+in the game header against the record of a round of one; a NaN weight; the argument errors;
 SelfPlay; the defaults.
 
 The model's trees are computed once per (network, K, pool capacity) for the 65-game pool and shared: games are
@@ -232,6 +233,52 @@ def test_rounds_of_one_leave_the_bytes_that_rollouts_leave(dtype):
     live = np.arange(a.capacity)[None, :] < ga["used"][:, None]
     assert np.array_equal(na[live].view(np.uint8), nb[live].view(np.uint8))
     assert np.array_equal(pa[live].view(np.uint8), pb[live].view(np.uint8))
+
+
+# ---------------------------------------------------------------- the header's path is the record's path
+PATH_SEED, PATH_POOL_FIRST = 6, 3      # roots 5, 6 and 8 plies deep first; under this seed the model's 13th select goes three
+#                                        edges deep in games 0 and 1 and expands a pair in game 0 (tests/value_tree_model.py)
+
+
+@pytest.mark.parametrize("G", [1, 3, 65])
+def test_select_leaves_the_path_in_the_header_that_a_round_of_one_records(G):
+    """qttt_tree_select and qttt_tree_select_batch(leaves = 1) on two copies of one tree, 12 value rollouts in: the game
+    header's depth, leaf and path entries below depth are the record's, the entries at and past depth keep the bytes they
+    had, the leaf states are equal and so are the pools over the used records."""
+    net, cap = _device_net("sharp", "f32"), 64
+    pool = LP.root_pool(PATH_POOL_FIRST + G)
+    env = env_from_arrays({k: np.asarray(v)[PATH_POOL_FIRST:] for k, v in pool.items()})
+    t = TreeSearch(G, capacity=cap, net=net, seed=PATH_SEED, board_offset=OFFSET, device=DEV, leaf_eval="value")
+    t.tree = torch.full((tree_layout.tree_bytes(G, cap) + TAIL,), SENTINEL, dtype=torch.uint8, device=DEV)
+    t.reset(env)
+    t.contemplate(12)
+    before, other = t.tree.clone(), t.tree.clone()
+    b = t._round_buffers(1)
+    t._call("qttt_tree_select", t.tree.data_ptr(), G, cap, t.seed, t.rollout_idx, t.board_offset, t.c_puct,
+            t.leaf.state.data_ptr())
+    t._call("qttt_tree_select_batch", other.data_ptr(), G, cap, t.seed, t.rollout_idx, 1, t.board_offset, t.c_puct,
+            t.virtual_loss, b["paths"].data_ptr(), b["leaf"].state.data_ptr())
+    g0, _, _, _ = tree_layout.decode(before.cpu().numpy(), G, cap)
+    ga, na, pa, tail_a = tree_layout.decode(t.tree.cpu().numpy(), G, cap)
+    gb, nb, pb, tail_b = tree_layout.decode(other.cpu().numpy(), G, cap)
+    rec = b["paths"].cpu().numpy()[:G * LP.PATH_BYTES].view(LP.PATH_DTYPE)
+    assert np.array_equal(ga["depth"], rec["depth"]) and np.array_equal(ga["leaf"], rec["leaf"])
+    on = np.arange(10)[None, :] < ga["depth"][:, None]
+    assert np.array_equal(ga["path_node"][on], rec["node"][on]) and np.array_equal(ga["path_action"][on], rec["action"][on])
+    assert np.array_equal(ga["path_node"][~on], g0["path_node"][~on])
+    assert np.array_equal(ga["path_action"][~on], g0["path_action"][~on])
+    assert torch.equal(t.leaf.state, b["leaf"].state)
+    assert np.array_equal(ga["used"], gb["used"]) and np.array_equal(ga["flags"] & 1, gb["flags"] & 1)
+    live = np.arange(cap)[None, :] < ga["used"][:, None]
+    marked = na.copy()                           # the round's copy holds one visit in flight on every edge of its path
+    for g in range(G):
+        for d in range(int(rec["depth"][g])):
+            marked["slots"]["N"][g, rec["node"][g, d], rec["action"][g, d]] += 1 << LP.FLIGHT_SHIFT
+            marked["Ntot"][g, rec["node"][g, d]] += 1 << LP.FLIGHT_SHIFT
+    assert np.array_equal(marked[live].view(np.uint8), nb[live].view(np.uint8))
+    assert np.array_equal(pa[live].view(np.uint8), pb[live].view(np.uint8))
+    assert (tail_a == SENTINEL).all() and (tail_b == SENTINEL).all()
+    assert ga["depth"].max() >= 3 and (ga["used"] > g0["used"]).any()          # the floor: a deep path, an expansion
 
 
 # ---------------------------------------------------------------- a NaN weight

@@ -81,32 +81,39 @@ class TreeModel:
         Q = node.W[a] / node.N[a] if node.N[a] else 0.0
         return Q + self.c_puct * U
 
-    # ---- _select with _expand_child; returns the leaves as OracleBoards
+    # ---- _select with _expand_child: the one descent, of select() and of leaf_parallel_model's select_batch()
+    def _descend(self, st, bits, score):
+        """One path of game `st` from its root under the collapse choices `bits`; score(node, i) = the key that ranks the
+        legal actions of node i.  Returns (path, leaf, overflowed, expanded): the edges [(node, action)], the leaf's
+        index, whether an expansion did not fit, and the children this descent expanded (None: none)."""
+        nodes = st["nodes"]
+        i = st["root"]
+        path, overflowed, expanded = [], False, None
+        while nodes[i].P is not None and not nodes[i].terminal and nodes[i].legal and len(path) < 10:
+            node = nodes[i]
+            a = max(node.legal, key=score(node, i))                          # first maximum, as Python's max
+            if node.children[a] is None:
+                nch, kids, _, _, _, _ = oracle.expand(_one(node.rec), np.array([a], dtype=np.uint8))
+                if self.capacity is not None and len(nodes) + int(nch[0]) > self.capacity:
+                    st["overflow"] = overflowed = True     # does not fit: the descent ends here, this edge is not on the path
+                    break
+                node.children[a] = []
+                for c in range(int(nch[0])):
+                    nodes.append(Node(kids[c].b[0].copy(), not node.turn))
+                    node.children[a].append(len(nodes) - 1)
+                expanded = node.children[a]
+            kids = node.children[a]
+            path.append((i, a))
+            i = kids[(bits >> (len(path) - 1)) & 1] if len(kids) == 2 else kids[0]
+        return path, i, overflowed, expanded
+
     def select(self):
-        bits_of = lambda g: oracle.hash64(self.seed, self.board_offset + g, SELECT_BASE + self.k) & 0xFFFFFFFF
+        """Returns the leaves as OracleBoards."""
         leaves = []
         for g, st in enumerate(self.games):
-            nodes = st["nodes"]
-            i = st["root"]
-            path = []
-            bits = bits_of(g)
-            while nodes[i].P is not None and not nodes[i].terminal and nodes[i].legal:
-                node = nodes[i]
-                a = max(node.legal, key=lambda x: self._score(node, x))      # first maximum, as Python's max
-                if node.children[a] is None:
-                    nch, kids, _, _, _, _ = oracle.expand(_one(node.rec), np.array([a], dtype=np.uint8))
-                    if self.capacity is not None and len(nodes) + int(nch[0]) > self.capacity:
-                        st["overflow"] = True      # does not fit: the select ends here, this edge is not on the path
-                        break
-                    node.children[a] = []
-                    for c in range(int(nch[0])):
-                        nodes.append(Node(kids[c].b[0].copy(), not node.turn))
-                        node.children[a].append(len(nodes) - 1)
-                kids = node.children[a]
-                path.append((i, a))
-                i = kids[(bits >> (len(path) - 1)) & 1] if len(kids) == 2 else kids[0]
-            st["path"], st["leaf"] = path, i
-            leaves.append(nodes[i].rec)
+            bits = oracle.hash64(self.seed, self.board_offset + g, SELECT_BASE + self.k) & 0xFFFFFFFF
+            st["path"], st["leaf"], _, _ = self._descend(st, bits, lambda node, i: lambda x: self._score(node, x))
+            leaves.append(st["nodes"][st["leaf"]].rec)
         return oracle.OracleBoards.from_records(leaves)
 
     def playouts(self, leaves):
@@ -122,6 +129,16 @@ class TreeModel:
             out[:, s] = oracle.rollout(leaves, self.seed, self.k * S * SIM_STRIDE + s * SIM_STRIDE, self.board_offset)[0]
         return out
 
+    # ---- _backpropogate: r = the leaf's value as the player to move there sees it
+    @staticmethod
+    def _back_up(st, path, r):
+        for i, a in reversed(path):
+            r = -r
+            node = st["nodes"][i]
+            node.W[a] += r
+            node.N[a] += 1
+            node.Ntot += 1
+
     # ---- _backpropogate and the leaf's priors
     def backup(self, result, probs=None):
         S = self.n_sims
@@ -132,13 +149,7 @@ class TreeModel:
             for s in range(S):
                 r = int(result[g][s])
                 r_tot += r if leaf.turn else -r
-            r = r_tot / S
-            for i, a in reversed(st["path"]):
-                r = -r
-                node = nodes[i]
-                node.W[a] += r
-                node.N[a] += 1
-                node.Ntot += 1
+            self._back_up(st, st["path"], r_tot / S)
             if not leaf.terminal and leaf.P is None:
                 if probs is None:
                     leaf.P = {a: 1 / len(leaf.legal) for a in leaf.legal}

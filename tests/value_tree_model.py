@@ -58,12 +58,7 @@ class ValueTreeModel(TreeModel):
                 r = float(np.float32(values[g]))
                 if leaf.P is not None:
                     self.ends["overflowed"] += 1
-            for i, a in reversed(st["path"]):
-                r = -r
-                node = nodes[i]
-                node.W[a] += r
-                node.N[a] += 1
-                node.Ntot += 1
+            self._back_up(st, st["path"], r)
             if not leaf.terminal and leaf.P is None:
                 self.ends["fresh"] += 1
                 leaf.P = {a: float(np.float32(probs[g][a])) for a in leaf.legal}
