@@ -8,6 +8,7 @@ the new weights for the search and repeats.
                                       [--dtype f32|bf16] [--out model.pt] [--model model.pt] [--value-targets 1,0]
                                       [--symmetries] [--leaf-eval playouts|value]
                                       [--root-noise EPS,ALPHA] [--temperature T] [--sample-plies K] [--leaves K]
+                                      [--eval-symmetries all|0,4]
 
 The network is nn.Model's (nn.py:7-28) under its own parameter names (qtttgym_amd.policy_value.SHAPES), so --out is a
 state dict that the reference, PolicyValueNet and examples/tree_tournament.py --model all load.  The loss is the
@@ -23,7 +24,9 @@ run trains is then what the next run searches with; use --value-targets 1,-1 wit
 draws the move of the first K plies from the visit counts (N ** (1 / --temperature)) instead of playing the best one:
 AlphaZero's root exploration (SelfPlay(root_noise=, temperature=, sample_plies=)), without which the games of a run under
 --leaf-eval value all open alike.  --leaves K (with --leaf-eval value) searches K leaves per game per round, kept apart
-by virtual loss (SelfPlay(leaves=K)): one network launch per round evaluates games * K leaves.
+by virtual loss (SelfPlay(leaves=K)): one network launch per round evaluates games * K leaves.  --eval-symmetries all
+(or a list of 1, 2, 4 or 8 symmetries such as 0,4; with --leaf-eval value) searches with the network's outputs averaged
+over every leaf's images (SelfPlay(eval_symmetries=...)): a search that treats mirrored positions alike.
 """
 import argparse
 import os
@@ -66,6 +69,11 @@ def loss_terms(net, s, pi, mask, v_target, done):
     return 0.5 * (v - v_target).pow(2), J.sum(-1)
 
 
+def parse_eval_symmetries(spec):
+    """--eval-symmetries: None, "all", or the comma-separated list as ints."""
+    return spec if spec in (None, "all") else tuple(int(k) for k in spec.split(","))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--games", type=int, default=1024, help="games per run (the reference's M = 50)")
@@ -82,6 +90,8 @@ def main():
                     help="what scores a leaf of the search: --sims playouts, or the network's value head")
     ap.add_argument("--leaves", type=int, default=1,
                     help="leaves per game per round of the search (SelfPlay(leaves=K): virtual loss; needs --leaf-eval value)")
+    ap.add_argument("--eval-symmetries", default=None, metavar="all|K,K,...",
+                    help="average the search's network over these symmetries of every leaf (needs --leaf-eval value)")
     ap.add_argument("--root-noise", default=None, metavar="EPS,ALPHA",
                     help="Dirichlet(ALPHA) noise with weight EPS on the roots' priors before every searched move")
     ap.add_argument("--temperature", type=float, default=1.0, help="the sampled moves follow N ** (1 / temperature)")
@@ -99,7 +109,8 @@ def main():
     sp = SelfPlay(args.games, n_rollouts=args.rollouts, num_simulations=args.sims, net=net, value_targets=targets,
                   seed=args.seed, leaf_eval=args.leaf_eval, leaves=args.leaves,
                   root_noise=None if args.root_noise is None else tuple(float(x) for x in args.root_noise.split(",")),
-                  temperature=args.temperature, sample_plies=args.sample_plies)
+                  temperature=args.temperature, sample_plies=args.sample_plies,
+                  eval_symmetries=parse_eval_symmetries(args.eval_symmetries))
     for run in range(args.runs):
         batch = sp.play()
         s, pi, mask, v_target, done = (batch.augment() if args.symmetries else batch).flat()

@@ -7,12 +7,14 @@ syncs after every move (strat_eval.play_game).  Finished games are frozen: their
     python examples/tree_tournament.py --p1 az:300 --p2 mcts:3000 [--games 1024] [--sims 10] [--dtype f32|bf16]
                                        [--weights tests/golden/model_eval.npz | --model model.pt]
                                        [--compact [--carry N]] [--leaves K [--p2-leaves K2]]
+                                       [--eval-symmetries all|0,4]
 
 A player is mcts:R (uniform playouts and priors, MCTS(R)), az:R (the network's playouts and priors, AlphaZero(R)),
 azv:R (the network's value head at the leaf and its priors, TreeSearch(leaf_eval="value"): no playouts) or random (the
 uniform-legal policy).  --leaves K gives the azv players K leaves per game per round (TreeSearch(leaves=K), virtual
 loss; --p2-leaves K2 when player 2's differs: azv:304 --leaves 8 --p2-leaves 1 plays the leaf-parallel search against
-the plain one).  Prints player 1's win, loss and draw counts and rates.
+the plain one).  --eval-symmetries all (or a list of 1, 2, 4 or 8 symmetries such as 0,4) gives the azv players the
+network's outputs averaged over every leaf's images (TreeSearch(eval_symmetries=...)).  Prints player 1's win, loss and draw counts and rates.
 
 --compact: every tree gives the nodes outside its new root's subtree back after each sync (TreeSearch.compact, the
 reference's _prune), so its pool holds 2 * R + carry nodes instead of every node of the game.
@@ -48,8 +50,9 @@ def load_state_dict(args):
         return {k: torch.from_numpy(d[k.replace(".", "_")]) for k in SHAPES}
 
 
-def play(players, G, sims, net, seed, carry=None, leaves=(1, 1)):
-    """One half: players[0] moves first; leaves[i] = the leaves per round of players[i] when it is an azv player.  Returns winner i8[G] (1 = the first mover, 0 = the second, -1 = none).
+def play(players, G, sims, net, seed, carry=None, leaves=(1, 1), eval_symmetries=None):
+    """One half: players[0] moves first; leaves[i] = the leaves per round of players[i] when it is an azv player, and
+    eval_symmetries what the azv players average the network over.  Returns winner i8[G] (1 = the first mover, 0 = the second, -1 = none).
     carry: None = the trees never compact; else they compact after every sync and hold 2 * R + carry nodes (carry < 0:
     2 * R + 2 of them)."""
     env = VecEnv(G, seed=seed)
@@ -62,7 +65,8 @@ def play(players, G, sims, net, seed, carry=None, leaves=(1, 1)):
         capacity = 1 + 2 * R * own_moves + 9 if carry is None else 2 * R + (carry if carry >= 0 else 2 * R + 2)
         t = TreeSearch(G, capacity=capacity, num_simulations=sims, net=net if kind in ("az", "azv") else None,
                        seed=seed * 2 + 1 + i, device=env.device, leaf_eval="value" if kind == "azv" else "playouts",
-                       leaves=leaves[i] if kind == "azv" else 1)
+                       leaves=leaves[i] if kind == "azv" else 1,
+                       eval_symmetries=eval_symmetries if kind == "azv" else None)
         t.reset(env)
         trees.append(t)
     finished = torch.zeros(G, dtype=torch.bool, device=env.device)
@@ -107,7 +111,11 @@ def main():
     ap.add_argument("--leaves", type=int, default=1,
                     help="leaves per game per round of the azv players (TreeSearch(leaves=K): virtual loss)")
     ap.add_argument("--p2-leaves", type=int, default=None, help="player 2's, when it differs (default: --leaves)")
+    ap.add_argument("--eval-symmetries", default=None, metavar="all|K,K,...",
+                    help="the azv players average the network over these symmetries of every leaf")
     args = ap.parse_args()
+    syms = args.eval_symmetries
+    syms = syms if syms in (None, "all") else tuple(int(k) for k in syms.split(","))
     p1, p2 = parse_player(args.p1), parse_player(args.p2)
     k1, k2 = args.leaves, args.leaves if args.p2_leaves is None else args.p2_leaves
     half = args.games // 2
@@ -124,8 +132,8 @@ def main():
         if args.carry is not None and args.carry < 0:
             raise SystemExit("--carry must be >= 0")
         carry = args.carry if args.carry is not None else -1
-    w_a = play((p1, p2), half, args.sims, net, args.seed, carry, (k1, k2))           # player 1 moves first
-    w_b = play((p2, p1), half, args.sims, net, args.seed + 1, carry, (k2, k1))       # player 2 moves first
+    w_a = play((p1, p2), half, args.sims, net, args.seed, carry, (k1, k2), syms)       # player 1 moves first
+    w_b = play((p2, p1), half, args.sims, net, args.seed + 1, carry, (k2, k1), syms)   # player 2 moves first
     wins = int((w_a == 1).sum()) + int((w_b == 0).sum())
     losses = int((w_a == 0).sum()) + int((w_b == 1).sum())
     draws = int((w_a == -1).sum()) + int((w_b == -1).sum())

@@ -136,6 +136,12 @@ TREE_EXPLORE_SIGNATURES = {
     "qttt_selfplay_record_sampled": (_i32, SELFPLAY_SIGNATURES["qttt_selfplay_record"][1][:-1]
                                      + [_u64, _i64, _f64, _i32, _vp]),
 }
+# every symbol include/qttt_nn_symmetric.h declares (the network averaged over a position's symmetries; qttt.h
+# includes it)
+NN_SYMMETRIC_SIZES = (1, 2, 4, 8)
+NN_SYMMETRIC_SIGNATURES = {
+    "qttt_evaluate_symmetric": (_i32, [_vp, _vp, _i32, _u8p, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+}
 
 _lib = None
 
@@ -201,7 +207,8 @@ def lib():
                                   + list(POLICY_ROLLOUT_SIGNATURES.items()) + list(TREE_SIGNATURES.items())
                                   + list(TREE_COMPACT_SIGNATURES.items()) + list(SELFPLAY_SIGNATURES.items())
                                   + list(SYMMETRY_SIGNATURES.items()) + list(TREE_VALUE_SIGNATURES.items())
-                                  + list(TREE_EXPLORE_SIGNATURES.items()) + list(TREE_LEAVES_SIGNATURES.items())):
+                                  + list(TREE_EXPLORE_SIGNATURES.items()) + list(TREE_LEAVES_SIGNATURES.items())
+                                  + list(NN_SYMMETRIC_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

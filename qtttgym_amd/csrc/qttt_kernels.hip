@@ -51,6 +51,7 @@
 // qttt_nn_kernels.h (the policy/value network) -> qttt_policy_rollout_kernels.h (network-guided playouts);
 // qttt_tree_kernels.h (the batched search trees) -> qttt_selfplay_kernels.h (the self-play record) ->
 // qttt_symmetry_kernels.h (the board's symmetries: images of states, the augmented self-play batch);
+// qttt_nn_symmetric_kernels.h (the network averaged over a position's symmetries, on qttt_nn_kernels.h's trunk and head);
 // qttt_tree_value_kernels.h (the value rollout: network evaluation of the leaves and backup in one launch);
 // qttt_tree_leaves_kernels.h (leaf-parallel rounds: K descents per game under virtual loss, and their backup);
 // qttt_tree_explore_kernels.h (root exploration: Dirichlet noise on the roots' priors, the sampled move).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
@@ -67,6 +68,7 @@
 #include "qttt_tree_explore_kernels.h"
 #include "qttt_selfplay_kernels.h"
 #include "qttt_symmetry_kernels.h"
+#include "qttt_nn_symmetric_kernels.h"
 #include "qttt_tree_value_kernels.h"
 #include "qttt_tree_leaves_kernels.h"
 #include "qttt_launch.h"
@@ -791,6 +793,29 @@ int qttt_selfplay_augment(int64_t games, const uint8_t *symmetries, int n_sym, c
                              winner_out, actions_out};
     return launch(selfplay_augment_kernel, ceil_div(games * n_sym, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, games, (u32)n_sym,
                   syms, in, out);
+}
+
+// ---------------------------------------------------------------- the network over symmetries (include/qttt_nn_symmetric.h)
+int qttt_evaluate_symmetric(const void *state, const void *weights, int precision, const uint8_t *symmetries, int n_sym,
+                            const uint8_t *sym, float *value, float *logits, float *probs, int64_t n, void *stream) {
+    if (n < 0 || n > INT64_MAX / QTTT_SYMMETRIES || (precision != QTTT_NN_F32 && precision != QTTT_NN_BF16) ||
+        !(n_sym == 1 || n_sym == 2 || n_sym == 4 || n_sym == 8) || (sym && n_sym != 1))
+        return QTTT_ERR_SIZE;
+    u32 syms = 0, ls = 0;
+    for (int s = 0; s < n_sym && !sym && symmetries; ++s) {
+        if (symmetries[s] >= QTTT_SYMMETRIES) return QTTT_ERR_SIZE;
+        syms |= (u32)symmetries[s] << (4 * s);
+    }
+    while ((1 << ls) < n_sym) ++ls;
+    if (n == 0) return 0;
+    if (any_null(state, weights) || (!sym && !symmetries) || (!value && !logits && !probs)) return QTTT_ERR_NULL;
+    if (misaligned(weights, 16) || misaligned(value, 4) || misaligned(logits, 4) || misaligned(probs, 4))
+        return QTTT_ERR_ACTION;                                  // 16-byte fragment loads / f32 stores
+    const Planes p = planes(const_cast<void *>(state), n);
+    return with_int<QTTT_NN_F32, QTTT_NN_BF16>(precision, [&](auto P) {
+        return launch(evaluate_symmetric_kernel<P>, ceil_div(n, NNCfg<P>::M >> ls), QTTT_NN_BLOCK, stream, p.P, p.Q, weights,
+                      sym, syms, ls, value, logits, probs, n);
+    });
 }
 
 // ---------------------------------------------------------------- the value rollout (include/qttt_tree_value.h)

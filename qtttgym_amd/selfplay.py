@@ -89,6 +89,7 @@ class SelfPlay(LibCaller):
     for the device.
     leaf_eval is TreeSearch's: "playouts" (the reference's rollout) or "value" (the leaf scored by net's value head).
     leaves and virtual_loss are TreeSearch's too: leaves=K > 1 searches K leaves per game per round (value leaves only).
+    eval_symmetries is TreeSearch's as well: the leaves' values and priors averaged over their images (value leaves only).
     root_noise=(epsilon, alpha): every searched ply runs one rollout (so that every live root has priors), then
     TreeSearch.add_root_noise(epsilon, alpha), then the other n_rollouts - 1.  sample_plies=k > 0: the move of plies
     0..k-1 is drawn with probability proportional to N ** (1 / temperature) (qttt_selfplay_record_sampled, with the
@@ -97,8 +98,10 @@ class SelfPlay(LibCaller):
 
     def __init__(self, num_games, n_rollouts=100, num_simulations=10, net=None, alpha=1.0, c_puct=1.0,
                  value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts",
-                 root_noise=None, temperature=1.0, sample_plies=0, leaves=1, virtual_loss=1.0):
+                 root_noise=None, temperature=1.0, sample_plies=0, leaves=1, virtual_loss=1.0,
+                 eval_symmetries=None):
         self.leaves, self.virtual_loss = TreeSearch.check_search_args(leaf_eval, net, leaves, virtual_loss)
+        self.eval_symmetries = TreeSearch.check_eval_symmetries(leaf_eval, eval_symmetries)
         self.leaf_eval = leaf_eval
         self.num_games, self.n_rollouts = int(num_games), int(n_rollouts)
         self.num_simulations, self.net = int(num_simulations), net
@@ -177,7 +180,8 @@ class SelfPlay(LibCaller):
         env = self.env = VecEnv(G, device=self.device, seed=s)
         tree = self.tree = TreeSearch(G, capacity=self.capacity, num_simulations=self.num_simulations,
                                       c_puct=self.c_puct, net=self.net, seed=2 * s + 1, device=self.device,
-                                      leaf_eval=self.leaf_eval, leaves=self.leaves, virtual_loss=self.virtual_loss)
+                                      leaf_eval=self.leaf_eval, leaves=self.leaves, virtual_loss=self.virtual_loss,
+                                      eval_symmetries=self.eval_symmetries)
         tree.reset(env)
         batch = self.new_batch()
         for ply in range(ROWS):

@@ -56,6 +56,15 @@ def check_symmetries(symmetries):
     return sym
 
 
+def check_eval_symmetries(symmetries):
+    """The list a symmetry-averaged evaluation takes the mean over (include/qttt_nn_symmetric.h), as a tuple: "all" or a
+    sequence of 1, 2, 4 or 8 ints in 0..7."""
+    sym = tuple(range(N_SYMMETRIES)) if isinstance(symmetries, str) and symmetries == "all" else tuple(_k(k) for k in symmetries)
+    if len(sym) not in _native.NN_SYMMETRIC_SIZES:
+        raise ValueError("the mean is taken over %s symmetries, got %d" % (" | ".join(map(str, _native.NN_SYMMETRIC_SIZES)), len(sym)))
+    return sym
+
+
 def device_tables(device):
     """(cells u8[8, 9], actions u8[8, 36]) as tensors on `device`, the action table with 220 more columns that map
     36..255 to themselves (255: no action)."""

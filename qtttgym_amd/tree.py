@@ -16,6 +16,9 @@ rollouts is select_batch -> VecEnv.evaluate on the G * K leaves -> backup_batch,
 are kept apart by `virtual_loss`, which lives in spare bits of the visit counts between the two tree launches of a round
 and never touches W.
 
+eval_symmetries (value leaves only) averages the network over every leaf's images under the board's symmetries
+(include/qttt_nn_symmetric.h): every rollout is then such a round, a round of one leaf where leaves == 1.
+
 add_root_noise() is AlphaZero's root exploration (include/qttt_tree_explore.h): Dirichlet noise mixed into
 the priors of every root that has them, one launch.
 """
@@ -23,6 +26,7 @@ import torch
 
 from . import _native
 from ._host import LibCaller, _ptr, check_net, check_tensor, out_rows, out_tensor, resolve_device
+from .symmetry import check_eval_symmetries
 from .vec_env import VecEnv
 
 
@@ -34,16 +38,21 @@ class TreeSearch(LibCaller):
 
     LEAF_EVALS = ("playouts", "value")
     leaf_eval = "playouts"
+    eval_symmetries = None
 
     def __init__(self, num_games, capacity, num_simulations=10, c_puct=1.0, net=None, seed=0, board_offset=0,
-                 device=None, leaf_eval="playouts", leaves=1, virtual_loss=1.0):
+                 device=None, leaf_eval="playouts", leaves=1, virtual_loss=1.0, eval_symmetries=None):
         """leaf_eval="playouts": the reference's rollout, num_simulations playouts from the leaf (uniform, or guided by
         `net`).  leaf_eval="value" (needs `net`): the leaf is scored by the value head, seen by the player to move
         there; a terminal leaf by its reward.  num_simulations is then ignored: no playout draw is taken.
         leaves=K > 1 (needs leaf_eval="value"): contemplate() searches K leaves per game per round, each descent counted
         as a loss of `virtual_loss` by the ones after it until the round is backed up.  leaves=1 is the search as it
-        always was."""
+        always was.
+        eval_symmetries ("all" or 1, 2, 4 or 8 symmetries 0..7; needs leaf_eval="value"): every leaf's value and priors are
+        the network's mean over the leaf's images under them (VecEnv.evaluate(symmetries=...)).  Every
+        rollout is then a round — select_batch, evaluate, backup_batch — a round of one leaf where leaves == 1."""
         self.leaves, self.virtual_loss = self.check_search_args(leaf_eval, net, leaves, virtual_loss)
+        self.eval_symmetries = self.check_eval_symmetries(leaf_eval, eval_symmetries)
         self.leaf_eval = leaf_eval
         self.num_games, self.capacity = int(num_games), int(capacity)
         self.num_simulations, self.c_puct = int(num_simulations), float(c_puct)
@@ -99,6 +108,15 @@ class TreeSearch(LibCaller):
             raise ValueError("virtual_loss must be finite and >= 0")
         return leaves, virtual_loss
 
+    @staticmethod
+    def check_eval_symmetries(leaf_eval, eval_symmetries):
+        """The constructors' check of eval_symmetries: None, or the tuple VecEnv.evaluate(symmetries=...) takes."""
+        if eval_symmetries is None:
+            return None
+        if leaf_eval != "value":
+            raise ValueError('eval_symmetries needs leaf_eval="value"')
+        return check_eval_symmetries(eval_symmetries)
+
     def _need_reset(self):
         if self._bound is None:
             raise RuntimeError("reset() first")
@@ -126,7 +144,7 @@ class TreeSearch(LibCaller):
     def contemplate(self, rollouts):
         """`rollouts` x MCTS._rollout (mcts.py:166-176) in every game.  With leaves = K > 1 they are taken K at a time:
         after a reset() or sync() one single rollout first (K descents would all end on a root without priors), then
-        rounds of K and one shorter round for what is left."""
+        rounds of K and one shorter round for what is left.  Without eval_symmetries the calls are what they always were."""
         r = int(rollouts)
         if r < 0:
             raise ValueError("rollouts must be >= 0")
@@ -137,13 +155,15 @@ class TreeSearch(LibCaller):
         if self._bound + 2 * r > self.capacity:
             raise ValueError("%d rollouts could use %d nodes, more than capacity %d"
                              % (r, self._bound + 2 * r, self.capacity))
+        # a single rollout: the fused value rollout, or — under eval_symmetries — a round of one leaf
+        single = self._rollout if self.eval_symmetries is None else (lambda: self._round(1))
         if self.leaves == 1:
             for _ in range(r):
-                self._rollout()
+                single()
                 self._bound += 2
             return
         if r and self._fresh:
-            self._rollout()
+            single()
             self._bound += 2
             r -= 1
             self._fresh = False
@@ -179,7 +199,7 @@ class TreeSearch(LibCaller):
         G, cap, tree = self.num_games, self.capacity, self.tree.data_ptr()
         self._call("qttt_tree_select_batch", tree, G, cap, self.seed, self.rollout_idx, k, self.board_offset, self.c_puct,
                    self.virtual_loss, b["paths"].data_ptr(), b["leaf"].state.data_ptr())
-        b["leaf"].evaluate(self.net, out=b["out"])
+        b["leaf"].evaluate(self.net, out=b["out"], symmetries=self.eval_symmetries)
         self._call("qttt_tree_backup_batch", tree, G, cap, k, b["paths"].data_ptr(), b["out"]["value"].data_ptr(),
                    b["out"]["probs"].data_ptr())
         self.rollout_idx += k

@@ -14,6 +14,7 @@ import torch
 from . import _native
 from ._host import LibCaller, _ptr, _raw_stream, check_net, check_tensor, out_rows, out_tensor, out_tensors, resolve_device
 from .spaces import reference_action_space, reference_observation_space
+from .symmetry import check_eval_symmetries
 
 # The eight tensors of one step's outputs, in the order a default step() carves them out of one allocation
 # (csrc/fastviews.cpp has the same order, checked by tests/test_fastviews_cpu.py): key in the observation dict (None: not
@@ -698,14 +699,22 @@ class VecEnv(LibCaller):
         self._call("qttt_encode", self.state.data_ptr(), vec.data_ptr(), _ptr(mask), self.num_envs)
         return (vec, mask) if with_mask else vec
 
-    def evaluate(self, net, rows=("value", "logits"), out=None):
+    def evaluate(self, net, rows=("value", "logits"), out=None, symmetries=None):
         """nn.Model.forward(GameState.to_vector()) (nn.py:7-72, alphazero.py:294-300) for every board in ONE kernel
         (include/qttt_nn.h qttt_evaluate): a dict of the requested rows among value f32[N], logits f32[N,36] (-inf at
         illegal actions) and probs f32[N,36] (= Categorical(logits).probs; NaN rows where every action is masked).
         `net` = a PolicyValueNet on this device.  `out` = the dict of an earlier call: its tensors are overwritten and
-        its keys decide which rows are computed (`rows` is then ignored).  Runs on the current stream."""
+        its keys decide which rows are computed (`rows` is then ignored).  Runs on the current stream.
+        symmetries (include/qttt_nn_symmetric.h qttt_evaluate_symmetric, still one kernel): a sequence of 1, 2, 4 or 8
+        symmetries 0..7 ("all": the eight in order) — every row is the mean over the board's images under them, each
+        image's outputs mapped back to the board's own actions; or a uint8 tensor [N] on this device — board i is
+        evaluated under symmetries[i] alone and mapped back (an entry past 7 is the identity)."""
         n, dev = self.num_envs, self.state.device
         check_net(net, dev)
+        if torch.is_tensor(symmetries):
+            sym, lst = check_tensor(symmetries, torch.uint8, (n,), dev, "symmetries"), (0,)
+        elif symmetries is not None:
+            sym, lst = None, check_eval_symmetries(symmetries)
         if out is None:
             rows = (rows,) if isinstance(rows, str) else tuple(rows)
             if not rows or any(r not in self._EVAL_ROWS for r in rows):
@@ -713,8 +722,12 @@ class VecEnv(LibCaller):
         elif not any(out.get(r) is not None for r in self._EVAL_ROWS):
             raise ValueError("out must be a dict returned by evaluate()")
         out = out_rows(self._EVAL_ROWS, n, dev, out, rows, strict=True)
-        self._call("qttt_evaluate", self.state.data_ptr(), net.blob.data_ptr(), net.precision, _ptr(out.get("value")),
-                   _ptr(out.get("logits")), _ptr(out.get("probs")), n)
+        ptrs = (_ptr(out.get("value")), _ptr(out.get("logits")), _ptr(out.get("probs")), n)
+        if symmetries is None:
+            self._call("qttt_evaluate", self.state.data_ptr(), net.blob.data_ptr(), net.precision, *ptrs)
+        else:
+            self._call("qttt_evaluate_symmetric", self.state.data_ptr(), net.blob.data_ptr(), net.precision,
+                       (ctypes.c_uint8 * len(lst))(*lst), len(lst), _ptr(sym), *ptrs)
         return out
 
     def rollout_policy(self, net, n_sims=1, step_idx0=None, with_plies=False, with_trace=False, leaf=(), out=None):

@@ -8,6 +8,14 @@ the dtype, and — first — the largest deviation of each dtype from the refere
     python tools/evalbench.py [--sizes 4096,65536,1048576] [--reps 7] [--calls 20] [--out FILE]
 
 Kernel time alone: run it with --no-torch under `rocprofv3 --kernel-trace --stats` (a separate run).
+
+--symmetries: the evaluation averaged over the eight images of every board instead: the fused call
+(VecEnv.evaluate(symmetries="all"), one kernel), the composed route a caller had without it (eight transformed(k), eight
+evaluate, a gather through tau_k each and the pairwise sum, every buffer allocated beforehand) and plain evaluate at the same
+board count, alternating in one process with the same repetition scheme, rows value and probs (what the search reads).
+One JSON line per (dtype, N): the medians, the composed route's spread over its repetitions (max - min), and the ratios.
+
+    python tools/evalbench.py --symmetries [--sizes 4096,65536,1048576] [--out profiles/nn_symmetric/evalbench_symmetries.jsonl]
 """
 import argparse
 import json
@@ -57,6 +65,73 @@ def torch_route(env, W, vec_mask):
     return v, lg
 
 
+class ComposedSymmetric:
+    """The composed route over the eight symmetries, with every buffer of its own: images, their rows, the result."""
+
+    def __init__(self, env, net, rows):
+        from qtttgym_amd import symmetry
+        self.env, self.net = env, net
+        self.images = [VecEnv(env.num_envs, device=env.device) for _ in range(8)]
+        self.outs = [env.evaluate(net, rows=rows) for _ in range(8)]
+        self.tau = torch.tensor(symmetry.tables()[1], dtype=torch.int64, device=env.device)
+
+    def __call__(self):
+        terms = []
+        for k in range(8):
+            out = self.env.transformed(k, out=self.images[k]).evaluate(self.net, out=self.outs[k])
+            terms.append({r: (t if t.dim() == 1 else t[:, self.tau[k]]) for r, t in out.items()})
+        while len(terms) > 1:
+            terms = [{r: a[r] + b[r] for r in a} for a, b in zip(terms[0::2], terms[1::2])]
+        return {r: t * 0.125 for r, t in terms[0].items()}
+
+
+def symmetries_mode(args, dev, sd):
+    rows, lines = ("value", "probs"), []
+    for name in args.dtypes.split(","):
+        net = PolicyValueNet(sd, device=dev, dtype=DTYPES[name])
+        for n in (int(s) for s in args.sizes.split(",")):
+            env = VecEnv(n, device=dev, seed=11, auto_reset=True)
+            env.step_random_many(5)
+            out, plain_out = env.evaluate(net, rows=rows, symmetries="all"), env.evaluate(net, rows=rows)
+            composed = ComposedSymmetric(env, net, rows)
+            routes = {"fused": lambda: env.evaluate(net, out=out, symmetries="all"), "composed": composed,
+                      "plain": lambda: env.evaluate(net, out=plain_out)}
+            for _ in range(args.warmup):
+                for fn in routes.values():
+                    fn()
+            torch.cuda.synchronize()
+            want = composed()
+            agree = all(bool(((out[r] == want[r]) | (torch.isnan(out[r]) & torch.isnan(want[r]))).all()) for r in rows)
+            us = {k: [] for k in routes}
+            for _ in range(args.reps):                  # alternate the three routes
+                for k, fn in routes.items():
+                    us[k].append(timed(fn, args.calls))
+            med = {k: statistics.median(v) for k, v in us.items()}
+            rec = {"mode": "symmetries", "dtype": name, "boards": n, "n_sym": 8, "rows": list(rows),
+                   "fused_equals_composed": agree,
+                   "fused_us": round(med["fused"], 2), "fused_us_min": round(min(us["fused"]), 2),
+                   "fused_us_max": round(max(us["fused"]), 2),
+                   "composed_us": round(med["composed"], 2), "composed_us_min": round(min(us["composed"]), 2),
+                   "composed_us_max": round(max(us["composed"]), 2),
+                   "composed_spread_us": round(max(us["composed"]) - min(us["composed"]), 2),
+                   "plain_us": round(med["plain"], 2), "plain_us_min": round(min(us["plain"]), 2),
+                   "composed_over_fused": round(med["composed"] / med["fused"], 2),
+                   "fused_over_plain": round(med["fused"] / med["plain"], 2),
+                   "share_of_mfma_peak": 8 * FLOP_PER_BOARD * n / (med["fused"] * 1e-6) / PEAK[name]}
+            print(json.dumps(rec), flush=True)
+            lines.append(rec)
+            del env, out, plain_out, composed, routes, want
+            torch.cuda.empty_cache()
+    return lines
+
+
+def write_lines(path, lines):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        for r in lines:
+            f.write(json.dumps(r) + "\n")
+
+
 def timed(fn, calls):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -75,6 +150,8 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-torch", action="store_true", help="the fused kernel only (for a kernel trace)")
+    ap.add_argument("--symmetries", action="store_true",
+                    help="time evaluate(symmetries='all') beside the composed route and plain evaluate instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -82,6 +159,11 @@ def main():
     dev = torch.device("cuda", 0)
     g = load_golden()
     sd = golden_state_dict(g)
+    if args.symmetries:
+        lines = symmetries_mode(args, dev, sd)
+        if args.out:
+            write_lines(args.out, lines)
+        return
     lines = [{"parity_vs_reference": parity(g, sd, dev), "positions": int(len(g["value"]))}]
     print(json.dumps(lines[0]), flush=True)
     for name in args.dtypes.split(","):
@@ -114,10 +196,7 @@ def main():
             lines.append(rec)
             del env, out, vm
     if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            for r in lines:
-                f.write(json.dumps(r) + "\n")
+        write_lines(args.out, lines)
 
 
 if __name__ == "__main__":

@@ -18,7 +18,7 @@ def main():
     err = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True).stderr
     rows, cur = [], None
     for line in err.splitlines():
-        m = re.search(r"remark:\s+(Function Name|VGPRs|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
+        m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
         if not m:
             continue
         k, v = m.group(1), m.group(2)
@@ -28,10 +28,10 @@ def main():
             rows.append(cur)
         else:
             cur[k.split(" ")[0]] = v
-    print("%-72s %5s %5s %7s %7s %4s" % ("kernel", "VGPR", "SGPR", "scratch", "LDS", "occ"))
+    print("%-72s %5s %5s %5s %7s %7s %4s" % ("kernel", "VGPR", "AGPR", "SGPR", "scratch", "LDS", "occ"))
     for r in rows:
         if pat in r["name"]:
-            print("%-72s %5s %5s %7s %7s %4s" % (r["name"][:72], r.get("VGPRs"), r.get("SGPRs"), r.get("ScratchSize"),
+            print("%-72s %5s %5s %5s %7s %7s %4s" % (r["name"][:72], r.get("VGPRs"), r.get("AGPRs"), r.get("SGPRs"), r.get("ScratchSize"),
                                                   r.get("LDS"), r.get("Occupancy")))
 
 
