@@ -96,6 +96,10 @@ def main():
                     help="Dirichlet(ALPHA) noise with weight EPS on the roots' priors before every searched move")
     ap.add_argument("--temperature", type=float, default=1.0, help="the sampled moves follow N ** (1 / temperature)")
     ap.add_argument("--sample-plies", type=int, default=0, help="plies whose move is drawn from the visit counts")
+    ap.add_argument("--root-policy", choices=("puct", "gumbel"), default="puct",
+                    help="gumbel: the Gumbel root, sequential halving over --max-considered actions; pi is then the "
+                         "improved policy and the move the best survivor (needs --leaf-eval value; --rollouts of 16-32 do)")
+    ap.add_argument("--max-considered", type=int, default=16, help="actions the Gumbel root samples (1..36)")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     torch.manual_seed(args.seed)
@@ -110,7 +114,8 @@ def main():
                   seed=args.seed, leaf_eval=args.leaf_eval, leaves=args.leaves,
                   root_noise=None if args.root_noise is None else tuple(float(x) for x in args.root_noise.split(",")),
                   temperature=args.temperature, sample_plies=args.sample_plies,
-                  eval_symmetries=parse_eval_symmetries(args.eval_symmetries))
+                  eval_symmetries=parse_eval_symmetries(args.eval_symmetries), root_policy=args.root_policy,
+                  max_considered=args.max_considered)
     for run in range(args.runs):
         batch = sp.play()
         s, pi, mask, v_target, done = (batch.augment() if args.symmetries else batch).flat()

@@ -10,7 +10,8 @@ syncs after every move (strat_eval.play_game).  Finished games are frozen: their
                                        [--eval-symmetries all|0,4]
 
 A player is mcts:R (uniform playouts and priors, MCTS(R)), az:R (the network's playouts and priors, AlphaZero(R)),
-azv:R (the network's value head at the leaf and its priors, TreeSearch(leaf_eval="value"): no playouts) or random (the
+azv:R (the network's value head at the leaf and its priors, TreeSearch(leaf_eval="value"): no playouts), azg:R (azv with
+the Gumbel root, TreeSearch(root_policy="gumbel", max_considered=--max-considered): R of 16-32 is its range) or random (the
 uniform-legal policy).  --leaves K gives the azv players K leaves per game per round (TreeSearch(leaves=K), virtual
 loss; --p2-leaves K2 when player 2's differs: azv:304 --leaves 8 --p2-leaves 1 plays the leaf-parallel search against
 the plain one).  --eval-symmetries all (or a list of 1, 2, 4 or 8 symmetries such as 0,4) gives the azv players the
@@ -38,8 +39,8 @@ def parse_player(spec):
     kind, _, n = spec.partition(":")
     if kind == "random":
         return ("random", 0)
-    if kind not in ("mcts", "az", "azv") or not n.isdigit() or int(n) < 1:
-        raise SystemExit("a player is mcts:R, az:R, azv:R or random, not %r" % spec)
+    if kind not in ("mcts", "az", "azv", "azg") or not n.isdigit() or int(n) < 1:
+        raise SystemExit("a player is mcts:R, az:R, azv:R, azg:R or random, not %r" % spec)
     return (kind, int(n))
 
 
@@ -50,7 +51,10 @@ def load_state_dict(args):
         return {k: torch.from_numpy(d[k.replace(".", "_")]) for k in SHAPES}
 
 
-def play(players, G, sims, net, seed, carry=None, leaves=(1, 1), eval_symmetries=None):
+VALUE_KINDS = ("azv", "azg")           # the players that score a leaf by the value head
+
+
+def play(players, G, sims, net, seed, carry=None, leaves=(1, 1), eval_symmetries=None, max_considered=16):
     """One half: players[0] moves first; leaves[i] = the leaves per round of players[i] when it is an azv player, and
     eval_symmetries what the azv players average the network over.  Returns winner i8[G] (1 = the first mover, 0 = the second, -1 = none).
     carry: None = the trees never compact; else they compact after every sync and hold 2 * R + carry nodes (carry < 0:
@@ -63,10 +67,11 @@ def play(players, G, sims, net, seed, carry=None, leaves=(1, 1), eval_symmetries
             continue
         own_moves = 5 if i == 0 else 4
         capacity = 1 + 2 * R * own_moves + 9 if carry is None else 2 * R + (carry if carry >= 0 else 2 * R + 2)
-        t = TreeSearch(G, capacity=capacity, num_simulations=sims, net=net if kind in ("az", "azv") else None,
-                       seed=seed * 2 + 1 + i, device=env.device, leaf_eval="value" if kind == "azv" else "playouts",
-                       leaves=leaves[i] if kind == "azv" else 1,
-                       eval_symmetries=eval_symmetries if kind == "azv" else None)
+        value = kind in VALUE_KINDS
+        t = TreeSearch(G, capacity=capacity, num_simulations=sims, net=net if kind == "az" or value else None,
+                       seed=seed * 2 + 1 + i, device=env.device, leaf_eval="value" if value else "playouts",
+                       leaves=leaves[i] if value else 1, eval_symmetries=eval_symmetries if value else None,
+                       root_policy="gumbel" if kind == "azg" else "puct", max_considered=max_considered)
         t.reset(env)
         trees.append(t)
     finished = torch.zeros(G, dtype=torch.bool, device=env.device)
@@ -113,6 +118,7 @@ def main():
     ap.add_argument("--p2-leaves", type=int, default=None, help="player 2's, when it differs (default: --leaves)")
     ap.add_argument("--eval-symmetries", default=None, metavar="all|K,K,...",
                     help="the azv players average the network over these symmetries of every leaf")
+    ap.add_argument("--max-considered", type=int, default=16, help="actions the azg players' Gumbel root samples (1..36)")
     args = ap.parse_args()
     syms = args.eval_symmetries
     syms = syms if syms in (None, "all") else tuple(int(k) for k in syms.split(","))
@@ -122,7 +128,7 @@ def main():
     if half < 1:
         raise SystemExit("--games must be at least 2")
     net = None
-    if {"az", "azv"} & {p1[0], p2[0]}:
+    if {"az", "azv", "azg"} & {p1[0], p2[0]}:
         net = PolicyValueNet(load_state_dict(args), device="cuda",
                              dtype=torch.float32 if args.dtype == "f32" else torch.bfloat16)
     if args.carry is not None and not args.compact:
@@ -132,8 +138,8 @@ def main():
         if args.carry is not None and args.carry < 0:
             raise SystemExit("--carry must be >= 0")
         carry = args.carry if args.carry is not None else -1
-    w_a = play((p1, p2), half, args.sims, net, args.seed, carry, (k1, k2), syms)       # player 1 moves first
-    w_b = play((p2, p1), half, args.sims, net, args.seed + 1, carry, (k2, k1), syms)   # player 2 moves first
+    w_a = play((p1, p2), half, args.sims, net, args.seed, carry, (k1, k2), syms, args.max_considered)       # player 1 moves first
+    w_b = play((p2, p1), half, args.sims, net, args.seed + 1, carry, (k2, k1), syms, args.max_considered)   # player 2 moves first
     wins = int((w_a == 1).sum()) + int((w_b == 0).sum())
     losses = int((w_a == 0).sum()) + int((w_b == 1).sum())
     draws = int((w_a == -1).sum()) + int((w_b == -1).sum())

@@ -350,4 +350,5 @@ uint64_t qttt_hash(uint64_t seed, uint64_t board_id, uint32_t step_idx);
 #include "qttt_tree_leaves.h"
 #include "qttt_tree_explore.h"
 #include "qttt_nn_symmetric.h"
+#include "qttt_tree_gumbel.h"
 #endif

@@ -142,6 +142,20 @@ NN_SYMMETRIC_SIZES = (1, 2, 4, 8)
 NN_SYMMETRIC_SIGNATURES = {
     "qttt_evaluate_symmetric": (_i32, [_vp, _vp, _i32, _u8p, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
+# every symbol include/qttt_tree_gumbel.h declares (the Gumbel root of the search trees; qttt.h includes it)
+TREE_GUMBEL_BYTES = 880
+TREE_GUMBEL_BASE = 0xF0000000
+TREE_MAX_GUMBEL = 0x10000000 // 36
+TREE_GUMBEL_SIGNATURES = {
+    "qttt_tree_gumbel_bytes": (_i64, [_i64]),
+    "qttt_gumbel_visit_sequence": (_i32, [_i32, _i32, _vp]),
+    "qttt_tree_root_states": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    "qttt_tree_gumbel_begin": (_i32, [_vp, _i64, _i64, _u64, _u32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "qttt_tree_select_batch_gumbel": (_i32, TREE_LEAVES_SIGNATURES["qttt_tree_select_batch"][1][:-1]
+                                      + [_vp, _vp, _i32, _i32, _f64, _f64, _vp]),
+    "qttt_tree_gumbel_root": (_i32, [_vp, _vp, _i64, _i64, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "qttt_selfplay_record_gumbel": (_i32, SELFPLAY_SIGNATURES["qttt_selfplay_record"][1][:-1] + [_vp, _f64, _f64, _vp]),
+}
 
 _lib = None
 
@@ -208,7 +222,7 @@ def lib():
                                   + list(TREE_COMPACT_SIGNATURES.items()) + list(SELFPLAY_SIGNATURES.items())
                                   + list(SYMMETRY_SIGNATURES.items()) + list(TREE_VALUE_SIGNATURES.items())
                                   + list(TREE_EXPLORE_SIGNATURES.items()) + list(TREE_LEAVES_SIGNATURES.items())
-                                  + list(NN_SYMMETRIC_SIGNATURES.items())):
+                                  + list(NN_SYMMETRIC_SIGNATURES.items()) + list(TREE_GUMBEL_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

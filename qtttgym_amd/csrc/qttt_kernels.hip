@@ -54,7 +54,8 @@
 // qttt_nn_symmetric_kernels.h (the network averaged over a position's symmetries, on qttt_nn_kernels.h's trunk and head);
 // qttt_tree_value_kernels.h (the value rollout: network evaluation of the leaves and backup in one launch);
 // qttt_tree_leaves_kernels.h (leaf-parallel rounds: K descents per game under virtual loss, and their backup);
-// qttt_tree_explore_kernels.h (root exploration: Dirichlet noise on the roots' priors, the sampled move).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
+// qttt_tree_explore_kernels.h (root exploration: Dirichlet noise on the roots' priors, the sampled move);
+// qttt_tree_gumbel_kernels.h (the Gumbel root: considered actions, sequential halving, the improved policy).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
 // qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
@@ -71,6 +72,7 @@
 #include "qttt_nn_symmetric_kernels.h"
 #include "qttt_tree_value_kernels.h"
 #include "qttt_tree_leaves_kernels.h"
+#include "qttt_tree_gumbel_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -197,6 +199,9 @@ bool tree_size_bad(int64_t games, int64_t capacity) { return games < 0 || capaci
 bool tree_leaves_bad(int64_t games, int leaves) {
     return games < 0 || leaves < 1 || leaves > QTTT_TREE_MAX_LEAVES || games > INT64_MAX / (256 * (int64_t)QTTT_TREE_MAX_LEAVES);
 }
+
+// the scales of sigma (include/qttt_tree_gumbel.h): c_visit finite and >= 0, c_scale finite
+bool gumbel_scale_bad(double c_visit, double c_scale) { return !std::isfinite(c_visit) || c_visit < 0.0 || !std::isfinite(c_scale); }
 
 }  // namespace
 
@@ -742,8 +747,8 @@ int qttt_selfplay_record(const void *tree, int64_t games, int64_t capacity, int 
     if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions)) return QTTT_ERR_NULL;
     if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
     const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
-    return launch(selfplay_record_kernel<false>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
-                  ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, SelfPlaySampling<false>{});
+    return launch(selfplay_record_kernel<RECORD_PLAIN>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, SelfPlaySampling<RECORD_PLAIN>{});
 }
 
 // ---------------------------------------------------------------- symmetries (include/qttt_symmetry.h)
@@ -892,9 +897,105 @@ int qttt_selfplay_record_sampled(const void *tree, int64_t games, int64_t capaci
     if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions)) return QTTT_ERR_NULL;
     if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
     const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
-    const SelfPlaySampling<true> s = {(u64)seed, (u64)board_offset, temperature, sample_plies};
-    return launch(selfplay_record_kernel<true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+    const SelfPlaySampling<RECORD_SAMPLED> s = {(u64)seed, (u64)board_offset, temperature, sample_plies};
+    return launch(selfplay_record_kernel<RECORD_SAMPLED>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
                   ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
+}
+
+// ---------------------------------------------------------------- the Gumbel root (include/qttt_tree_gumbel.h)
+int64_t qttt_tree_gumbel_bytes(int64_t games) {
+    if (games < 0 || games > INT64_MAX / QTTT_TREE_GUMBEL_BYTES) return QTTT_ERR_SIZE;
+    return games * (int64_t)QTTT_TREE_GUMBEL_BYTES;
+}
+
+int qttt_gumbel_visit_sequence(int m, int n_sims, int32_t *out) {
+    if (m < 0 || m > 36 || n_sims < 1 || n_sims > QTTT_TREE_MAX_ROLLOUTS) return QTTT_ERR_SIZE;
+    if (!out) return QTTT_ERR_NULL;
+    const int n = n_sims;
+    if (m <= 1) {
+        for (int i = 0; i < n; ++i) out[i] = i;
+        return 0;
+    }
+    int L = 0;
+    while ((1 << L) < m) ++L;
+    int32_t visits[36] = {0};
+    int emitted = 0;
+    for (int c = m; emitted < n; c = c / 2 > 2 ? c / 2 : 2) {
+        const int e = n / (L * c) > 1 ? n / (L * c) : 1;
+        for (int t = 0; t < e; ++t)
+            for (int i = 0; i < c; ++i) {
+                if (emitted < n) out[emitted++] = visits[i];
+                ++visits[i];
+            }
+    }
+    return 0;
+}
+
+int qttt_tree_root_states(const void *tree, int64_t games, int64_t capacity, void *state_out, void *stream) {
+    if (tree_size_bad(games, capacity)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, state_out)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(state_out, 16)) return QTTT_ERR_ACTION;
+    const Planes p = planes(state_out, games);
+    return launch(tree_root_states_kernel, ceil_div(games, TREE_BLOCK), TREE_BLOCK, stream, tree, games, capacity, p.P, p.Q);
+}
+
+int qttt_tree_gumbel_begin(const void *tree, int64_t games, int64_t capacity, uint64_t seed, uint32_t move_idx,
+                           int64_t board_offset, int max_considered, const float *root_value, const float *root_logits,
+                           void *rec, void *stream) {
+    if (tree_size_bad(games, capacity) || board_offset < 0 || max_considered < 1 || max_considered > 36 ||
+        move_idx >= QTTT_TREE_MAX_GUMBEL || games > INT64_MAX / QTTT_TREE_GUMBEL_BYTES)
+        return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, root_value, root_logits, rec)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(rec, 16) || misaligned(root_value, 4) || misaligned(root_logits, 4)) return QTTT_ERR_ACTION;
+    return launch(tree_gumbel_begin_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (u64)seed, move_idx, (u64)board_offset, (u32)max_considered, root_value, root_logits, static_cast<GumbelRec *>(rec));
+}
+
+int qttt_tree_select_batch_gumbel(void *tree, int64_t games, int64_t capacity, uint64_t seed, uint32_t rollout_idx0,
+                                  int leaves, int64_t board_offset, double c_puct, double virtual_loss, void *paths,
+                                  void *leaf_state, const void *rec, const int32_t *visit_table, int n_sims, int sim_idx0,
+                                  double c_visit, double c_scale, void *stream) {
+    if (tree_size_bad(games, capacity) || board_offset < 0 || tree_leaves_bad(games, leaves) ||
+        (uint64_t)rollout_idx0 + (uint64_t)leaves > QTTT_TREE_MAX_ROLLOUTS || !std::isfinite(virtual_loss) || virtual_loss < 0.0 ||
+        n_sims < 1 || n_sims > QTTT_TREE_MAX_ROLLOUTS || sim_idx0 < 0 || (int64_t)sim_idx0 + leaves > n_sims ||
+        gumbel_scale_bad(c_visit, c_scale))
+        return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, paths, leaf_state, rec, visit_table)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(paths, 16) || misaligned(rec, 16) || misaligned(visit_table, 4)) return QTTT_ERR_ACTION;
+    const Planes l = planes(leaf_state, games * leaves);
+    return launch(tree_select_batch_gumbel_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (u64)seed, rollout_idx0, (u32)leaves, (u64)board_offset, c_puct, virtual_loss, static_cast<TreePathRec *>(paths),
+                  l.P, l.Q, static_cast<const GumbelRec *>(rec), visit_table, (u32)n_sims, (u32)sim_idx0, c_visit, c_scale);
+}
+
+int qttt_tree_gumbel_root(const void *tree, const void *rec, int64_t games, int64_t capacity, double c_visit,
+                          double c_scale, uint8_t *choose, double *pi, double *q_completed, void *stream) {
+    if (tree_size_bad(games, capacity) || gumbel_scale_bad(c_visit, c_scale)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, rec)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(rec, 16) || misaligned(pi, 8) || misaligned(q_completed, 8)) return QTTT_ERR_ACTION;
+    return launch(tree_gumbel_root_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree,
+                  static_cast<const GumbelRec *>(rec), games, capacity, c_visit, c_scale, choose, pi, q_completed);
+}
+
+int qttt_selfplay_record_gumbel(const void *tree, int64_t games, int64_t capacity, int ply, uint32_t n_rollouts,
+                                double alpha, double v_first, double v_second, void *states, double *pi, uint8_t *mask,
+                                uint8_t *done, float *v, uint8_t *action36, uint8_t *length, int8_t *winner,
+                                uint8_t *actions, const void *rec, double c_visit, double c_scale, void *stream) {
+    if (tree_size_bad(games, capacity) || ply < 0 || ply >= QTTT_SELFPLAY_ROWS || !std::isfinite(v_first) ||
+        !std::isfinite(v_second) || gumbel_scale_bad(c_visit, c_scale))
+        return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions, rec)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4) || misaligned(rec, 16))
+        return QTTT_ERR_ACTION;
+    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    const SelfPlaySampling<RECORD_GUMBEL> s = {static_cast<const GumbelRec *>(rec), c_visit, c_scale};
+    return launch(selfplay_record_kernel<RECORD_GUMBEL>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
+                  capacity, ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
 }
 
 }  // extern "C"

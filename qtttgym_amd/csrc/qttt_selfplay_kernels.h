@@ -7,13 +7,15 @@
 // columns of the outputs, so there are no atomics, and nothing is handed from lane to lane through memory.  No LDS
 // (the winner and the terminal flag are the root's node flags, no line table is needed), no loop but the two six-step
 // butterflies (the sum, and choose's argmax).
-// selfplay_record_kernel<true> is the sampled record of include/qttt_tree_explore.h: the same kernel with the move of
-// the first plies drawn from the visit counts (explore_sample_move); <false> is qttt_selfplay_record's, whose code the
-// flag does not touch.
+// selfplay_record_kernel<RECORD_SAMPLED> is the sampled record of include/qttt_tree_explore.h: the same kernel with the
+// move of the first plies drawn from the visit counts (explore_sample_move); <RECORD_GUMBEL> is the Gumbel record of
+// include/qttt_tree_gumbel.h: the move and the pi row are gumbel_final's (qttt_tree_gumbel_kernels.h), two more
+// butterflies and one exp per lane; <RECORD_PLAIN> is qttt_selfplay_record's, whose code the mode does not touch.
 #ifndef QTTT_SELFPLAY_KERNELS_H
 #define QTTT_SELFPLAY_KERNELS_H
 #include "qttt_tree_kernels.h"
 #include "qttt_tree_explore_kernels.h"
+#include "qttt_tree_gumbel_kernels.h"
 #include "qttt_selfplay.h"
 
 namespace {
@@ -30,21 +32,28 @@ struct SelfPlayOut {
     uint8_t *actions;                  // [games][2]
 };
 
-// what the sampled record takes besides: nothing at all in the plain one
-template <bool SAMPLED>
+constexpr int RECORD_PLAIN = 0, RECORD_SAMPLED = 1, RECORD_GUMBEL = 2;
+
+// what the sampled and the Gumbel record take besides: nothing at all in the plain one
+template <int MODE>
 struct SelfPlaySampling {};
 template <>
-struct SelfPlaySampling<true> {
+struct SelfPlaySampling<RECORD_SAMPLED> {
     u64 seed, board_offset;
     double temperature;
     int sample_plies;
 };
+template <>
+struct SelfPlaySampling<RECORD_GUMBEL> {
+    const GumbelRec *recs;
+    double c_visit, c_scale;
+};
 
-template <bool SAMPLED>
+template <int MODE>
 __global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void *tree, int64_t games, int64_t capacity,
                                                                      int ply, u32 n_rollouts, double alpha, float v_first,
                                                                      float v_second, SelfPlayOut o,
-                                                                     SelfPlaySampling<SAMPLED> sampling) {
+                                                                     SelfPlaySampling<MODE> sampling) {
     const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
     const u32 lane = threadIdx.x & 63u;
     if (g >= games) return;
@@ -83,20 +92,29 @@ __global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void 
         }
         return;
     }
-    // self_play.py:208-213: pi[a] = (N / n_rollouts) ** alpha on the legal actions, normalised
-    double x = r.legal ? (double)r.s.N / (double)n_rollouts : 0.0;
-    if (alpha != 1.0) x = r.legal ? pow(x, alpha) : 0.0;
-    const double sum = selfplay_wave_sum(x);
-    int a = tree_choose(r, lane);
-    if constexpr (SAMPLED) {
-        if (ply < sampling.sample_plies) {                       // wave-uniform
-            const int drawn = explore_sample_move(r.s.N, lane, sampling.seed, sampling.board_offset + (u64)g, ply,
-                                                  sampling.temperature);
-            a = drawn < 0 ? a : drawn;
+    int a;
+    double pi;
+    if constexpr (MODE == RECORD_GUMBEL) {                       // the Gumbel choice and the improved policy
+        const GumbelFinal f = gumbel_final(r, gumbel_lane(sampling.recs + g, lane), lane, sampling.c_visit, sampling.c_scale);
+        a = f.choose;
+        pi = f.pi;
+    } else {
+        // self_play.py:208-213: pi[a] = (N / n_rollouts) ** alpha on the legal actions, normalised
+        double x = r.legal ? (double)r.s.N / (double)n_rollouts : 0.0;
+        if (alpha != 1.0) x = r.legal ? pow(x, alpha) : 0.0;
+        const double sum = selfplay_wave_sum(x);
+        a = tree_choose(r, lane);
+        if constexpr (MODE == RECORD_SAMPLED) {
+            if (ply < sampling.sample_plies) {                   // wave-uniform
+                const int drawn = explore_sample_move(r.s.N, lane, sampling.seed, sampling.board_offset + (u64)g, ply,
+                                                      sampling.temperature);
+                a = drawn < 0 ? a : drawn;
+            }
         }
+        pi = r.legal ? x / sum : 0.0;
     }
     if (lane < 36u) {
-        o.pi[row * 36 + lane] = r.legal ? x / sum : 0.0;
+        o.pi[row * 36 + lane] = pi;
         o.mask[row * 36 + lane] = r.legal ? 1 : 0;
     }
     if (lane == 0u) {

@@ -7,7 +7,7 @@
 // 144-byte store.  A wave writes only its own game's root: no atomics, no LDS, nothing handed from lane to lane through
 // memory.  The one loop is the Marsaglia-Tsang try loop, bounded by QTTT_TREE_NOISE_TRIES; it ends early on the
 // wave-uniform "every lane accepted".  explore_sample_move is the sampled record's move: an inclusive scan over the
-// wave and one ballot (selfplay_record_kernel<true>, qttt_selfplay_kernels.h).
+// wave and one ballot (selfplay_record_kernel<RECORD_SAMPLED>, qttt_selfplay_kernels.h).
 #ifndef QTTT_TREE_EXPLORE_KERNELS_H
 #define QTTT_TREE_EXPLORE_KERNELS_H
 #include "qttt_tree_kernels.h"

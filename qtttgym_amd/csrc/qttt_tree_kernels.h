@@ -214,6 +214,14 @@ __device__ __forceinline__ bool tree_expand_child(const TreeView &v, int64_t g, 
 //   a value rollout, f32          4 096 games 102.36 -> 102.19 [0.37], 26.87 -> 26.65 [0.16], 23.66 -> 23.50 [0.03];
 //                                 65 536 games 393.57 -> 392.25 [1.84], 361.64 -> 360.06 [0.85], 331.05 -> 330.09 [0.17]
 // Both kernels keep their registers, their 2 048 B of LDS and no scratch (device_code_parent_vs_change.txt there).
+// The rule at the root of a descent.  TreePuctRoot: none, the root is scored like every node (`on` is a constant, so the
+// descents that use it hold no trace of the hook).  A rule with on = true is asked once, at depth 0, with the root's header
+// and every lane's slot, and returns the wave-uniform action to take, or -1 for the ordinary score
+// (qttt_tree_gumbel_kernels.h's GumbelRootRule).
+struct TreePuctRoot {
+    static constexpr bool on = false;
+    __device__ __forceinline__ int operator()(const TreeNodeHdr &, const TreeSlot &, u32) const { return -1; }
+};
 struct TreeDescent {
     int32_t leaf, depth;
     TreeNodeHdr h;                     // the leaf's header
@@ -221,9 +229,10 @@ struct TreeDescent {
     int32_t edge_node;                 // lane d < depth: edge d
     u32 edge_action;
 };
-template <typename Score>
+template <typename Score, typename Root = TreePuctRoot>
 __device__ __forceinline__ TreeDescent tree_descend(const TreeView &v, int64_t g, int32_t root, u32 bits, int32_t &used,
-                                                    const uint8_t *lut, u32 lane, double c_puct, Score &&score) {
+                                                    const uint8_t *lut, u32 lane, double c_puct, Score &&score,
+                                                    const Root &root_rule = Root()) {
     TreeDescent d;
     d.leaf = root; d.depth = 0;
     d.overflow = false;
@@ -234,9 +243,15 @@ __device__ __forceinline__ TreeDescent tree_descend(const TreeView &v, int64_t g
         TreeSlot s;
         s.W = 0.0; s.N = 0u; s.child = -1;
         if (lane < 36u) s = v.slots(g, d.leaf)[lane];
-        double sc = 0.0;
-        if (legal) sc = score(s.W, s.N, tree_prior(v, g, d.leaf, d.h, lane), d.h.Ntot, c_puct);
-        const int a = __builtin_amdgcn_readfirstlane(wave_argmax(legal, sc, lane));
+        int a = -1;
+        if constexpr (Root::on) {
+            if (d.depth == 0) a = root_rule(d.h, s, lane);
+        }
+        if (a < 0) {                                             // always, but at a root whose rule has chosen
+            double sc = 0.0;
+            if (legal) sc = score(s.W, s.N, tree_prior(v, g, d.leaf, d.h, lane), d.h.Ntot, c_puct);
+            a = __builtin_amdgcn_readfirstlane(wave_argmax(legal, sc, lane));
+        }
         const int32_t child = __shfl(s.child, a);
         const u32 bit = (bits >> d.depth) & 1u;
         const int32_t parent = d.leaf;

@@ -51,16 +51,13 @@ __device__ __forceinline__ double tree_score_in_flight(double W, u32 Nword, doub
     return q + c_puct * u;
 }
 
-__global__ __launch_bounds__(TREE_BLOCK) void tree_select_batch_kernel(void *tree, int64_t games, int64_t capacity, u64 seed,
-                                                                       u32 rollout_idx0, u32 leaves, u64 board_offset,
-                                                                       double c_puct, double vloss, TreePathRec *paths,
-                                                                       u64 *leafP, u64 *leafQ) {
-    __shared__ __attribute__((aligned(16))) uint8_t lut[LINE_LUT_BYTES];
-    fill_line_lut<TREE_BLOCK>(lut);                              // ends with the workgroup barrier
-    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
-    const u32 lane = threadIdx.x & 63u;
-    if (g >= games) return;
-    const TreeView v = tree_view(tree, games, capacity);
+// The K descents of one game (the wave's), the body of tree_select_batch_kernel and of the Gumbel select
+// (qttt_tree_gumbel_kernels.h): root_of(j) = the root rule of descent j, TreePuctRoot for the plain round.
+template <typename RootOf>
+__device__ __forceinline__ void tree_select_batch_game(const TreeView &v, int64_t g, u32 lane, const uint8_t *lut, u64 seed,
+                                                       u32 rollout_idx0, u32 leaves, u64 board_offset, double c_puct,
+                                                       double vloss, TreePathRec *paths, u64 *leafP, u64 *leafQ,
+                                                       RootOf &&root_of) {
     TreeGame *gh = &v.games[g];
     const int32_t root = gh->root;
     int32_t used = gh->used;
@@ -72,7 +69,7 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_select_batch_kernel(void *tre
         const TreeDescent d = tree_descend(v, g, root, bits, used, lut, lane, c_puct,
                                            [vloss](double W, u32 N, double prior, u32 Ntot, double c) {
                                                return tree_score_in_flight(W, N, prior, tree_sqrt(tree_effective(Ntot)), c, vloss);
-                                           });
+                                           }, root_of(j));
         const u32 over = d.overflow ? TG_OVERFLOW : 0u;
         overflow |= over;
         // one in-flight visit on every edge of the path: lane d owns edge d, and the edges lie in different nodes
@@ -99,6 +96,19 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_select_batch_kernel(void *tre
         gh->leaf = root;
         gh->flags = (gh->flags & TG_OVERFLOW) | overflow | tree_leaf_flags(v.hdr(g, root)->flags);
     }
+}
+
+__global__ __launch_bounds__(TREE_BLOCK) void tree_select_batch_kernel(void *tree, int64_t games, int64_t capacity, u64 seed,
+                                                                       u32 rollout_idx0, u32 leaves, u64 board_offset,
+                                                                       double c_puct, double vloss, TreePathRec *paths,
+                                                                       u64 *leafP, u64 *leafQ) {
+    __shared__ __attribute__((aligned(16))) uint8_t lut[LINE_LUT_BYTES];
+    fill_line_lut<TREE_BLOCK>(lut);                              // ends with the workgroup barrier
+    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
+    const u32 lane = threadIdx.x & 63u;
+    if (g >= games) return;
+    tree_select_batch_game(tree_view(tree, games, capacity), g, lane, lut, seed, rollout_idx0, leaves, board_offset, c_puct,
+                           vloss, paths, leafP, leafQ, [](u32) { return TreePuctRoot(); });
 }
 
 // record j + 1 is fetched while record j is backed up: the records are not written here, so their loads need no order

@@ -94,13 +94,19 @@ class SelfPlay(LibCaller):
     TreeSearch.add_root_noise(epsilon, alpha), then the other n_rollouts - 1.  sample_plies=k > 0: the move of plies
     0..k-1 is drawn with probability proportional to N ** (1 / temperature) (qttt_selfplay_record_sampled, with the
     trees' seed); later plies play MCTS.choose.  pi stays the visit-count target either way.  With the defaults play()
-    issues the calls it always did."""
+    issues the calls it always did.
+    root_policy="gumbel" (with max_considered, c_visit, c_scale: TreeSearch's; value leaves only) searches every move with
+    the Gumbel root: the move is the Gumbel choice and pi the improved policy softmax(logits + sigma(completed Q))
+    (qttt_selfplay_record_gumbel); alpha is then unused.  root_noise and sample_plies are rejected with it: the Gumbel
+    noise is the exploration."""
 
     def __init__(self, num_games, n_rollouts=100, num_simulations=10, net=None, alpha=1.0, c_puct=1.0,
                  value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts",
                  root_noise=None, temperature=1.0, sample_plies=0, leaves=1, virtual_loss=1.0,
-                 eval_symmetries=None):
+                 eval_symmetries=None, root_policy="puct", max_considered=16, c_visit=50.0, c_scale=1.0):
         self.leaves, self.virtual_loss = TreeSearch.check_search_args(leaf_eval, net, leaves, virtual_loss)
+        self.root_policy, self.max_considered, self.c_visit, self.c_scale = TreeSearch.check_root_args(
+            leaf_eval, net, root_policy, max_considered, c_visit, c_scale)
         self.eval_symmetries = TreeSearch.check_eval_symmetries(leaf_eval, eval_symmetries)
         self.leaf_eval = leaf_eval
         self.num_games, self.n_rollouts = int(num_games), int(n_rollouts)
@@ -123,6 +129,10 @@ class SelfPlay(LibCaller):
             raise ValueError("temperature must be positive and finite")
         if not 0 <= self.sample_plies <= ROWS:
             raise ValueError("sample_plies must be in 0..%d" % ROWS)
+        if self.root_policy == "gumbel" and (self.root_noise is not None or self.sample_plies > 0):
+            raise ValueError('root_policy="gumbel" takes neither root_noise nor sample_plies: Gumbel noise is the exploration')
+        if self.root_policy == "gumbel" and self.n_rollouts < 2:
+            raise ValueError('root_policy="gumbel" needs n_rollouts >= 2: the rollout that gives the root its priors, then the budget')
         R = self.n_rollouts
         if self.compact:
             self.carry = 2 * R + 2 if carry is None else int(carry)
@@ -162,7 +172,11 @@ class SelfPlay(LibCaller):
                 batch.states.data_ptr(), batch.pi.data_ptr(), batch.mask.data_ptr(), batch.done.data_ptr(),
                 batch.v.data_ptr(), batch.action36.data_ptr(), batch.length.data_ptr(), batch.winner.data_ptr(),
                 batch.actions.data_ptr())
-        if self.sample_plies > 0:
+        if self.root_policy == "gumbel":
+            if tree.root_policy != "gumbel" or tree._gumbel is None:
+                raise ValueError("the Gumbel record needs a tree searched with root_policy=\"gumbel\"")
+            self._call("qttt_selfplay_record_gumbel", *args, tree._gumbel["rec"].data_ptr(), tree.c_visit, tree.c_scale)
+        elif self.sample_plies > 0:
             self._call("qttt_selfplay_record_sampled", *args, tree.seed, tree.board_offset, self.temperature,
                        self.sample_plies)
         else:
@@ -181,7 +195,8 @@ class SelfPlay(LibCaller):
         tree = self.tree = TreeSearch(G, capacity=self.capacity, num_simulations=self.num_simulations,
                                       c_puct=self.c_puct, net=self.net, seed=2 * s + 1, device=self.device,
                                       leaf_eval=self.leaf_eval, leaves=self.leaves, virtual_loss=self.virtual_loss,
-                                      eval_symmetries=self.eval_symmetries)
+                                      eval_symmetries=self.eval_symmetries, root_policy=self.root_policy,
+                                      max_considered=self.max_considered, c_visit=self.c_visit, c_scale=self.c_scale)
         tree.reset(env)
         batch = self.new_batch()
         for ply in range(ROWS):

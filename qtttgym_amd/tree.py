@@ -19,6 +19,11 @@ and never touches W.
 eval_symmetries (value leaves only) averages the network over every leaf's images under the board's symmetries
 (include/qttt_nn_symmetric.h): every rollout is then such a round, a round of one leaf where leaves == 1.
 
+root_policy="gumbel" (value leaves only) is the Gumbel root (include/qttt_tree_gumbel.h): contemplate(n)
+samples max_considered actions without replacement with Gumbel noise, spends the n simulations on them by sequential
+halving, rounds of `leaves` at a time, and choose() / root_stats() give the best survivor and the improved policy
+softmax(logits + sigma(completed Q)).  Below the root the search is the leaf-parallel one.
+
 add_root_noise() is AlphaZero's root exploration (include/qttt_tree_explore.h): Dirichlet noise mixed into
 the priors of every root that has them, one launch.
 """
@@ -36,12 +41,18 @@ class TreeSearch(LibCaller):
                   "P": (torch.float64, (36,)), "Ntot": (torch.int32, ()), "choose": (torch.uint8, ()),
                   "nodes_used": (torch.int32, ()), "overflow": (torch.uint8, ())}
 
+    # what the Gumbel root adds to them (qttt_tree_gumbel_root)
+    _GUMBEL_ROWS = {"choose": (torch.uint8, ()), "pi": (torch.float64, (36,)), "q_completed": (torch.float64, (36,))}
+
     LEAF_EVALS = ("playouts", "value")
+    ROOT_POLICIES = ("puct", "gumbel")
     leaf_eval = "playouts"
+    root_policy = "puct"
     eval_symmetries = None
 
     def __init__(self, num_games, capacity, num_simulations=10, c_puct=1.0, net=None, seed=0, board_offset=0,
-                 device=None, leaf_eval="playouts", leaves=1, virtual_loss=1.0, eval_symmetries=None):
+                 device=None, leaf_eval="playouts", leaves=1, virtual_loss=1.0, eval_symmetries=None, root_policy="puct",
+                 max_considered=16, c_visit=50.0, c_scale=1.0):
         """leaf_eval="playouts": the reference's rollout, num_simulations playouts from the leaf (uniform, or guided by
         `net`).  leaf_eval="value" (needs `net`): the leaf is scored by the value head, seen by the player to move
         there; a terminal leaf by its reward.  num_simulations is then ignored: no playout draw is taken.
@@ -50,8 +61,13 @@ class TreeSearch(LibCaller):
         always was.
         eval_symmetries ("all" or 1, 2, 4 or 8 symmetries 0..7; needs leaf_eval="value"): every leaf's value and priors are
         the network's mean over the leaf's images under them (VecEnv.evaluate(symmetries=...)).  Every
-        rollout is then a round — select_batch, evaluate, backup_batch — a round of one leaf where leaves == 1."""
+        rollout is then a round — select_batch, evaluate, backup_batch — a round of one leaf where leaves == 1.
+        root_policy="gumbel" (needs leaf_eval="value"): the root considers max_considered actions drawn with Gumbel noise
+        and halves them down over the budget of a contemplate(); sigma(q) = (c_visit + max N) * c_scale * q weighs the
+        completed Q against the logits.  root_policy="puct" is the search as it always was."""
         self.leaves, self.virtual_loss = self.check_search_args(leaf_eval, net, leaves, virtual_loss)
+        self.root_policy, self.max_considered, self.c_visit, self.c_scale = self.check_root_args(
+            leaf_eval, net, root_policy, max_considered, c_visit, c_scale)
         self.eval_symmetries = self.check_eval_symmetries(leaf_eval, eval_symmetries)
         self.leaf_eval = leaf_eval
         self.num_games, self.capacity = int(num_games), int(capacity)
@@ -89,6 +105,9 @@ class TreeSearch(LibCaller):
         self._scratch = None          # compact()'s forwarding table, allocated by its first call
         self._rounds = {}             # k -> the buffers of a round of k leaves per game, allocated by its first round
         self._fresh = True            # no contemplate since the last reset() or sync(): the root may lack priors
+        self.gumbel_idx = 0           # Gumbel begins since the last reset: what addresses their draws
+        self._gumbel = None           # the Gumbel root's buffers, allocated by its first begin
+        self._tables = {}             # n -> the visit table i32[37, n] of a budget of n simulations, on the device
 
     # ------------------------------------------------------------------ helpers
     @staticmethod
@@ -107,6 +126,22 @@ class TreeSearch(LibCaller):
         if not 0.0 <= virtual_loss < float("inf"):
             raise ValueError("virtual_loss must be finite and >= 0")
         return leaves, virtual_loss
+
+    @staticmethod
+    def check_root_args(leaf_eval, net, root_policy, max_considered, c_visit, c_scale):
+        """The constructors' check of the root's rule; returns (root_policy, max_considered, c_visit, c_scale)."""
+        if root_policy not in TreeSearch.ROOT_POLICIES:
+            raise ValueError("root_policy must be one of %s" % (TreeSearch.ROOT_POLICIES,))
+        max_considered, c_visit, c_scale = int(max_considered), float(c_visit), float(c_scale)
+        if root_policy == "gumbel" and (leaf_eval != "value" or net is None):
+            raise ValueError('root_policy="gumbel" needs a net and leaf_eval="value"')
+        if not 1 <= max_considered <= 36:
+            raise ValueError("max_considered must be in 1..36")
+        if not 0.0 <= c_visit < float("inf"):
+            raise ValueError("c_visit must be finite and >= 0")
+        if not abs(c_scale) < float("inf"):
+            raise ValueError("c_scale must be finite")
+        return root_policy, max_considered, c_visit, c_scale
 
     @staticmethod
     def check_eval_symmetries(leaf_eval, eval_symmetries):
@@ -140,11 +175,15 @@ class TreeSearch(LibCaller):
         self._check_env(env)
         self._call("qttt_tree_reset", self.tree.data_ptr(), self.num_games, self.capacity, env.state.data_ptr())
         self.rollout_idx, self.noise_idx, self._bound, self._fresh = 0, 0, 1, True
+        self.gumbel_idx = 0
 
     def contemplate(self, rollouts):
         """`rollouts` x MCTS._rollout (mcts.py:166-176) in every game.  With leaves = K > 1 they are taken K at a time:
         after a reset() or sync() one single rollout first (K descents would all end on a root without priors), then
-        rounds of K and one shorter round for what is left.  Without eval_symmetries the calls are what they always were."""
+        rounds of K and one shorter round for what is left.  Without eval_symmetries the calls are what they always were.
+        root_policy="gumbel": after that single rollout (the root needs its priors to be descended from) the roots are
+        evaluated, the Gumbel state of the move is drawn for the budget n = the rollouts that remain, and the rounds go
+        through the Gumbel select; every contemplate() is one budget of its own."""
         r = int(rollouts)
         if r < 0:
             raise ValueError("rollouts must be >= 0")
@@ -157,6 +196,24 @@ class TreeSearch(LibCaller):
                              % (r, self._bound + 2 * r, self.capacity))
         # a single rollout: the fused value rollout, or — under eval_symmetries — a round of one leaf
         single = self._rollout if self.eval_symmetries is None else (lambda: self._round(1))
+        if self.root_policy == "gumbel":
+            if r and self._fresh:
+                single()
+                self._bound += 2
+                r -= 1
+                self._fresh = False
+            if r:
+                if self.gumbel_idx >= _native.TREE_MAX_GUMBEL:
+                    raise ValueError("%d Gumbel roots since reset: the bound is %d (draw indices)"
+                                     % (self.gumbel_idx, _native.TREE_MAX_GUMBEL))
+                self._gumbel_begin(r)
+            elif self._gumbel is not None:
+                self._gumbel["n"] = 0     # no budget: no Gumbel state of this root
+            K = self.leaves
+            for k in [K] * (r // K) + [r % K] * (r % K > 0):
+                self._gumbel_round(k)
+                self._bound += 2 * k
+            return
         if self.leaves == 1:
             for _ in range(r):
                 single()
@@ -204,6 +261,68 @@ class TreeSearch(LibCaller):
                    b["out"]["probs"].data_ptr())
         self.rollout_idx += k
 
+    def _gumbel_buffers(self):
+        g = self._gumbel
+        if g is None:
+            G, dev = self.num_games, self.device
+            nbytes = int(self._lib.qttt_tree_gumbel_bytes(G))
+            if nbytes < 0:
+                raise ValueError("qttt_tree_gumbel_bytes(%d) failed" % G)
+            state = torch.zeros(int(self._lib.qttt_state_bytes(G)), dtype=torch.uint8, device=dev)
+            g = self._gumbel = {"root": VecEnv.from_state(state, G, seed=self.seed, board_offset=self.board_offset),
+                                "rec": torch.zeros(max(nbytes, 16), dtype=torch.uint8, device=dev),
+                                "out": out_rows(VecEnv._EVAL_ROWS, G, dev, keys=("value", "logits")),
+                                "n": 0, "sim": 0, "table": None}
+        return g
+
+    def _visit_table(self, n):
+        """The visit table i32[37, n] of a budget of n simulations (qttt_gumbel_visit_sequence), on the device."""
+        t = self._tables.get(n)
+        if t is None:
+            host = torch.empty((37, n), dtype=torch.int32)
+            for m in range(37):
+                _native.check(self._lib.qttt_gumbel_visit_sequence(m, n, host[m].data_ptr()), "qttt_gumbel_visit_sequence")
+            t = self._tables[n] = host.to(self.device)
+        return t
+
+    def _gumbel_begin(self, n):
+        """The Gumbel state of a move with a budget of n simulations, without contemplate's bounds: the roots' states,
+        their evaluation (value and masked logits, over eval_symmetries), qttt_tree_gumbel_begin."""
+        n = int(n)
+        if self.root_policy != "gumbel" or n < 1:
+            raise ValueError('a Gumbel root needs root_policy="gumbel" and a budget >= 1')
+        g = self._gumbel_buffers()
+        G, cap, tree = self.num_games, self.capacity, self.tree.data_ptr()
+        g["table"], g["n"], g["sim"] = self._visit_table(n), n, 0
+        self._call("qttt_tree_root_states", tree, G, cap, g["root"].state.data_ptr())
+        g["root"].evaluate(self.net, out=g["out"], symmetries=self.eval_symmetries)
+        self._call("qttt_tree_gumbel_begin", tree, G, cap, self.seed, self.gumbel_idx, self.board_offset, self.max_considered,
+                   g["out"]["value"].data_ptr(), g["out"]["logits"].data_ptr(), g["rec"].data_ptr())
+        self.gumbel_idx += 1
+
+    def _gumbel_round(self, k):
+        """One round of k simulations of the budget that the last _gumbel_begin opened: _round(k) with the Gumbel select."""
+        k, g = int(k), self._gumbel
+        if g is None or not 1 <= k <= _native.TREE_MAX_LEAVES or g["sim"] + k > g["n"]:
+            raise ValueError("a Gumbel round holds 1..%d leaves within the budget of the last begin" % _native.TREE_MAX_LEAVES)
+        b = self._round_buffers(k)
+        G, cap, tree = self.num_games, self.capacity, self.tree.data_ptr()
+        self._call("qttt_tree_select_batch_gumbel", tree, G, cap, self.seed, self.rollout_idx, k, self.board_offset,
+                   self.c_puct, self.virtual_loss, b["paths"].data_ptr(), b["leaf"].state.data_ptr(), g["rec"].data_ptr(),
+                   g["table"].data_ptr(), g["n"], g["sim"], self.c_visit, self.c_scale)
+        b["leaf"].evaluate(self.net, out=b["out"], symmetries=self.eval_symmetries)
+        self._call("qttt_tree_backup_batch", tree, G, cap, k, b["paths"].data_ptr(), b["out"]["value"].data_ptr(),
+                   b["out"]["probs"].data_ptr())
+        self.rollout_idx += k
+        g["sim"] += k
+
+    def _gumbel_root(self, choose=None, pi=None, q_completed=None):
+        self._need_reset()
+        if self._gumbel is None or self._gumbel["n"] == 0:
+            raise RuntimeError("contemplate() first: the Gumbel root has no state yet")
+        self._call("qttt_tree_gumbel_root", self.tree.data_ptr(), self._gumbel["rec"].data_ptr(), self.num_games,
+                   self.capacity, self.c_visit, self.c_scale, _ptr(choose), _ptr(pi), _ptr(q_completed))
+
     def _rollout(self):
         """One rollout, without contemplate's bounds: select, the playouts from the leaves, backup; or select and the
         value rollout."""
@@ -249,10 +368,14 @@ class TreeSearch(LibCaller):
 
     def root_stats(self):
         """The roots' statistics: N i32[G,36], W / Q / P f64[G,36], Ntot i32[G], choose u8[G], nodes_used i32[G],
-        overflow bool[G]."""
+        overflow bool[G].  root_policy="gumbel": choose is the Gumbel choice, and pi f64[G,36] (the improved policy) and
+        q_completed f64[G,36] are there too."""
         o = out_rows(self._ROOT_ROWS, self.num_games, self.device)
         self._root(**o)
         o["overflow"] = o["overflow"].bool()
+        if self.root_policy == "gumbel":
+            o.update(out_rows(self._GUMBEL_ROWS, self.num_games, self.device))
+            self._gumbel_root(o["choose"], o["pi"], o["q_completed"])
         return o
 
     def _root(self, N=None, W=None, Q=None, P=None, Ntot=None, choose=None, nodes_used=None, overflow=None):
@@ -263,7 +386,10 @@ class TreeSearch(LibCaller):
     def choose(self):
         """MCTS.choose (mcts.py:308-315) per game: action36 u8[G], 255 where the root has no legal action."""
         a = out_tensor(*self._ROOT_ROWS["choose"], self.num_games, self.device)
-        self._root(choose=a)
+        if self.root_policy == "gumbel":      # the best survivor of the halving (255 also at a terminal root)
+            self._gumbel_root(choose=a)
+        else:
+            self._root(choose=a)
         return a
 
     def nodes_used(self):
@@ -282,6 +408,8 @@ class TreeSearch(LibCaller):
         self._call("qttt_tree_sync", self.tree.data_ptr(), self.num_games, self.capacity, env.state.data_ptr())
         self._bound += 1
         self._fresh = True
+        if self._gumbel is not None:
+            self._gumbel["n"] = 0     # the Gumbel state belonged to the root that was left
 
     def compact(self, update_bound=True):
         """MCTS._prune as sync does it (mcts.py:222-231, 330-337): every game keeps the nodes reachable from its root,
