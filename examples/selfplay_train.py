@@ -8,7 +8,7 @@ the new weights for the search and repeats.
                                       [--dtype f32|bf16] [--out model.pt] [--model model.pt] [--value-targets 1,0]
                                       [--symmetries] [--leaf-eval playouts|value]
                                       [--root-noise EPS,ALPHA] [--temperature T] [--sample-plies K] [--leaves K]
-                                      [--eval-symmetries all|0,4]
+                                      [--eval-symmetries all|0,4] [--replay CAPACITY --batch B --steps S]
 
 The network is nn.Model's (nn.py:7-28) under its own parameter names (qtttgym_amd.policy_value.SHAPES), so --out is a
 state dict that the reference, PolicyValueNet and examples/tree_tournament.py --model all load.  The loss is the
@@ -27,6 +27,11 @@ AlphaZero's root exploration (SelfPlay(root_noise=, temperature=, sample_plies=)
 by virtual loss (SelfPlay(leaves=K)): one network launch per round evaluates games * K leaves.  --eval-symmetries all
 (or a list of 1, 2, 4 or 8 symmetries such as 0,4; with --leaf-eval value) searches with the network's outputs averaged
 over every leaf's images (SelfPlay(eval_symmetries=...)): a search that treats mirrored positions alike.
+--replay CAPACITY keeps a window of the last CAPACITY samples on the device (qtttgym_amd.ReplayBuffer) instead of training
+on the latest run's games only: every run appends its games to the ring and trains --steps minibatches of --batch samples
+drawn from it, each sample under a random symmetry of the board.  ReplayBuffer.add and .sample themselves never wait for
+the host; the loss below (its boolean indexing) and the printed counts do.  --epochs and --symmetries are the full-batch
+path's and are not used with it.
 """
 import argparse
 import os
@@ -35,7 +40,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from qtttgym_amd import PolicyValueNet, SelfPlay  # noqa: E402
+from qtttgym_amd import PolicyValueNet, ReplayBuffer, SelfPlay  # noqa: E402
 from qtttgym_amd import recommended_env  # noqa: E402
 from qtttgym_amd.policy_value import HIDDEN, SHAPES  # noqa: E402
 recommended_env(apply=True)
@@ -69,6 +74,17 @@ def loss_terms(net, s, pi, mask, v_target, done):
     return 0.5 * (v - v_target).pow(2), J.sum(-1)
 
 
+def train(model, optim, batches):
+    """One optimiser step on every (s, pi, mask, v_target, done) of `batches`; the last step's (L, J)."""
+    for samples in batches:
+        L, J = loss_terms(model, *samples)
+        loss = L.mean() + J.mean(0)
+        optim.zero_grad()
+        loss.backward()
+        optim.step()
+    return L, J
+
+
 def parse_eval_symmetries(spec):
     """--eval-symmetries: None, "all", or the comma-separated list as ints."""
     return spec if spec in (None, "all") else tuple(int(k) for k in spec.split(","))
@@ -100,8 +116,14 @@ def main():
                     help="gumbel: the Gumbel root, sequential halving over --max-considered actions; pi is then the "
                          "improved policy and the move the best survivor (needs --leaf-eval value; --rollouts of 16-32 do)")
     ap.add_argument("--max-considered", type=int, default=16, help="actions the Gumbel root samples (1..36)")
+    ap.add_argument("--replay", type=int, default=0, metavar="CAPACITY",
+                    help="train on minibatches drawn from a ring of the last CAPACITY samples (0: on the latest run's games)")
+    ap.add_argument("--batch", type=int, default=1024, help="with --replay: samples per minibatch")
+    ap.add_argument("--steps", type=int, default=50, help="with --replay: minibatch steps per run")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
+    if args.replay and (args.batch < 1 or args.steps < 1):
+        ap.error("--replay needs --batch >= 1 and --steps >= 1")
     torch.manual_seed(args.seed)
     dev = torch.device("cuda", torch.cuda.current_device())
     model = Net().to(dev)
@@ -116,21 +138,22 @@ def main():
                   temperature=args.temperature, sample_plies=args.sample_plies,
                   eval_symmetries=parse_eval_symmetries(args.eval_symmetries), root_policy=args.root_policy,
                   max_considered=args.max_considered)
+    ring = ReplayBuffer(args.replay, device=dev, seed=args.seed) if args.replay else None
     for run in range(args.runs):
         batch = sp.play()
-        s, pi, mask, v_target, done = (batch.augment() if args.symmetries else batch).flat()
         won = [int((batch.winner == w).sum()) for w in (1, 0, -1)]
-        for _ in range(args.epochs):
-            L, J = loss_terms(model, s, pi, mask, v_target, done)
-            loss = L.mean() + J.mean(0)
-            optim.zero_grad()
-            loss.backward()
-            optim.step()
-        print("run %d: %d samples of %d games (first player won %d, lost %d, drew %d); L: %.4f, J: %.4f"
-              % (run, len(s), args.games, won[0], won[1], won[2], L.mean().item(), J.mean().item()), flush=True)
+        if ring is not None:
+            ring.add(batch)
+            L, J = train(model, optim, (ring.sample(args.batch, "random") for _ in range(args.steps)))
+            what = "%d games appended, the ring holds %d samples; %d steps of %d" % (args.games, ring.size(), args.steps, args.batch)
+        else:
+            samples = (batch.augment() if args.symmetries else batch).flat()
+            L, J = train(model, optim, (samples for _ in range(args.epochs)))
+            what = "%d samples of %d games" % (len(samples[0]), args.games)
+        print("run %d: %s (first player won %d, lost %d, drew %d); L: %.4f, J: %.4f"
+              % (run, what, won[0], won[1], won[2], L.mean().item(), J.mean().item()), flush=True)
         net.load_state_dict(model)                           # the next run searches with the new weights
         torch.save(model.state_dict(), args.out)
-
 
 if __name__ == "__main__":
     main()

@@ -2,7 +2,8 @@
 
 Exports the reference package's four names (qtttgym/__init__.py:1-4) plus `VecEnv`, `PolicyValueNet` (the
 reference's nn.py network, evaluated on the GPU), `TreeSearch` (batched
-MCTS / AlphaZero search trees on the device), `SelfPlay` (self_play.py's games and training samples, batched) and the
+MCTS / AlphaZero search trees on the device), `SelfPlay` (self_play.py's games and training samples, batched),
+`ReplayBuffer` (the window of recent samples a trainer draws its minibatches from, on the device) and the
 36-action
 indexing L3 callers share (mcts.py:339-350)."""
 from .vec_env import VecEnv
@@ -13,6 +14,7 @@ from ._native import recommended_env, retire_mailbox
 from .policy_value import PolicyValueNet
 from .tree import TreeSearch
 from .selfplay import SelfPlay, SelfPlayBatch
+from .replay import ReplayBuffer
 
-__all__ = ["Board", "QEvalClassic", "displayBoard", "Env", "VecEnv", "PolicyValueNet", "TreeSearch", "SelfPlay", "SelfPlayBatch", "ind2move", "move2ind", "recommended_env",
+__all__ = ["Board", "QEvalClassic", "displayBoard", "Env", "VecEnv", "PolicyValueNet", "TreeSearch", "SelfPlay", "SelfPlayBatch", "ReplayBuffer", "ind2move", "move2ind", "recommended_env",
            "retire_mailbox"]

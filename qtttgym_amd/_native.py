@@ -156,6 +156,18 @@ TREE_GUMBEL_SIGNATURES = {
     "qttt_tree_gumbel_root": (_i32, [_vp, _vp, _i64, _i64, _f64, _f64, _vp, _vp, _vp, _vp]),
     "qttt_selfplay_record_gumbel": (_i32, SELFPLAY_SIGNATURES["qttt_selfplay_record"][1][:-1] + [_vp, _f64, _f64, _vp]),
 }
+# every symbol include/qttt_replay.h declares (the replay ring: append self-play, sample minibatches; qttt.h includes it)
+REPLAY_MAX_CAPACITY = 1 << 30
+REPLAY_MAX_GAMES = 1 << 30
+REPLAY_SCAN_BLOCK = 256
+REPLAY_ARRAYS = ("P", "Q", "pi", "mask", "v", "done")          # the order of qttt_replay_layout's offsets
+REPLAY_SIGNATURES = {
+    "qttt_replay_bytes": (_i64, [_i64]),
+    "qttt_replay_layout": (_i32, [_i64, ctypes.POINTER(ctypes.c_int64)]),
+    "qttt_replay_append_scratch_bytes": (_i64, [_i64]),
+    "qttt_replay_append": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qttt_replay_sample": (_i32, [_vp, _i64, _i64, _u64, _u32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
 
 _lib = None
 
@@ -222,7 +234,8 @@ def lib():
                                   + list(TREE_COMPACT_SIGNATURES.items()) + list(SELFPLAY_SIGNATURES.items())
                                   + list(SYMMETRY_SIGNATURES.items()) + list(TREE_VALUE_SIGNATURES.items())
                                   + list(TREE_EXPLORE_SIGNATURES.items()) + list(TREE_LEAVES_SIGNATURES.items())
-                                  + list(NN_SYMMETRIC_SIGNATURES.items()) + list(TREE_GUMBEL_SIGNATURES.items())):
+                                  + list(NN_SYMMETRIC_SIGNATURES.items()) + list(TREE_GUMBEL_SIGNATURES.items())
+                                  + list(REPLAY_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -55,7 +55,9 @@
 // qttt_tree_value_kernels.h (the value rollout: network evaluation of the leaves and backup in one launch);
 // qttt_tree_leaves_kernels.h (leaf-parallel rounds: K descents per game under virtual loss, and their backup);
 // qttt_tree_explore_kernels.h (root exploration: Dirichlet noise on the roots' priors, the sampled move);
-// qttt_tree_gumbel_kernels.h (the Gumbel root: considered actions, sequential halving, the improved policy).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
+// qttt_tree_gumbel_kernels.h (the Gumbel root: considered actions, sequential halving, the improved policy);
+// qttt_replay_kernels.h (the replay ring: the append's scan and move, the sampled minibatch) with qttt_replay_host.h (host
+// only and free of HIP: the ring's layout, the scan plan, the argument checks).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
 // qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
@@ -73,6 +75,7 @@
 #include "qttt_tree_value_kernels.h"
 #include "qttt_tree_leaves_kernels.h"
 #include "qttt_tree_gumbel_kernels.h"
+#include "qttt_replay_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -996,6 +999,67 @@ int qttt_selfplay_record_gumbel(const void *tree, int64_t games, int64_t capacit
     const SelfPlaySampling<RECORD_GUMBEL> s = {static_cast<const GumbelRec *>(rec), c_visit, c_scale};
     return launch(selfplay_record_kernel<RECORD_GUMBEL>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
                   capacity, ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
+}
+
+// ---------------------------------------------------------------- the replay ring (include/qttt_replay.h)
+int64_t qttt_replay_bytes(int64_t capacity) {
+    return replay_capacity_bad(capacity) ? (int64_t)QTTT_ERR_SIZE : replay_layout(capacity).bytes;
+}
+
+int qttt_replay_layout(int64_t capacity, int64_t *offsets) {
+    if (replay_capacity_bad(capacity)) return QTTT_ERR_SIZE;
+    if (!offsets) return QTTT_ERR_NULL;
+    const ReplayLayout l = replay_layout(capacity);
+    for (int k = 0; k < 6; ++k) offsets[k] = l.off[k];
+    return 0;
+}
+
+int64_t qttt_replay_append_scratch_bytes(int64_t games) {
+    return replay_games_bad(games) ? (int64_t)QTTT_ERR_SIZE : replay_scan_plan(games).words * 8;
+}
+
+int qttt_replay_append(void *replay, int64_t capacity, int64_t games, const void *states, const double *pi,
+                       const uint8_t *mask, const uint8_t *done, const float *v, const uint8_t *length, void *scratch,
+                       void *stream) {
+    bool work;
+    if (const int rc = replay_append_check(replay, capacity, games, states, pi, mask, done, v, length, scratch, work)) return rc;
+    if (!work) return 0;
+    const ReplayRing ring = replay_ring(replay, capacity);
+    const ReplayScanPlan plan = replay_scan_plan(games);
+    u64 *words = static_cast<u64 *>(scratch);
+    ReplayRanks rk = {};
+    for (int k = 0; k < plan.levels; ++k) {
+        const int64_t grid = plan.n[k + 1];                      // one workgroup per total of the next level
+        u64 *arr = words + plan.off[k], *totals = words + plan.off[k + 1];
+        const int rc = k == 0 ? launch(replay_scan_kernel<true>, grid, QTTT_REPLAY_SCAN_BLOCK, stream, length, arr, totals, plan.n[k],
+                                       (const u64 *)ring.header, words)
+                              : launch(replay_scan_kernel<false>, grid, QTTT_REPLAY_SCAN_BLOCK, stream, length, arr, totals, plan.n[k],
+                                       (const u64 *)ring.header, words);
+        if (rc) return rc;
+        rk.excl[k] = arr;
+    }
+    rk.total = words + plan.off[plan.levels];
+    rk.written0 = words;
+    rk.levels = (u32)plan.levels;
+    return launch(replay_append_kernel, ceil_div(games, REPLAY_APPEND_GAMES), REPLAY_APPEND_BLOCK, stream, ring, capacity, games,
+                  static_cast<const u64 *>(states), reinterpret_cast<const u64 *>(pi), mask, done, reinterpret_cast<const u32 *>(v),
+                  length, rk);
+}
+
+int qttt_replay_sample(const void *replay, int64_t capacity, int64_t n, uint64_t seed, uint32_t draw, const uint8_t *sym,
+                       int random_symmetry, float *s_out, double *pi_out, uint8_t *mask_out, float *v_out,
+                       uint8_t *done_out, int32_t *index_out, uint8_t *sym_out, void *stream) {
+    bool work;
+    if (const int rc = replay_sample_check(replay, capacity, n, draw, s_out, pi_out, mask_out, v_out, done_out, index_out, work))
+        return rc;
+    if (!work) return 0;
+    const ReplayRing ring = replay_ring(const_cast<void *>(replay), capacity);
+    const u64 key_slot = launch_key(seed, draw), key_sym = launch_key(seed, draw | 0x80000000u);
+    return with_bools([&](auto SYM) {
+        return launch(replay_sample_kernel<SYM>, ceil_div(n, REPLAY_TILE), REPLAY_SAMPLE_BLOCK, stream, ring, capacity, n, key_slot,
+                      key_sym, sym, (u32)(random_symmetry != 0), s_out, reinterpret_cast<u64 *>(pi_out), mask_out,
+                      reinterpret_cast<u32 *>(v_out), done_out, index_out, sym_out);
+    }, sym != nullptr || random_symmetry != 0);
 }
 
 }  // extern "C"

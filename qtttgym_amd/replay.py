@@ -1,0 +1,115 @@
+"""ReplayBuffer — the window of recent self-play samples an AlphaZero-style trainer draws its minibatches from, on the
+device (include/qttt_replay.h): a ring of `capacity` samples that SelfPlayBatches are appended to in
+flat()'s order without a host read-back, and that one launch samples from with an optional random symmetry per sample.
+
+    rb = ReplayBuffer(1 << 20)
+    rb.add(sp.play())                                     # no host synchronisation
+    s, pi, mask, v, done = rb.sample(4096, "random")      # the trainer's tensors, one launch
+
+Loss, gradients and the optimiser stay ordinary torch (examples/selfplay_train.py --replay).
+"""
+import ctypes
+
+import torch
+
+from . import _native
+from ._host import LibCaller, _ptr, check_tensor, resolve_device
+from .selfplay import ROWS, SelfPlayBatch
+
+_MAX_DRAW = 1 << 31
+# the ring's arrays as torch sees them (torch has no arithmetic on uint64: the words travel as int64)
+_VIEWS = {"P": (torch.int64, 8, ()), "Q": (torch.int64, 8, ()), "pi": (torch.float64, 8, (36,)),
+          "mask": (torch.int64, 8, ()), "v": (torch.float32, 4, ()), "done": (torch.uint8, 1, ())}
+_OUT = (("s", torch.float32, (18, 10)), ("pi", torch.float64, (36,)), ("mask", torch.bool, (36,)), ("v", torch.float32, ()),
+        ("done", torch.bool, ()))
+
+
+class ReplayBuffer(LibCaller):
+    """A ring of `capacity` training samples in device memory.  add(batch) appends a SelfPlayBatch's samples (the rows
+    below every game's length, game-major: flat()'s order); once the ring is full the oldest samples are overwritten.
+    sample(n, symmetries) draws n of the samples held, uniformly with replacement, by the counter hash of (seed, the
+    number of sample() calls so far): the same seed and call number give the same minibatch."""
+
+    def __init__(self, capacity, device=None, seed=0):
+        self.capacity, self.seed = int(capacity), int(seed) & (2 ** 64 - 1)
+        if not 1 <= self.capacity <= _native.REPLAY_MAX_CAPACITY:
+            raise ValueError("capacity must be in 1..%d" % _native.REPLAY_MAX_CAPACITY)
+        self._open(resolve_device("cuda" if device is None else device, "ReplayBuffer"))
+        offsets = (ctypes.c_int64 * len(_native.REPLAY_ARRAYS))()
+        _native.check(self._lib.qttt_replay_layout(self.capacity, offsets), "qttt_replay_layout")
+        self.offsets = dict(zip(_native.REPLAY_ARRAYS, offsets))
+        self.buffer = torch.zeros(int(self._lib.qttt_replay_bytes(self.capacity)), dtype=torch.uint8, device=self.device)
+        self.draw = 0                   # sample() calls so far: the draw index of the next
+        self.adds = 0                   # add() calls that appended games
+        self.last_index = self.last_symmetry = None
+        self._scratch = None
+
+    def views(self):
+        """The ring's arrays as views of `buffer` (qttt_replay_layout): written i64[1], P, Q and mask i64[capacity] (the
+        u64 words), pi f64[capacity, 36], v f32[capacity], done u8[capacity]."""
+        C, out = self.capacity, {"written": self.buffer[:8].view(torch.int64)}
+        for name, (dtype, size, shape) in _VIEWS.items():
+            at, count = self.offsets[name], C * (36 if shape else 1)
+            out[name] = self.buffer[at:at + size * count].view(dtype).view((C,) + shape)
+        return out
+
+    def size(self):
+        """Samples held, min(written, capacity).  One host read-back."""
+        return min(int(self.views()["written"].item()), self.capacity)
+
+    def add(self, batch):
+        """Appends the samples of a SelfPlayBatch (qttt_replay_append).  No host read-back; the batch is not changed."""
+        G, dev = batch.num_games, self.device
+        check_tensor(batch.states, torch.uint8, (ROWS, int(self._lib.qttt_state_bytes(G))), dev, "batch.states")
+        for k in ("pi", "mask", "done", "v"):
+            dt, shp = SelfPlayBatch._ROWS[k]
+            check_tensor(getattr(batch, k), dt, (ROWS, G) + shp, dev, "batch." + k)
+        check_tensor(batch.length, torch.uint8, (G,), dev, "batch.length")
+        if G == 0:
+            return
+        need = int(self._lib.qttt_replay_append_scratch_bytes(G))
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        self._call("qttt_replay_append", self.buffer.data_ptr(), self.capacity, G, batch.states.data_ptr(), batch.pi.data_ptr(),
+                   batch.mask.data_ptr(), batch.done.data_ptr(), batch.v.data_ptr(), batch.length.data_ptr(),
+                   self._scratch.data_ptr())
+        self.adds += 1
+
+    def sample(self, n, symmetries=None, out=None):
+        """A minibatch (s f32[n, 18, 10], pi f64[n, 36], mask bool[n, 36], v f32[n], done bool[n]) of samples drawn from
+        the ring, one launch (qttt_replay_sample).  symmetries: None = the samples as stored; "random" = every sample
+        under a symmetry of its own, drawn by the hash; a uint8 tensor [n] = sample i under symmetries[i] (a value past 7:
+        the identity).  out: the five tensors of an earlier call, to be written again.  The slots and symmetries drawn
+        are kept as last_index i32[n] and last_symmetry u8[n].  Raises before any add() of games: that is the host's count
+        of add() calls, because `written` lives on the device and sample() reads nothing back.  What the ring holds is
+        decided on the device: after adds whose games all had length 0 the rows are zero and last_index is -1, as the C
+        entry gives for an empty ring."""
+        n, dev = int(n), self.device
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        if self.adds == 0:
+            raise ValueError("sample() before any add(): the ring is empty")
+        if self.draw >= _MAX_DRAW:
+            raise ValueError("the draw counter is exhausted (2**31 sample() calls): take a new seed")
+        sym, random_symmetry = None, 0
+        if isinstance(symmetries, str):
+            if symmetries != "random":
+                raise ValueError('symmetries must be None, "random" or a uint8 tensor')
+            random_symmetry = 1
+        elif symmetries is not None:
+            sym = check_tensor(symmetries, torch.uint8, (n,), dev, "symmetries")
+        if out is None:                 # mask and done: u8 outputs of the kernel (0 / 1), handed out as bool views
+            out = tuple(torch.empty((n,) + shp, dtype=torch.uint8 if dt == torch.bool else dt, device=dev).view(dt)
+                        for _, dt, shp in _OUT)
+        elif len(out) != len(_OUT):
+            raise ValueError("out must hold the %d tensors sample() returns" % len(_OUT))
+        else:
+            for t, (name, dt, shp) in zip(out, _OUT):
+                check_tensor(t, dt, (n,) + shp, dev, "out." + name)
+        index = torch.empty(n, dtype=torch.int32, device=dev)
+        k = torch.empty(n, dtype=torch.uint8, device=dev)
+        self._call("qttt_replay_sample", self.buffer.data_ptr(), self.capacity, n, self.seed, self.draw, _ptr(sym),
+                   random_symmetry, *[t.data_ptr() for t in out], index.data_ptr(), k.data_ptr())
+        self.draw += 1
+        self.last_index, self.last_symmetry = index, k
+        return tuple(out)
