@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """The reference's self_play.py main loop (self_play.py:176-242) with the games on the device: every run plays --games
 games of AlphaZero self-play under the current weights (qtttgym_amd.SelfPlay: the search trees, the moves and the
-training samples never leave the GPU), trains the policy/value network on the batch with ordinary torch autograd, packs
-the new weights for the search and repeats.
+training samples never leave the GPU), trains the policy/value network on the batch with ordinary torch autograd (or,
+with --device-train, on the device), packs the new weights for the search and repeats.
 
     python examples/selfplay_train.py [--games 1024] [--rollouts 100] [--sims 10] [--epochs 50] [--runs 30]
                                       [--dtype f32|bf16] [--out model.pt] [--model model.pt] [--value-targets 1,0]
                                       [--symmetries] [--leaf-eval playouts|value]
                                       [--root-noise EPS,ALPHA] [--temperature T] [--sample-plies K] [--leaves K]
                                       [--eval-symmetries all|0,4] [--replay CAPACITY --batch B --steps S]
+                                      [--device-train]
 
 The network is nn.Model's (nn.py:7-28) under its own parameter names (qtttgym_amd.policy_value.SHAPES), so --out is a
 state dict that the reference, PolicyValueNet and examples/tree_tournament.py --model all load.  The loss is the
@@ -32,6 +33,9 @@ on the latest run's games only: every run appends its games to the ring and trai
 drawn from it, each sample under a random symmetry of the board.  ReplayBuffer.add and .sample themselves never wait for
 the host; the loss below (its boolean indexing) and the printed counts do.  --epochs and --symmetries are the full-batch
 path's and are not used with it.
+--device-train takes the training step to the device as well (qtttgym_amd.Trainer): the loss, its gradients and the
+AMSGrad step run as HIP kernels on the packed weights that the search reads, so there is no autograd, no torch optimiser
+and no repacking of the weights between runs; --out is then the trainer's state dict.
 """
 import argparse
 import os
@@ -40,7 +44,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from qtttgym_amd import PolicyValueNet, ReplayBuffer, SelfPlay  # noqa: E402
+from qtttgym_amd import PolicyValueNet, ReplayBuffer, SelfPlay, Trainer  # noqa: E402
 from qtttgym_amd import recommended_env  # noqa: E402
 from qtttgym_amd.policy_value import HIDDEN, SHAPES  # noqa: E402
 recommended_env(apply=True)
@@ -85,6 +89,14 @@ def train(model, optim, batches):
     return L, J
 
 
+def train_on_device(trainer, batches):
+    """The same with qtttgym_amd.Trainer: one step() per batch, no host synchronisation; the last step's (L, J), J over the
+    samples that are not terminal as loss_terms gives it."""
+    for samples in batches:
+        L, J = trainer.step(*samples)
+    return L, J[~samples[4]]
+
+
 def parse_eval_symmetries(spec):
     """--eval-symmetries: None, "all", or the comma-separated list as ints."""
     return spec if spec in (None, "all") else tuple(int(k) for k in spec.split(","))
@@ -120,6 +132,8 @@ def main():
                     help="train on minibatches drawn from a ring of the last CAPACITY samples (0: on the latest run's games)")
     ap.add_argument("--batch", type=int, default=1024, help="with --replay: samples per minibatch")
     ap.add_argument("--steps", type=int, default=50, help="with --replay: minibatch steps per run")
+    ap.add_argument("--device-train", action="store_true",
+                    help="loss, gradients and the optimiser on the device, on the search's packed weights (Trainer)")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     if args.replay and (args.batch < 1 or args.steps < 1):
@@ -139,21 +153,27 @@ def main():
                   eval_symmetries=parse_eval_symmetries(args.eval_symmetries), root_policy=args.root_policy,
                   max_considered=args.max_considered)
     ring = ReplayBuffer(args.replay, device=dev, seed=args.seed) if args.replay else None
+    trainer = Trainer(model, device=dev, net=net) if args.device_train else None      # nn.py:27's defaults
+    if trainer is not None:
+        fit, save = (lambda batches: train_on_device(trainer, batches)), trainer.state_dict
+    else:
+        fit, save = (lambda batches: train(model, optim, batches)), model.state_dict
     for run in range(args.runs):
         batch = sp.play()
         won = [int((batch.winner == w).sum()) for w in (1, 0, -1)]
         if ring is not None:
             ring.add(batch)
-            L, J = train(model, optim, (ring.sample(args.batch, "random") for _ in range(args.steps)))
+            L, J = fit(ring.sample(args.batch, "random") for _ in range(args.steps))
             what = "%d games appended, the ring holds %d samples; %d steps of %d" % (args.games, ring.size(), args.steps, args.batch)
         else:
             samples = (batch.augment() if args.symmetries else batch).flat()
-            L, J = train(model, optim, (samples for _ in range(args.epochs)))
+            L, J = fit(samples for _ in range(args.epochs))
             what = "%d samples of %d games" % (len(samples[0]), args.games)
         print("run %d: %s (first player won %d, lost %d, drew %d); L: %.4f, J: %.4f"
               % (run, what, won[0], won[1], won[2], L.mean().item(), J.mean().item()), flush=True)
-        net.load_state_dict(model)                           # the next run searches with the new weights
-        torch.save(model.state_dict(), args.out)
+        if trainer is None:
+            net.load_state_dict(model)                       # the next run searches with the new weights
+        torch.save(save(), args.out)
 
 if __name__ == "__main__":
     main()

@@ -339,8 +339,8 @@ uint64_t qttt_hash(uint64_t seed, uint64_t board_id, uint32_t step_idx);
  * self-play record in qttt_selfplay.h, the board's symmetries in qttt_symmetry.h, the value rollout of the trees in
  * qttt_tree_value.h, their leaf-parallel rounds in qttt_tree_leaves.h and root exploration (qttt_tree_root_noise,
  * qttt_selfplay_record_sampled) in qttt_tree_explore.h, and the network averaged over a position's symmetries in
- * qttt_nn_symmetric.h, the Gumbel root in qttt_tree_gumbel.h and the replay ring in qttt_replay.h, included here so that
- * this one header gives a C caller the whole library. */
+ * qttt_nn_symmetric.h, the Gumbel root in qttt_tree_gumbel.h, the replay ring in qttt_replay.h and the training step in
+ * qttt_train.h, included here so that this one header gives a C caller the whole library. */
 #include "qttt_nn.h"
 #include "qttt_policy_rollout.h"
 #include "qttt_tree.h"
@@ -353,4 +353,5 @@ uint64_t qttt_hash(uint64_t seed, uint64_t board_id, uint32_t step_idx);
 #include "qttt_nn_symmetric.h"
 #include "qttt_tree_gumbel.h"
 #include "qttt_replay.h"
+#include "qttt_train.h"
 #endif

@@ -168,6 +168,15 @@ REPLAY_SIGNATURES = {
     "qttt_replay_append": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qttt_replay_sample": (_i32, [_vp, _i64, _i64, _u64, _u32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# every symbol include/qttt_train.h declares (the training step: loss, gradients, AMSGrad on the f32 blob; qttt.h includes it)
+TRAIN_CHUNK = 256
+TRAIN_MAX_SAMPLES = 1 << 24
+_f32 = ctypes.c_float
+TRAIN_SIGNATURES = {
+    "qttt_train_workspace_bytes": (_i64, [_i64]),
+    "qttt_train_gradients": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qttt_train_adam": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
+}
 
 _lib = None
 
@@ -235,7 +244,7 @@ def lib():
                                   + list(SYMMETRY_SIGNATURES.items()) + list(TREE_VALUE_SIGNATURES.items())
                                   + list(TREE_EXPLORE_SIGNATURES.items()) + list(TREE_LEAVES_SIGNATURES.items())
                                   + list(NN_SYMMETRIC_SIGNATURES.items()) + list(TREE_GUMBEL_SIGNATURES.items())
-                                  + list(REPLAY_SIGNATURES.items())):
+                                  + list(REPLAY_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

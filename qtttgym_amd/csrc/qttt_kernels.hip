@@ -57,7 +57,9 @@
 // qttt_tree_explore_kernels.h (root exploration: Dirichlet noise on the roots' priors, the sampled move);
 // qttt_tree_gumbel_kernels.h (the Gumbel root: considered actions, sequential halving, the improved policy);
 // qttt_replay_kernels.h (the replay ring: the append's scan and move, the sampled minibatch) with qttt_replay_host.h (host
-// only and free of HIP: the ring's layout, the scan plan, the argument checks).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
+// only and free of HIP: the ring's layout, the scan plan, the argument checks);
+// qttt_train_kernels.h (the training step: loss, gradients and AMSGrad on the packed f32 blob, on qttt_nn_kernels.h's layers)
+// with qttt_train_host.h (host only and free of HIP: the workspace layout and the launch plan).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
 // qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
@@ -76,6 +78,7 @@
 #include "qttt_tree_leaves_kernels.h"
 #include "qttt_tree_gumbel_kernels.h"
 #include "qttt_replay_kernels.h"
+#include "qttt_train_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -1060,6 +1063,50 @@ int qttt_replay_sample(const void *replay, int64_t capacity, int64_t n, uint64_t
                       key_sym, sym, (u32)(random_symmetry != 0), s_out, reinterpret_cast<u64 *>(pi_out), mask_out,
                       reinterpret_cast<u32 *>(v_out), done_out, index_out, sym_out);
     }, sym != nullptr || random_symmetry != 0);
+}
+
+// ---------------------------------------------------------------- the training step (include/qttt_train.h)
+int64_t qttt_train_workspace_bytes(int64_t n) { return train_samples_bad(n) ? -1 : train_plan(n).bytes; }
+
+int qttt_train_gradients(const float *s, const double *pi, const uint8_t *mask, const float *v, const uint8_t *done,
+                         int64_t n, const void *weights, void *grads, float *L, float *J, void *workspace, void *stream) {
+    if (train_samples_bad(n)) return QTTT_ERR_SIZE;
+    if (any_null(s, pi, mask, v, done) || any_null(weights, grads, workspace)) return QTTT_ERR_NULL;
+    if (misaligned(weights, 16) || misaligned(grads, 16) || misaligned(workspace, 256) || misaligned(pi, 8) ||
+        misaligned(s, 4) || misaligned(v, 4) || misaligned(L, 4) || misaligned(J, 4))
+        return QTTT_ERR_ACTION;
+    const TrainPlan p = train_plan(n);
+    char *ws = static_cast<char *>(workspace);
+    const auto f32_at = [&](int64_t off) { return reinterpret_cast<float *>(ws + off); };
+    float *h[3] = {f32_at(p.h[0]), f32_at(p.h[1]), f32_at(p.h[2])}, *dz[3] = {f32_at(p.dz[0]), f32_at(p.dz[1]), f32_at(p.dz[2])};
+    float *dout = f32_at(p.dout), *partials = f32_at(p.partials);
+    u32 *n_keep = reinterpret_cast<u32 *>(ws + p.count);
+    const float *W = static_cast<const float *>(weights);
+    if (const int rc = launch(train_count_kernel, 1, QTTT_NN_BLOCK, stream, done, n, n_keep)) return rc;
+    if (const int rc = launch(train_forward_kernel, p.tiles, QTTT_NN_BLOCK, stream, s, pi, mask, v, done, n, W,
+                              (const u32 *)n_keep, h[0], h[1], h[2], dout, L, J))
+        return rc;
+    if (const int rc = launch(train_backward_kernel, p.tiles, QTTT_NN_BLOCK, stream, W, (const float *)dout, (const float *)h[0],
+                              (const float *)h[1], (const float *)h[2], dz[0], dz[1], dz[2], n))
+        return rc;
+    const TrainWgradArgs a = {{s, h[0], h[1], h[2]}, {dz[0], dz[1], dz[2], dout}};
+    if (const int rc = launch(train_wgrad_kernel, p.wgrad_groups, QTTT_NN_BLOCK, stream, a, n, partials)) return rc;
+    return launch(train_reduce_kernel, p.reduce_groups, QTTT_NN_BLOCK, stream, (const float *)partials, p.chunks,
+                  static_cast<float *>(grads));
+}
+
+int qttt_train_adam(void *weights, const void *grads, void *m, void *v2, void *vmax, int64_t step, float lr, float beta1,
+                    float beta2, float eps, float weight_decay, void *weights_bf16, void *stream) {
+    if (step < 1) return QTTT_ERR_SIZE;
+    if (any_null(weights, grads, m, v2, vmax)) return QTTT_ERR_NULL;
+    if (misaligned(weights, 16) || misaligned(grads, 16) || misaligned(m, 16) || misaligned(v2, 16) || misaligned(vmax, 16) ||
+        misaligned(weights_bf16, 16))
+        return QTTT_ERR_ACTION;
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)step), bc2 = 1.0 - std::pow((double)beta2, (double)step);
+    const TrainAdam h = {beta1, beta2, eps, weight_decay, (float)((double)lr / bc1), (float)std::sqrt(bc2)};
+    return launch(train_adam_kernel, ceil_div(TRAIN_BLOB_FLOATS, QTTT_NN_BLOCK), QTTT_NN_BLOCK, stream, static_cast<float *>(weights),
+                  static_cast<const float *>(grads), static_cast<float *>(m), static_cast<float *>(v2),
+                  static_cast<float *>(vmax), h, weights_bf16);
 }
 
 }  // extern "C"

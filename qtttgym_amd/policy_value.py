@@ -81,6 +81,39 @@ def pack_weights(sd, dtype=torch.float32):
     return torch.cat([weights.view(torch.uint8), biases.contiguous().view(torch.uint8)])
 
 
+def _matrix(frag, K, C, dtype):
+    """The inverse of _fragments: the fragment-ordered elements of one matrix -> B[K][C]."""
+    if dtype == torch.float32:
+        return frag.reshape(K // 4, C // 16, 4, 16).permute(0, 2, 1, 3).reshape(K, C)
+    return frag.reshape(K // 32, C // 16, 4, 16, 8).permute(0, 2, 4, 1, 3).reshape(K, C)
+
+
+def unpack_weights(blob, dtype=torch.float32):
+    """The inverse of pack_weights: the state dict (nn.Model's ten keys, f32 tensors on the blob's device) of a packed
+    blob of weights_bytes(dtype) bytes, given as a uint8 tensor or any contiguous tensor of that many bytes.  Torch ops
+    only; CPU tensors work.  A bf16 blob gives its weights widened to f32 (exactly), so
+    pack_weights(unpack_weights(blob, dtype), dtype) is the blob again as long as its pad elements are zero."""
+    _check_dtype(dtype)
+    raw = blob.detach().contiguous().view(torch.uint8).reshape(-1)
+    if raw.numel() != weights_bytes(dtype):
+        raise ValueError("a %s blob has %d bytes, not %d" % (dtype, weights_bytes(dtype), raw.numel()))
+    size = 4 if dtype == torch.float32 else 2
+    k1, mats, at = _K1[dtype], [], 0
+    for K, C in ((k1, HIDDEN), (HIDDEN, HIDDEN), (HIDDEN, HIDDEN), (HIDDEN, HEAD_COLS)):
+        mats.append(_matrix(raw[at:at + K * C * size].view(dtype), K, C, dtype).float())
+        at += K * C * size
+    biases = raw[at:].view(torch.float32)
+    w1, w2, w3, wh = mats
+    hb = biases[3 * HIDDEN:]
+    return {
+        "fc.0.weight": w1[:180].t().contiguous(), "fc.0.bias": biases[:HIDDEN].clone(),
+        "fc.2.weight": w2.t().contiguous(), "fc.2.bias": biases[HIDDEN:2 * HIDDEN].clone(),
+        "fc.4.weight": w3.t().contiguous(), "fc.4.bias": biases[2 * HIDDEN:3 * HIDDEN].clone(),
+        "V_head.1.weight": wh[:, 36:37].t().contiguous(), "V_head.1.bias": hb[36:37].clone(),
+        "pi_head.1.weight": wh[:, :36].t().contiguous(), "pi_head.1.bias": hb[:36].clone(),
+    }
+
+
 class PolicyValueNet:
     """The network of nn.py, packed once for the device: VecEnv.evaluate(net) runs it on every board of an
     environment in one kernel.  dtype torch.float32 (exact-f32 MFMA, the reference's numerics) or torch.bfloat16

@@ -6,7 +6,8 @@ flat()'s order without a host read-back, and that one launch samples from with a
     rb.add(sp.play())                                     # no host synchronisation
     s, pi, mask, v, done = rb.sample(4096, "random")      # the trainer's tensors, one launch
 
-Loss, gradients and the optimiser stay ordinary torch (examples/selfplay_train.py --replay).
+Loss, gradients and the optimiser are ordinary torch or qtttgym_amd.Trainer (examples/selfplay_train.py --replay
+[--device-train]).
 """
 import ctypes
 

@@ -5,8 +5,8 @@ root turned into a training sample (self_play.py:193-216) by one kernel per ply.
     sp = SelfPlay(1024, n_rollouts=100, net=PolicyValueNet(sd))
     s, pi, mask, v, done = sp.play().flat()         # the reference's s_batch, pi_batch, mask_batch, v_batch, done
 
-Training on the batch is ordinary torch autograd (examples/selfplay_train.py); there is no loss, gradient or optimiser
-here.  By default the move played is MCTS.choose, as in the reference.  AlphaZero's root exploration is optional
+Training on the batch is ordinary torch autograd or qtttgym_amd.Trainer (examples/selfplay_train.py [--device-train]);
+there is no loss, gradient or optimiser here.  By default the move played is MCTS.choose, as in the reference.  AlphaZero's root exploration is optional
 (include/qttt_tree_explore.h): root_noise=(epsilon, alpha) mixes Dirichlet noise into the roots' priors
 before every searched move, and sample_plies / temperature draw the move of the first plies from the visit counts.  The
 board's eight symmetries, which the reference left as a stub (self_play.py expand_symetries), are SelfPlayBatch.augment (DESIGN.md
