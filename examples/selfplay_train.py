@@ -9,7 +9,7 @@ with --device-train, on the device), packs the new weights for the search and re
                                       [--symmetries] [--leaf-eval playouts|value]
                                       [--root-noise EPS,ALPHA] [--temperature T] [--sample-plies K] [--leaves K]
                                       [--eval-symmetries all|0,4] [--replay CAPACITY --batch B --steps S]
-                                      [--device-train]
+                                      [--device-train] [--stream PLIES]
 
 The network is nn.Model's (nn.py:7-28) under its own parameter names (qtttgym_amd.policy_value.SHAPES), so --out is a
 state dict that the reference, PolicyValueNet and examples/tree_tournament.py --model all load.  The loss is the
@@ -36,6 +36,10 @@ path's and are not used with it.
 --device-train takes the training step to the device as well (qtttgym_amd.Trainer): the loss, its gradients and the
 AMSGrad step run as HIP kernels on the packed weights that the search reads, so there is no autograd, no torch optimiser
 and no repacking of the weights between runs; --out is then the trainer's state dict.
+--stream PLIES (with --replay) keeps the batch of --games game slots full instead of playing them in lockstep
+(SelfPlay.stream): every run advances the slots by PLIES searched plies, a slot whose game ends hands its samples to the ring
+and starts a new game at once, and the run's --steps minibatches follow.  The counters stay on the device; the printed
+line reads them back once per run.
 """
 import argparse
 import os
@@ -134,8 +138,13 @@ def main():
     ap.add_argument("--steps", type=int, default=50, help="with --replay: minibatch steps per run")
     ap.add_argument("--device-train", action="store_true",
                     help="loss, gradients and the optimiser on the device, on the search's packed weights (Trainer)")
+    ap.add_argument("--stream", type=int, default=0, metavar="PLIES",
+                    help="with --replay: every run is PLIES plies of continuous self-play (finished games restart in "
+                         "place and feed the ring) instead of one batch of games in lockstep")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
+    if args.stream < 0 or (args.stream and not args.replay):
+        ap.error("--stream needs PLIES >= 1 and --replay")
     if args.replay and (args.batch < 1 or args.steps < 1):
         ap.error("--replay needs --batch >= 1 and --steps >= 1")
     torch.manual_seed(args.seed)
@@ -158,17 +167,28 @@ def main():
         fit, save = (lambda batches: train_on_device(trainer, batches)), trainer.state_dict
     else:
         fit, save = (lambda batches: train(model, optim, batches)), model.state_dict
+    seen = torch.zeros(5, dtype=torch.int64)                  # games, samples, winners[3] of the stream so far
     for run in range(args.runs):
-        batch = sp.play()
-        won = [int((batch.winner == w).sum()) for w in (1, 0, -1)]
-        if ring is not None:
-            ring.add(batch)
+        if args.stream:
+            stats = sp.stream(ring, args.stream)
             L, J = fit(ring.sample(args.batch, "random") for _ in range(args.steps))
-            what = "%d games appended, the ring holds %d samples; %d steps of %d" % (args.games, ring.size(), args.steps, args.batch)
+            now = torch.cat([stats.games.sum().view(1), stats.samples.view(1), stats.winners]).cpu()     # the one read-back
+            new, seen = (now - seen).tolist(), now
+            won = new[2:]
+            what = ("%d plies: %d games harvested, %d samples appended, the ring holds %d; %d steps of %d"
+                    % (args.stream, new[0], new[1], min(int(now[1]), args.replay), args.steps, args.batch))
         else:
-            samples = (batch.augment() if args.symmetries else batch).flat()
-            L, J = fit(samples for _ in range(args.epochs))
-            what = "%d samples of %d games" % (len(samples[0]), args.games)
+            batch = sp.play()
+            won = [int((batch.winner == w).sum()) for w in (1, 0, -1)]
+            if ring is not None:
+                ring.add(batch)
+                L, J = fit(ring.sample(args.batch, "random") for _ in range(args.steps))
+                what = ("%d games appended, the ring holds %d samples; %d steps of %d"
+                        % (args.games, ring.size(), args.steps, args.batch))
+            else:
+                samples = (batch.augment() if args.symmetries else batch).flat()
+                L, J = fit(samples for _ in range(args.epochs))
+                what = "%d samples of %d games" % (len(samples[0]), args.games)
         print("run %d: %s (first player won %d, lost %d, drew %d); L: %.4f, J: %.4f"
               % (run, what, won[0], won[1], won[2], L.mean().item(), J.mean().item()), flush=True)
         if trainer is None:

@@ -13,9 +13,9 @@ from .actions import ind2move, move2ind
 from ._native import recommended_env, retire_mailbox
 from .policy_value import PolicyValueNet
 from .tree import TreeSearch
-from .selfplay import SelfPlay, SelfPlayBatch
+from .selfplay import SelfPlay, SelfPlayBatch, StreamStats
 from .replay import ReplayBuffer
 from .train import Trainer
 
-__all__ = ["Board", "QEvalClassic", "displayBoard", "Env", "VecEnv", "PolicyValueNet", "TreeSearch", "SelfPlay", "SelfPlayBatch", "ReplayBuffer", "Trainer", "ind2move", "move2ind", "recommended_env",
+__all__ = ["Board", "QEvalClassic", "displayBoard", "Env", "VecEnv", "PolicyValueNet", "TreeSearch", "SelfPlay", "SelfPlayBatch", "StreamStats", "ReplayBuffer", "Trainer", "ind2move", "move2ind", "recommended_env",
            "retire_mailbox"]

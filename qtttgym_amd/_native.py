@@ -177,6 +177,18 @@ TRAIN_SIGNATURES = {
     "qttt_train_gradients": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qttt_train_adam": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
 }
+# every symbol include/qttt_selfplay_stream.h declares (continuous self-play: the per-game record, harvest, restart; qttt.h
+# includes it)
+SELFPLAY_MAX_MOVE_DRAWS = 1 << 28
+SELFPLAY_TALLIES = 4
+_RECORD_STREAM = [a for i, a in enumerate(SELFPLAY_SIGNATURES["qttt_selfplay_record"][1][:-1]) if i != 3]    # no ply
+SELFPLAY_STREAM_SIGNATURES = {
+    "qttt_selfplay_record_stream": (_i32, _RECORD_STREAM + [_vp]),
+    "qttt_selfplay_record_stream_sampled": (_i32, _RECORD_STREAM + [_u64, _i64, _f64, _i32, _u32, _vp]),
+    "qttt_selfplay_record_stream_gumbel": (_i32, _RECORD_STREAM + [_vp, _f64, _f64, _vp]),
+    "qttt_selfplay_harvest": (_i32, [_vp, _i64, _i64, _f64, _f64] + [_vp] * 13 + [_vp]),
+    "qttt_selfplay_restart": (_i32, [_vp, _i64, _i64, _vp, _vp] + [_vp] * 7 + [_vp]),
+}
 
 _lib = None
 
@@ -244,7 +256,8 @@ def lib():
                                   + list(SYMMETRY_SIGNATURES.items()) + list(TREE_VALUE_SIGNATURES.items())
                                   + list(TREE_EXPLORE_SIGNATURES.items()) + list(TREE_LEAVES_SIGNATURES.items())
                                   + list(NN_SYMMETRIC_SIGNATURES.items()) + list(TREE_GUMBEL_SIGNATURES.items())
-                                  + list(REPLAY_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())):
+                                  + list(REPLAY_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())
+                                  + list(SELFPLAY_STREAM_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -59,7 +59,8 @@
 // qttt_replay_kernels.h (the replay ring: the append's scan and move, the sampled minibatch) with qttt_replay_host.h (host
 // only and free of HIP: the ring's layout, the scan plan, the argument checks);
 // qttt_train_kernels.h (the training step: loss, gradients and AMSGrad on the packed f32 blob, on qttt_nn_kernels.h's layers)
-// with qttt_train_host.h (host only and free of HIP: the workspace layout and the launch plan).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
+// with qttt_train_host.h (host only and free of HIP: the workspace layout and the launch plan);
+// qttt_selfplay_stream_kernels.h (continuous self-play: the harvest of finished games and their restart in place).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
 // qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
@@ -79,6 +80,7 @@
 #include "qttt_tree_gumbel_kernels.h"
 #include "qttt_replay_kernels.h"
 #include "qttt_train_kernels.h"
+#include "qttt_selfplay_stream_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -1107,6 +1109,89 @@ int qttt_train_adam(void *weights, const void *grads, void *m, void *v2, void *v
     return launch(train_adam_kernel, ceil_div(TRAIN_BLOB_FLOATS, QTTT_NN_BLOCK), QTTT_NN_BLOCK, stream, static_cast<float *>(weights),
                   static_cast<const float *>(grads), static_cast<float *>(m), static_cast<float *>(v2),
                   static_cast<float *>(vmax), h, weights_bf16);
+}
+
+// ---------------------------------------------------------------- continuous self-play (include/qttt_selfplay_stream.h)
+int qttt_selfplay_record_stream(const void *tree, int64_t games, int64_t capacity, uint32_t n_rollouts, double alpha,
+                                double v_first, double v_second, void *states, double *pi, uint8_t *mask, uint8_t *done,
+                                float *v, uint8_t *action36, uint8_t *length, int8_t *winner, uint8_t *actions,
+                                void *stream) {
+    if (tree_size_bad(games, capacity) || n_rollouts == 0u || !std::isfinite(alpha) || !std::isfinite(v_first) ||
+        !std::isfinite(v_second) || alpha <= 0.0)
+        return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
+    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    return launch(selfplay_record_kernel<RECORD_PLAIN, true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
+                  capacity, 0, n_rollouts, alpha, (float)v_first, (float)v_second, o, SelfPlaySampling<RECORD_PLAIN>{});
+}
+
+int qttt_selfplay_record_stream_sampled(const void *tree, int64_t games, int64_t capacity, uint32_t n_rollouts, double alpha,
+                                        double v_first, double v_second, void *states, double *pi, uint8_t *mask,
+                                        uint8_t *done, float *v, uint8_t *action36, uint8_t *length, int8_t *winner,
+                                        uint8_t *actions, uint64_t seed, int64_t board_offset, double temperature,
+                                        int sample_plies, uint32_t draw_index, void *stream) {
+    if (tree_size_bad(games, capacity) || n_rollouts == 0u || !std::isfinite(alpha) || !std::isfinite(v_first) ||
+        !std::isfinite(v_second) || alpha <= 0.0 || board_offset < 0 || !std::isfinite(temperature) || temperature <= 0.0 ||
+        sample_plies < 0 || sample_plies > QTTT_SELFPLAY_ROWS || draw_index >= QTTT_SELFPLAY_MAX_MOVE_DRAWS)
+        return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
+    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    const SelfPlaySampling<RECORD_SAMPLED> s = {(u64)seed, (u64)board_offset, temperature, sample_plies};
+    // (the stream kernels take the draw index where the lockstep ones take the ply)
+    return launch(selfplay_record_kernel<RECORD_SAMPLED, true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
+                  capacity, (int)draw_index, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
+}
+
+int qttt_selfplay_record_stream_gumbel(const void *tree, int64_t games, int64_t capacity, uint32_t n_rollouts, double alpha,
+                                       double v_first, double v_second, void *states, double *pi, uint8_t *mask,
+                                       uint8_t *done, float *v, uint8_t *action36, uint8_t *length, int8_t *winner,
+                                       uint8_t *actions, const void *rec, double c_visit, double c_scale, void *stream) {
+    if (tree_size_bad(games, capacity) || !std::isfinite(v_first) || !std::isfinite(v_second) || gumbel_scale_bad(c_visit, c_scale))
+        return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions, rec)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4) || misaligned(rec, 16))
+        return QTTT_ERR_ACTION;
+    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    const SelfPlaySampling<RECORD_GUMBEL> s = {static_cast<const GumbelRec *>(rec), c_visit, c_scale};
+    return launch(selfplay_record_kernel<RECORD_GUMBEL, true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
+                  capacity, 0, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
+}
+
+int qttt_selfplay_harvest(const void *tree, int64_t games, int64_t capacity, double v_first, double v_second, void *states,
+                          double *pi, uint8_t *mask, uint8_t *done, float *v, uint8_t *action36, uint8_t *length,
+                          int8_t *winner, uint8_t *actions, uint8_t *harvest_len, uint8_t *finished, int64_t *games_done,
+                          int64_t *tally, void *stream) {
+    if (tree_size_bad(games, capacity) || !std::isfinite(v_first) || !std::isfinite(v_second)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions) ||
+        any_null(harvest_len, finished, games_done, tally))
+        return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(games_done, 8) || misaligned(tally, 8) ||
+        misaligned(v, 4))
+        return QTTT_ERR_ACTION;
+    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    const SelfPlayHarvest hv = {harvest_len, finished, games_done, tally};
+    return launch(selfplay_harvest_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (float)v_first, (float)v_second, o, hv);
+}
+
+int qttt_selfplay_restart(void *tree, int64_t games, int64_t capacity, void *state, const uint8_t *finished, void *states,
+                          double *pi, uint8_t *mask, uint8_t *done, float *v, uint8_t *action36, uint8_t *length,
+                          void *stream) {
+    if (tree_size_bad(games, capacity)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, state, finished, states, pi, mask, done, v, action36, length)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(state, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4))
+        return QTTT_ERR_ACTION;
+    const Planes p = planes(state, games);
+    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, nullptr, nullptr};
+    return launch(selfplay_restart_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity, p.P, p.Q,
+                  finished, o);
 }
 
 }  // extern "C"

@@ -11,6 +11,10 @@
 // move of the first plies drawn from the visit counts (explore_sample_move); <RECORD_GUMBEL> is the Gumbel record of
 // include/qttt_tree_gumbel.h: the move and the pi row are gumbel_final's (qttt_tree_gumbel_kernels.h), two more
 // butterflies and one exp per lane; <RECORD_PLAIN> is qttt_selfplay_record's, whose code the mode does not touch.
+// selfplay_record_kernel<MODE, true> is the stream record of include/qttt_selfplay_stream.h: the same body with the row
+// read per game from length[g]; the lockstep instantiations compile to what they were without it
+// (profiles/stream/record_kernels_before_after.txt).  A root's row is written by selfplay_row_head and, at a terminal
+// root, selfplay_terminal_row: the harvest (qttt_selfplay_stream_kernels.h) writes its terminal rows through the same two.
 #ifndef QTTT_SELFPLAY_KERNELS_H
 #define QTTT_SELFPLAY_KERNELS_H
 #include "qttt_tree_kernels.h"
@@ -49,7 +53,43 @@ struct SelfPlaySampling<RECORD_GUMBEL> {
     double c_visit, c_scale;
 };
 
-template <int MODE>
+// what every recorded root writes first: its packed state, the done byte and the game's new length
+// (stride = plane_stride(games), row = ply * games + g: the caller's, which it needs itself)
+__device__ __forceinline__ void selfplay_row_head(const SelfPlayOut &o, int64_t stride, int64_t row, int64_t g, int ply,
+                                                  const TreeNodeHdr &h, bool terminal, u32 lane) {
+    if (lane == 0u) {
+        u64 *planes_t = o.states + (int64_t)ply * 2 * stride;
+        planes_t[g] = h.P;
+        planes_t[stride + g] = h.Q;
+        o.done[row] = terminal ? 1 : 0;
+        o.length[g] = (uint8_t)(ply + 1);
+    }
+}
+
+// the rest of a terminal root's row (self_play.py:203-206) and the v of the whole game (:195-216)
+__device__ __forceinline__ void selfplay_terminal_row(const SelfPlayOut &o, int64_t games, int64_t row, int64_t g, int ply,
+                                                      const TreeNodeHdr &h, float v_first, float v_second, u32 lane) {
+    uint8_t *act = o.actions + 2 * g;
+    if (lane < 36u) {
+        o.pi[row * 36 + lane] = 1.0 / 36.0;
+        o.mask[row * 36 + lane] = 1;
+    }
+    const int w = (int)((h.flags >> 8) & 3u) - 1;                // 1 / 0 / -1 = True / False / None
+    const float v0 = w > 0 ? v_first : (w == 0 ? v_second : 0.0f);
+    if ((int)lane <= ply) {
+        const float x = (lane & 1u) ? -v0 : v0;
+        o.v[(int64_t)lane * games + g] = x == 0.0f ? 0.0f : x;            // a zero is +0.0
+    }
+    if (lane == 0u) {
+        o.winner[g] = (int8_t)w;
+        o.action36[row] = 255;
+        act[0] = 255; act[1] = 255;
+    }
+}
+
+// STREAM: `ply` is the index of the sampled move's draw and the row is the game's own ply, length[g]; a game whose
+// terminal row is recorded (or whose ten rows are full) is not live
+template <int MODE, bool STREAM = false>
 __global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void *tree, int64_t games, int64_t capacity,
                                                                      int ply, u32 n_rollouts, double alpha, float v_first,
                                                                      float v_second, SelfPlayOut o,
@@ -58,38 +98,27 @@ __global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void 
     const u32 lane = threadIdx.x & 63u;
     if (g >= games) return;
     uint8_t *act = o.actions + 2 * g;
-    // live: the row before this one was recorded and was not the terminal one
-    if (ply != 0 && ((int)o.length[g] != ply || o.done[(int64_t)(ply - 1) * games + g] != 0)) {
-        if (lane == 0u) { act[0] = 255; act[1] = 255; }
-        return;
+    const int draw = ply;
+    if constexpr (STREAM) {
+        ply = (int)o.length[g];
+        if (ply >= QTTT_SELFPLAY_ROWS || (ply != 0 && o.done[(int64_t)(ply - 1) * games + g] != 0)) {
+            if (lane == 0u) { act[0] = 255; act[1] = 255; }
+            return;
+        }
+    } else {
+        // live: the row before this one was recorded and was not the terminal one
+        if (ply != 0 && ((int)o.length[g] != ply || o.done[(int64_t)(ply - 1) * games + g] != 0)) {
+            if (lane == 0u) { act[0] = 255; act[1] = 255; }
+            return;
+        }
     }
     const TreeView v = tree_view(const_cast<void *>(tree), games, capacity);
     const TreeRootLane r = tree_root_lane(v, g, lane);
     const int64_t stride = plane_stride(games), row = (int64_t)ply * games + g;
     const bool terminal = (r.h.flags & TN_TERMINAL) != 0u;
-    if (lane == 0u) {
-        u64 *planes_t = o.states + (int64_t)ply * 2 * stride;
-        planes_t[g] = r.h.P;
-        planes_t[stride + g] = r.h.Q;
-        o.done[row] = terminal ? 1 : 0;
-        o.length[g] = (uint8_t)(ply + 1);
-    }
-    if (terminal) {                                              // self_play.py:203-206 and the v of :195-216
-        if (lane < 36u) {
-            o.pi[row * 36 + lane] = 1.0 / 36.0;
-            o.mask[row * 36 + lane] = 1;
-        }
-        const int w = (int)((r.h.flags >> 8) & 3u) - 1;          // 1 / 0 / -1 = True / False / None
-        const float v0 = w > 0 ? v_first : (w == 0 ? v_second : 0.0f);
-        if ((int)lane <= ply) {
-            const float x = (lane & 1u) ? -v0 : v0;
-            o.v[(int64_t)lane * games + g] = x == 0.0f ? 0.0f : x;        // a zero is +0.0
-        }
-        if (lane == 0u) {
-            o.winner[g] = (int8_t)w;
-            o.action36[row] = 255;
-            act[0] = 255; act[1] = 255;
-        }
+    selfplay_row_head(o, stride, row, g, ply, r.h, terminal, lane);
+    if (terminal) {
+        selfplay_terminal_row(o, games, row, g, ply, r.h, v_first, v_second, lane);
         return;
     }
     int a;
@@ -106,7 +135,7 @@ __global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void 
         a = tree_choose(r, lane);
         if constexpr (MODE == RECORD_SAMPLED) {
             if (ply < sampling.sample_plies) {                   // wave-uniform
-                const int drawn = explore_sample_move(r.s.N, lane, sampling.seed, sampling.board_offset + (u64)g, ply,
+                const int drawn = explore_sample_move(r.s.N, lane, sampling.seed, sampling.board_offset + (u64)g, draw,
                                                       sampling.temperature);
                 a = drawn < 0 ? a : drawn;
             }

@@ -58,21 +58,24 @@ class ReplayBuffer(LibCaller):
         """Samples held, min(written, capacity).  One host read-back."""
         return min(int(self.views()["written"].item()), self.capacity)
 
-    def add(self, batch):
-        """Appends the samples of a SelfPlayBatch (qttt_replay_append).  No host read-back; the batch is not changed."""
+    def add(self, batch, length=None):
+        """Appends the samples of a SelfPlayBatch (qttt_replay_append).  No host read-back; the batch is not changed.
+        length (u8[G], optional) stands in for batch.length: the rows below length[g] of game g are appended, none of a
+        game with 0 (SelfPlay.stream appends the games that finished at a ply this way)."""
         G, dev = batch.num_games, self.device
         check_tensor(batch.states, torch.uint8, (ROWS, int(self._lib.qttt_state_bytes(G))), dev, "batch.states")
         for k in ("pi", "mask", "done", "v"):
             dt, shp = SelfPlayBatch._ROWS[k]
             check_tensor(getattr(batch, k), dt, (ROWS, G) + shp, dev, "batch." + k)
-        check_tensor(batch.length, torch.uint8, (G,), dev, "batch.length")
+        length = check_tensor(batch.length if length is None else length, torch.uint8, (G,), dev,
+                              "batch.length" if length is None else "length")
         if G == 0:
             return
         need = int(self._lib.qttt_replay_append_scratch_bytes(G))
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=dev)
         self._call("qttt_replay_append", self.buffer.data_ptr(), self.capacity, G, batch.states.data_ptr(), batch.pi.data_ptr(),
-                   batch.mask.data_ptr(), batch.done.data_ptr(), batch.v.data_ptr(), batch.length.data_ptr(),
+                   batch.mask.data_ptr(), batch.done.data_ptr(), batch.v.data_ptr(), length.data_ptr(),
                    self._scratch.data_ptr())
         self.adds += 1
 

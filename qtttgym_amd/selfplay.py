@@ -10,7 +10,9 @@ there is no loss, gradient or optimiser here.  By default the move played is MCT
 (include/qttt_tree_explore.h): root_noise=(epsilon, alpha) mixes Dirichlet noise into the roots' priors
 before every searched move, and sample_plies / temperature draw the move of the first plies from the visit counts.  The
 board's eight symmetries, which the reference left as a stub (self_play.py expand_symetries), are SelfPlayBatch.augment (DESIGN.md
-§14): one launch turns the batch of G games into the batch of 8 G games it stands for.
+§14): one launch turns the batch of G games into the batch of 8 G games it stands for.  sp.stream(ring, plies) is
+continuous self-play (include/qttt_selfplay_stream.h): the G slots stay full, a finished game hands its rows
+to a ReplayBuffer and restarts in place.
 """
 import ctypes
 
@@ -149,16 +151,20 @@ class SelfPlay(LibCaller):
         if net is not None:
             check_net(net, self.device)
         self.plays = 0                # play() calls so far: the default seed of the next
-        self.env = self.tree = None   # the last play()'s environment (at the final positions) and trees
+        self.env = self.tree = None   # the last play()'s or stream()'s environment (at its positions) and trees
+        self._stream = None           # stream()'s games in progress: environment, trees, staging batch, counters
+        self.stream_epoch_plies = None    # None: a seed serves as many plies as the draw counters allow (epoch_plies)
 
     def new_batch(self):
         """A zero-filled SelfPlayBatch for num_games games."""
         return SelfPlayBatch(self.num_games, self.device, self._lib.qttt_state_bytes(self.num_games))
 
-    def record(self, tree, ply, batch):
+    def record(self, tree, ply, batch, draw_index=None):
         """One qttt_selfplay_record: the roots of `tree` become row `ply` of `batch`; returns batch.actions, the move
         to step with.  With sample_plies > 0 it is qttt_selfplay_record_sampled, drawing with the tree's seed and
-        board_offset."""
+        board_offset.  ply=None is the stream record (include/qttt_selfplay_stream.h): every game's row is its own
+        length[g].  draw_index (the sampled move's draw, where it is not the ply: stream() and play(start_ply=p)) goes
+        through the stream record too, which writes a lockstep batch's rows exactly as the lockstep entry does."""
         G, dev = self.num_games, self.device
         if tree.num_games != G or tree.device != dev or batch.num_games != G:
             raise ValueError("tree and batch must hold %d games on %s" % (G, dev))
@@ -168,47 +174,190 @@ class SelfPlay(LibCaller):
         check_tensor(batch.length, torch.uint8, (G,), dev, "batch.length")
         check_tensor(batch.winner, torch.int8, (G,), dev, "batch.winner")
         check_tensor(batch.actions, torch.uint8, (G, 2), dev, "batch.actions")
-        args = (tree.tree.data_ptr(), G, tree.capacity, int(ply), self.n_rollouts, self.alpha, self.v_first, self.v_second,
-                batch.states.data_ptr(), batch.pi.data_ptr(), batch.mask.data_ptr(), batch.done.data_ptr(),
-                batch.v.data_ptr(), batch.action36.data_ptr(), batch.length.data_ptr(), batch.winner.data_ptr(),
-                batch.actions.data_ptr())
+        sampled = self.root_policy != "gumbel" and self.sample_plies > 0
+        per_game = ply is None or (sampled and draw_index is not None)
+        if sampled and ply is None and draw_index is None:
+            raise ValueError("the sampled stream record needs a draw_index")
+        args = (tree.tree.data_ptr(), G, tree.capacity) + (() if per_game else (int(ply),)) + (
+            self.n_rollouts, self.alpha, self.v_first, self.v_second,
+            batch.states.data_ptr(), batch.pi.data_ptr(), batch.mask.data_ptr(), batch.done.data_ptr(),
+            batch.v.data_ptr(), batch.action36.data_ptr(), batch.length.data_ptr(), batch.winner.data_ptr(),
+            batch.actions.data_ptr())
+        entry = "qttt_selfplay_record_stream" if per_game else "qttt_selfplay_record"
         if self.root_policy == "gumbel":
             if tree.root_policy != "gumbel" or tree._gumbel is None:
                 raise ValueError("the Gumbel record needs a tree searched with root_policy=\"gumbel\"")
-            self._call("qttt_selfplay_record_gumbel", *args, tree._gumbel["rec"].data_ptr(), tree.c_visit, tree.c_scale)
-        elif self.sample_plies > 0:
-            self._call("qttt_selfplay_record_sampled", *args, tree.seed, tree.board_offset, self.temperature,
-                       self.sample_plies)
+            self._call(entry + "_gumbel", *args, tree._gumbel["rec"].data_ptr(), tree.c_visit, tree.c_scale)
+        elif sampled:
+            self._call(entry + "_sampled", *args, tree.seed, tree.board_offset, self.temperature, self.sample_plies,
+                       *((int(draw_index),) if per_game else ()))
         else:
-            self._call("qttt_selfplay_record", *args)
+            self._call(entry, *args)
         return batch.actions
 
-    def play(self, seed=None):
+    def _new_game_objects(self, s):
+        """The environment (seed s) and the trees (seed 2 s + 1) of a play() or a stream, the trees reset at the empty
+        boards."""
+        G = self.num_games
+        env = VecEnv(G, device=self.device, seed=s)
+        tree = TreeSearch(G, capacity=self.capacity, num_simulations=self.num_simulations,
+                          c_puct=self.c_puct, net=self.net, seed=2 * s + 1, device=self.device,
+                          leaf_eval=self.leaf_eval, leaves=self.leaves, virtual_loss=self.virtual_loss,
+                          eval_symmetries=self.eval_symmetries, root_policy=self.root_policy,
+                          max_considered=self.max_considered, c_visit=self.c_visit, c_scale=self.c_scale)
+        tree.reset(env)
+        return env, tree
+
+    def _search(self, tree):
+        """The search before a move, play()'s and stream()'s: R rollouts, with root_noise the noise after the one that
+        gives the priors."""
+        R = self.n_rollouts
+        if self.root_noise is None:
+            tree.contemplate(R)
+        else:
+            tree.contemplate(1)
+            tree.add_root_noise(*self.root_noise)
+            tree.contemplate(R - 1)
+
+    def epoch_plies(self, tree):
+        """Searched plies that one seed serves before one of the draw counters would pass its limit: the environment's
+        step index (u32), the trees' rollout index (R per ply), the noise and Gumbel indices and the sampled move's
+        (one per ply each).  stream() moves to a fresh seed after that many plies; play(start_ply=p) needs p + 10 of
+        them.  stream_epoch_plies, when set, replaces it by something smaller (tests)."""
+        limits = [1 << 32, tree.max_rollouts // self.n_rollouts, _native.SELFPLAY_MAX_MOVE_DRAWS]
+        if self.root_noise is not None:
+            limits.append(_native.TREE_MAX_NOISE)
+        if self.root_policy == "gumbel":
+            limits.append(_native.TREE_MAX_GUMBEL)
+        n = min(limits)
+        return n if self.stream_epoch_plies is None else min(n, int(self.stream_epoch_plies))
+
+    def _set_counters(self, env, tree, p):
+        """Every draw counter at what p searched plies since the seed's first consume: the environment's step index, the
+        trees' rollout index, and the noise and Gumbel indices where the search uses them."""
+        env.step_idx = p
+        tree.rollout_idx = p * self.n_rollouts
+        tree.noise_idx = p if self.root_noise is not None else 0
+        tree.gumbel_idx = p if self.root_policy == "gumbel" else 0
+
+    def play(self, seed=None, start_ply=0):
         """play_game (self_play.py:43-76) of num_games games from the empty board and their samples
         (self_play.py:193-216) as a SelfPlayBatch.  seed=None: self.seed + the number of earlier play() calls.  The
         environment draws its collapse bits with `seed`, the trees their playouts with 2 * seed + 1.  A finished game
-        rides along: its moves are noops, its tree keeps its root."""
+        rides along: its moves are noops, its tree keeps its root.
+        start_ply=p > 0 plays the same games with every draw counter started at what p plies of a stream() consume
+        (the environment's step index, the trees' rollout, noise and Gumbel indices, the sampled move's index) instead
+        of 0: the games that a stream with this seed starts at its ply p.  With 0 the calls are what they always were."""
         s = self.seed + self.plays if seed is None else int(seed)
+        p = int(start_ply)
+        if p < 0:
+            raise ValueError("start_ply must be >= 0")
         self.plays += 1
-        G, R = self.num_games, self.n_rollouts
-        env = self.env = VecEnv(G, device=self.device, seed=s)
-        tree = self.tree = TreeSearch(G, capacity=self.capacity, num_simulations=self.num_simulations,
-                                      c_puct=self.c_puct, net=self.net, seed=2 * s + 1, device=self.device,
-                                      leaf_eval=self.leaf_eval, leaves=self.leaves, virtual_loss=self.virtual_loss,
-                                      eval_symmetries=self.eval_symmetries, root_policy=self.root_policy,
-                                      max_considered=self.max_considered, c_visit=self.c_visit, c_scale=self.c_scale)
-        tree.reset(env)
+        env, tree = self.env, self.tree = self._new_game_objects(s)
+        if p:
+            if p + ROWS > self.epoch_plies(tree):
+                raise ValueError("start_ply %d passes the draw counters' limit of %d plies" % (p, self.epoch_plies(tree)))
+            self._set_counters(env, tree, p)
         batch = self.new_batch()
         for ply in range(ROWS):
             if ply < ROWS - 1:                  # at ply 9 every game is over: nine moves fill the board
-                if self.root_noise is None:
-                    tree.contemplate(R)
-                else:                           # the same R rollouts, the noise after the one that gives the priors
-                    tree.contemplate(1)
-                    tree.add_root_noise(*self.root_noise)
-                    tree.contemplate(R - 1)
-            env.step_raw(self.record(tree, ply, batch))
+                self._search(tree)
+            env.step_raw(self.record(tree, ply, batch, draw_index=p + ply if p else None))
             tree.sync(env)
             if self.compact:
                 tree.compact()
         return batch
+
+    # ------------------------------------------------------------------ continuous self-play (DESIGN.md §22)
+    def stream_reset(self):
+        """Forgets the games of stream(): the next call starts every slot from the empty board, with fresh counters."""
+        self._stream = None
+
+    def stream(self, ring, plies, seed=None):
+        """Advances the persistent batch of num_games game slots by `plies` stream plies (include/qttt_selfplay_stream.h).
+        One stream ply: the search of play() in every slot (every root is live) -> the record at each slot's OWN ply
+        (row length[g] of the staging batch) -> step, sync [, compact] -> harvest: a slot whose new root is terminal
+        gets its terminal row and value targets, its rows are appended to `ring` (a ReplayBuffer on this device; slots
+        ascending, rows in order), and the slot restarts from the empty board.  Three launches and the append's on top
+        of play()'s per ply, and no host read-back (compact=True keeps its one per move).
+        The first call (and the first after stream_reset()) starts every slot from the empty board with `seed`
+        (None: self.seed + the number of earlier play() / stream starts); later calls continue the games in progress,
+        and take seed=None or the running stream's.  The draw counters run on across restarts and calls, so no
+        (seed, board, index) is used twice: until a slot first finishes its game is play(seed)'s in that slot, and a
+        game that starts at stream ply p is play(seed, start_ply=p)'s.  After epoch_plies() plies the stream moves to
+        the seed `seed + 2**32` (and so on) with the counters at 0; games in progress carry on.
+        Returns StreamStats: games i64[G] finished per slot, samples i64 rows appended, winners i64[3] first / second /
+        none, all cumulative since the stream began, device tensors that nothing here reads back."""
+        from .replay import ReplayBuffer
+        T = int(plies)
+        if T < 0:
+            raise ValueError("plies must be >= 0")
+        if not isinstance(ring, ReplayBuffer) or ring.device != self.device:
+            raise ValueError("ring must be a ReplayBuffer on %s" % (self.device,))
+        st = self._stream
+        if st is None:
+            s = self.seed + self.plays if seed is None else int(seed)
+            self.plays += 1
+            st = self._stream = self._stream_begin(s)
+        elif seed is not None and int(seed) != st["seed"]:
+            raise ValueError("a stream with seed %d is in progress: stream_reset() first" % st["seed"])
+        self.env, self.tree = st["env"], st["tree"]
+        for _ in range(T):
+            self._stream_ply(st, ring)
+        totals = st["tally"].sum(0)
+        return StreamStats(st["games_done"].clone(), totals[3], totals[:3])
+
+    def _stream_begin(self, s):
+        G, dev = self.num_games, self.device
+        env, tree = self._new_game_objects(s)
+        return {"seed": s, "epoch": 0, "ply": 0, "plies": 0, "env": env, "tree": tree, "batch": self.new_batch(),
+                "harvest_len": torch.zeros(G, dtype=torch.uint8, device=dev),
+                "finished": torch.zeros(G, dtype=torch.uint8, device=dev),
+                "games_done": torch.zeros(G, dtype=torch.int64, device=dev),
+                "tally": torch.zeros((G, _native.SELFPLAY_TALLIES), dtype=torch.int64, device=dev)}
+
+    def _stream_ply(self, st, ring):
+        env, tree, batch, R = st["env"], st["tree"], st["batch"], self.n_rollouts
+        if st["ply"] >= self.epoch_plies(tree):         # a counter would pass its limit: a fresh seed, the counters at 0
+            st["epoch"] += 1
+            s = st["seed"] + (st["epoch"] << 32)
+            env.seed = s
+            tree.reseed(2 * s + 1)
+            st["ply"] = 0
+            self._set_counters(env, tree, 0)
+        if not self.compact:
+            # what the host cannot know without a read-back, it knows from the game: a live root has at most eight moves
+            # behind it, and a restart gives the slot's nodes back, so no slot holds more than this before its search
+            tree._bound = 1 + (ROWS - 2) * (2 * R + 1)
+        self._search(tree)
+        env.step_raw(self.record(tree, None, batch, draw_index=st["ply"]))
+        tree.sync(env)
+        if self.compact:
+            tree.compact()
+        self._stream_harvest(st)
+        ring.add(batch, length=st["harvest_len"])
+        self._stream_restart(st)
+        st["ply"] += 1
+        st["plies"] += 1
+
+    def _staging(self, batch, fields):
+        return [getattr(batch, f).data_ptr() for f in fields]
+
+    def _stream_harvest(self, st):
+        tree = st["tree"]
+        self._call("qttt_selfplay_harvest", tree.tree.data_ptr(), self.num_games, tree.capacity, self.v_first, self.v_second,
+                   *self._staging(st["batch"], SelfPlayBatch._FIELDS), st["harvest_len"].data_ptr(),
+                   st["finished"].data_ptr(), st["games_done"].data_ptr(), st["tally"].data_ptr())
+
+    def _stream_restart(self, st):
+        tree = st["tree"]
+        self._call("qttt_selfplay_restart", tree.tree.data_ptr(), self.num_games, tree.capacity, st["env"].state.data_ptr(),
+                   st["finished"].data_ptr(), *self._staging(st["batch"], SelfPlayBatch._FIELDS[:7]))
+
+
+class StreamStats:
+    """What SelfPlay.stream() returns: games i64[G] (finished per slot), samples i64 (rows appended) and winners i64[3]
+    (first player / second player / nobody), cumulative since the stream began; device tensors."""
+
+    def __init__(self, games, samples, winners):
+        self.games, self.samples, self.winners = games, samples, winners

@@ -177,6 +177,15 @@ class TreeSearch(LibCaller):
         self.rollout_idx, self.noise_idx, self._bound, self._fresh = 0, 0, 1, True
         self.gumbel_idx = 0
 
+    def reseed(self, seed):
+        """A fresh seed for every draw from here on, the draw counters (rollout, noise, Gumbel) back at 0; the trees are
+        not touched.  What a search that never resets (SelfPlay.stream) does before a counter would pass its bound."""
+        self.seed = int(seed)
+        envs = [self.leaf] + [b["leaf"] for b in self._rounds.values()] + ([self._gumbel["root"]] if self._gumbel else [])
+        for env in envs:
+            env.seed = self.seed
+        self.rollout_idx = self.noise_idx = self.gumbel_idx = 0
+
     def contemplate(self, rollouts):
         """`rollouts` x MCTS._rollout (mcts.py:166-176) in every game.  With leaves = K > 1 they are taken K at a time:
         after a reset() or sync() one single rollout first (K descents would all end on a root without priors), then
