@@ -4,7 +4,8 @@ Exports the reference package's four names (qtttgym/__init__.py:1-4) plus `VecEn
 reference's nn.py network, evaluated on the GPU), `TreeSearch` (batched
 MCTS / AlphaZero search trees on the device), `SelfPlay` (self_play.py's games and training samples, batched),
 `ReplayBuffer` (the window of recent samples a trainer draws its minibatches from, on the device), `Trainer` (the
-reference's loss, its gradients and its AMSGrad step on the packed weights the search reads) and the 36-action
+reference's loss, its gradients and its AMSGrad step on the packed weights the search reads), `SolveResult` (what
+`VecEnv.solve`, the exact endgame solver, returns) and the 36-action
 indexing L3 callers share (mcts.py:339-350)."""
 from .vec_env import VecEnv
 from .board import Board, QEvalClassic, displayBoard
@@ -16,6 +17,7 @@ from .tree import TreeSearch
 from .selfplay import SelfPlay, SelfPlayBatch, StreamStats
 from .replay import ReplayBuffer
 from .train import Trainer
+from .solve import SolveResult
 
-__all__ = ["Board", "QEvalClassic", "displayBoard", "Env", "VecEnv", "PolicyValueNet", "TreeSearch", "SelfPlay", "SelfPlayBatch", "StreamStats", "ReplayBuffer", "Trainer", "ind2move", "move2ind", "recommended_env",
+__all__ = ["Board", "QEvalClassic", "displayBoard", "Env", "VecEnv", "PolicyValueNet", "TreeSearch", "SelfPlay", "SelfPlayBatch", "StreamStats", "ReplayBuffer", "Trainer", "SolveResult", "ind2move", "move2ind", "recommended_env",
            "retire_mailbox"]

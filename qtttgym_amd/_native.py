@@ -189,6 +189,12 @@ SELFPLAY_STREAM_SIGNATURES = {
     "qttt_selfplay_harvest": (_i32, [_vp, _i64, _i64, _f64, _f64] + [_vp] * 13 + [_vp]),
     "qttt_selfplay_restart": (_i32, [_vp, _i64, _i64, _vp, _vp] + [_vp] * 7 + [_vp]),
 }
+# every symbol include/qttt_solve.h declares (the exact endgame solver; qttt.h includes it)
+SOLVE_MIN_PLY, SOLVE_MAX_PLY = 4, 9
+SOLVE_DENOMINATOR = 16
+SOLVE_SIGNATURES = {
+    "qttt_solve": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
 
 _lib = None
 
@@ -257,7 +263,7 @@ def lib():
                                   + list(TREE_EXPLORE_SIGNATURES.items()) + list(TREE_LEAVES_SIGNATURES.items())
                                   + list(NN_SYMMETRIC_SIGNATURES.items()) + list(TREE_GUMBEL_SIGNATURES.items())
                                   + list(REPLAY_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())
-                                  + list(SELFPLAY_STREAM_SIGNATURES.items())):
+                                  + list(SELFPLAY_STREAM_SIGNATURES.items()) + list(SOLVE_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -60,7 +60,8 @@
 // only and free of HIP: the ring's layout, the scan plan, the argument checks);
 // qttt_train_kernels.h (the training step: loss, gradients and AMSGrad on the packed f32 blob, on qttt_nn_kernels.h's layers)
 // with qttt_train_host.h (host only and free of HIP: the workspace layout and the launch plan);
-// qttt_selfplay_stream_kernels.h (continuous self-play: the harvest of finished games and their restart in place).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
+// qttt_selfplay_stream_kernels.h (continuous self-play: the harvest of finished games and their restart in place);
+// qttt_solve_kernels.h (the exact endgame solver: the full expectimax tree of a late position, a workgroup per board).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
 // qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
@@ -81,6 +82,7 @@
 #include "qttt_replay_kernels.h"
 #include "qttt_train_kernels.h"
 #include "qttt_selfplay_stream_kernels.h"
+#include "qttt_solve_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -1192,6 +1194,25 @@ int qttt_selfplay_restart(void *tree, int64_t games, int64_t capacity, void *sta
     const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, nullptr, nullptr};
     return launch(selfplay_restart_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity, p.P, p.Q,
                   finished, o);
+}
+
+// ---------------------------------------------------------------- the exact endgame solver (include/qttt_solve.h)
+int qttt_solve(const void *state, int64_t n, int min_ply, float *value, float *q, uint8_t *best, int64_t *nodes,
+               uint8_t *status, void *stream) {
+    if (n < 0 || min_ply < QTTT_SOLVE_MIN_PLY || min_ply > QTTT_SOLVE_MAX_PLY) return QTTT_ERR_SIZE;
+    if (n == 0) return 0;
+    if (!state) return QTTT_ERR_NULL;
+    if (misaligned(state, 16) || misaligned(value, 4) || misaligned(q, 4) || misaligned(nodes, 8)) return QTTT_ERR_ACTION;
+    if (!value && !q && !best && !nodes && !status) return 0;                // nothing asked for
+    const Planes p = planes(const_cast<void *>(state), n);
+    const SolveOut o = {value, q, best, nodes, status};
+    // a workgroup per board; a grid holds at most 2^30 of them
+    constexpr int64_t GRID_MAX = (int64_t)1 << 30;
+    for (int64_t i0 = 0; i0 < n; i0 += GRID_MAX)
+        if (const int rc = launch(solve_kernel, n - i0 < GRID_MAX ? n - i0 : GRID_MAX, SOLVE_BLOCK, stream, (const u64 *)p.P,
+                                  (const u64 *)p.Q, i0, min_ply, o))
+            return rc;
+    return 0;
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@ from . import _native
 from ._host import LibCaller, _ptr, _raw_stream, check_net, check_tensor, out_rows, out_tensor, out_tensors, resolve_device
 from .spaces import reference_action_space, reference_observation_space
 from .symmetry import check_eval_symmetries
+from .solve import SolveResult, check_min_ply, default_boards_per_launch
 
 # The eight tensors of one step's outputs, in the order a default step() carves them out of one allocation
 # (csrc/fastviews.cpp has the same order, checked by tests/test_fastviews_cpu.py): key in the observation dict (None: not
@@ -687,6 +688,42 @@ class VecEnv(LibCaller):
         self._call("qttt_rollout_many", self.state.data_ptr(), self.seed, int(step_idx0), self.board_offset, S,
                    result.data_ptr(), _ptr(plies), self.num_envs)
         return (result, plies) if with_plies else result
+
+    _SOLVE_ROWS = ((torch.float32, ()), (torch.float32, (36,)), (torch.uint8, ()), (torch.int64, ()), (torch.bool, ()))
+
+    def solve(self, min_ply=5, out=None, boards_per_launch=None):
+        """The exact expectimax solution of every board with at least min_ply (4..9) moves played, and of every finished
+        board (include/qttt_solve.h qttt_solve: the full tree below the position, one workgroup per board, nothing
+        sampled or pruned): a SolveResult of value f32[N], q f32[N, 36], best u8[N], nodes i64[N], solved bool[N].  An
+        earlier, unfinished board is skipped (solved False, NaN) and costs nothing.  The boards are not changed.
+        out = the SolveResult of an earlier call on N boards, to be overwritten.  boards_per_launch: the batch goes out
+        in launches of at most this many boards, with the same results — at min_ply 4 a board is up to a few 10^7
+        positions, and the default (qtttgym_amd.solve.BOARDS_PER_LAUNCH) keeps one launch under a second on a device
+        that others share; None at min_ply >= 6 = one launch."""
+        n, dev = self.num_envs, self.device
+        min_ply = check_min_ply(min_ply)
+        per = default_boards_per_launch(min_ply) if boards_per_launch is None else int(boards_per_launch)
+        if per is not None and per < 1:
+            raise ValueError("boards_per_launch must be >= 1")
+        if out is not None and not isinstance(out, SolveResult):
+            raise ValueError("out must be a SolveResult")
+        given = None if out is None else (out.value, out.q, out.best, out.nodes, out.solved)
+        value, q, best, nodes, solved = out_tensors(self._SOLVE_ROWS, n, dev, given)
+        status = solved.view(torch.uint8)
+        if per is None or n <= per:
+            self._call("qttt_solve", self.state.data_ptr(), n, min_ply, value.data_ptr(), q.data_ptr(), best.data_ptr(),
+                       nodes.data_ptr(), status.data_ptr())
+        else:
+            # a launch reads one contiguous run of both planes; their stride is that of the whole batch, so each run is
+            # copied into a batch of its own
+            for lo in range(0, n, per):
+                hi = min(n, lo + per)
+                part = self.take(torch.arange(lo, hi, device=dev))
+                self._call("qttt_solve", part.state.data_ptr(), hi - lo, min_ply, value[lo:hi].data_ptr(),
+                           q[lo:hi].data_ptr(), best[lo:hi].data_ptr(), nodes[lo:hi].data_ptr(), status[lo:hi].data_ptr())
+        if n:
+            torch.logical_not(solved, out=solved)           # the library's status: 0 = solved, 1 = skipped
+        return out if out is not None else SolveResult(value, q, best, nodes, solved)
 
     def encode(self, with_mask=True, out=None):
         """GameState.to_vector (mcts.py:67-85) as f32[N,18,10] and action_mask (mcts.py:87-91) as
