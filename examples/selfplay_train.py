@@ -141,6 +141,9 @@ def main():
     ap.add_argument("--stream", type=int, default=0, metavar="PLIES",
                     help="with --replay: every run is PLIES plies of continuous self-play (finished games restart in "
                          "place and feed the ring) instead of one batch of games in lockstep")
+    ap.add_argument("--exact-from", type=int, default=None, metavar="M",
+                    help="leaves with at least M (6..9) moves played are solved exactly on the device "
+                         "(SelfPlay(exact_from=M); needs --leaf-eval value)")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     if args.stream < 0 or (args.stream and not args.replay):
@@ -160,7 +163,7 @@ def main():
                   root_noise=None if args.root_noise is None else tuple(float(x) for x in args.root_noise.split(",")),
                   temperature=args.temperature, sample_plies=args.sample_plies,
                   eval_symmetries=parse_eval_symmetries(args.eval_symmetries), root_policy=args.root_policy,
-                  max_considered=args.max_considered)
+                  max_considered=args.max_considered, exact_from=args.exact_from)
     ring = ReplayBuffer(args.replay, device=dev, seed=args.seed) if args.replay else None
     trainer = Trainer(model, device=dev, net=net) if args.device_train else None      # nn.py:27's defaults
     if trainer is not None:

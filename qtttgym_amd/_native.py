@@ -195,6 +195,15 @@ SOLVE_DENOMINATOR = 16
 SOLVE_SIGNATURES = {
     "qttt_solve": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# every symbol include/qttt_tree_exact.h declares (exact leaves in the search trees; qttt.h includes it)
+TREE_EXACT_MIN_PLY = 6
+TREE_NODE_SOLVED = 1 << 4
+TREE_NODE_VALUE_SHIFT = 16
+TREE_NODE_VALUE_MASK = 63 << TREE_NODE_VALUE_SHIFT
+TREE_EXACT_SIGNATURES = {
+    "qttt_tree_solve_leaves": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "qttt_tree_backup_batch_exact": TREE_LEAVES_SIGNATURES["qttt_tree_backup_batch"],
+}
 
 _lib = None
 
@@ -263,7 +272,8 @@ def lib():
                                   + list(TREE_EXPLORE_SIGNATURES.items()) + list(TREE_LEAVES_SIGNATURES.items())
                                   + list(NN_SYMMETRIC_SIGNATURES.items()) + list(TREE_GUMBEL_SIGNATURES.items())
                                   + list(REPLAY_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())
-                                  + list(SELFPLAY_STREAM_SIGNATURES.items()) + list(SOLVE_SIGNATURES.items())):
+                                  + list(SELFPLAY_STREAM_SIGNATURES.items()) + list(SOLVE_SIGNATURES.items())
+                                  + list(TREE_EXACT_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -61,7 +61,9 @@
 // qttt_train_kernels.h (the training step: loss, gradients and AMSGrad on the packed f32 blob, on qttt_nn_kernels.h's layers)
 // with qttt_train_host.h (host only and free of HIP: the workspace layout and the launch plan);
 // qttt_selfplay_stream_kernels.h (continuous self-play: the harvest of finished games and their restart in place);
-// qttt_solve_kernels.h (the exact endgame solver: the full expectimax tree of a late position, a workgroup per board).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
+// qttt_solve_kernels.h (the exact endgame solver: the full expectimax tree of a late position, a workgroup per board);
+// qttt_tree_exact_kernels.h (exact leaves in the search trees: a lane per path record, the solver's recursion for the leaves
+// that need it).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
 // qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
@@ -83,6 +85,7 @@
 #include "qttt_train_kernels.h"
 #include "qttt_selfplay_stream_kernels.h"
 #include "qttt_solve_kernels.h"
+#include "qttt_tree_exact_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -876,7 +879,7 @@ int qttt_tree_backup_batch(void *tree, int64_t games, int64_t capacity, int leav
     if (any_null(tree, paths, leaf_value, leaf_probs)) return QTTT_ERR_NULL;
     if (misaligned(tree, 16) || misaligned(paths, 16) || misaligned(leaf_value, 4) || misaligned(leaf_probs, 4))
         return QTTT_ERR_ACTION;
-    return launch(tree_backup_batch_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+    return launch(tree_backup_batch_kernel<false>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
                   (u32)leaves, static_cast<const TreePathRec *>(paths), leaf_value, leaf_probs);
 }
 
@@ -1213,6 +1216,40 @@ int qttt_solve(const void *state, int64_t n, int min_ply, float *value, float *q
                                   (const u64 *)p.Q, i0, min_ply, o))
             return rc;
     return 0;
+}
+
+// ---------------------------------------------------------------- exact leaves in the search trees (include/qttt_tree_exact.h)
+int qttt_tree_solve_leaves(void *tree, int64_t games, int64_t capacity, int leaves, const void *paths,
+                           const void *leaf_state, int min_ply, float *leaf_value, uint8_t *leaf_exact, void *stream) {
+    if (tree_size_bad(games, capacity) || tree_leaves_bad(games, leaves) || min_ply < QTTT_TREE_EXACT_MIN_PLY ||
+        min_ply > QTTT_SOLVE_MAX_PLY)
+        return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, paths, leaf_state)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(paths, 16) || misaligned(leaf_state, 16) || misaligned(leaf_value, 4))
+        return QTTT_ERR_ACTION;
+    const int64_t rows = games * leaves;
+    const Planes l = planes(const_cast<void *>(leaf_state), rows);
+    // a lane per record; a grid holds at most 2^30 workgroups
+    constexpr int64_t GRID_MAX = (int64_t)1 << 30;
+    const int64_t blocks = ceil_div(rows, EXACT_RECORDS);
+    for (int64_t b0 = 0; b0 < blocks; b0 += GRID_MAX)
+        if (const int rc = launch(tree_solve_leaves_kernel, blocks - b0 < GRID_MAX ? blocks - b0 : GRID_MAX, EXACT_BLOCK, stream,
+                                  tree, games, capacity, (u32)leaves, static_cast<const TreePathRec *>(paths), (const u64 *)l.P,
+                                  (const u64 *)l.Q, b0 * EXACT_RECORDS, rows, min_ply, leaf_value, leaf_exact))
+            return rc;
+    return 0;
+}
+
+int qttt_tree_backup_batch_exact(void *tree, int64_t games, int64_t capacity, int leaves, const void *paths,
+                                 const float *leaf_value, const float *leaf_probs, void *stream) {
+    if (tree_size_bad(games, capacity) || tree_leaves_bad(games, leaves)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, paths, leaf_value, leaf_probs)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(paths, 16) || misaligned(leaf_value, 4) || misaligned(leaf_probs, 4))
+        return QTTT_ERR_ACTION;
+    return launch(tree_backup_batch_kernel<true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (u32)leaves, static_cast<const TreePathRec *>(paths), leaf_value, leaf_probs);
 }
 
 }  // extern "C"

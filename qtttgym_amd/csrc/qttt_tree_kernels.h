@@ -23,6 +23,7 @@ namespace {
 constexpr int TREE_BLOCK = 256;                                 // 4 games per workgroup
 constexpr int TREE_GAMES_PER_BLOCK = TREE_BLOCK / 64;
 constexpr u32 TN_PRIORS = 1u, TN_UNIFORM = 2u, TN_TERMINAL = 4u, TN_TURN = 8u;      // node flags
+constexpr u32 TN_SOLVED = 16u, TN_VALUE_SHIFT = 16u, TN_VALUE_MASK = 63u << TN_VALUE_SHIFT;   // include/qttt_tree_exact.h
 constexpr u32 TG_OVERFLOW = 1u, TG_LEAF_TURN = 2u, TG_LEAF_TERMINAL = 4u;          // game-header and path-record flags
 constexpr int TREE_CHILD_PAIR = 1 << 30;
 

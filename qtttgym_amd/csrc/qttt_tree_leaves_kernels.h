@@ -128,6 +128,9 @@ __device__ __forceinline__ TreePathLane tree_path_lane(const TreePathRec *paths,
     return p;
 }
 
+// EXACT: qttt_tree_backup_batch_exact (include/qttt_tree_exact.h): a record of depth >= 1 that ends on a solved leaf is
+// backed up with the node's stored value and the leaf gets no priors; EXACT = false is qttt_tree_backup_batch.
+template <bool EXACT>
 __global__ __launch_bounds__(TREE_BLOCK) void tree_backup_batch_kernel(void *tree, int64_t games, int64_t capacity, u32 leaves,
                                                                        const TreePathRec *paths, const float *leaf_value,
                                                                        const float *leaf_probs) {
@@ -146,7 +149,12 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_backup_batch_kernel(void *tre
         const bool bad_edge = edge && (p.node < 0 || (int64_t)p.node >= capacity || p.action >= 36u);
         if (p.depth > (u32)QTTT_TREE_MAX_DEPTH || p.leaf < 0 || (int64_t)p.leaf >= capacity || __ballot(bad_edge) != 0ull) continue;
         const u32 lf = v.hdr(g, p.leaf)->flags;
-        const double val = (lf & TN_TERMINAL) ? tree_terminal_value(lf) : (double)p.value;
+        double val = (lf & TN_TERMINAL) ? tree_terminal_value(lf) : (double)p.value;
+        bool solved = false;
+        if constexpr (EXACT) {
+            solved = p.depth >= 1u && (lf & (TN_SOLVED | TN_TERMINAL | TN_PRIORS)) == TN_SOLVED;
+            if (solved) val = (double)((int32_t)((lf & TN_VALUE_MASK) >> TN_VALUE_SHIFT) - 16) / 16.0;
+        }
         if (edge) {
             TreeSlot *slot = &v.slots(g, p.node)[p.action];
             TreeNodeHdr *nh = v.hdr(g, p.node);
@@ -154,7 +162,7 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_backup_batch_kernel(void *tre
             slot->N = slot->N + 1u - TREE_FLIGHT_ONE;
             nh->Ntot = nh->Ntot + 1u - TREE_FLIGHT_ONE;
         }
-        tree_leaf_priors(v, g, p.leaf, lf, lane, true, [&](u32 a) { return leaf_probs[(row0 + j) * 36 + a]; });
+        if (!solved) tree_leaf_priors(v, g, p.leaf, lf, lane, true, [&](u32 a) { return leaf_probs[(row0 + j) * 36 + a]; });
         tree_wave_sync();                                        // the next record may pass the same edges and leaf
     }
 }

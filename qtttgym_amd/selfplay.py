@@ -100,12 +100,15 @@ class SelfPlay(LibCaller):
     root_policy="gumbel" (with max_considered, c_visit, c_scale: TreeSearch's; value leaves only) searches every move with
     the Gumbel root: the move is the Gumbel choice and pi the improved policy softmax(logits + sigma(completed Q))
     (qttt_selfplay_record_gumbel); alpha is then unused.  root_noise and sample_plies are rejected with it: the Gumbel
-    noise is the exploration."""
+    noise is the exploration.
+    exact_from is TreeSearch's: leaves with at least that many moves played are solved exactly on the device (value leaves
+    only; play() and stream() alike).  The batch's targets are not changed by it."""
 
     def __init__(self, num_games, n_rollouts=100, num_simulations=10, net=None, alpha=1.0, c_puct=1.0,
                  value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts",
                  root_noise=None, temperature=1.0, sample_plies=0, leaves=1, virtual_loss=1.0,
-                 eval_symmetries=None, root_policy="puct", max_considered=16, c_visit=50.0, c_scale=1.0):
+                 eval_symmetries=None, root_policy="puct", max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None):
+        self.exact_from = TreeSearch.check_exact_from(leaf_eval, net, exact_from)
         self.leaves, self.virtual_loss = TreeSearch.check_search_args(leaf_eval, net, leaves, virtual_loss)
         self.root_policy, self.max_considered, self.c_visit, self.c_scale = TreeSearch.check_root_args(
             leaf_eval, net, root_policy, max_considered, c_visit, c_scale)
@@ -204,7 +207,8 @@ class SelfPlay(LibCaller):
                           c_puct=self.c_puct, net=self.net, seed=2 * s + 1, device=self.device,
                           leaf_eval=self.leaf_eval, leaves=self.leaves, virtual_loss=self.virtual_loss,
                           eval_symmetries=self.eval_symmetries, root_policy=self.root_policy,
-                          max_considered=self.max_considered, c_visit=self.c_visit, c_scale=self.c_scale)
+                          max_considered=self.max_considered, c_visit=self.c_visit, c_scale=self.c_scale,
+                          exact_from=self.exact_from)
         tree.reset(env)
         return env, tree
 

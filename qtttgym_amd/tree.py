@@ -24,6 +24,11 @@ samples max_considered actions without replacement with Gumbel noise, spends the
 halving, rounds of `leaves` at a time, and choose() / root_stats() give the best survivor and the improved policy
 softmax(logits + sigma(completed Q)).  Below the root the search is the leaf-parallel one.
 
+exact_from=M (value leaves only) gives the search exact leaves (include/qttt_tree_exact.h): a leaf with at
+least M moves played is solved on the device, once, by the endgame solver's definition, backed up with its exact value
+instead of the network's, and stays a leaf.  Every rollout is then a round with qttt_tree_solve_leaves between the
+evaluation and the backup.
+
 add_root_noise() is AlphaZero's root exploration (include/qttt_tree_explore.h): Dirichlet noise mixed into
 the priors of every root that has them, one launch.
 """
@@ -49,10 +54,11 @@ class TreeSearch(LibCaller):
     leaf_eval = "playouts"
     root_policy = "puct"
     eval_symmetries = None
+    exact_from = None
 
     def __init__(self, num_games, capacity, num_simulations=10, c_puct=1.0, net=None, seed=0, board_offset=0,
                  device=None, leaf_eval="playouts", leaves=1, virtual_loss=1.0, eval_symmetries=None, root_policy="puct",
-                 max_considered=16, c_visit=50.0, c_scale=1.0):
+                 max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None):
         """leaf_eval="playouts": the reference's rollout, num_simulations playouts from the leaf (uniform, or guided by
         `net`).  leaf_eval="value" (needs `net`): the leaf is scored by the value head, seen by the player to move
         there; a terminal leaf by its reward.  num_simulations is then ignored: no playout draw is taken.
@@ -64,7 +70,12 @@ class TreeSearch(LibCaller):
         rollout is then a round — select_batch, evaluate, backup_batch — a round of one leaf where leaves == 1.
         root_policy="gumbel" (needs leaf_eval="value"): the root considers max_considered actions drawn with Gumbel noise
         and halves them down over the budget of a contemplate(); sigma(q) = (c_visit + max N) * c_scale * q weighs the
-        completed Q against the logits.  root_policy="puct" is the search as it always was."""
+        completed Q against the logits.  root_policy="puct" is the search as it always was.
+        exact_from=M (6..9; needs leaf_eval="value"): a leaf below the root with at least M moves played is solved
+        exactly on the device the first time a round ends on it, and is from then on a leaf with that value: it is backed
+        up with it and never gets priors or children.  Every rollout is then a round — select_batch, evaluate,
+        solve_leaves, backup_batch_exact — also the first after a reset() or sync().  None is the search as it always was."""
+        self.exact_from = self.check_exact_from(leaf_eval, net, exact_from)
         self.leaves, self.virtual_loss = self.check_search_args(leaf_eval, net, leaves, virtual_loss)
         self.root_policy, self.max_considered, self.c_visit, self.c_scale = self.check_root_args(
             leaf_eval, net, root_policy, max_considered, c_visit, c_scale)
@@ -152,6 +163,19 @@ class TreeSearch(LibCaller):
             raise ValueError('eval_symmetries needs leaf_eval="value"')
         return check_eval_symmetries(eval_symmetries)
 
+    @staticmethod
+    def check_exact_from(leaf_eval, net, exact_from):
+        """The constructors' check of exact_from: None, or the least number of moves played of an exact leaf."""
+        if exact_from is None:
+            return None
+        if leaf_eval != "value" or net is None:
+            raise ValueError('exact_from needs a net and leaf_eval="value": exact leaves replace the value head\'s estimate')
+        if isinstance(exact_from, bool) or int(exact_from) != exact_from or \
+                not _native.TREE_EXACT_MIN_PLY <= int(exact_from) <= _native.SOLVE_MAX_PLY:
+            raise ValueError("exact_from must be None or an integer in %d..%d (moves played)"
+                             % (_native.TREE_EXACT_MIN_PLY, _native.SOLVE_MAX_PLY))
+        return int(exact_from)
+
     def _need_reset(self):
         if self._bound is None:
             raise RuntimeError("reset() first")
@@ -203,8 +227,9 @@ class TreeSearch(LibCaller):
         if self._bound + 2 * r > self.capacity:
             raise ValueError("%d rollouts could use %d nodes, more than capacity %d"
                              % (r, self._bound + 2 * r, self.capacity))
-        # a single rollout: the fused value rollout, or — under eval_symmetries — a round of one leaf
-        single = self._rollout if self.eval_symmetries is None else (lambda: self._round(1))
+        # a single rollout: the fused value rollout, or — under eval_symmetries or exact_from — a round of one leaf
+        rounds_only = self.eval_symmetries is not None or self.exact_from is not None
+        single = (lambda: self._round(1)) if rounds_only else self._rollout
         if self.root_policy == "gumbel":
             if r and self._fresh:
                 single()
@@ -251,7 +276,22 @@ class TreeSearch(LibCaller):
             b = self._rounds[k] = {"leaf": VecEnv.from_state(state, n, seed=self.seed, board_offset=self.board_offset),
                                    "paths": torch.zeros(max(nbytes, 16), dtype=torch.uint8, device=dev),
                                    "out": out_rows(VecEnv._EVAL_ROWS, n, dev, keys=("value", "probs"))}
+            if self.exact_from is not None:
+                b["exact"] = torch.zeros(n, dtype=torch.uint8, device=dev)
         return b
+
+    def _backup_round(self, b, k):
+        """The backup of a round of k leaves whose leaves were just evaluated into b["out"]; with exact_from the eligible
+        leaves are solved first (their rows of b["out"]["value"] become exact, b["exact"] says which) and the backup is
+        the one that honours solved nodes."""
+        G, cap, tree = self.num_games, self.capacity, self.tree.data_ptr()
+        value, probs = b["out"]["value"].data_ptr(), b["out"]["probs"].data_ptr()
+        if self.exact_from is None:
+            self._call("qttt_tree_backup_batch", tree, G, cap, k, b["paths"].data_ptr(), value, probs)
+            return
+        self._call("qttt_tree_solve_leaves", tree, G, cap, k, b["paths"].data_ptr(), b["leaf"].state.data_ptr(),
+                   self.exact_from, value, b["exact"].data_ptr())
+        self._call("qttt_tree_backup_batch_exact", tree, G, cap, k, b["paths"].data_ptr(), value, probs)
 
     def _round(self, k):
         """One round of k rollouts (1..TREE_MAX_LEAVES) through the leaf-parallel entries, without contemplate's bounds:
@@ -266,8 +306,7 @@ class TreeSearch(LibCaller):
         self._call("qttt_tree_select_batch", tree, G, cap, self.seed, self.rollout_idx, k, self.board_offset, self.c_puct,
                    self.virtual_loss, b["paths"].data_ptr(), b["leaf"].state.data_ptr())
         b["leaf"].evaluate(self.net, out=b["out"], symmetries=self.eval_symmetries)
-        self._call("qttt_tree_backup_batch", tree, G, cap, k, b["paths"].data_ptr(), b["out"]["value"].data_ptr(),
-                   b["out"]["probs"].data_ptr())
+        self._backup_round(b, k)
         self.rollout_idx += k
 
     def _gumbel_buffers(self):
@@ -320,8 +359,7 @@ class TreeSearch(LibCaller):
                    self.c_puct, self.virtual_loss, b["paths"].data_ptr(), b["leaf"].state.data_ptr(), g["rec"].data_ptr(),
                    g["table"].data_ptr(), g["n"], g["sim"], self.c_visit, self.c_scale)
         b["leaf"].evaluate(self.net, out=b["out"], symmetries=self.eval_symmetries)
-        self._call("qttt_tree_backup_batch", tree, G, cap, k, b["paths"].data_ptr(), b["out"]["value"].data_ptr(),
-                   b["out"]["probs"].data_ptr())
+        self._backup_round(b, k)
         self.rollout_idx += k
         g["sim"] += k
 
@@ -400,6 +438,17 @@ class TreeSearch(LibCaller):
         else:
             self._root(choose=a)
         return a
+
+    def solved_count(self):
+        """i64[G], on the device: the nodes of every game (below its `used`) that carry the solved flag of
+        include/qttt_tree_exact.h; zeros without exact_from.  Torch on the tree buffer, for tests and reports."""
+        self._need_reset()
+        G, cap = self.num_games, self.capacity
+        gb, nb = _native.TREE_GAME_BYTES, _native.TREE_NODE_BYTES
+        used = self.tree[:G * gb].view(G, gb)[:, :4].contiguous().view(torch.int32).view(G)
+        flags = self.tree[G * gb:G * gb + G * cap * nb].view(G, cap, nb)[:, :, 28:32].contiguous().view(torch.int32).view(G, cap)
+        live = torch.arange(cap, device=self.device)[None, :] < used[:, None]
+        return (((flags & _native.TREE_NODE_SOLVED) != 0) & live).sum(1)
 
     def nodes_used(self):
         n = out_tensor(*self._ROOT_ROWS["nodes_used"], self.num_games, self.device)
