@@ -32,9 +32,11 @@
  *   a solved non-leaf:  value, q (-inf at illegal actions), best, nodes as defined;
  *   a skipped board:    status = 1, value = NaN, q = NaN everywhere, best = 255, nodes = 0; it costs no enumeration.
  * min_ply lies in QTTT_SOLVE_MIN_PLY..QTTT_SOLVE_MAX_PLY.  Below four moves played one board is 10^9 positions or more,
- * and nothing should start that by accident; at four moves played a board is up to a few 10^7 positions, at five under
- * 10^6, at six under 5 * 10^4.  One launch solves all n boards, one 256-thread workgroup per board: a caller on a shared
- * device bounds a launch's run time by the number of boards it passes (VecEnv.solve's boards_per_launch).
+ * and nothing should start that by accident.  The largest trees seen in uniform play, none of them a bound
+ * (tests/golden/make_golden_solve_deep.py): 29 695 353 positions in 96 boards with four moves played (29 796 849 in the
+ * benchmark's 256), 1 244 383 in 1 280 boards with five (1 251 779 in the benchmark's 256), 51 268 in 2 000 boards with
+ * six.  One launch solves all n boards, one 256-thread workgroup per board: a caller on a shared device bounds a launch's
+ * run time by the number of boards it passes (VecEnv.solve's boards_per_launch).
  *
  * ---- qttt_solve(state, n, min_ply, value, q, best, nodes, status, stream).  state: the packed state of n boards
  * (qttt_state_bytes(n) bytes), read only.  Outputs, each nullable: value f32[n], q f32[n, 36], best u8[n], nodes

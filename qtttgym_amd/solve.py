@@ -12,7 +12,7 @@ from . import _native
 #     full round of 1 280 copies: twice a full round is over a second, twice one board per CU is 0.68 s -> 256 boards;
 #   five moves played: the largest (1.25 M positions) takes 29.6 ms as a full round; 1 s / (2 x 29.6 ms) = 16 rounds
 #     = 20 480 boards -> 16 384, the power of two below.
-# From six moves played on a board is at most 5 * 10^4 positions (4 096 of them: 1 ms) and no split is needed.
+# From six moves played on the largest board seen is 5.1 * 10^4 positions (4 096 boards: 1 ms) and no split is needed.
 BOARDS_PER_LAUNCH = {4: 256, 5: 16384}
 
 

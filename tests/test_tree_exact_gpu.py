@@ -5,6 +5,7 @@ nothing is eligible; sync, compact and further search; guard bytes and nullable 
 tests/test_tree_exact_cpu.py asserts, without a GPU, that every search compared here solves nodes."""
 import copy
 import functools
+import os
 
 import numpy as np
 import pytest
@@ -190,14 +191,14 @@ def test_every_solved_node_holds_the_solver_s_value_and_is_a_leaf(K, M):
 
 
 # ---------------------------------------------------------------- the test that fails without the feature
-@pytest.mark.parametrize("K", [1, 4])
-def test_root_statistics_of_five_move_boards_are_the_solver_s_q(K):
+def _root_statistics_are_the_solver_s_q(arrays, K):
     """From a root with five moves played every child has six, so with exact_from = 6 every child is a solved leaf and W
     of a root action is a sum of sixteenths, exact in f64: for an action that is no collapse W / N == the solver's q, bit
     for bit; for a collapse W / N lies between the two children's negated values.  Without exact_from the same search
-    backs the network's values up and differs."""
-    G, rollouts, net = 16, 41, _net("sharp")
-    arrays, _ = E.roots(G, played=5)
+    backs the network's values up and differs.  Returns the q compared: (of the actions that are no collapse, of the
+    collapses whose two children were both visited)."""
+    G, rollouts, net = len(arrays["n_moves"]), 41, _net("sharp")
+    seen_exact, seen_between = [], []
     env = env_from_arrays(arrays)
     q = env.solve(min_ply=5).q.double().cpu().numpy()
     t, _ = _search(arrays, 2 + 2 * rollouts, net, leaves=K, exact_from=6)
@@ -214,12 +215,14 @@ def test_root_statistics_of_five_move_boards_are_the_solver_s_q(K):
             if not c & tree_layout.CHILD_PAIR:
                 assert mean == q[g, a] == st["Q"][g, a], (g, a)
                 exact += 1
+                seen_exact.append(q[g, a])
             else:
                 kids = nodes[g, [c & (tree_layout.CHILD_PAIR - 1), (c & (tree_layout.CHILD_PAIR - 1)) + 1]]
                 vals = [0.0 - (((int(f) & MASK) >> SHIFT) - 16) / 16.0 for f in kids["flags"] if f & SOLVED]
                 if len(vals) == 2:                       # both children were visited, and neither is terminal
                     assert min(vals) <= mean <= max(vals) and (min(vals) + max(vals)) / 2 == q[g, a], (g, a)
                     between += 1
+                    seen_between.append(q[g, a])
     assert exact >= 3 * G and between > 0
     plain, _ = _search(arrays, 2 + 2 * rollouts, net, leaves=K)
     plain.contemplate(rollouts)
@@ -227,6 +230,31 @@ def test_root_statistics_of_five_move_boards_are_the_solver_s_q(K):
     seen = ps["N"] > 0
     assert (ps["W"][seen] / ps["N"][seen] != q[seen]).any()
     assert int(plain.solved_count().sum()) == 0
+    return np.array(seen_exact), np.array(seen_between)
+
+
+@pytest.mark.parametrize("K", [1, 4])
+def test_root_statistics_of_five_move_boards_are_the_solver_s_q(K):
+    _root_statistics_are_the_solver_s_q(E.roots(16, played=5)[0], K)
+
+
+@pytest.mark.parametrize("K", [1, 4])
+def test_root_statistics_of_the_deep_five_move_boards_are_the_solver_s_q_down_to_sixteenths(K):
+    """The same from tests/golden/solve_deep.npz's five-move boards that carry sixteenths and eighths: the value kept in
+    a node's spare flag bits is then compared at odd multiples of 1/8 (W / N of a single child) and its halved sum at odd
+    multiples of 1/16 (a collapse whose two children were visited)."""
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "solve_deep.npz")) as z:
+        five = np.flatnonzero(z["played"] == 5)
+        q16 = z["q"][five].astype(np.float64) * 16
+        fin = np.isfinite(q16)
+        odd8 = (fin & (np.where(fin, q16, 0) % 4 != 0)).any(1)           # an eighth or a sixteenth among the board's q
+        assert (fin & (np.where(fin, q16, 0) % 2 != 0)).any(1).sum() >= 1 and odd8.sum() >= 9
+        arrays = {k: z[k][five[odd8]] for k in E.ARRAYS}
+    exact, between = _root_statistics_are_the_solver_s_q(arrays, K)
+    odd = lambda x, m: int((np.round(x * 16).astype(np.int64) % m != 0).sum())  # noqa: E731
+    print("deep roots K=%d: %d boards, %d single-child q (%d eighths), %d collapse q (%d eighths or sixteenths, %d sixteenths)"
+          % (K, len(five[odd8]), len(exact), odd(exact, 4), len(between), odd(between, 4), odd(between, 2)))
+    assert odd(exact, 4) + odd(between, 4) > 0
 
 
 # ---------------------------------------------------------------- unchanged results
