@@ -9,7 +9,8 @@ with --device-train, on the device), packs the new weights for the search and re
                                       [--symmetries] [--leaf-eval playouts|value]
                                       [--root-noise EPS,ALPHA] [--temperature T] [--sample-plies K] [--leaves K]
                                       [--eval-symmetries all|0,4] [--replay CAPACITY --batch B --steps S]
-                                      [--device-train] [--stream PLIES]
+                                      [--device-train] [--stream PLIES] [--exact-from M]
+                                      [--exact-targets M [--exact-value-only]]
 
 The network is nn.Model's (nn.py:7-28) under its own parameter names (qtttgym_amd.policy_value.SHAPES), so --out is a
 state dict that the reference, PolicyValueNet and examples/tree_tournament.py --model all load.  The loss is the
@@ -40,6 +41,10 @@ and no repacking of the weights between runs; --out is then the trainer's state 
 (SelfPlay.stream): every run advances the slots by PLIES searched plies, a slot whose game ends hands its samples to the ring
 and starts a new game at once, and the run's --steps minibatches follow.  The counters stay on the device; the printed
 line reads them back once per run.
+--exact-targets M (6..9) trains the late positions on the truth (SelfPlay(exact_targets=M)): every recorded, non-terminal
+position with at least M moves played is enumerated on the device, its value target becomes its exact value for the
+player to move and its policy target the uniform distribution over its optimal moves (--exact-value-only keeps the
+visit-count policy).  The exact value is the mover's, in [-1, 1], so the option sets --value-targets to 1,-1 itself.
 """
 import argparse
 import os
@@ -144,6 +149,12 @@ def main():
     ap.add_argument("--exact-from", type=int, default=None, metavar="M",
                     help="leaves with at least M (6..9) moves played are solved exactly on the device "
                          "(SelfPlay(exact_from=M); needs --leaf-eval value)")
+    ap.add_argument("--exact-targets", type=int, default=None, metavar="M",
+                    help="positions with at least M (6..9) moves played get their exact value and optimal-move policy as "
+                         "targets (SelfPlay(exact_targets=M)); sets --value-targets 1,-1.  From M = 7 the relabelling is nearly "
+                         "free; at M = 6 a --stream ply takes about four times as long (DESIGN.md §25)")
+    ap.add_argument("--exact-value-only", action="store_true",
+                    help="with --exact-targets: relabel the value target only, keep the visit-count policy")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     if args.stream < 0 or (args.stream and not args.replay):
@@ -157,13 +168,16 @@ def main():
         model.load_state_dict(torch.load(args.model, map_location=dev))
     optim = torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-3, amsgrad=True)      # nn.py:27
     net = PolicyValueNet(model, device=dev, dtype=torch.float32 if args.dtype == "f32" else torch.bfloat16)
-    targets = tuple(float(x) for x in args.value_targets.split(","))
+    if args.exact_value_only and args.exact_targets is None:
+        ap.error("--exact-value-only needs --exact-targets")
+    targets = (1.0, -1.0) if args.exact_targets is not None else tuple(float(x) for x in args.value_targets.split(","))
     sp = SelfPlay(args.games, n_rollouts=args.rollouts, num_simulations=args.sims, net=net, value_targets=targets,
                   seed=args.seed, leaf_eval=args.leaf_eval, leaves=args.leaves,
                   root_noise=None if args.root_noise is None else tuple(float(x) for x in args.root_noise.split(",")),
                   temperature=args.temperature, sample_plies=args.sample_plies,
                   eval_symmetries=parse_eval_symmetries(args.eval_symmetries), root_policy=args.root_policy,
-                  max_considered=args.max_considered, exact_from=args.exact_from)
+                  max_considered=args.max_considered, exact_from=args.exact_from,
+                  exact_targets=args.exact_targets, exact_policy=not args.exact_value_only)
     ring = ReplayBuffer(args.replay, device=dev, seed=args.seed) if args.replay else None
     trainer = Trainer(model, device=dev, net=net) if args.device_train else None      # nn.py:27's defaults
     if trainer is not None:

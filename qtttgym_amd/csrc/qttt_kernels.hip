@@ -63,8 +63,10 @@
 // qttt_selfplay_stream_kernels.h (continuous self-play: the harvest of finished games and their restart in place);
 // qttt_solve_kernels.h (the exact endgame solver: the full expectimax tree of a late position, a workgroup per board);
 // qttt_tree_exact_kernels.h (exact leaves in the search trees: a lane per path record, the solver's recursion for the leaves
-// that need it).  Host only: qttt_launch.h (launch shape, kernel selection, the one launch form, the argument checks),
-// qttt_mailbox.h (the host half of the single-record mailbox); this file: the step's launch logic + the C ABI.
+// that need it); qttt_selfplay_exact_kernels.h (exact targets for the late rows of a self-play batch: a lane per staging row,
+// the same recursion, every action's value kept for the policy).  Host only: qttt_launch.h (launch shape, kernel selection,
+// the one launch form, the argument checks), qttt_mailbox.h (the host half of the single-record mailbox); this file: the
+// step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -86,6 +88,7 @@
 #include "qttt_selfplay_stream_kernels.h"
 #include "qttt_solve_kernels.h"
 #include "qttt_tree_exact_kernels.h"
+#include "qttt_selfplay_exact_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -1250,6 +1253,26 @@ int qttt_tree_backup_batch_exact(void *tree, int64_t games, int64_t capacity, in
         return QTTT_ERR_ACTION;
     return launch(tree_backup_batch_kernel<true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
                   (u32)leaves, static_cast<const TreePathRec *>(paths), leaf_value, leaf_probs);
+}
+
+// ---------------------------------------------------------------- exact targets of a self-play batch (include/qttt_selfplay_exact.h)
+int qttt_selfplay_exact_targets(const void *states, int64_t games, int min_ply, int policy, const uint8_t *rows,
+                                const uint8_t *length, const uint8_t *done, const uint8_t *mask, double *pi, float *v,
+                                uint8_t *exact, void *stream) {
+    if (games < 0 || min_ply < QTTT_SELFPLAY_EXACT_MIN_PLY || min_ply > QTTT_SELFPLAY_EXACT_MAX_PLY || policy < 0 || policy > 1)
+        return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(states, length, done, mask) || any_null(pi, v)) return QTTT_ERR_NULL;
+    if (misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
+    const ExactTargets o = {static_cast<const u64 *>(states), rows, length, done, pi, v, exact};
+    // a lane per record; a grid holds at most 2^30 workgroups
+    constexpr int64_t GRID_MAX = (int64_t)1 << 30;
+    const int64_t blocks = ceil_div((int64_t)QTTT_SELFPLAY_ROWS * games, TARGETS_RECORDS);
+    for (int64_t b0 = 0; b0 < blocks; b0 += GRID_MAX)
+        if (const int rc = launch(selfplay_exact_targets_kernel, blocks - b0 < GRID_MAX ? blocks - b0 : GRID_MAX, TARGETS_BLOCK,
+                                  stream, o, games, b0 * TARGETS_RECORDS, min_ply, policy))
+            return rc;
+    return 0;
 }
 
 }  // extern "C"

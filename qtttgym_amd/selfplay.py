@@ -12,14 +12,15 @@ before every searched move, and sample_plies / temperature draw the move of the 
 board's eight symmetries, which the reference left as a stub (self_play.py expand_symetries), are SelfPlayBatch.augment (DESIGN.md
 §14): one launch turns the batch of G games into the batch of 8 G games it stands for.  sp.stream(ring, plies) is
 continuous self-play (include/qttt_selfplay_stream.h): the G slots stay full, a finished game hands its rows
-to a ReplayBuffer and restarts in place.
+to a ReplayBuffer and restarts in place.  exact_targets=M replaces the value and policy targets of the positions with at
+least M moves played by the truth, enumerated on the device (include/qttt_selfplay_exact.h).
 """
 import ctypes
 
 import torch
 
 from . import _native
-from ._host import LibCaller, _raw_stream, check_net, check_tensor, resolve_device
+from ._host import LibCaller, _ptr, _raw_stream, check_net, check_tensor, resolve_device
 from .symmetry import check_symmetries
 from .tree import TreeSearch
 from .vec_env import VecEnv
@@ -69,6 +70,30 @@ class SelfPlayBatch:
         _native.check(rc, "qttt_selfplay_augment")
         return out
 
+    def exact_targets(self, min_ply, policy=True, rows=None):
+        """Relabels the late rows in place (include/qttt_selfplay_exact.h qttt_selfplay_exact_targets, one launch, no host
+        synchronisation): every recorded, non-terminal row with at least `min_ply` (6..9) moves played gets v = the exact
+        expectimax value of its position for the player to move and, with policy=True, pi = the uniform distribution
+        over its optimal actions; every other byte of the batch stays.  rows (u8[G], optional) stands in for `length`: the
+        rows below rows[g] of game g are looked at, none of a game with 0.  Returns u8[10, G], 1 where a row was
+        relabelled.  The exact value is the mover's, in [-1, 1]: it belongs with value targets (1, -1), which SelfPlay
+        enforces and this method cannot know."""
+        m = SelfPlay.check_min_ply(min_ply, "min_ply")
+        G, dev = self.num_games, self.device
+        if rows is not None:
+            check_tensor(rows, torch.uint8, (G,), dev, "rows")
+        exact = torch.empty((ROWS, G), dtype=torch.uint8, device=dev)
+        self._exact_targets(m, policy, rows, exact)
+        return exact
+
+    def _exact_targets(self, min_ply, policy, rows, exact):
+        with torch.cuda.device(self.device):
+            rc = _native.lib().qttt_selfplay_exact_targets(
+                self.states.data_ptr(), self.num_games, min_ply, 1 if policy else 0, _ptr(rows), self.length.data_ptr(),
+                self.done.data_ptr(), self.mask.data_ptr(), self.pi.data_ptr(), self.v.data_ptr(), _ptr(exact),
+                _raw_stream(self.device.index))
+        _native.check(rc, "qttt_selfplay_exact_targets")
+
     def flat(self):
         """The reference's batch, game-major and in the order self_play.py:200-216 appends: s f32[n, 18, 10]
         (GameState.to_vector, by encode()), pi f64[n, 36], mask bool[n, 36], v f32[n], done bool[n], with
@@ -102,12 +127,24 @@ class SelfPlay(LibCaller):
     (qttt_selfplay_record_gumbel); alpha is then unused.  root_noise and sample_plies are rejected with it: the Gumbel
     noise is the exploration.
     exact_from is TreeSearch's: leaves with at least that many moves played are solved exactly on the device (value leaves
-    only; play() and stream() alike).  The batch's targets are not changed by it."""
+    only; play() and stream() alike).  It changes the search, not the batch's targets: that is exact_targets.
+    exact_targets=M (6..9; independent of exact_from, leaf_eval, root_policy and net) relabels the targets themselves
+    (SelfPlayBatch.exact_targets, one launch): every recorded, non-terminal position with at least M moves played gets its
+    exact value as v and, with exact_policy=True, the uniform distribution over its optimal moves as pi.  play() does it
+    after its last ply and keeps the mask of relabelled rows as batch.exact; stream() does it between the harvest and the
+    ring's append, for the games that ply hands to the ring only.  No host synchronisation on either route.  It needs
+    value_targets=(1.0, -1.0): the exact value is the mover's, in [-1, 1], and the reference's (1, 0) is not zero-sum.
+    Cost: from M = 7 the launch is cheaper than VecEnv.solve per row and adds under a tenth to a stream
+    ply; at M = 6 it is several times dearer than that composition and a stream ply takes about four times as long.
+    With the default None play() and stream() issue the calls they always did, and batch.exact is absent."""
 
     def __init__(self, num_games, n_rollouts=100, num_simulations=10, net=None, alpha=1.0, c_puct=1.0,
                  value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts",
                  root_noise=None, temperature=1.0, sample_plies=0, leaves=1, virtual_loss=1.0,
-                 eval_symmetries=None, root_policy="puct", max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None):
+                 eval_symmetries=None, root_policy="puct", max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None,
+                 exact_targets=None, exact_policy=True):
+        self.exact_targets = self.check_exact_targets(exact_targets, value_targets)
+        self.exact_policy = bool(exact_policy)
         self.exact_from = TreeSearch.check_exact_from(leaf_eval, net, exact_from)
         self.leaves, self.virtual_loss = TreeSearch.check_search_args(leaf_eval, net, leaves, virtual_loss)
         self.root_policy, self.max_considered, self.c_visit, self.c_scale = TreeSearch.check_root_args(
@@ -157,6 +194,27 @@ class SelfPlay(LibCaller):
         self.env = self.tree = None   # the last play()'s or stream()'s environment (at its positions) and trees
         self._stream = None           # stream()'s games in progress: environment, trees, staging batch, counters
         self.stream_epoch_plies = None    # None: a seed serves as many plies as the draw counters allow (epoch_plies)
+
+    @staticmethod
+    def check_min_ply(m, what):
+        if isinstance(m, bool) or not isinstance(m, (int, float)) or int(m) != m or \
+                not _native.SELFPLAY_EXACT_MIN_PLY <= int(m) <= _native.SELFPLAY_EXACT_MAX_PLY:
+            raise ValueError("%s must be an integer in %d..%d (moves played): below six one board is milliseconds of work, "
+                             "which VecEnv.solve is for" % (what, _native.SELFPLAY_EXACT_MIN_PLY,
+                                                            _native.SELFPLAY_EXACT_MAX_PLY))
+        return int(m)
+
+    @staticmethod
+    def check_exact_targets(exact_targets, value_targets):
+        """The constructor's check of exact_targets: None, or the least number of moves played of a relabelled row."""
+        if exact_targets is None:
+            return None
+        m = SelfPlay.check_min_ply(exact_targets, "exact_targets")
+        if tuple(float(x) for x in value_targets) != (1.0, -1.0):
+            raise ValueError("exact_targets needs value_targets=(1.0, -1.0): the exact value is the mover's, in [-1, 1], and "
+                             "the reference's (1, 0) is not zero-sum, so the relabelled rows would be on another scale "
+                             "than the rest of the batch")
+        return m
 
     def new_batch(self):
         """A zero-filled SelfPlayBatch for num_games games."""
@@ -270,6 +328,8 @@ class SelfPlay(LibCaller):
             tree.sync(env)
             if self.compact:
                 tree.compact()
+        if self.exact_targets is not None:
+            batch.exact = batch.exact_targets(self.exact_targets, self.exact_policy)
         return batch
 
     # ------------------------------------------------------------------ continuous self-play
@@ -282,8 +342,9 @@ class SelfPlay(LibCaller):
         One stream ply: the search of play() in every slot (every root is live) -> the record at each slot's OWN ply
         (row length[g] of the staging batch) -> step, sync [, compact] -> harvest: a slot whose new root is terminal
         gets its terminal row and value targets, its rows are appended to `ring` (a ReplayBuffer on this device; slots
-        ascending, rows in order), and the slot restarts from the empty board.  Three launches and the append's on top
-        of play()'s per ply, and no host read-back (compact=True keeps its one per move).
+        ascending, rows in order; with exact_targets relabelled first), and the slot restarts from the empty board.
+        Three launches and the append's on top of play()'s per ply, and no host read-back (compact=True keeps its one per
+        move).
         The first call (and the first after stream_reset()) starts every slot from the empty board with `seed`
         (None: self.seed + the number of earlier play() / stream starts); later calls continue the games in progress,
         and take seed=None or the running stream's.  The draw counters run on across restarts and calls, so no
@@ -339,6 +400,8 @@ class SelfPlay(LibCaller):
         if self.compact:
             tree.compact()
         self._stream_harvest(st)
+        if self.exact_targets is not None:          # only the games this ply hands to the ring, once each
+            batch._exact_targets(self.exact_targets, self.exact_policy, st["harvest_len"], None)
         ring.add(batch, length=st["harvest_len"])
         self._stream_restart(st)
         st["ply"] += 1
