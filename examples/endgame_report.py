@@ -65,18 +65,19 @@ def random_positions(games, min_ply, seed):
     return joined(parts) if parts else None
 
 
-def searched_moves(pos, player, net, sims, seed, exact_from=None):
+def searched_moves(pos, player, net, sims, seed, exact_from=None, prove=False):
     kind, R = player
     value = kind in VALUE_KINDS
     tree = TreeSearch(pos.num_envs, capacity=2 * R + 10, num_simulations=sims, net=net if kind == "az" or value else None,
                       seed=2 * seed + 1, device=pos.device, leaf_eval="value" if value else "playouts",
-                      root_policy="gumbel" if kind == "azg" else "puct", exact_from=exact_from if value else None)
+                      root_policy="gumbel" if kind == "azg" else "puct", exact_from=exact_from if value else None,
+                      prove=prove and value and exact_from is not None)
     tree.reset(pos)
     tree.contemplate(R)
-    return tree.choose()
+    return tree.choose(exact=True) if tree.prove else tree.choose()
 
 
-def report(pos, sol, net, player, sims, seed, exact_from=None):
+def report(pos, sol, net, player, sims, seed, exact_from=None, prove=False):
     """The figures as a dict; `pos` holds unfinished positions only, all of them solved."""
     V, Q = sol.value.double(), sol.q.double()
     legal = torch.isfinite(Q)
@@ -91,7 +92,7 @@ def report(pos, sol, net, player, sims, seed, exact_from=None):
            "uniform_optimal": float(((gap == 0) & legal).double().sum(1).div(legal.sum(1)).mean()),
            "uniform_regret": float((uniform * gap).sum(1).mean())}
     if player[0] != "random":
-        reg = sol.regret(searched_moves(pos, player, net, sims, seed, exact_from)).double()
+        reg = sol.regret(searched_moves(pos, player, net, sims, seed, exact_from, prove)).double()
         out["search_optimal"], out["search_regret"] = float((reg == 0).double().mean()), float(reg.mean())
     values, counts = torch.unique(sol.value, return_counts=True)
     out["histogram"] = [(float(v), int(c)) for v, c in zip(values.cpu(), counts.cpu())]
@@ -115,7 +116,12 @@ def main(argv=None):
     ap.add_argument("--exact-from", type=int, default=None, metavar="M",
                     help="an azv or azg --player solves leaves with at least M (6..9) moves played exactly "
                          "(TreeSearch(exact_from=M))")
+    ap.add_argument("--prove", action="store_true",
+                    help="with --exact-from: prove interior nodes too and play the exact move at a proven root "
+                         "(TreeSearch(prove=True), choose(exact=True))")
     args = ap.parse_args(argv)
+    if args.prove and args.exact_from is None:
+        raise SystemExit("--prove needs --exact-from")
     if not _native.SOLVE_MIN_PLY <= args.min_ply <= 8:
         raise SystemExit("--min-ply must be in %d..8" % _native.SOLVE_MIN_PLY)
     player = parse_player(args.player)
@@ -126,14 +132,15 @@ def main(argv=None):
         raise SystemExit("no unfinished position with %d or more moves played" % args.min_ply)
     sol = pos.solve(min_ply=args.min_ply)
     assert bool(sol.solved.all()) and bool((sol.best < 36).all())
-    r = report(pos, sol, net, player, args.sims, args.seed, args.exact_from)
+    r = report(pos, sol, net, player, args.sims, args.seed, args.exact_from, args.prove)
     src = "the uniform-legal policy" if args.random else "self-play (azv, %d rollouts per move)" % args.rollouts
     print("%d unfinished positions with >= %d moves played from %d games of %s, seed %d; %d positions enumerated"
           % (r["positions"], args.min_ply, args.games, src, args.seed, r["nodes"]))
     print("value head: mean absolute error %.4f, bias %+.4f" % (r["value_mae"], r["value_bias"]))
     print("policy: argmax optimal %.4f, expected regret %.4f" % (r["policy_optimal"], r["policy_regret"]))
     if "search_regret" in r:
-        name = args.player + ("" if args.exact_from is None else " with exact leaves from %d moves" % args.exact_from)
+        name = args.player + ("" if args.exact_from is None else " with exact leaves from %d moves" % args.exact_from) \
+            + (" and proven nodes" if args.prove else "")
         print("search %s: move optimal %.4f, regret %.4f" % (name, r["search_optimal"], r["search_regret"]))
     print("uniform policy: move optimal %.4f, expected regret %.4f" % (r["uniform_optimal"], r["uniform_regret"]))
     print("exact values: " + ", ".join("%+.4f x %d" % vc for vc in r["histogram"]))

@@ -9,7 +9,7 @@ with --device-train, on the device), packs the new weights for the search and re
                                       [--symmetries] [--leaf-eval playouts|value]
                                       [--root-noise EPS,ALPHA] [--temperature T] [--sample-plies K] [--leaves K]
                                       [--eval-symmetries all|0,4] [--replay CAPACITY --batch B --steps S]
-                                      [--device-train] [--stream PLIES] [--exact-from M]
+                                      [--device-train] [--stream PLIES] [--exact-from M] [--prove]
                                       [--exact-targets M [--exact-value-only]]
 
 The network is nn.Model's (nn.py:7-28) under its own parameter names (qtttgym_amd.policy_value.SHAPES), so --out is a
@@ -149,6 +149,8 @@ def main():
     ap.add_argument("--exact-from", type=int, default=None, metavar="M",
                     help="leaves with at least M (6..9) moves played are solved exactly on the device "
                          "(SelfPlay(exact_from=M); needs --leaf-eval value)")
+    ap.add_argument("--prove", action="store_true",
+                    help="with --exact-from: the search proves interior nodes too (SelfPlay(prove=True))")
     ap.add_argument("--exact-targets", type=int, default=None, metavar="M",
                     help="positions with at least M (6..9) moves played get their exact value and optimal-move policy as "
                          "targets (SelfPlay(exact_targets=M)); sets --value-targets 1,-1.  From M = 7 the relabelling is nearly "
@@ -159,6 +161,8 @@ def main():
     args = ap.parse_args()
     if args.stream < 0 or (args.stream and not args.replay):
         ap.error("--stream needs PLIES >= 1 and --replay")
+    if args.prove and args.exact_from is None:
+        ap.error("--prove needs --exact-from")
     if args.replay and (args.batch < 1 or args.steps < 1):
         ap.error("--replay needs --batch >= 1 and --steps >= 1")
     torch.manual_seed(args.seed)
@@ -176,7 +180,7 @@ def main():
                   root_noise=None if args.root_noise is None else tuple(float(x) for x in args.root_noise.split(",")),
                   temperature=args.temperature, sample_plies=args.sample_plies,
                   eval_symmetries=parse_eval_symmetries(args.eval_symmetries), root_policy=args.root_policy,
-                  max_considered=args.max_considered, exact_from=args.exact_from,
+                  max_considered=args.max_considered, exact_from=args.exact_from, prove=args.prove,
                   exact_targets=args.exact_targets, exact_policy=not args.exact_value_only)
     ring = ReplayBuffer(args.replay, device=dev, seed=args.seed) if args.replay else None
     trainer = Trainer(model, device=dev, net=net) if args.device_train else None      # nn.py:27's defaults

@@ -54,11 +54,13 @@ def load_state_dict(args):
 VALUE_KINDS = ("azv", "azg")           # the players that score a leaf by the value head
 
 
-def play(players, G, sims, net, seed, carry=None, leaves=(1, 1), eval_symmetries=None, max_considered=16, exact_from=None):
+def play(players, G, sims, net, seed, carry=None, leaves=(1, 1), eval_symmetries=None, max_considered=16, exact_from=None,
+         prove=False):
     """One half: players[0] moves first; leaves[i] = the leaves per round of players[i] when it is an azv player, and
     eval_symmetries what the azv players average the network over.  Returns winner i8[G] (1 = the first mover, 0 = the second, -1 = none).
     carry: None = the trees never compact; else they compact after every sync and hold 2 * R + carry nodes (carry < 0:
-    2 * R + 2 of them).  exact_from: the azv and azg players solve leaves with that many moves played exactly."""
+    2 * R + 2 of them).  exact_from: the azv and azg players solve leaves with that many moves played exactly; prove: they
+    prove interior nodes as well (the played move stays the search's own choice)."""
     env = VecEnv(G, seed=seed)
     trees = []
     for i, (kind, R) in enumerate(players):
@@ -72,7 +74,7 @@ def play(players, G, sims, net, seed, carry=None, leaves=(1, 1), eval_symmetries
                        seed=seed * 2 + 1 + i, device=env.device, leaf_eval="value" if value else "playouts",
                        leaves=leaves[i] if value else 1, eval_symmetries=eval_symmetries if value else None,
                        root_policy="gumbel" if kind == "azg" else "puct", max_considered=max_considered,
-                       exact_from=exact_from if value else None)
+                       exact_from=exact_from if value else None, prove=prove and value and exact_from is not None)
         t.reset(env)
         trees.append(t)
     finished = torch.zeros(G, dtype=torch.bool, device=env.device)
@@ -123,7 +125,11 @@ def main():
     ap.add_argument("--exact-from", type=int, default=None, metavar="M",
                     help="the azv and azg players solve leaves with at least M (6..9) moves played exactly on the device "
                          "(TreeSearch(exact_from=M))")
+    ap.add_argument("--prove", action="store_true",
+                    help="with --exact-from: those players prove interior nodes too (TreeSearch(prove=True))")
     args = ap.parse_args()
+    if args.prove and args.exact_from is None:
+        raise SystemExit("--prove needs --exact-from")
     syms = args.eval_symmetries
     syms = syms if syms in (None, "all") else tuple(int(k) for k in syms.split(","))
     p1, p2 = parse_player(args.p1), parse_player(args.p2)
@@ -143,9 +149,9 @@ def main():
             raise SystemExit("--carry must be >= 0")
         carry = args.carry if args.carry is not None else -1
     w_a = play((p1, p2), half, args.sims, net, args.seed, carry, (k1, k2), syms, args.max_considered,
-               args.exact_from)                                                                             # player 1 moves first
+               args.exact_from, args.prove)                                                                 # player 1 moves first
     w_b = play((p2, p1), half, args.sims, net, args.seed + 1, carry, (k2, k1), syms, args.max_considered,
-               args.exact_from)                                                                             # player 2 moves first
+               args.exact_from, args.prove)                                                                 # player 2 moves first
     wins = int((w_a == 1).sum()) + int((w_b == 0).sum())
     losses = int((w_a == 0).sum()) + int((w_b == 1).sum())
     draws = int((w_a == -1).sum()) + int((w_b == -1).sum())

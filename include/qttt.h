@@ -357,5 +357,6 @@ uint64_t qttt_hash(uint64_t seed, uint64_t board_id, uint32_t step_idx);
 #include "qttt_selfplay_stream.h"
 #include "qttt_solve.h"
 #include "qttt_tree_exact.h"
+#include "qttt_tree_prove.h"
 #include "qttt_selfplay_exact.h"
 #endif

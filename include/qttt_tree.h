@@ -31,7 +31,8 @@
  *     header 32 B:  u64 P, u64 Q (the packed state, planes P / Q of the state layout) | u64 legal (bit a = action a)
  *                   | u32 Ntot | u32 flags (bit 0 has priors, 1 uniform priors, 2 terminal, 3 turn (True = the first
  *                   player to move), bits 8-9 winner + 1: 0 None, 1 False, 2 True)
- *                   (bit 4 and bits 16-21, the exact leaves' solved flag and value: qttt_tree_exact.h)
+ *                   (bit 4 and bits 16-21, the exact leaves' solved flag and value: qttt_tree_exact.h; set for proven
+ *                   interior nodes too: qttt_tree_prove.h)
  *     36 action slots of 16 B at 32 + 16 a:  f64 W | u32 N | i32 child (-1 = not expanded; else bits [0,30) = the
  *                   index of child 0 and bit 30 = a collapse, whose child 1 sits at index + 1)
  *   priors of node i of game g at 128 games + QTTT_TREE_NODE_BYTES games capacity + 144 (g capacity + i): f32[36], the

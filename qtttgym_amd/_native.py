@@ -204,6 +204,11 @@ TREE_EXACT_SIGNATURES = {
     "qttt_tree_solve_leaves": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "qttt_tree_backup_batch_exact": TREE_LEAVES_SIGNATURES["qttt_tree_backup_batch"],
 }
+# every symbol include/qttt_tree_prove.h declares (proven interior nodes of the search trees; qttt.h includes it)
+TREE_PROVE_SIGNATURES = {
+    "qttt_tree_prove": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "qttt_tree_root_exact": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+}
 # every symbol include/qttt_selfplay_exact.h declares (exact targets for the late rows of a self-play batch; qttt.h includes it)
 SELFPLAY_EXACT_MIN_PLY, SELFPLAY_EXACT_MAX_PLY = 6, 9
 SELFPLAY_EXACT_SIGNATURES = {
@@ -278,7 +283,8 @@ def lib():
                                   + list(NN_SYMMETRIC_SIGNATURES.items()) + list(TREE_GUMBEL_SIGNATURES.items())
                                   + list(REPLAY_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())
                                   + list(SELFPLAY_STREAM_SIGNATURES.items()) + list(SOLVE_SIGNATURES.items())
-                                  + list(TREE_EXACT_SIGNATURES.items()) + list(SELFPLAY_EXACT_SIGNATURES.items())):
+                                  + list(TREE_EXACT_SIGNATURES.items()) + list(SELFPLAY_EXACT_SIGNATURES.items())
+                                  + list(TREE_PROVE_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -64,7 +64,8 @@
 // qttt_solve_kernels.h (the exact endgame solver: the full expectimax tree of a late position, a workgroup per board);
 // qttt_tree_exact_kernels.h (exact leaves in the search trees: a lane per path record, the solver's recursion for the leaves
 // that need it); qttt_selfplay_exact_kernels.h (exact targets for the late rows of a self-play batch: a lane per staging row,
-// the same recursion, every action's value kept for the policy).  Host only: qttt_launch.h (launch shape, kernel selection,
+// the same recursion, every action's value kept for the policy); qttt_tree_prove_kernels.h (proven interior nodes: a round's
+// records walked upwards, a wave per game, integers only, and the roots' exact q).  Host only: qttt_launch.h (launch shape, kernel selection,
 // the one launch form, the argument checks), qttt_mailbox.h (the host half of the single-record mailbox); this file: the
 // step's launch logic + the C ABI.
 #include <atomic>
@@ -89,6 +90,7 @@
 #include "qttt_solve_kernels.h"
 #include "qttt_tree_exact_kernels.h"
 #include "qttt_selfplay_exact_kernels.h"
+#include "qttt_tree_prove_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -1253,6 +1255,27 @@ int qttt_tree_backup_batch_exact(void *tree, int64_t games, int64_t capacity, in
         return QTTT_ERR_ACTION;
     return launch(tree_backup_batch_kernel<true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
                   (u32)leaves, static_cast<const TreePathRec *>(paths), leaf_value, leaf_probs);
+}
+
+// ---------------------------------------------------------------- proven interior nodes (include/qttt_tree_prove.h)
+int qttt_tree_prove(void *tree, int64_t games, int64_t capacity, int leaves, const void *paths, int32_t *proved,
+                    void *stream) {
+    if (tree_size_bad(games, capacity) || tree_leaves_bad(games, leaves)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, paths)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(paths, 16) || misaligned(proved, 4)) return QTTT_ERR_ACTION;
+    return launch(tree_prove_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity, (u32)leaves,
+                  static_cast<const TreePathRec *>(paths), proved);
+}
+
+int qttt_tree_root_exact(const void *tree, int64_t games, int64_t capacity, float *q, uint8_t *proven, float *value,
+                         uint8_t *solved, void *stream) {
+    if (tree_size_bad(games, capacity)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (!tree) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(q, 4) || misaligned(value, 4)) return QTTT_ERR_ACTION;
+    return launch(tree_root_exact_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity, q,
+                  proven, value, solved);
 }
 
 // ---------------------------------------------------------------- exact targets of a self-play batch (include/qttt_selfplay_exact.h)

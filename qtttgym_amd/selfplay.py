@@ -128,6 +128,8 @@ class SelfPlay(LibCaller):
     noise is the exploration.
     exact_from is TreeSearch's: leaves with at least that many moves played are solved exactly on the device (value leaves
     only; play() and stream() alike).  It changes the search, not the batch's targets: that is exact_targets.
+    prove=True (with exact_from) is TreeSearch's too: every round also proves the interior nodes whose children are all
+    terminal or solved (include/qttt_tree_prove.h).  The record kernels and the played move are what they were.
     exact_targets=M (6..9; independent of exact_from, leaf_eval, root_policy and net) relabels the targets themselves
     (SelfPlayBatch.exact_targets, one launch): every recorded, non-terminal position with at least M moves played gets its
     exact value as v and, with exact_policy=True, the uniform distribution over its optimal moves as pi.  play() does it
@@ -142,10 +144,11 @@ class SelfPlay(LibCaller):
                  value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts",
                  root_noise=None, temperature=1.0, sample_plies=0, leaves=1, virtual_loss=1.0,
                  eval_symmetries=None, root_policy="puct", max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None,
-                 exact_targets=None, exact_policy=True):
+                 exact_targets=None, exact_policy=True, prove=False):
         self.exact_targets = self.check_exact_targets(exact_targets, value_targets)
         self.exact_policy = bool(exact_policy)
         self.exact_from = TreeSearch.check_exact_from(leaf_eval, net, exact_from)
+        self.prove = TreeSearch.check_prove(self.exact_from, prove)
         self.leaves, self.virtual_loss = TreeSearch.check_search_args(leaf_eval, net, leaves, virtual_loss)
         self.root_policy, self.max_considered, self.c_visit, self.c_scale = TreeSearch.check_root_args(
             leaf_eval, net, root_policy, max_considered, c_visit, c_scale)
@@ -266,7 +269,7 @@ class SelfPlay(LibCaller):
                           leaf_eval=self.leaf_eval, leaves=self.leaves, virtual_loss=self.virtual_loss,
                           eval_symmetries=self.eval_symmetries, root_policy=self.root_policy,
                           max_considered=self.max_considered, c_visit=self.c_visit, c_scale=self.c_scale,
-                          exact_from=self.exact_from)
+                          exact_from=self.exact_from, prove=self.prove)
         tree.reset(env)
         return env, tree
 

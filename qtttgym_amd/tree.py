@@ -29,6 +29,12 @@ least M moves played is solved on the device, once, by the endgame solver's defi
 instead of the network's, and stays a leaf.  Every rollout is then a round with qttt_tree_solve_leaves between the
 evaluation and the backup.
 
+prove=True (with exact_from) proves interior nodes as well (include/qttt_tree_prove.h): after every round's
+backup qttt_tree_prove walks the round's paths upwards and solves each node all of whose legal actions lead to terminal or
+solved children, with the solver's own formula; a proven node below the root ends every later descent like an exact leaf.
+root_stats() then says which root actions are proven and their exact q, and choose(exact=True) plays the solver's move at
+a proven root.
+
 add_root_noise() is AlphaZero's root exploration (include/qttt_tree_explore.h): Dirichlet noise mixed into
 the priors of every root that has them, one launch.
 """
@@ -46,6 +52,10 @@ class TreeSearch(LibCaller):
                   "P": (torch.float64, (36,)), "Ntot": (torch.int32, ()), "choose": (torch.uint8, ()),
                   "nodes_used": (torch.int32, ()), "overflow": (torch.uint8, ())}
 
+    # what prove=True adds to them (qttt_tree_root_exact): key -> (dtype, per-game shape)
+    _EXACT_ROWS = {"q_exact": (torch.float32, (36,)), "proven": (torch.uint8, (36,)),
+                   "root_value_exact": (torch.float32, ()), "root_solved": (torch.uint8, ())}
+
     # what the Gumbel root adds to them (qttt_tree_gumbel_root)
     _GUMBEL_ROWS = {"choose": (torch.uint8, ()), "pi": (torch.float64, (36,)), "q_completed": (torch.float64, (36,))}
 
@@ -55,10 +65,11 @@ class TreeSearch(LibCaller):
     root_policy = "puct"
     eval_symmetries = None
     exact_from = None
+    prove = False
 
     def __init__(self, num_games, capacity, num_simulations=10, c_puct=1.0, net=None, seed=0, board_offset=0,
                  device=None, leaf_eval="playouts", leaves=1, virtual_loss=1.0, eval_symmetries=None, root_policy="puct",
-                 max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None):
+                 max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None, prove=False):
         """leaf_eval="playouts": the reference's rollout, num_simulations playouts from the leaf (uniform, or guided by
         `net`).  leaf_eval="value" (needs `net`): the leaf is scored by the value head, seen by the player to move
         there; a terminal leaf by its reward.  num_simulations is then ignored: no playout draw is taken.
@@ -74,8 +85,13 @@ class TreeSearch(LibCaller):
         exact_from=M (6..9; needs leaf_eval="value"): a leaf below the root with at least M moves played is solved
         exactly on the device the first time a round ends on it, and is from then on a leaf with that value: it is backed
         up with it and never gets priors or children.  Every rollout is then a round — select_batch, evaluate,
-        solve_leaves, backup_batch_exact — also the first after a reset() or sync().  None is the search as it always was."""
+        solve_leaves, backup_batch_exact — also the first after a reset() or sync().  None is the search as it always was.
+        prove=True (needs exact_from; 9 is allowed: only terminal children prove anything then): every round ends with
+        qttt_tree_prove, a fifth launch, which solves the nodes on the round's paths whose children are all terminal or
+        solved.  A proven node below the root loses its priors, so descents end on it and it is backed up with its exact
+        value; the root keeps its priors.  False is the search as it always was."""
         self.exact_from = self.check_exact_from(leaf_eval, net, exact_from)
+        self.prove = self.check_prove(self.exact_from, prove)
         self.leaves, self.virtual_loss = self.check_search_args(leaf_eval, net, leaves, virtual_loss)
         self.root_policy, self.max_considered, self.c_visit, self.c_scale = self.check_root_args(
             leaf_eval, net, root_policy, max_considered, c_visit, c_scale)
@@ -175,6 +191,15 @@ class TreeSearch(LibCaller):
             raise ValueError("exact_from must be None or an integer in %d..%d (moves played)"
                              % (_native.TREE_EXACT_MIN_PLY, _native.SOLVE_MAX_PLY))
         return int(exact_from)
+
+    @staticmethod
+    def check_prove(exact_from, prove):
+        """The constructors' check of prove: a bool, True only with exact_from."""
+        if not isinstance(prove, bool):
+            raise ValueError("prove must be True or False")
+        if prove and exact_from is None:
+            raise ValueError("prove=True needs exact_from: the plain backup would hand a proven node its priors back")
+        return prove
 
     def _need_reset(self):
         if self._bound is None:
@@ -278,12 +303,15 @@ class TreeSearch(LibCaller):
                                    "out": out_rows(VecEnv._EVAL_ROWS, n, dev, keys=("value", "probs"))}
             if self.exact_from is not None:
                 b["exact"] = torch.zeros(n, dtype=torch.uint8, device=dev)
+            if self.prove:
+                b["proved"] = torch.zeros(self.num_games, dtype=torch.int32, device=dev)
         return b
 
     def _backup_round(self, b, k):
         """The backup of a round of k leaves whose leaves were just evaluated into b["out"]; with exact_from the eligible
         leaves are solved first (their rows of b["out"]["value"] become exact, b["exact"] says which) and the backup is
-        the one that honours solved nodes."""
+        the one that honours solved nodes; with prove the round's paths are then walked upwards (b["proved"] counts the
+        nodes of every game that this round proved)."""
         G, cap, tree = self.num_games, self.capacity, self.tree.data_ptr()
         value, probs = b["out"]["value"].data_ptr(), b["out"]["probs"].data_ptr()
         if self.exact_from is None:
@@ -292,6 +320,8 @@ class TreeSearch(LibCaller):
         self._call("qttt_tree_solve_leaves", tree, G, cap, k, b["paths"].data_ptr(), b["leaf"].state.data_ptr(),
                    self.exact_from, value, b["exact"].data_ptr())
         self._call("qttt_tree_backup_batch_exact", tree, G, cap, k, b["paths"].data_ptr(), value, probs)
+        if self.prove:
+            self._call("qttt_tree_prove", tree, G, cap, k, b["paths"].data_ptr(), b["proved"].data_ptr())
 
     def _round(self, k):
         """One round of k rollouts (1..TREE_MAX_LEAVES) through the leaf-parallel entries, without contemplate's bounds:
@@ -416,10 +446,14 @@ class TreeSearch(LibCaller):
     def root_stats(self):
         """The roots' statistics: N i32[G,36], W / Q / P f64[G,36], Ntot i32[G], choose u8[G], nodes_used i32[G],
         overflow bool[G].  root_policy="gumbel": choose is the Gumbel choice, and pi f64[G,36] (the improved policy) and
-        q_completed f64[G,36] are there too."""
+        q_completed f64[G,36] are there too.  prove=True: proven bool[G,36] (the action's children are all terminal or
+        solved), q_exact f32[G,36] (its exact q, NaN where it is not proven), root_solved bool[G] and root_value_exact
+        f32[G] (NaN where the root is not solved), one qttt_tree_root_exact launch."""
         o = out_rows(self._ROOT_ROWS, self.num_games, self.device)
         self._root(**o)
         o["overflow"] = o["overflow"].bool()
+        if self.prove:
+            o.update(self._root_exact())
         if self.root_policy == "gumbel":
             o.update(out_rows(self._GUMBEL_ROWS, self.num_games, self.device))
             self._gumbel_root(o["choose"], o["pi"], o["q_completed"])
@@ -430,14 +464,36 @@ class TreeSearch(LibCaller):
         self._call("qttt_tree_root", self.tree.data_ptr(), self.num_games, self.capacity, _ptr(N), _ptr(W), _ptr(Q),
                    _ptr(P), _ptr(Ntot), _ptr(choose), _ptr(nodes_used), _ptr(overflow))
 
-    def choose(self):
-        """MCTS.choose (mcts.py:308-315) per game: action36 u8[G], 255 where the root has no legal action."""
+    def _root_exact(self):
+        """What the proofs say of the roots (qttt_tree_root_exact): proven, q_exact, root_solved, root_value_exact."""
+        self._need_reset()
+        e = out_rows(self._EXACT_ROWS, self.num_games, self.device)
+        self._call("qttt_tree_root_exact", self.tree.data_ptr(), self.num_games, self.capacity, e["q_exact"].data_ptr(),
+                   e["proven"].data_ptr(), e["root_value_exact"].data_ptr(), e["root_solved"].data_ptr())
+        e["proven"], e["root_solved"] = e["proven"].bool(), e["root_solved"].bool()
+        return e
+
+    def choose(self, exact=False):
+        """MCTS.choose (mcts.py:308-315) per game: action36 u8[G], 255 where the root has no legal action.
+        exact=True (needs prove=True): a game whose root is solved plays the lowest action that attains the maximal
+        q_exact, the solver's best move (where a root was solved as a leaf and not all its actions are proven yet: the
+        lowest proven action whose q_exact is the root's value, if there is one); every other game its ordinary choice.  Composed on the device, no host
+        synchronisation."""
+        if exact and not self.prove:
+            raise ValueError("choose(exact=True) needs prove=True")
         a = out_tensor(*self._ROOT_ROWS["choose"], self.num_games, self.device)
         if self.root_policy == "gumbel":      # the best survivor of the halving (255 also at a terminal root)
             self._gumbel_root(choose=a)
         else:
             self._root(choose=a)
-        return a
+        if not exact:
+            return a
+        e = self._root_exact()
+        # a proven action whose q is the root's value is optimal; at a root that a round proved every legal action is
+        # proven and the maximal q_exact is that value.  (A root that was solved as a leaf may have none: its own choice.)
+        best = e["proven"] & (e["q_exact"] == e["root_value_exact"][:, None])          # NaN compares unequal
+        first = best.to(torch.uint8).argmax(1).to(torch.uint8)                         # the lowest action among them
+        return torch.where(best.any(1), first, a)
 
     def solved_count(self):
         """i64[G], on the device: the nodes of every game (below its `used`) that carry the solved flag of
