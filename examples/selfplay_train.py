@@ -11,6 +11,7 @@ with --device-train, on the device), packs the new weights for the search and re
                                       [--eval-symmetries all|0,4] [--replay CAPACITY --batch B --steps S]
                                       [--device-train] [--stream PLIES] [--exact-from M] [--prove]
                                       [--exact-targets M [--exact-value-only]]
+                                      [--reanalyse N [--reanalyse-value-mix L]]
 
 The network is nn.Model's (nn.py:7-28) under its own parameter names (qtttgym_amd.policy_value.SHAPES), so --out is a
 state dict that the reference, PolicyValueNet and examples/tree_tournament.py --model all load.  The loss is the
@@ -45,6 +46,11 @@ line reads them back once per run.
 position with at least M moves played is enumerated on the device, its value target becomes its exact value for the
 player to move and its policy target the uniform distribution over its optimal moves (--exact-value-only keeps the
 visit-count policy).  The exact value is the mover's, in [-1, 1], so the option sets --value-targets to 1,-1 itself.
+--reanalyse N (with --replay) refreshes the ring's targets (qtttgym_amd.Reanalyser): every run, after its games are in the
+ring and before its minibatch steps, a window of N positions of the ring is searched again with the current weights and
+the new policy targets are written into their slots; terminal rows and slots that were appended over in between keep what
+they hold.  --reanalyse-value-mix L in (0, 1] also moves the value target towards the searched root value (needs
+--value-targets 1,-1).  The printed count of refreshed samples is one more read-back per run.
 """
 import argparse
 import os
@@ -53,7 +59,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from qtttgym_amd import PolicyValueNet, ReplayBuffer, SelfPlay, Trainer  # noqa: E402
+from qtttgym_amd import PolicyValueNet, Reanalyser, ReplayBuffer, SelfPlay, Trainer  # noqa: E402
 from qtttgym_amd import recommended_env  # noqa: E402
 from qtttgym_amd.policy_value import HIDDEN, SHAPES  # noqa: E402
 recommended_env(apply=True)
@@ -157,8 +163,17 @@ def main():
                          "free; at M = 6 a --stream ply takes about four times as long (DESIGN.md §25)")
     ap.add_argument("--exact-value-only", action="store_true",
                     help="with --exact-targets: relabel the value target only, keep the visit-count policy")
+    ap.add_argument("--reanalyse", type=int, default=0, metavar="N",
+                    help="with --replay: every run searches N positions of the ring again with the current weights and "
+                         "refreshes their policy targets in place (Reanalyser)")
+    ap.add_argument("--reanalyse-value-mix", type=float, default=0.0, metavar="L",
+                    help="with --reanalyse: v = (1 - L) * stored v + L * the searched root value (needs --value-targets 1,-1)")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
+    if args.reanalyse < 0 or (args.reanalyse and not args.replay):
+        ap.error("--reanalyse needs N >= 1 and --replay")
+    if args.reanalyse_value_mix and not args.reanalyse:
+        ap.error("--reanalyse-value-mix needs --reanalyse")
     if args.stream < 0 or (args.stream and not args.replay):
         ap.error("--stream needs PLIES >= 1 and --replay")
     if args.prove and args.exact_from is None:
@@ -183,6 +198,7 @@ def main():
                   max_considered=args.max_considered, exact_from=args.exact_from, prove=args.prove,
                   exact_targets=args.exact_targets, exact_policy=not args.exact_value_only)
     ring = ReplayBuffer(args.replay, device=dev, seed=args.seed) if args.replay else None
+    reanalyser = Reanalyser(sp, ring, args.reanalyse, value_mix=args.reanalyse_value_mix, seed=args.seed) if args.reanalyse else None
     trainer = Trainer(model, device=dev, net=net) if args.device_train else None      # nn.py:27's defaults
     if trainer is not None:
         fit, save = (lambda batches: train_on_device(trainer, batches)), trainer.state_dict
@@ -192,6 +208,7 @@ def main():
     for run in range(args.runs):
         if args.stream:
             stats = sp.stream(ring, args.stream)
+            refreshed = reanalyser.run().updated if reanalyser is not None else None
             L, J = fit(ring.sample(args.batch, "random") for _ in range(args.steps))
             now = torch.cat([stats.games.sum().view(1), stats.samples.view(1), stats.winners]).cpu()     # the one read-back
             new, seen = (now - seen).tolist(), now
@@ -203,6 +220,7 @@ def main():
             won = [int((batch.winner == w).sum()) for w in (1, 0, -1)]
             if ring is not None:
                 ring.add(batch)
+                refreshed = reanalyser.run().updated if reanalyser is not None else None
                 L, J = fit(ring.sample(args.batch, "random") for _ in range(args.steps))
                 what = ("%d games appended, the ring holds %d samples; %d steps of %d"
                         % (args.games, ring.size(), args.steps, args.batch))
@@ -210,6 +228,8 @@ def main():
                 samples = (batch.augment() if args.symmetries else batch).flat()
                 L, J = fit(samples for _ in range(args.epochs))
                 what = "%d samples of %d games" % (len(samples[0]), args.games)
+        if reanalyser is not None:
+            what += "; %d of %d reanalysed samples refreshed" % (int(refreshed.sum()), args.reanalyse)
         print("run %d: %s (first player won %d, lost %d, drew %d); L: %.4f, J: %.4f"
               % (run, what, won[0], won[1], won[2], L.mean().item(), J.mean().item()), flush=True)
         if trainer is None:

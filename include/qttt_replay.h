@@ -54,7 +54,11 @@
  *   Errors, in this order, before any device work: QTTT_ERR_SIZE for capacity outside 1..QTTT_REPLAY_MAX_CAPACITY, n
  * outside 0..QTTT_REPLAY_MAX_CAPACITY or draw >= 2^31; 0 with no device work for n == 0; QTTT_ERR_NULL for a null replay,
  * s_out, pi_out, mask_out, v_out or done_out; QTTT_ERR_ACTION for replay not 64-byte, s_out or pi_out not 16-byte (the
- * tiles leave as 16-byte stores), or mask_out, v_out or index_out not 4-byte aligned. */
+ * tiles leave as 16-byte stores), or mask_out, v_out or index_out not 4-byte aligned.
+ *
+ * ---- Reanalysis.  qttt_replay_gather (a window of consecutive slots as a state buffer, with the sample number each slot
+ * holds) and qttt_replay_update (refreshed pi / v written back into those slots, unless a later append went over them or
+ * the row is terminal) work on this ring and are declared in qttt_replay_reanalyse.h, which qttt.h includes as well. */
 #ifndef QTTT_REPLAY_H
 #define QTTT_REPLAY_H
 #include <stdint.h>

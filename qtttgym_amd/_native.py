@@ -214,6 +214,13 @@ SELFPLAY_EXACT_MIN_PLY, SELFPLAY_EXACT_MAX_PLY = 6, 9
 SELFPLAY_EXACT_SIGNATURES = {
     "qttt_selfplay_exact_targets": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# every symbol include/qttt_replay_reanalyse.h declares (reanalysis: a window of the ring as a state buffer, the guarded
+# write-back of refreshed targets; qttt.h includes it)
+REPLAY_WINDOW_ID = 1 << 32
+REPLAY_REANALYSE_SIGNATURES = {
+    "qttt_replay_gather": (_i32, [_vp, _i64, _i64, _u64, _u32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qttt_replay_update": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
 
 _lib = None
 
@@ -284,7 +291,7 @@ def lib():
                                   + list(REPLAY_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())
                                   + list(SELFPLAY_STREAM_SIGNATURES.items()) + list(SOLVE_SIGNATURES.items())
                                   + list(TREE_EXACT_SIGNATURES.items()) + list(SELFPLAY_EXACT_SIGNATURES.items())
-                                  + list(TREE_PROVE_SIGNATURES.items())):
+                                  + list(TREE_PROVE_SIGNATURES.items()) + list(REPLAY_REANALYSE_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

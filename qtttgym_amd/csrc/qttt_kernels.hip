@@ -56,8 +56,9 @@
 // qttt_tree_leaves_kernels.h (leaf-parallel rounds: K descents per game under virtual loss, and their backup);
 // qttt_tree_explore_kernels.h (root exploration: Dirichlet noise on the roots' priors, the sampled move);
 // qttt_tree_gumbel_kernels.h (the Gumbel root: considered actions, sequential halving, the improved policy);
-// qttt_replay_kernels.h (the replay ring: the append's scan and move, the sampled minibatch) with qttt_replay_host.h (host
-// only and free of HIP: the ring's layout, the scan plan, the argument checks);
+// qttt_replay_kernels.h (the replay ring: the append's scan and move, the sampled minibatch, and reanalysis: the gathered
+// window and the guarded update) with qttt_replay_host.h (host only and free of HIP: the ring's layout, the scan plan, the
+// window and holder arithmetic, the argument checks);
 // qttt_train_kernels.h (the training step: loss, gradients and AMSGrad on the packed f32 blob, on qttt_nn_kernels.h's layers)
 // with qttt_train_host.h (host only and free of HIP: the workspace layout and the launch plan);
 // qttt_selfplay_stream_kernels.h (continuous self-play: the harvest of finished games and their restart in place);
@@ -1296,6 +1297,28 @@ int qttt_selfplay_exact_targets(const void *states, int64_t games, int min_ply, 
                                   stream, o, games, b0 * TARGETS_RECORDS, min_ply, policy))
             return rc;
     return 0;
+}
+
+// ---------------------------------------------------------------- reanalysis of the replay ring (include/qttt_replay_reanalyse.h)
+int qttt_replay_gather(const void *replay, int64_t capacity, int64_t n, uint64_t seed, uint32_t draw, int64_t start,
+                       void *state_out, int32_t *slot_out, int64_t *number_out, float *v_out, uint8_t *done_out,
+                       void *stream) {
+    bool work;
+    if (const int rc = replay_gather_check(replay, capacity, n, draw, state_out, slot_out, number_out, v_out, work)) return rc;
+    if (!work) return 0;
+    const ReplayRing ring = replay_ring(const_cast<void *>(replay), capacity);
+    return launch(replay_gather_kernel, ceil_div(plane_stride(n), REPLAY_GATHER_BLOCK), REPLAY_GATHER_BLOCK, stream, ring, capacity,
+                  n, qttt_hash(seed, QTTT_REPLAY_WINDOW_ID, draw), start, static_cast<u64 *>(state_out), slot_out, number_out,
+                  reinterpret_cast<u32 *>(v_out), done_out);
+}
+
+int qttt_replay_update(void *replay, int64_t capacity, int64_t n, const int32_t *slot, const int64_t *number,
+                       const double *pi, const float *v, uint8_t *updated_out, void *stream) {
+    bool work;
+    if (const int rc = replay_update_check(replay, capacity, n, slot, number, pi, v, work)) return rc;
+    if (!work) return 0;
+    return launch(replay_update_kernel, ceil_div(n, REPLAY_UPDATE_SAMPLES), REPLAY_UPDATE_BLOCK, stream, replay_ring(replay, capacity),
+                  capacity, n, slot, number, reinterpret_cast<const u64 *>(pi), reinterpret_cast<const u32 *>(v), updated_out);
 }
 
 }  // extern "C"

@@ -6,6 +6,12 @@
 #include <stdint.h>
 #include "qttt.h"
 
+#ifdef __HIPCC__
+#define QTTT_REPLAY_HD __host__ __device__
+#else
+#define QTTT_REPLAY_HD
+#endif
+
 namespace {
 
 inline int64_t replay_align64(int64_t bytes) { return (bytes + 63) & ~(int64_t)63; }
@@ -83,6 +89,54 @@ inline int replay_sample_check(const void *replay, int64_t capacity, int64_t n, 
     if (!replay || !s_out || !pi_out || !mask_out || !v_out || !done_out) return QTTT_ERR_NULL;
     if (replay_misaligned(replay, 64) || replay_misaligned(s_out, 16) || replay_misaligned(pi_out, 16) ||
         replay_misaligned(mask_out, 4) || replay_misaligned(v_out, 4) || replay_misaligned(index_out, 4))
+        return QTTT_ERR_ACTION;
+    launch = true;
+    return 0;
+}
+
+// ---- reanalysis (include/qttt_replay_reanalyse.h): the arithmetic the two kernels and the host program share.
+// The sample number that slot s < min(written, capacity) holds: the largest w < written with w % capacity == s.
+QTTT_REPLAY_HD inline uint64_t replay_holder(uint64_t s, uint64_t written, uint64_t capacity) {
+    return written - 1u - (written - 1u - s) % capacity;
+}
+// The slot of sample i < F of a window that starts at s0 < F: (s0 + i) mod F without a division.
+QTTT_REPLAY_HD inline uint64_t replay_window_slot(uint64_t s0, uint64_t i, uint64_t F) {
+    const uint64_t s = s0 + i;
+    return s >= F ? s - F : s;
+}
+// The window's first slot: start mod F when start >= 0, else the high 64 bits of hash * F (hash = the window's draw).
+QTTT_REPLAY_HD inline uint64_t replay_window_start(int64_t start, uint64_t hash, uint64_t F) {
+    if (start >= 0) return (uint64_t)start % F;
+#ifdef __HIP_DEVICE_COMPILE__
+    return __umul64hi(hash, F);
+#else
+    return (uint64_t)(((unsigned __int128)hash * F) >> 64);
+#endif
+}
+
+// The checks of qttt_replay_gather.
+inline int replay_gather_check(const void *replay, int64_t capacity, int64_t n, uint32_t draw, const void *state_out,
+                               const int32_t *slot_out, const int64_t *number_out, const float *v_out, bool &launch) {
+    launch = false;
+    if (replay_capacity_bad(capacity) || n < 0 || n > QTTT_REPLAY_MAX_CAPACITY || draw >= 0x80000000u) return QTTT_ERR_SIZE;
+    if (n == 0) return 0;
+    if (!replay || !state_out || !slot_out || !number_out) return QTTT_ERR_NULL;
+    if (replay_misaligned(replay, 64) || replay_misaligned(state_out, 16) || replay_misaligned(number_out, 8) ||
+        replay_misaligned(slot_out, 4) || replay_misaligned(v_out, 4))
+        return QTTT_ERR_ACTION;
+    launch = true;
+    return 0;
+}
+
+// The checks of qttt_replay_update.
+inline int replay_update_check(const void *replay, int64_t capacity, int64_t n, const int32_t *slot, const int64_t *number,
+                               const double *pi, const float *v, bool &launch) {
+    launch = false;
+    if (replay_capacity_bad(capacity) || n < 0 || n > QTTT_REPLAY_MAX_CAPACITY) return QTTT_ERR_SIZE;
+    if (n == 0) return 0;
+    if (!replay || !slot || !number || (!pi && !v)) return QTTT_ERR_NULL;
+    if (replay_misaligned(replay, 64) || replay_misaligned(pi, 8) || replay_misaligned(number, 8) ||
+        replay_misaligned(slot, 4) || replay_misaligned(v, 4))
         return QTTT_ERR_ACTION;
     launch = true;
     return 0;

@@ -1,13 +1,15 @@
 // qttt_replay_kernels.h — the replay ring on the device (include/qttt_replay.h): the scan levels and the
 // move of qttt_replay_append, and the one launch of qttt_replay_sample, which gathers whole rows from random slots,
 // builds the (permuted) to_vector encoding and the permuted pi / mask rows of a tile of samples in LDS — encode_kernel's
-// plan — and streams them out as coalesced 16-byte stores.
+// plan — and streams them out as coalesced 16-byte stores.  Behind them the two launches of reanalysis
+// (include/qttt_replay_reanalyse.h): a window of the ring as a state buffer, and the guarded write-back.
 #ifndef QTTT_REPLAY_KERNELS_H
 #define QTTT_REPLAY_KERNELS_H
 #include "qttt_mcts_kernels.h"
 #include "qttt_symmetry_kernels.h"
 #include "qttt_replay_host.h"
 #include "qttt_replay.h"
+#include "qttt_replay_reanalyse.h"
 
 namespace {
 
@@ -198,6 +200,66 @@ __global__ __launch_bounds__(REPLAY_SAMPLE_BLOCK) void replay_sample_kernel(Repl
         u32 *dst = reinterpret_cast<u32 *>(mask_out + base * 36);
         for (u32 q = threadIdx.x; q < n4; q += REPLAY_SAMPLE_BLOCK) dst[q] = src[q];
     }
+}
+
+// ---- reanalysis (include/qttt_replay_reanalyse.h)
+// The gather: a lane per board of the state buffer, the padding behind board n - 1 included (it gets the empty board, as
+// qttt_reset gives it).  The window is consecutive slots, so consecutive lanes load and store consecutive addresses in
+// every array; the one break is where the window wraps.  `hash` is the window's draw, taken on the host.
+constexpr int REPLAY_GATHER_BLOCK = 256;
+__global__ __launch_bounds__(REPLAY_GATHER_BLOCK) void replay_gather_kernel(ReplayRing ring, int64_t capacity, int64_t n, u64 hash,
+                                                                            int64_t start, u64 *state_out, int32_t *slot_out,
+                                                                            int64_t *number_out, u32 *v_out, uint8_t *done_out) {
+    const int64_t i = (int64_t)blockIdx.x * REPLAY_GATHER_BLOCK + threadIdx.x;
+    const int64_t stride = plane_stride(n);
+    if (i >= stride) return;
+    u64 P = 0ull, Q = 0ull;                                      // the empty board is the all-zero state
+    if (i < n) {
+        const u64 written = ring.header[0];
+        const u64 filled = written < (u64)capacity ? written : (u64)capacity;
+        int64_t slot = -1, number = -1;
+        u32 v = 0u;
+        uint8_t done = 0;
+        if ((u64)i < filled) {
+            const u64 s = replay_window_slot(replay_window_start(start, hash, filled), (u64)i, filled);   // < filled <= capacity
+            slot = (int64_t)s;
+            number = (int64_t)replay_holder(s, written, (u64)capacity);
+            P = ring.P[s];
+            Q = ring.Q[s];
+            if (v_out) v = ring.v[s];
+            if (done_out) done = ring.done[s];
+        }
+        slot_out[i] = (int32_t)slot;
+        number_out[i] = number;
+        if (v_out) v_out[i] = v;
+        if (done_out) done_out[i] = done;
+    }
+    state_out[i] = P;
+    state_out[stride + i] = Q;
+}
+
+// The update: sixteen lanes per sample (the sample kernel's group), part j moving the pi words j, j + 16, j + 32 of the
+// row, so a group's stores are consecutive addresses.  Part 0 evaluates the guard once — the slot is held, still by the
+// sample it was gathered for, and not a terminal row — writes v and the flag, and broadcasts the slot (or -1) to its group.
+// Distinct slots (the header's condition): no two groups store to one slot.  No lane leaves before the broadcast.
+constexpr int REPLAY_UPDATE_BLOCK = 256, REPLAY_UPDATE_LANES = 16, REPLAY_UPDATE_SAMPLES = REPLAY_UPDATE_BLOCK / REPLAY_UPDATE_LANES;
+__global__ __launch_bounds__(REPLAY_UPDATE_BLOCK) void replay_update_kernel(ReplayRing ring, int64_t capacity, int64_t n,
+                                                                            const int32_t *slot, const int64_t *number, const u64 *pi,
+                                                                            const u32 *v, uint8_t *updated_out) {
+    const u32 j = threadIdx.x & (u32)(REPLAY_UPDATE_LANES - 1);
+    const int64_t i = (int64_t)blockIdx.x * REPLAY_UPDATE_SAMPLES + threadIdx.x / REPLAY_UPDATE_LANES;
+    int32_t to = -1;
+    if (j == 0u && i < n) {
+        const u64 written = ring.header[0];
+        const u64 filled = written < (u64)capacity ? written : (u64)capacity;
+        const int32_t s = slot[i];
+        if (s >= 0 && (u64)s < filled && replay_holder((u64)s, written, (u64)capacity) == (u64)number[i] && ring.done[s] == 0) to = s;
+        if (to >= 0 && v) ring.v[to] = v[i];
+        if (updated_out) updated_out[i] = to >= 0 ? 1 : 0;
+    }
+    to = __shfl(to, (int)((threadIdx.x & 63u) & ~(u32)(REPLAY_UPDATE_LANES - 1)), 64);
+    if (to < 0 || !pi) return;
+    for (u32 a = j; a < 36u; a += (u32)REPLAY_UPDATE_LANES) ring.pi[(u64)to * 36u + a] = pi[i * 36 + a];
 }
 
 }  // namespace

@@ -6,6 +6,9 @@ flat()'s order without a host read-back, and that one launch samples from with a
     rb.add(sp.play())                                     # no host synchronisation
     s, pi, mask, v, done = rb.sample(4096, "random")      # the trainer's tensors, one launch
 
+    window = rb.gather(4096)                              # reanalysis: positions out as a VecEnv ...
+    rb.update(window, pi=new_pi)                          # ... and refreshed targets back, unless appended over since
+
 Loss, gradients and the optimiser are ordinary torch or qtttgym_amd.Trainer (examples/selfplay_train.py --replay
 [--device-train]).
 """
@@ -16,6 +19,7 @@ import torch
 from . import _native
 from ._host import LibCaller, _ptr, check_tensor, resolve_device
 from .selfplay import ROWS, SelfPlayBatch
+from .vec_env import VecEnv
 
 _MAX_DRAW = 1 << 31
 # the ring's arrays as torch sees them (torch has no arithmetic on uint64: the words travel as int64)
@@ -42,6 +46,7 @@ class ReplayBuffer(LibCaller):
         self.buffer = torch.zeros(int(self._lib.qttt_replay_bytes(self.capacity)), dtype=torch.uint8, device=self.device)
         self.draw = 0                   # sample() calls so far: the draw index of the next
         self.adds = 0                   # add() calls that appended games
+        self.gathers = 0                # gather() calls so far: the draw index of the next window
         self.last_index = self.last_symmetry = None
         self._scratch = None
 
@@ -117,3 +122,72 @@ class ReplayBuffer(LibCaller):
         self.draw += 1
         self.last_index, self.last_symmetry = index, k
         return tuple(out)
+
+    def gather(self, n, start=None, env=None):
+        """A window of n consecutive slots of the ring as a state buffer, one launch and no host read-back
+        (include/qttt_replay_reanalyse.h qttt_replay_gather): a ReplayWindow of env (a VecEnv of n boards at the stored
+        positions; made here, or the caller's, whose state is overwritten), slot i32[n], number i64[n] (the sample number
+        each slot held, what update() compares), v f32[n] and done u8[n] as stored.  start=None draws the window's first
+        slot by the counter hash of (seed, the number of gather() calls so far); an integer is taken modulo the samples
+        held.  Sample i of a window longer than the ring holds has no slot: slot and number -1, the empty board.  Raises
+        before any add() of games, as sample() does."""
+        n, dev = int(n), self.device
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        if self.adds == 0:
+            raise ValueError("gather() before any add(): the ring is empty")
+        if self.gathers >= _MAX_DRAW:
+            raise ValueError("the draw counter is exhausted (2**31 gather() calls): take a new seed")
+        start = -1 if start is None else int(start)
+        if start < -1:
+            raise ValueError("start must be None or >= 0")
+        if env is None:
+            env = VecEnv(n, device=dev)
+        elif not isinstance(env, VecEnv) or env.num_envs != n or env.state.device != dev:
+            raise ValueError("env must be a VecEnv of %d boards on %s" % (n, dev))
+        slot = torch.empty(n, dtype=torch.int32, device=dev)
+        number = torch.empty(n, dtype=torch.int64, device=dev)
+        v = torch.empty(n, dtype=torch.float32, device=dev)
+        done = torch.empty(n, dtype=torch.uint8, device=dev)
+        self._call("qttt_replay_gather", self.buffer.data_ptr(), self.capacity, n, self.seed, self.gathers, start,
+                   env.state.data_ptr(), slot.data_ptr(), number.data_ptr(), v.data_ptr(), done.data_ptr())
+        self.gathers += 1
+        return ReplayWindow(self, env, slot, number, v, done)
+
+    def update(self, window, pi=None, v=None):
+        """Writes refreshed targets into the slots of a gather()'s window, one launch and no host read-back
+        (qttt_replay_update): pi f64[n, 36] and / or v f32[n], at least one.  A sample is written only while its slot
+        still holds the sample it was gathered for — an add() since then that went over the slot leaves the newer
+        sample alone — and only where the stored done byte is 0: a terminal row keeps its targets.  Nothing but pi and v
+        of the written slots changes.  Returns updated bool[n]."""
+        if not isinstance(window, ReplayWindow) or window.ring is not self:
+            raise ValueError("window must be a ReplayWindow of this ring's gather()")
+        n, dev = len(window.slot), self.device
+        if pi is None and v is None:
+            raise ValueError("update() needs pi, v or both")
+        if pi is not None:
+            check_tensor(pi, torch.float64, (n, 36), dev, "pi")
+        if v is not None:
+            check_tensor(v, torch.float32, (n,), dev, "v")
+        updated = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self._call("qttt_replay_update", self.buffer.data_ptr(), self.capacity, n, window.slot.data_ptr(),
+                   window.number.data_ptr(), _ptr(pi), _ptr(v), updated.data_ptr())
+        return updated.view(torch.bool)
+
+
+class ReplayWindow:
+    """What ReplayBuffer.gather returns: env (VecEnv of n boards), slot i32[n] (-1: no slot), number i64[n], v f32[n], done
+    u8[n]; and mask i64[n], the legal-mask words of the window's slots (0 where there is none), indexed out of the ring
+    by torch when first asked for."""
+
+    def __init__(self, ring, env, slot, number, v, done):
+        self.ring, self.env, self.slot, self.number, self.v, self.done = ring, env, slot, number, v, done
+        self._mask = None
+
+    @property
+    def mask(self):
+        if self._mask is None:
+            held = self.slot >= 0
+            words = self.ring.views()["mask"][self.slot.clamp(min=0).to(torch.int64)]
+            self._mask = torch.where(held, words, torch.zeros_like(words))
+        return self._mask
