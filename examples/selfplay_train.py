@@ -9,7 +9,7 @@ with --device-train, on the device), packs the new weights for the search and re
                                       [--symmetries] [--leaf-eval playouts|value]
                                       [--root-noise EPS,ALPHA] [--temperature T] [--sample-plies K] [--leaves K]
                                       [--eval-symmetries all|0,4] [--replay CAPACITY --batch B --steps S]
-                                      [--device-train] [--stream PLIES] [--exact-from M] [--prove]
+                                      [--device-train] [--prioritized ALPHA,BETA] [--stream PLIES] [--exact-from M] [--prove]
                                       [--exact-targets M [--exact-value-only]]
                                       [--reanalyse N [--reanalyse-value-mix L]]
 
@@ -38,6 +38,10 @@ path's and are not used with it.
 --device-train takes the training step to the device as well (qtttgym_amd.Trainer): the loss, its gradients and the
 AMSGrad step run as HIP kernels on the packed weights that the search reads, so there is no autograd, no torch optimiser
 and no repacking of the weights between runs; --out is then the trainer's state dict.
+--prioritized ALPHA,BETA (with --replay and --device-train) draws the minibatches by priority (ReplayBuffer(prioritized=
+True), Schaul et al.): every step weights the loss by the importance weights (F q / T) ** -BETA of its draw and writes
+(L + J) ** ALPHA, the samples' own loss terms, back as their new priorities; a new sample enters at the largest priority
+stored so far.  Nothing of it is read back.
 --stream PLIES (with --replay) keeps the batch of --games game slots full instead of playing them in lockstep
 (SelfPlay.stream): every run advances the slots by PLIES searched plies, a slot whose game ends hands its samples to the ring
 and starts a new game at once, and the run's --steps minibatches follow.  The counters stay on the device; the printed
@@ -112,6 +116,16 @@ def train_on_device(trainer, batches):
     return L, J[~samples[4]]
 
 
+def train_prioritized(trainer, ring, batch, steps, alpha, beta):
+    """`steps` minibatches drawn by priority: the importance weights of the draw go into the loss, the per-sample loss
+    terms come back as the new priorities.  No host synchronisation; the last step's (L, J) as train_on_device gives them."""
+    for _ in range(steps):
+        samples = ring.sample(batch, "random")
+        L, J = trainer.step(*samples, weight=ring.weights(beta))
+        ring.update_priorities((L + J).clamp_min(0.0) ** alpha)
+    return L, J[~samples[4]]
+
+
 def parse_eval_symmetries(spec):
     """--eval-symmetries: None, "all", or the comma-separated list as ints."""
     return spec if spec in (None, "all") else tuple(int(k) for k in spec.split(","))
@@ -149,6 +163,9 @@ def main():
     ap.add_argument("--steps", type=int, default=50, help="with --replay: minibatch steps per run")
     ap.add_argument("--device-train", action="store_true",
                     help="loss, gradients and the optimiser on the device, on the search's packed weights (Trainer)")
+    ap.add_argument("--prioritized", default=None, metavar="ALPHA,BETA",
+                    help="with --replay and --device-train: draw the minibatches by priority (L + J) ** ALPHA and weight the "
+                         "loss by the importance weights (F q / T) ** -BETA")
     ap.add_argument("--stream", type=int, default=0, metavar="PLIES",
                     help="with --replay: every run is PLIES plies of continuous self-play (finished games restart in "
                          "place and feed the ring) instead of one batch of games in lockstep")
@@ -180,6 +197,9 @@ def main():
         ap.error("--prove needs --exact-from")
     if args.replay and (args.batch < 1 or args.steps < 1):
         ap.error("--replay needs --batch >= 1 and --steps >= 1")
+    if args.prioritized is not None and not (args.replay and args.device_train):
+        ap.error("--prioritized needs --replay and --device-train (the weighted loss is the device trainer's)")
+    alpha, beta = (float(x) for x in args.prioritized.split(",")) if args.prioritized is not None else (0.0, 0.0)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda", torch.cuda.current_device())
     model = Net().to(dev)
@@ -197,10 +217,12 @@ def main():
                   eval_symmetries=parse_eval_symmetries(args.eval_symmetries), root_policy=args.root_policy,
                   max_considered=args.max_considered, exact_from=args.exact_from, prove=args.prove,
                   exact_targets=args.exact_targets, exact_policy=not args.exact_value_only)
-    ring = ReplayBuffer(args.replay, device=dev, seed=args.seed) if args.replay else None
+    ring = ReplayBuffer(args.replay, device=dev, seed=args.seed, prioritized=args.prioritized is not None) if args.replay else None
     reanalyser = Reanalyser(sp, ring, args.reanalyse, value_mix=args.reanalyse_value_mix, seed=args.seed) if args.reanalyse else None
     trainer = Trainer(model, device=dev, net=net) if args.device_train else None      # nn.py:27's defaults
-    if trainer is not None:
+    if args.prioritized is not None:
+        fit, save = (lambda batches: train_prioritized(trainer, ring, args.batch, args.steps, alpha, beta)), trainer.state_dict
+    elif trainer is not None:
         fit, save = (lambda batches: train_on_device(trainer, batches)), trainer.state_dict
     else:
         fit, save = (lambda batches: train(model, optim, batches)), model.state_dict

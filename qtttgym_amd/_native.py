@@ -221,6 +221,22 @@ REPLAY_REANALYSE_SIGNATURES = {
     "qttt_replay_gather": (_i32, [_vp, _i64, _i64, _u64, _u32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qttt_replay_update": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# every symbol include/qttt_replay_priority.h declares (prioritised replay: the priority table beside the ring, its sync,
+# the guarded write-back, the proportional draw; qttt.h includes it)
+PRIORITY_ONE = 1 << 16
+PRIORITY_HEADER_BYTES = 64
+PRIORITY_MAX_LEVELS = 4
+REPLAY_PRIORITY_SIGNATURES = {
+    "qttt_replay_priority_bytes": (_i64, [_i64]),
+    "qttt_replay_priority_layout": (_i32, [_i64, ctypes.POINTER(ctypes.c_int64)]),
+    "qttt_replay_priority_sync": (_i32, [_vp, _vp, _i64, _vp]),
+    "qttt_replay_priority_update": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "qttt_replay_sample_prioritized": (_i32, [_vp, _vp, _i64, _i64, _u64, _u32, _vp, _i32] + [_vp] * 10 + [_vp]),
+}
+# every symbol include/qttt_train_weighted.h declares (importance weights in the training step's loss; qttt.h includes it)
+TRAIN_WEIGHTED_SIGNATURES = {
+    "qttt_train_gradients_weighted": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
 
 _lib = None
 
@@ -291,7 +307,8 @@ def lib():
                                   + list(REPLAY_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())
                                   + list(SELFPLAY_STREAM_SIGNATURES.items()) + list(SOLVE_SIGNATURES.items())
                                   + list(TREE_EXACT_SIGNATURES.items()) + list(SELFPLAY_EXACT_SIGNATURES.items())
-                                  + list(TREE_PROVE_SIGNATURES.items()) + list(REPLAY_REANALYSE_SIGNATURES.items())):
+                                  + list(TREE_PROVE_SIGNATURES.items()) + list(REPLAY_REANALYSE_SIGNATURES.items())
+                                  + list(REPLAY_PRIORITY_SIGNATURES.items()) + list(TRAIN_WEIGHTED_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

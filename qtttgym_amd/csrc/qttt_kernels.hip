@@ -61,6 +61,8 @@
 // window and holder arithmetic, the argument checks);
 // qttt_train_kernels.h (the training step: loss, gradients and AMSGrad on the packed f32 blob, on qttt_nn_kernels.h's layers)
 // with qttt_train_host.h (host only and free of HIP: the workspace layout and the launch plan);
+// qttt_replay_priority_kernels.h (prioritised replay: the priority table's sums, the guarded write-back, the proportional draw
+// on the sample kernel's row functions) with qttt_replay_priority_host.h (host only and free of HIP: layout, guard, quantiser);
 // qttt_selfplay_stream_kernels.h (continuous self-play: the harvest of finished games and their restart in place);
 // qttt_solve_kernels.h (the exact endgame solver: the full expectimax tree of a late position, a workgroup per board);
 // qttt_tree_exact_kernels.h (exact leaves in the search trees: a lane per path record, the solver's recursion for the leaves
@@ -87,6 +89,7 @@
 #include "qttt_tree_gumbel_kernels.h"
 #include "qttt_replay_kernels.h"
 #include "qttt_train_kernels.h"
+#include "qttt_replay_priority_kernels.h"
 #include "qttt_selfplay_stream_kernels.h"
 #include "qttt_solve_kernels.h"
 #include "qttt_tree_exact_kernels.h"
@@ -1081,13 +1084,10 @@ int qttt_replay_sample(const void *replay, int64_t capacity, int64_t n, uint64_t
 // ---------------------------------------------------------------- the training step (include/qttt_train.h)
 int64_t qttt_train_workspace_bytes(int64_t n) { return train_samples_bad(n) ? -1 : train_plan(n).bytes; }
 
-int qttt_train_gradients(const float *s, const double *pi, const uint8_t *mask, const float *v, const uint8_t *done,
-                         int64_t n, const void *weights, void *grads, float *L, float *J, void *workspace, void *stream) {
-    if (train_samples_bad(n)) return QTTT_ERR_SIZE;
-    if (any_null(s, pi, mask, v, done) || any_null(weights, grads, workspace)) return QTTT_ERR_NULL;
-    if (misaligned(weights, 16) || misaligned(grads, 16) || misaligned(workspace, 256) || misaligned(pi, 8) ||
-        misaligned(s, 4) || misaligned(v, 4) || misaligned(L, 4) || misaligned(J, 4))
-        return QTTT_ERR_ACTION;
+// qttt_train_gradients and qttt_train_gradients_weighted (include/qttt_train_weighted.h): one body, `weight` null for the first
+static int train_gradients(const float *s, const double *pi, const uint8_t *mask, const float *v, const uint8_t *done,
+                           const float *weight, int64_t n, const void *weights, void *grads, float *L, float *J, void *workspace,
+                           void *stream) {
     const TrainPlan p = train_plan(n);
     char *ws = static_cast<char *>(workspace);
     const auto f32_at = [&](int64_t off) { return reinterpret_cast<float *>(ws + off); };
@@ -1096,8 +1096,10 @@ int qttt_train_gradients(const float *s, const double *pi, const uint8_t *mask, 
     u32 *n_keep = reinterpret_cast<u32 *>(ws + p.count);
     const float *W = static_cast<const float *>(weights);
     if (const int rc = launch(train_count_kernel, 1, QTTT_NN_BLOCK, stream, done, n, n_keep)) return rc;
-    if (const int rc = launch(train_forward_kernel, p.tiles, QTTT_NN_BLOCK, stream, s, pi, mask, v, done, n, W,
-                              (const u32 *)n_keep, h[0], h[1], h[2], dout, L, J))
+    if (const int rc = with_bools([&](auto WEIGHTED) {
+            return launch(train_forward_kernel<WEIGHTED>, p.tiles, QTTT_NN_BLOCK, stream, s, pi, mask, v, done, n, W,
+                          (const u32 *)n_keep, h[0], h[1], h[2], dout, L, J, weight);
+        }, weight != nullptr))
         return rc;
     if (const int rc = launch(train_backward_kernel, p.tiles, QTTT_NN_BLOCK, stream, W, (const float *)dout, (const float *)h[0],
                               (const float *)h[1], (const float *)h[2], dz[0], dz[1], dz[2], n))
@@ -1106,6 +1108,27 @@ int qttt_train_gradients(const float *s, const double *pi, const uint8_t *mask, 
     if (const int rc = launch(train_wgrad_kernel, p.wgrad_groups, QTTT_NN_BLOCK, stream, a, n, partials)) return rc;
     return launch(train_reduce_kernel, p.reduce_groups, QTTT_NN_BLOCK, stream, (const float *)partials, p.chunks,
                   static_cast<float *>(grads));
+}
+
+int qttt_train_gradients(const float *s, const double *pi, const uint8_t *mask, const float *v, const uint8_t *done,
+                         int64_t n, const void *weights, void *grads, float *L, float *J, void *workspace, void *stream) {
+    if (train_samples_bad(n)) return QTTT_ERR_SIZE;
+    if (any_null(s, pi, mask, v, done) || any_null(weights, grads, workspace)) return QTTT_ERR_NULL;
+    if (misaligned(weights, 16) || misaligned(grads, 16) || misaligned(workspace, 256) || misaligned(pi, 8) ||
+        misaligned(s, 4) || misaligned(v, 4) || misaligned(L, 4) || misaligned(J, 4))
+        return QTTT_ERR_ACTION;
+    return train_gradients(s, pi, mask, v, done, nullptr, n, weights, grads, L, J, workspace, stream);
+}
+
+int qttt_train_gradients_weighted(const float *s, const double *pi, const uint8_t *mask, const float *v, const uint8_t *done,
+                                  const float *weight, int64_t n, const void *weights, void *grads, float *L, float *J,
+                                  void *workspace, void *stream) {
+    if (train_samples_bad(n)) return QTTT_ERR_SIZE;
+    if (any_null(s, pi, mask, v, done) || any_null(weight, weights, grads, workspace)) return QTTT_ERR_NULL;
+    if (misaligned(weights, 16) || misaligned(grads, 16) || misaligned(workspace, 256) || misaligned(pi, 8) ||
+        misaligned(s, 4) || misaligned(v, 4) || misaligned(L, 4) || misaligned(J, 4) || misaligned(weight, 4))
+        return QTTT_ERR_ACTION;
+    return train_gradients(s, pi, mask, v, done, weight, n, weights, grads, L, J, workspace, stream);
 }
 
 int qttt_train_adam(void *weights, const void *grads, void *m, void *v2, void *vmax, int64_t step, float lr, float beta1,
@@ -1319,6 +1342,75 @@ int qttt_replay_update(void *replay, int64_t capacity, int64_t n, const int32_t 
     if (!work) return 0;
     return launch(replay_update_kernel, ceil_div(n, REPLAY_UPDATE_SAMPLES), REPLAY_UPDATE_BLOCK, stream, replay_ring(replay, capacity),
                   capacity, n, slot, number, reinterpret_cast<const u64 *>(pi), reinterpret_cast<const u32 *>(v), updated_out);
+}
+
+// ---------------------------------------------------------------- prioritised replay (include/qttt_replay_priority.h)
+int64_t qttt_replay_priority_bytes(int64_t capacity) {
+    return replay_capacity_bad(capacity) ? (int64_t)QTTT_ERR_SIZE : priority_layout(capacity).bytes;
+}
+
+int qttt_replay_priority_layout(int64_t capacity, int64_t *offsets) {
+    if (replay_capacity_bad(capacity)) return QTTT_ERR_SIZE;
+    if (!offsets) return QTTT_ERR_NULL;
+    const PriorityLayout l = priority_layout(capacity);
+    for (int k = 0; k <= QTTT_PRIORITY_MAX_LEVELS; ++k) offsets[k] = k <= l.levels ? l.off[k] : 0;
+    return l.levels;
+}
+
+// every sum level from the level below; ASSIGN and `seen`: the sync's first and last launch
+static int priority_rebuild(bool assign, const u64 *ring_header, const PriorityTable &tab, int64_t capacity, void *stream) {
+    u64 *seen = assign ? tab.header + PRIORITY_SEEN_WORD : nullptr;
+    if (const int rc = with_bools([&](auto ASSIGN) {
+            return launch(priority_sum0_kernel<ASSIGN>, tab.n[1], QTTT_REPLAY_SCAN_BLOCK, stream, ring_header, (const u64 *)tab.header,
+                          tab.q, tab.sum[0], capacity, tab.levels == 1u ? seen : (u64 *)nullptr);
+        }, assign))
+        return rc;
+    for (u32 k = 1; k < tab.levels; ++k)
+        if (const int rc = launch(priority_sum_kernel, tab.n[k + 1], QTTT_REPLAY_SCAN_BLOCK, stream, ring_header,
+                                  (const u64 *)tab.sum[k - 1], tab.sum[k], tab.n[k], k + 1u == tab.levels ? seen : (u64 *)nullptr))
+            return rc;
+    return 0;
+}
+
+int qttt_replay_priority_sync(const void *replay, void *prio, int64_t capacity, void *stream) {
+    if (const int rc = priority_sync_check(replay, prio, capacity)) return rc;
+    return priority_rebuild(true, static_cast<const u64 *>(replay), priority_table(prio, capacity), capacity, stream);
+}
+
+int qttt_replay_priority_update(const void *replay, void *prio, int64_t capacity, int64_t n, const int32_t *slot,
+                                const int64_t *number, const float *priority, uint8_t *updated_out, void *stream) {
+    bool work;
+    if (const int rc = priority_update_check(replay, prio, capacity, n, slot, number, priority, work)) return rc;
+    if (!work) return 0;
+    const u64 *ring_header = static_cast<const u64 *>(replay);
+    const PriorityTable tab = priority_table(prio, capacity);
+    const int64_t groups = ceil_div(n, PRIORITY_UPDATE_BLOCK);
+    if (const int rc = launch(priority_update_kernel<false>, groups, PRIORITY_UPDATE_BLOCK, stream, ring_header, tab, capacity, n, slot,
+                              number, priority, updated_out))
+        return rc;
+    if (const int rc = launch(priority_update_kernel<true>, groups, PRIORITY_UPDATE_BLOCK, stream, ring_header, tab, capacity, n, slot,
+                              number, priority, updated_out))
+        return rc;
+    return priority_rebuild(false, ring_header, tab, capacity, stream);
+}
+
+int qttt_replay_sample_prioritized(const void *replay, const void *prio, int64_t capacity, int64_t n, uint64_t seed,
+                                   uint32_t draw, const uint8_t *sym, int random_symmetry, float *s_out, double *pi_out,
+                                   uint8_t *mask_out, float *v_out, uint8_t *done_out, int32_t *index_out, uint8_t *sym_out,
+                                   int64_t *number_out, uint32_t *q_out, uint64_t *total_out, void *stream) {
+    bool work;
+    if (const int rc = priority_sample_check(replay, prio, capacity, n, draw, s_out, pi_out, mask_out, v_out, done_out, index_out,
+                                             number_out, q_out, total_out, work))
+        return rc;
+    if (!work) return 0;
+    const ReplayRing ring = replay_ring(const_cast<void *>(replay), capacity);
+    const PriorityTable tab = priority_table(const_cast<void *>(prio), capacity);
+    const u64 key_slot = launch_key(seed, draw), key_sym = launch_key(seed, draw | 0x80000000u);
+    return with_bools([&](auto SYM) {
+        return launch(replay_sample_prioritized_kernel<SYM>, ceil_div(n, REPLAY_TILE), REPLAY_SAMPLE_BLOCK, stream, ring, tab, capacity,
+                      n, key_slot, key_sym, sym, (u32)(random_symmetry != 0), s_out, reinterpret_cast<u64 *>(pi_out), mask_out,
+                      reinterpret_cast<u32 *>(v_out), done_out, index_out, sym_out, number_out, q_out, reinterpret_cast<u64 *>(total_out));
+    }, sym != nullptr || random_symmetry != 0);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // qttt_replay_kernels.h — the replay ring on the device (include/qttt_replay.h): the scan levels and the
 // move of qttt_replay_append, and the one launch of qttt_replay_sample, which gathers whole rows from random slots,
 // builds the (permuted) to_vector encoding and the permuted pi / mask rows of a tile of samples in LDS — encode_kernel's
-// plan — and streams them out as coalesced 16-byte stores.  Behind them the two launches of reanalysis
+// plan — and streams them out as coalesced 16-byte stores (its row functions serve the prioritised draw of
+// qttt_replay_priority_kernels.h as well).  Behind them the two launches of reanalysis
 // (include/qttt_replay_reanalyse.h): a window of the ring as a state buffer, and the guarded write-back.
 #ifndef QTTT_REPLAY_KERNELS_H
 #define QTTT_REPLAY_KERNELS_H
@@ -113,6 +114,108 @@ __global__ __launch_bounds__(REPLAY_APPEND_BLOCK) void replay_append_kernel(Repl
 // stream the three LDS tiles out.  16 samples: 16.3 KB of LDS, so eight workgroups fit a CU and the 32-wave cap, not LDS,
 // bounds the occupancy; and a minibatch of 4 096 is 256 workgroups, one per CU.
 constexpr int REPLAY_TILE = 16, REPLAY_SAMPLE_BLOCK = 256;
+// The three LDS tiles of a workgroup's samples.  The row functions below are what qttt_replay_sample and
+// qttt_replay_sample_prioritized (qttt_replay_priority_kernels.h) share: the two differ in how a sample's slot is drawn.
+struct ReplayTiles {
+    float *tile;                                                 // [REPLAY_TILE * 180]
+    u64 *ptile;                                                  // [REPLAY_TILE * 36]
+    uint8_t *mtile;                                              // [REPLAY_TILE * 36]
+};
+struct ReplaySampleOut {
+    float *s_out;
+    u64 *pi_out;
+    uint8_t *mask_out;
+    u32 *v_out;
+    uint8_t *done_out;
+    int32_t *index_out;
+    uint8_t *sym_out;
+};
+
+// sample i's symmetry: sym[i] when given (a value past 7: the identity), else the hash's top three bits, else 0
+template <bool SYM>
+__device__ __forceinline__ u32 replay_sample_symmetry(int64_t i, u32 id, u64 key_sym, const uint8_t *sym, u32 random_symmetry) {
+    u32 k = 0;
+    if constexpr (SYM) {
+        if (sym) k = sym[i] < (u32)QTTT_SYMMETRIES ? sym[i] : 0u;
+        else if (random_symmetry) k = counter_draw(id, key_sym).h2 >> 29;
+    }
+    return k;
+}
+
+// part j of sample b of the tile when there is nothing to draw from: zero rows, index -1
+__device__ __forceinline__ void replay_sample_empty_rows(const ReplayTiles &t, const ReplaySampleOut &out, int64_t i, u32 b, u32 j) {
+    float *o = t.tile + b * 180u;
+    for (u32 c = j; c < 180u; c += 16u) o[c] = 0.0f;
+    for (u32 a = j; a < 36u; a += 16u) {
+        t.ptile[b * 36u + a] = 0ull;
+        t.mtile[b * 36u + a] = 0;
+    }
+    if (j == 15u) {
+        out.v_out[i] = 0u;
+        out.done_out[i] = 0;
+        if (out.index_out) out.index_out[i] = -1;
+        if (out.sym_out) out.sym_out[i] = 0;
+    }
+}
+
+// part j of sample b of the tile: the rows of slot `slot` under symmetry k into the LDS tiles, the scalars straight out
+template <bool SYM>
+__device__ __forceinline__ void replay_sample_rows(const ReplayRing &ring, const ReplayTiles &t, const ReplaySampleOut &out,
+                                                   int64_t i, u32 b, u32 j, u64 slot, u32 k) {
+    float *o = t.tile + b * 180u;
+    const u64 cells = g_sym_tables.cells[k];
+    if (j < 9u) {                                        // encode_kernel's rows, spelled out: one square per thread
+        Cold s;                                          // here, and that kernel's own stream (a leg of bench.py) stays
+        cold_unpack(ring.P[slot], ring.Q[slot], s);
+        const u32 v = j, w = SYM ? sym_cell(cells, v) : v;
+        const u32 qsets = s.comp(0) | s.comp(1) | s.comp(2) | s.comp(3);
+        const u32 col = (s.cl >> v & 1u) ? s.sqv(v) : 9u;   // board -1 indexes column 9
+        u32 touched = 0;                                    // rounds whose move touches v
+        for (u32 r = 0; r < s.n; ++r)
+            if ((s.mv(r) & 0xFu) == v || (s.mv(r) >> 4) == v) touched |= 1u << r;
+        for (u32 c = 0; c < 10u; ++c) {
+            o[w * 10u + c] = c == col ? 1.0f : 0.0f;
+            float q = (touched >> c & 1u) ? (1.0f / 3.0f) : 0.0f;   // 1/math.sqrt(9)
+            if (c == 9u && !(qsets >> v & 1u)) q = 1.0f;    // square in no qstruct
+            o[90u + w * 10u + c] = q;
+        }
+    }
+    const u64 mbits = ring.mask[slot];
+    for (u32 a = j; a < 36u; a += 16u) {
+        const u32 to = SYM ? sym_action_of_pair(cells, g_pair_lut.b[a]) : a;
+        t.ptile[b * 36u + to] = ring.pi[slot * 36u + a];
+        t.mtile[b * 36u + to] = (uint8_t)(mbits >> a & 1ull);
+    }
+    if (j == 15u) {
+        out.v_out[i] = ring.v[slot];
+        out.done_out[i] = ring.done[slot] != 0 ? 1 : 0;
+        if (out.index_out) out.index_out[i] = (int32_t)slot;
+        if (out.sym_out) out.sym_out[i] = (uint8_t)k;
+    }
+}
+
+// all four waves stream the three LDS tiles of the tile's `valid` samples out (after a __syncthreads)
+__device__ __forceinline__ void replay_sample_stream(const ReplayTiles &t, const ReplaySampleOut &out, int64_t base, u32 valid) {
+    {
+        const u32 n4 = valid * 45u;                                // 16-byte pieces of the encoding in this tile
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(t.tile);
+        u32x4 *dst = reinterpret_cast<u32x4 *>(out.s_out + base * 180);
+        for (u32 q = threadIdx.x; q < n4; q += REPLAY_SAMPLE_BLOCK) __builtin_nontemporal_store(src[q], &dst[q]);
+    }
+    {
+        const u32 n4 = valid * 18u;                                // 16-byte pieces of pi (36 x 8 bytes = 18 x 16)
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(t.ptile);
+        u32x4 *dst = reinterpret_cast<u32x4 *>(out.pi_out + base * 36);
+        for (u32 q = threadIdx.x; q < n4; q += REPLAY_SAMPLE_BLOCK) __builtin_nontemporal_store(src[q], &dst[q]);
+    }
+    {
+        const u32 n4 = valid * 9u;                                 // 4-byte pieces of the mask (36 = 9 x 4)
+        const u32 *src = reinterpret_cast<const u32 *>(t.mtile);
+        u32 *dst = reinterpret_cast<u32 *>(out.mask_out + base * 36);
+        for (u32 q = threadIdx.x; q < n4; q += REPLAY_SAMPLE_BLOCK) dst[q] = src[q];
+    }
+}
+
 template <bool SYM>
 __global__ __launch_bounds__(REPLAY_SAMPLE_BLOCK) void replay_sample_kernel(ReplayRing ring, int64_t capacity, int64_t n, u64 key_slot,
                                                                             u64 key_sym, const uint8_t *sym, u32 random_symmetry,
@@ -121,6 +224,8 @@ __global__ __launch_bounds__(REPLAY_SAMPLE_BLOCK) void replay_sample_kernel(Repl
     __shared__ __attribute__((aligned(16))) float tile[REPLAY_TILE * 180];
     __shared__ __attribute__((aligned(16))) u64 ptile[REPLAY_TILE * 36];
     __shared__ __attribute__((aligned(16))) uint8_t mtile[REPLAY_TILE * 36];
+    const ReplayTiles tiles = {tile, ptile, mtile};
+    const ReplaySampleOut out = {s_out, pi_out, mask_out, v_out, done_out, index_out, sym_out};
     const int64_t base = (int64_t)blockIdx.x * REPLAY_TILE;
     const u32 b = threadIdx.x >> 4, j = threadIdx.x & 15u;
     const int64_t i = base + b;
@@ -128,78 +233,17 @@ __global__ __launch_bounds__(REPLAY_SAMPLE_BLOCK) void replay_sample_kernel(Repl
     const u64 written = ring.header[0];
     const u64 filled = written < (u64)capacity ? written : (u64)capacity;
     if (b < valid) {
-        float *o = tile + b * 180u;
         if (filled == 0ull) {                                    // an empty ring: zero rows, index -1
-            for (u32 c = j; c < 180u; c += 16u) o[c] = 0.0f;
-            for (u32 a = j; a < 36u; a += 16u) {
-                ptile[b * 36u + a] = 0ull;
-                mtile[b * 36u + a] = 0;
-            }
-            if (j == 15u) {
-                v_out[i] = 0u;
-                done_out[i] = 0;
-                if (index_out) index_out[i] = -1;
-                if (sym_out) sym_out[i] = 0;
-            }
+            replay_sample_empty_rows(tiles, out, i, b, j);
         } else {
             const u32 id = fold_id((u64)i);
             const Draw d = counter_draw(id, key_slot);
             const u64 slot = __umul64hi(((u64)d.h2 << 32) | d.h1, filled);   // < filled <= capacity
-            u32 k = 0;
-            if constexpr (SYM) {
-                if (sym) k = sym[i] < (u32)QTTT_SYMMETRIES ? sym[i] : 0u;
-                else if (random_symmetry) k = counter_draw(id, key_sym).h2 >> 29;
-            }
-            const u64 cells = g_sym_tables.cells[k];
-            if (j < 9u) {                                        // encode_kernel's rows, spelled out: one square per thread
-                Cold s;                                          // here, and that kernel's own stream (a leg of bench.py) stays
-                cold_unpack(ring.P[slot], ring.Q[slot], s);
-                const u32 v = j, w = SYM ? sym_cell(cells, v) : v;
-                const u32 qsets = s.comp(0) | s.comp(1) | s.comp(2) | s.comp(3);
-                const u32 col = (s.cl >> v & 1u) ? s.sqv(v) : 9u;   // board -1 indexes column 9
-                u32 touched = 0;                                    // rounds whose move touches v
-                for (u32 t = 0; t < s.n; ++t)
-                    if ((s.mv(t) & 0xFu) == v || (s.mv(t) >> 4) == v) touched |= 1u << t;
-                for (u32 c = 0; c < 10u; ++c) {
-                    o[w * 10u + c] = c == col ? 1.0f : 0.0f;
-                    float q = (touched >> c & 1u) ? (1.0f / 3.0f) : 0.0f;   // 1/math.sqrt(9)
-                    if (c == 9u && !(qsets >> v & 1u)) q = 1.0f;    // square in no qstruct
-                    o[90u + w * 10u + c] = q;
-                }
-            }
-            const u64 mbits = ring.mask[slot];
-            for (u32 a = j; a < 36u; a += 16u) {
-                const u32 to = SYM ? sym_action_of_pair(cells, g_pair_lut.b[a]) : a;
-                ptile[b * 36u + to] = ring.pi[slot * 36u + a];
-                mtile[b * 36u + to] = (uint8_t)(mbits >> a & 1ull);
-            }
-            if (j == 15u) {
-                v_out[i] = ring.v[slot];
-                done_out[i] = ring.done[slot] != 0 ? 1 : 0;
-                if (index_out) index_out[i] = (int32_t)slot;
-                if (sym_out) sym_out[i] = (uint8_t)k;
-            }
+            replay_sample_rows<SYM>(ring, tiles, out, i, b, j, slot, replay_sample_symmetry<SYM>(i, id, key_sym, sym, random_symmetry));
         }
     }
     __syncthreads();
-    {
-        const u32 n4 = valid * 45u;                                // 16-byte pieces of the encoding in this tile
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(tile);
-        u32x4 *dst = reinterpret_cast<u32x4 *>(s_out + base * 180);
-        for (u32 q = threadIdx.x; q < n4; q += REPLAY_SAMPLE_BLOCK) __builtin_nontemporal_store(src[q], &dst[q]);
-    }
-    {
-        const u32 n4 = valid * 18u;                                // 16-byte pieces of pi (36 x 8 bytes = 18 x 16)
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(ptile);
-        u32x4 *dst = reinterpret_cast<u32x4 *>(pi_out + base * 36);
-        for (u32 q = threadIdx.x; q < n4; q += REPLAY_SAMPLE_BLOCK) __builtin_nontemporal_store(src[q], &dst[q]);
-    }
-    {
-        const u32 n4 = valid * 9u;                                 // 4-byte pieces of the mask (36 = 9 x 4)
-        const u32 *src = reinterpret_cast<const u32 *>(mtile);
-        u32 *dst = reinterpret_cast<u32 *>(mask_out + base * 36);
-        for (u32 q = threadIdx.x; q < n4; q += REPLAY_SAMPLE_BLOCK) dst[q] = src[q];
-    }
+    replay_sample_stream(tiles, out, base, valid);
 }
 
 // ---- reanalysis (include/qttt_replay_reanalyse.h)

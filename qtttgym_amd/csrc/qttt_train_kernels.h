@@ -46,11 +46,15 @@ __device__ __forceinline__ void train_store_tile(const float *H, float *__restri
         h[base * QTTT_NN_HIDDEN + k] = H[(k >> 8) * NNCfg<0>::LD + (k & 255u)];
 }
 
+// WEIGHTED (qttt_train_gradients_weighted, include/qttt_train_weighted.h): the loss tail multiplies the sample's output
+// gradient, rounded as without weights, by weight[i] in f32; L and J stay unweighted.  A compile-time variant: the
+// unweighted instantiation never looks at `weight` and keeps its code and registers (profiles/priority/kernel_resources.txt).
+template <bool WEIGHTED>
 __global__ __launch_bounds__(QTTT_NN_BLOCK) void train_forward_kernel(
     const float *__restrict__ s, const double *__restrict__ pi, const uint8_t *__restrict__ mask, const float *__restrict__ v,
     const uint8_t *__restrict__ done, int64_t n, const float *__restrict__ W, const u32 *__restrict__ n_keep_p,
     float *__restrict__ h1, float *__restrict__ h2, float *__restrict__ h3, float *__restrict__ dOut, float *__restrict__ Lout,
-    float *__restrict__ Jout) {
+    float *__restrict__ Jout, const float *__restrict__ weight) {
     typedef NNCfg<0> C;
     typedef NNBlob<0> B;
     __shared__ __attribute__((aligned(16))) float H[C::M * C::LD];
@@ -82,6 +86,8 @@ __global__ __launch_bounds__(QTTT_NN_BLOCK) void train_forward_kernel(
         const float *o = O + tid * QTTT_NN_OUT_LD;
         float *dO = dOut + i * QTTT_NN_HEAD_COLS;
         const float diff = o[36] - v[i];
+        float wi = 1.0f;
+        if constexpr (WEIGHTED) wi = weight[i];
         float Jv = 0.f;
         if (done[i] == 0) {
             u64 lm = 0;
@@ -101,13 +107,13 @@ __global__ __launch_bounds__(QTTT_NN_BLOCK) void train_forward_kernel(
                     Jd += p * (log(p + 1e-7) - (double)(z - lse));
                     d = (float)(((double)(expf(z) / sum) * S - p) / keep);
                 }
-                dO[a] = d;
+                dO[a] = WEIGHTED ? d * wi : d;
             }
             Jv = (float)Jd;
         } else {
             for (u32 a = 0; a < 36u; ++a) dO[a] = 0.f;
         }
-        dO[36] = diff / (float)n;
+        dO[36] = WEIGHTED ? (diff / (float)n) * wi : diff / (float)n;
         for (u32 a = 37u; a < (u32)QTTT_NN_HEAD_COLS; ++a) dO[a] = 0.f;
         if (Lout) Lout[i] = 0.5f * diff * diff;
         if (Jout) Jout[i] = Jv;

@@ -9,6 +9,11 @@ flat()'s order without a host read-back, and that one launch samples from with a
     window = rb.gather(4096)                              # reanalysis: positions out as a VecEnv ...
     rb.update(window, pi=new_pi)                          # ... and refreshed targets back, unless appended over since
 
+    rb = ReplayBuffer(1 << 20, prioritized=True)          # prioritised replay: slots drawn by priority,
+    batch = rb.sample(4096, "random")                     # ... two entries, no read-back ...
+    L, J = trainer.step(*batch, weight=rb.weights(1.0))   # ... importance weights in the loss ...
+    rb.update_priorities((L + J) ** 0.5)                  # ... and the per-sample loss back as the new priorities
+
 Loss, gradients and the optimiser are ordinary torch or qtttgym_amd.Trainer (examples/selfplay_train.py --replay
 [--device-train]).
 """
@@ -33,9 +38,12 @@ class ReplayBuffer(LibCaller):
     """A ring of `capacity` training samples in device memory.  add(batch) appends a SelfPlayBatch's samples (the rows
     below every game's length, game-major: flat()'s order); once the ring is full the oldest samples are overwritten.
     sample(n, symmetries) draws n of the samples held, uniformly with replacement, by the counter hash of (seed, the
-    number of sample() calls so far): the same seed and call number give the same minibatch."""
+    number of sample() calls so far): the same seed and call number give the same minibatch.  prioritized=True: the ring
+    owns a priority table (include/qttt_replay_priority.h) and sample() draws slot s with probability q[s] / T, the
+    fixed-point priorities and their total; a new sample enters at the largest priority stored so far, and
+    update_priorities() writes the trainer's per-sample loss back.  The ring's own bytes are the same either way."""
 
-    def __init__(self, capacity, device=None, seed=0):
+    def __init__(self, capacity, device=None, seed=0, prioritized=False):
         self.capacity, self.seed = int(capacity), int(seed) & (2 ** 64 - 1)
         if not 1 <= self.capacity <= _native.REPLAY_MAX_CAPACITY:
             raise ValueError("capacity must be in 1..%d" % _native.REPLAY_MAX_CAPACITY)
@@ -49,6 +57,16 @@ class ReplayBuffer(LibCaller):
         self.gathers = 0                # gather() calls so far: the draw index of the next window
         self.last_index = self.last_symmetry = None
         self._scratch = None
+        self.prioritized = bool(prioritized)
+        self.last_number = self.last_priority = self.last_total = None
+        if self.prioritized:
+            offs = (ctypes.c_int64 * (_native.PRIORITY_MAX_LEVELS + 1))()
+            self.priority_levels = self._lib.qttt_replay_priority_layout(self.capacity, offs)
+            if self.priority_levels < 1:
+                _native.check(self.priority_levels, "qttt_replay_priority_layout")
+            self.priority_offsets = list(offs)[:self.priority_levels + 1]
+            self.priority = torch.zeros(int(self._lib.qttt_replay_priority_bytes(self.capacity)), dtype=torch.uint8,
+                                        device=self.device)
 
     def views(self):
         """The ring's arrays as views of `buffer` (qttt_replay_layout): written i64[1], P, Q and mask i64[capacity] (the
@@ -58,6 +76,62 @@ class ReplayBuffer(LibCaller):
             at, count = self.offsets[name], C * (36 if shape else 1)
             out[name] = self.buffer[at:at + size * count].view(dtype).view((C,) + shape)
         return out
+
+    def priority_views(self):
+        """The priority table's arrays as views of `priority` (qttt_replay_priority_layout): seen i64[1], pmax i32[1] (the
+        u32 word), q i32[capacity] (the u32 words) and sums, one i64 tensor per sum level, the last of one entry: T."""
+        self._need_priorities("priority_views()")
+        n, out = self.capacity, {"seen": self.priority[:8].view(torch.int64), "pmax": self.priority[8:12].view(torch.int32)}
+        at = self.priority_offsets[0]
+        out["q"] = self.priority[at:at + 4 * n].view(torch.int32)
+        out["sums"] = []
+        for at in self.priority_offsets[1:]:
+            n = -(-n // _native.REPLAY_SCAN_BLOCK)
+            out["sums"].append(self.priority[at:at + 8 * n].view(torch.int64))
+        return out
+
+    def _need_priorities(self, what):
+        if not self.prioritized:
+            raise ValueError("%s needs a ring built with prioritized=True" % what)
+
+    def sync_priorities(self):
+        """qttt_replay_priority_sync: the samples appended since the last sync get the largest priority stored so far, and
+        the sums are rebuilt.  sample() does this itself; no host read-back."""
+        self._need_priorities("sync_priorities()")
+        self._call("qttt_replay_priority_sync", self.buffer.data_ptr(), self.priority.data_ptr(), self.capacity)
+
+    def weights(self, beta):
+        """The importance weights of the last draw, f32[n]: (F q / T) ** -beta divided by its maximum, with q / T the f64
+        quotient of the drawn slot's priority and the total, and F the samples held.  Torch ops on device tensors; no host
+        read.  What Trainer.step(..., weight=) takes."""
+        self._need_priorities("weights()")
+        if self.last_priority is None:
+            raise ValueError("weights() before any sample()")
+        q = (self._last_q.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)
+        held = self.views()["written"].clamp(max=self.capacity).to(torch.float64)
+        w = (held * (q / self.last_total.to(torch.float64))) ** (-float(beta))
+        return (w / w.max()).to(torch.float32)
+
+    def update_priorities(self, priority, index=None, number=None):
+        """New priorities (f32[n], the real values: they are stored as fixed point, times 2**16, in 1..2**32-1) for the
+        slots `index` (i32[n]) that held the samples `number` (i64[n]) when drawn; both default to the last sample()'s.
+        qttt_replay_priority_update: a slot appended over since the draw keeps the newcomer's priority, a slot drawn
+        several times receives the largest of its values.  No host read-back.  Returns updated bool[n]."""
+        self._need_priorities("update_priorities()")
+        if (index is None) != (number is None):
+            raise ValueError("give index and number together, or neither for the last draw's")
+        if index is None:
+            if self.last_number is None:
+                raise ValueError("update_priorities() before any sample()")
+            index, number = self.last_index, self.last_number
+        n, dev = int(index.numel()), self.device
+        check_tensor(index, torch.int32, (n,), dev, "index")
+        check_tensor(number, torch.int64, (n,), dev, "number")
+        check_tensor(priority, torch.float32, (n,), dev, "priority")
+        updated = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self._call("qttt_replay_priority_update", self.buffer.data_ptr(), self.priority.data_ptr(), self.capacity, n,
+                   index.data_ptr(), number.data_ptr(), priority.data_ptr(), updated.data_ptr())
+        return updated.view(torch.bool)
 
     def size(self):
         """Samples held, min(written, capacity).  One host read-back."""
@@ -89,7 +163,9 @@ class ReplayBuffer(LibCaller):
         the ring, one launch (qttt_replay_sample).  symmetries: None = the samples as stored; "random" = every sample
         under a symmetry of its own, drawn by the hash; a uint8 tensor [n] = sample i under symmetries[i] (a value past 7:
         the identity).  out: the five tensors of an earlier call, to be written again.  The slots and symmetries drawn
-        are kept as last_index i32[n] and last_symmetry u8[n].  Raises before any add() of games: that is the host's count
+        are kept as last_index i32[n] and last_symmetry u8[n]; a prioritised ring syncs its table and draws by priority
+        (qttt_replay_priority_sync, qttt_replay_sample_prioritized), and keeps last_number i64[n] (the sample number each
+        slot held), last_priority u32[n] and last_total i64[1] (T) as well.  Raises before any add() of games: that is the host's count
         of add() calls, because `written` lives on the device and sample() reads nothing back.  What the ring holds is
         decided on the device: after adds whose games all had length 0 the rows are zero and last_index is -1, as the C
         entry gives for an empty ring."""
@@ -117,8 +193,19 @@ class ReplayBuffer(LibCaller):
                 check_tensor(t, dt, (n,) + shp, dev, "out." + name)
         index = torch.empty(n, dtype=torch.int32, device=dev)
         k = torch.empty(n, dtype=torch.uint8, device=dev)
-        self._call("qttt_replay_sample", self.buffer.data_ptr(), self.capacity, n, self.seed, self.draw, _ptr(sym),
-                   random_symmetry, *[t.data_ptr() for t in out], index.data_ptr(), k.data_ptr())
+        if self.prioritized:            # sync, then the proportional draw: two entries, nothing read back
+            number = torch.empty(n, dtype=torch.int64, device=dev)
+            q = torch.empty(n, dtype=torch.int32, device=dev)
+            total = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.sync_priorities()
+            self._call("qttt_replay_sample_prioritized", self.buffer.data_ptr(), self.priority.data_ptr(), self.capacity, n,
+                       self.seed, self.draw, _ptr(sym), random_symmetry, *[t.data_ptr() for t in out], index.data_ptr(),
+                       k.data_ptr(), number.data_ptr(), q.data_ptr(), total.data_ptr())
+            self.last_number, self._last_q, self.last_total = number, q, total
+            self.last_priority = q.view(torch.uint32)
+        else:
+            self._call("qttt_replay_sample", self.buffer.data_ptr(), self.capacity, n, self.seed, self.draw, _ptr(sym),
+                       random_symmetry, *[t.data_ptr() for t in out], index.data_ptr(), k.data_ptr())
         self.draw += 1
         self.last_index, self.last_symmetry = index, k
         return tuple(out)

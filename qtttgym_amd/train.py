@@ -5,6 +5,7 @@ gradients and the optimiser state all in the layout of the packed f32 weight blo
     net = PolicyValueNet(model)                          # what SelfPlay / TreeSearch / VecEnv.evaluate read
     trainer = Trainer(model, net=net)                    # an f32 net: trainer.weights IS net.blob
     L, J = trainer.step(*ring.sample(4096, "random"))    # six launches, no host synchronisation, no repack
+    L, J = trainer.step(*batch, weight=ring.weights(1.0))   # a prioritised ring's importance weights in the loss (§28)
     torch.save(trainer.state_dict(), "model.pt")
 
 Training is f32.  A bf16 `net` gets its blob rewritten from the new weights by the optimiser's own launch.
@@ -46,8 +47,10 @@ class Trainer(LibCaller):
         self.step_count = 0
         self._workspace = None
 
-    def gradients(self, s, pi, mask, v, done):
-        """Fills `grads` with d loss / d weights for the minibatch and returns (L, J) (qttt_train_gradients)."""
+    def gradients(self, s, pi, mask, v, done, weight=None):
+        """Fills `grads` with d loss / d weights for the minibatch and returns (L, J) (qttt_train_gradients).  weight
+        (f32[n], optional): importance weights, loss = mean(w L) + sum(w J over the non-terminal) / n_keep
+        (qttt_train_gradients_weighted, include/qttt_train_weighted.h); L and J come back unweighted either way."""
         n, dev = int(s.shape[0]) if s.dim() else 0, self.device
         if not 1 <= n <= _native.TRAIN_MAX_SAMPLES:
             raise ValueError("a minibatch has 1..%d samples" % _native.TRAIN_MAX_SAMPLES)
@@ -57,13 +60,19 @@ class Trainer(LibCaller):
         if self._workspace is None or self._workspace.numel() < need:
             self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
         L, J = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+        if weight is not None:
+            check_tensor(weight, torch.float32, (n,), dev, "weight")
+            self._call("qttt_train_gradients_weighted", s.data_ptr(), pi.data_ptr(), mask.data_ptr(), v.data_ptr(),
+                       done.data_ptr(), weight.data_ptr(), n, self.weights.data_ptr(), self.grads.data_ptr(), L.data_ptr(),
+                       J.data_ptr(), self._workspace.data_ptr())
+            return L, J
         self._call("qttt_train_gradients", s.data_ptr(), pi.data_ptr(), mask.data_ptr(), v.data_ptr(), done.data_ptr(), n,
                    self.weights.data_ptr(), self.grads.data_ptr(), L.data_ptr(), J.data_ptr(), self._workspace.data_ptr())
         return L, J
 
-    def step(self, s, pi, mask, v, done):
+    def step(self, s, pi, mask, v, done, weight=None):
         """gradients(...), then one AMSGrad step on `weights` (qttt_train_adam); returns (L, J) of the weights before it."""
-        out = self.gradients(s, pi, mask, v, done)
+        out = self.gradients(s, pi, mask, v, done, weight)
         self.step_count += 1
         bf16 = self.net.blob.data_ptr() if self.net is not None and self.net.dtype == torch.bfloat16 else 0
         self._call("qttt_train_adam", self.weights.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v2.data_ptr(),
