@@ -208,6 +208,58 @@ __device__ __forceinline__ u32 step_core(u32 &P0, u32 &P1, u32 &Q0, u32 &Q1, u32
     return step_line(P0, P1, lut);
 }
 
+//@isa table
+// ====================================================================== the resident ply's action table
+// The decode of the action's two bytes (step_prep's first half) has no input but the action, and is only ever right for
+// 72 of the 65 536 pairs: in the output-free step_fused_kernel it is ONE 16-byte LDS read, requested a ply ahead, from a
+// table of 256 entries indexed by the two low nibbles, entry = a_lo + 16 * b_lo.  An entry holds every action-derived
+// operand in the register form its consumer wants:
+//   x  lo        y  hi          the sorted squares, each a shift count as it stands; hi doubles as the validity mark
+//   z  x16       lo ^ hi at `last x`'s place
+//   w  pmS | ACTION_REJECT      the two squares at the classical mask's place (pm = w >> P1_CL_SHIFT), and the mask that
+//                               picks the two HIGH nibbles out of the action
+// Entries whose nibbles are not two distinct squares below 9 are all zero: hi == 0 is "illegal whatever the board is", and
+// the zero operands are harmless to the code that runs regardless (the slots of lo / hi).  An action with a bit in either
+// high nibble aliases some entry, a valid one perhaps: the ply rejects it itself (ResidentBoard::ply, the one compare).
+// The byte order does not matter: (a, b) and (b, a) hold the same lo, hi, x16 and pmS.
+// Like the line table it is COMPUTED by the workgroup (thread w makes entry w) in front of the same barrier, not loaded
+// (see fill_line_lut_nosync, qttt_state.h, on what a global load in front of the barrier costs).
+constexpr u32 ACTION_LUT_BYTES = 256u * 16u;
+constexpr u32 ACTION_REJECT = 0xF0F0u;                      // a's high nibble at bits 4..7, b's at 12..15
+static_assert(0xFFFFu < (1u << P1_CL_SHIFT), "the action stays below the classical mask's place");
+
+__device__ __forceinline__ u32x4 action_lut_entry(u32 w) {
+    const u32 a = w & 15u, b = (w >> 4) & 15u;
+    const u32 lo = min(a, b), hi = max(a, b);
+    const bool valid = hi < 9u && lo != hi;                 // board.py:10-18 as far as the board is not needed
+    const u32 pm = (1u << lo) | (1u << hi);
+    u32x4 e;
+    e.x = valid ? lo : 0u;
+    e.y = valid ? hi : 0u;
+    e.z = valid ? (a ^ b) << P1_LX_SHIFT : 0u;
+    e.w = valid ? (pm << P1_CL_SHIFT) | ACTION_REJECT : 0u;
+    return e;
+}
+template <int BLOCK>
+__device__ inline void fill_action_lut_nosync(uint8_t *atab) {
+    for (u32 w = threadIdx.x; w < ACTION_LUT_BYTES / 16u; w += BLOCK) reinterpret_cast<u32x4 *>(atab)[w] = action_lut_entry(w);
+}
+
+//@isa decode
+// The request: act = the action's two bytes in bits 0..15.  ((act << 4) | act) & 0xFF0 is 16 * (a_lo + 16 * b_lo) when
+// both high nibbles are zero, and some offset inside the table when not: nothing outside the 4 KB is ever addressed.
+// (v_lshl_or + v_and with a literal: as one v_bitop3 the mask travels in an SGPR, the slow class.  The empty asm on
+// either side of the read names memory so that the request stays where it is written: behind the reads requested before
+// it, and in the ply it is written in — left alone, the compiler merges the request in front of the loop with the one
+// inside it into one read at the top of the ply that consumes it.)
+__device__ __forceinline__ u32x4 action_lut_read(const uint8_t *atab, u32 act) {
+    u32 off = lshl_or<4>(act, act);
+    asm volatile("" : "+v"(off) : : "memory");
+    const u32x4 e = *reinterpret_cast<const u32x4 *>(atab + (off & (ACTION_LUT_BYTES - 16u)));
+    asm volatile("" ::: "memory");
+    return e;
+}
+
 //@isa other
 // ====================================================================== the resident ply
 // The ply of the output-free step_fused_kernel (qttt_step_kernels.h), which touches the packed words twice per launch and
@@ -217,6 +269,7 @@ __device__ __forceinline__ u32 step_core(u32 &P0, u32 &P1, u32 &Q0, u32 &Q1, u32
 //          extract in front of the 64-bit shifts, no mask in front of the line test, no clear-and-merge of P1 behind the move
 //   P1     square 8's nibble, n and `last x` only (bits 20,21 pass through); the other fields are zero
 //   wx, wo the last ply's two lookups: the reward is formed from them once, behind the loop
+// The action arrives decoded: an entry of the action table above, requested by the ply before (by the kernel for the first).
 // The walk and the rooting rule are step_core's own functions.  The slots, the qstructs and the lookups are written out again,
 // operand for operand: as shared pieces (tried) they reorder the instruction streams of every other kernel that steps.
 // What each part is worth is listed above the kernel.
@@ -241,8 +294,11 @@ struct ResidentBoard {
         win = wx | wo;
     }
 
-    // act: the action's two bytes in bits 0..15 (the bits above are not looked at)
-    __device__ __forceinline__ void ply(u32 act, u32 bit, const uint8_t *lut) {
+    // e: this ply's entry of the action table (action_lut_read, above), replaced by the next ply's; act, act_next: the two
+    // plies' actions, two bytes in bits 0..15 and zero above.  The next entry is requested BEHIND the line test's two
+    // lookups — LDS answers in order, so they do not wait for it (a counted wait) — and into the registers this ply has
+    // finished with; it is looked at first in the next ply's decode.
+    __device__ __forceinline__ void ply(u32x4 &e, u32 act, u32 act_next, u32 bit, const uint8_t *lut, const uint8_t *atab) {
 //@isa reset
         if (AUTO_RESET) {                                   // finished boards restart: empty = all zero
             u32 g = gone;
@@ -256,19 +312,14 @@ struct ResidentBoard {
         }
 //@isa decode
         StepPrep s;
-        // SDWA reads the two bytes where they lie; x lands at `last x`'s place in the same instruction
-        asm("v_min_u32_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_1" : "=v"(s.lo) : "v"(act));
-        asm("v_max_u32_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_1" : "=v"(s.hi) : "v"(act));
-        asm("v_xor_b32_sdwa %0, %1, %1 dst_sel:WORD_1 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_1" : "=v"(s.x16) : "v"(act));
-        // the two squares as a mask at the classical mask's place (only looked at when hi < 9)
-        const u32 cl_bit0 = 1u << P1_CL_SHIFT;
-        u32 pmS;
-        asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(pmS) : "v"(cl_bit0), "v"(s.lo), "v"(cl_bit0 << (s.hi & 31u)));
-        const u32 z = CL & pmS;
-        s.pm = pmS >> P1_CL_SHIFT;
-        // board.py:10-15.  With hi < 9, x16 is 0 (lo == hi) or lies in [1 << 16, 0xF0000], and z is 0 or at least 1 << 22 (one
-        // of the squares is classical): ONE compare answers "lo != hi and neither square is classical"
-        s.legal = s.hi < 9u && s.x16 > z;
+        s.lo = e.x, s.hi = e.y, s.x16 = e.z;
+        // CL holds bits 22..30 only and act bits 0..15 only, so ONE or-and against e.w gives: the classical squares among the
+        // move's two (0 or at least 1 << 22) | the action's high nibbles (0 or at least 1 << 4)
+        const u32 z = BITOP3(CL, act, e.w, (A | B) & C);
+        s.pm = e.w >> P1_CL_SHIFT;
+        // board.py:10-15.  hi is 1..8 in an entry of two distinct squares below 9 and 0 in every other: ONE compare answers
+        // "two distinct squares, both bytes below 16 (so below 9), neither square classical"
+        s.legal = s.hi > z;
 //@isa comps
         s.n6 = P1 >> (P1_N_SHIFT - 2u);
         s.comps = (u64)Q1 | ((u64)H << 32);
@@ -316,6 +367,9 @@ struct ResidentBoard {
         const u32 X4 = pc >= 8u ? (O4 ^ 0x7FCu) : (cl4 & even4);
         wx = *reinterpret_cast<const u32 *>(lut + X4);
         wo = *reinterpret_cast<const u32 *>(lut + O4);
+//@isa decode
+        e = action_lut_read(atab, act_next);
+//@isa line
         // env.py:51 as in step_line: bit 3 of (win | pc), spread over the lane's word by the sign-extending extract
         u32 nw = (u32)__builtin_amdgcn_sbfe(BITOP3(wx, wo, pc, A | B | C), 3u, 1u);
         asm("" : "+v"(nw));

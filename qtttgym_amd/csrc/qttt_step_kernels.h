@@ -339,6 +339,31 @@ constexpr int FUSED_PREFETCH = 2;
 //            pays a v_alignbit to rotate them; by the model +0.7 ns, not run
 //   dropped  the slots / qstructs / lookups as pieces shared with step_core: the other kernels' instruction streams reorder
 //   not tried: the walk's cost per node, the classical mask "times four" (the one compare above needs it above x16)
+// The decode — the action table (qttt_step_core.h, action_lut_entry): lo, hi, x16 and the two-square mask of ply t + 1 come
+// from ONE ds_read_b128, requested by ply t behind its line test's two lookups (they are waited for before it is issued: their
+// wait is what it was) and looked at first in ply t + 1's decode.  What is left per ply: the index (v_lshl_or, v_and), z (one
+// v_bitop3 that meets the action's high nibbles as well), the one compare, pm's shift.  isa_budget, the loop: decode 9.0 -> 5.0
+// VALU = 14.3 -> 6.6 ns, in all 113.8 -> 108.8 VALU = 157.6 -> 148.9 ns per wave-ply (the v_and 0xffff of the action's zero
+// extension went too); SQ_INSTS_VALU per board-ply 116.76 -> 111.80; LDS 2 -> 6 KB, still 8 waves per SIMD.  Predicted
+// 8.7 ns x 16 waves = 0.14 us per step.  Measured (profiles/resident_decode/), bench.py, parent / this tree alternately, five runs
+// each, two sessions: K = 1000 medians 2.886 -> 2.787 and 2.911 -> 2.815 us, every run of this tree below every run of the
+// parent in both; the gain, 0.100 and 0.096, is 2.4 x and 3.4 x the parent's max - min of its session (0.042, 0.029): the margin
+// of three spreads is met in the second session and missed in the first, whose parent runs scatter further than in any session
+// before (0.013 - 0.026).  K = 20: 3.776 -> 3.720 and 3.776 -> 3.730 (the parent's max - min 0.12, 0.14).  tools/stepbench interleaved,
+// median (min): 2.95 (2.92) -> 2.88 (2.83) at K = 1000, 3.31 (3.24) -> 3.22 (3.14) at K = 20.  0.020 us per VALU taken out,
+// the low end of the model's 0.016 - 0.028: the wait for the entry at the top of the ply is a wait for the key's scalar load
+// too (scalar loads answer out of order, so the count is 0), seven instructions behind its request where it had a whole ply.
+//   kept     the entry's four words as they are consumed: lo and hi clean (the rooting rule multiplies them by four), hi as the
+//            validity mark (0 in an entry that is not two distinct squares below 9), pmS | 0xF0F0 as one or-and operand
+//   dropped  the entry requested at the top of ply t (a whole ply ahead): it is live beside ply t's own, two v_mov_b64 per ply
+//            hand it over (by the model + 3.5 ns), and left to itself the compiler merges the two requests into one read at
+//            the top of the ply that consumes it; not run
+//   dropped  the index as one v_bitop3 with the mask 0xFF0: the mask travels in an SGPR (slow class), + 0.7 ns; not run
+//   dropped  the key's scalar load requested behind the ply: its destination is a register the loop's head writes, so the wait
+//            moves to the loop's first instruction, in front of the action's load; not run
+//   LDS      the pipe serves 3 instead of 2 reads per wave-ply; the read's latency and its bank conflicts (64 lanes, 72 live
+//            entries of 16 bytes) were not counted on their own: what shows is the whole, 740 - 744 -> 727 - 728 us per dispatch
+//            of 256 plies under the profiler, two thirds of the model's gain
 constexpr int RESIDENT_MAX_PLIES = 256;
 constexpr int RESIDENT_BLOCK = QTTT_BLOCK;
 template <int CAP>
@@ -350,12 +375,15 @@ __global__ __launch_bounds__(BLOCK) void step_fused_kernel(
     u32 *__restrict__ reward_bits, uint8_t *__restrict__ terminated, int64_t n, int32_t n_steps) {
     static_assert(OUT == FUSED_OUT_LAST || OUT == FUSED_OUT_NONE, "every ply's outputs: the kernel above");
     static_assert(sizeof(ResidentKeys<CAP>) + 64 + 256 <= 4096, "4 KB of kernel arguments, the hidden ones included");
+    static_assert(FUSED_PREFETCH >= 2, "the entry of ply t + 1 is requested from act[1] while ply t runs");
     __shared__ __attribute__((aligned(16))) uint8_t lut[LINE_LUT_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t atab[ACTION_LUT_BYTES];
     const int64_t ib = (int64_t)blockIdx.x * BLOCK;                 // first board of the workgroup (block-uniform)
     const int64_t i = ib + threadIdx.x;
     const int64_t il = i < n ? i : 0;                               // idle lanes re-read board 0, store nothing
-    const u64 P = load_stream(&pP[il]), Q = load_stream(&pQ[il]);   // requested before the table fills
-    fill_line_lut<BLOCK>(lut);
+    const u64 P = load_stream(&pP[il]), Q = load_stream(&pQ[il]);   // requested before the tables fill
+    fill_action_lut_nosync<BLOCK>(atab);
+    fill_line_lut<BLOCK>(lut);                                      // ends with the workgroup barrier
     if (i >= n) return;
     u32 P0 = (u32)P, P1 = (u32)(P >> 32), Q0 = (u32)Q, Q1 = (u32)(Q >> 32);
     const u32 id = (id_base + (u32)i) ^ id_hi_fold;
@@ -366,7 +394,8 @@ __global__ __launch_bounds__(BLOCK) void step_fused_kernel(
     u32 win = 0;
     u64 key = keys.k[0];
     // the actions (and bits) of plies 0 .. FUSED_PREFETCH - 1 are in flight before the first step; a ply past the
-    // launch's last re-reads the last one's (the base stops advancing), so every address stays inside the run
+    // launch's last re-reads the last one's (the base stops advancing), so every address stays inside the run — and so
+    // does every action an entry of the action table is requested for
     u32 act[FUSED_PREFETCH], bit_in[FUSED_PREFETCH];
 #pragma unroll
     for (int k = 0; k < FUSED_PREFETCH; ++k) {
@@ -380,6 +409,8 @@ __global__ __launch_bounds__(BLOCK) void step_fused_kernel(
     }
     ResidentBoard<AUTO_RESET> board;
     board.unpack(P0, P1, Q0, Q1);                                   // (consumes the state in front of the loop)
+    // the decoded action travels a ply ahead of the board: ply 0's entry is requested here, ply t + 1's while ply t runs
+    u32x4 entry = action_lut_read(atab, act[0]);
     for (int32_t t = 0; t < n_steps; ++t) {
         // one scalar load, requested a ply ahead; the index wraps at CAP (a mask where CAP is a power of two)
         const u64 key_next = keys.k[(CAP & (CAP - 1)) == 0 ? (t + 1) & (CAP - 1) : t + 1 < CAP ? t + 1 : 0];
@@ -388,7 +419,7 @@ __global__ __launch_bounds__(BLOCK) void step_fused_kernel(
         if (HAS_BITS) b_blk += more ? n : 0;
         const u32 act_far = load_stream(&a_blk[lane]), bit_far = HAS_BITS ? (u32)load_stream(&b_blk[lane]) : 0u;
         const u32 bit = HAS_BITS ? (bit_in[0] & 1u) : collapse_bit_of(id ^ (u32)key);
-        board.ply(act[0], bit, lut);
+        board.ply(entry, act[0], act[1], bit, lut, atab);
         key = key_next;
 #pragma unroll
         for (int k = 0; k + 1 < FUSED_PREFETCH; ++k) {
