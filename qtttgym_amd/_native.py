@@ -237,6 +237,13 @@ REPLAY_PRIORITY_SIGNATURES = {
 TRAIN_WEIGHTED_SIGNATURES = {
     "qttt_train_gradients_weighted": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# every symbol include/qttt_selfplay_value.h declares (search-value targets for self-play: the roots' searched value and the
+# value targets made of it; qttt.h includes it)
+VALUE_MIX, VALUE_TD = 0, 1
+SELFPLAY_VALUE_SIGNATURES = {
+    "qttt_selfplay_record_value": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "qttt_selfplay_value_targets": (_i32, [_i64, _i32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
 
 _lib = None
 
@@ -308,7 +315,8 @@ def lib():
                                   + list(SELFPLAY_STREAM_SIGNATURES.items()) + list(SOLVE_SIGNATURES.items())
                                   + list(TREE_EXACT_SIGNATURES.items()) + list(SELFPLAY_EXACT_SIGNATURES.items())
                                   + list(TREE_PROVE_SIGNATURES.items()) + list(REPLAY_REANALYSE_SIGNATURES.items())
-                                  + list(REPLAY_PRIORITY_SIGNATURES.items()) + list(TRAIN_WEIGHTED_SIGNATURES.items())):
+                                  + list(REPLAY_PRIORITY_SIGNATURES.items()) + list(TRAIN_WEIGHTED_SIGNATURES.items())
+                                  + list(SELFPLAY_VALUE_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

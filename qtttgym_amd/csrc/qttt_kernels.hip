@@ -68,7 +68,9 @@
 // qttt_tree_exact_kernels.h (exact leaves in the search trees: a lane per path record, the solver's recursion for the leaves
 // that need it); qttt_selfplay_exact_kernels.h (exact targets for the late rows of a self-play batch: a lane per staging row,
 // the same recursion, every action's value kept for the policy); qttt_tree_prove_kernels.h (proven interior nodes: a round's
-// records walked upwards, a wave per game, integers only, and the roots' exact q).  Host only: qttt_launch.h (launch shape, kernel selection,
+// records walked upwards, a wave per game, integers only, and the roots' exact q);
+// qttt_selfplay_value_kernels.h (search-value targets: the roots' searched value, a wave per game, and the value targets made
+// of it, a lane per game) with qttt_selfplay_value_host.h (free of HIP: the argument checks and one game's row arithmetic).  Host only: qttt_launch.h (launch shape, kernel selection,
 // the one launch form, the argument checks), qttt_mailbox.h (the host half of the single-record mailbox); this file: the
 // step's launch logic + the C ABI.
 #include <atomic>
@@ -95,6 +97,7 @@
 #include "qttt_tree_exact_kernels.h"
 #include "qttt_selfplay_exact_kernels.h"
 #include "qttt_tree_prove_kernels.h"
+#include "qttt_selfplay_value_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -1411,6 +1414,25 @@ int qttt_replay_sample_prioritized(const void *replay, const void *prio, int64_t
                       n, key_slot, key_sym, sym, (u32)(random_symmetry != 0), s_out, reinterpret_cast<u64 *>(pi_out), mask_out,
                       reinterpret_cast<u32 *>(v_out), done_out, index_out, sym_out, number_out, q_out, reinterpret_cast<u64 *>(total_out));
     }, sym != nullptr || random_symmetry != 0);
+}
+
+// ---------------------------------------------------------------- search-value targets for self-play (include/qttt_selfplay_value.h)
+int qttt_selfplay_record_value(const void *tree, int64_t games, int64_t capacity, int ply, const uint8_t *length, float *q,
+                               const float *v, void *stream) {
+    bool work;
+    if (const int rc = value_record_check(tree, games, capacity, ply, length, q, v, work)) return rc;
+    if (!work) return 0;
+    return launch(selfplay_record_value_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  ply, length, q, v);
+}
+
+int qttt_selfplay_value_targets(int64_t games, int mode, double lambda, const uint8_t *rows, const uint8_t *length,
+                                const uint8_t *done, const uint8_t *exact, const float *q, float *v, void *stream) {
+    bool work;
+    if (const int rc = value_targets_check(games, mode, lambda, length, done, q, v, work)) return rc;
+    if (!work) return 0;
+    return launch(selfplay_value_targets_kernel, ceil_div(games, VALUE_TARGETS_BLOCK), VALUE_TARGETS_BLOCK, stream, games, mode,
+                  lambda, rows, length, done, exact, q, v);
 }
 
 }  // extern "C"

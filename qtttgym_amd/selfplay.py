@@ -14,6 +14,8 @@ board's eight symmetries, which the reference left as a stub (self_play.py expan
 continuous self-play (include/qttt_selfplay_stream.h): the G slots stay full, a finished game hands its rows
 to a ReplayBuffer and restarts in place.  exact_targets=M replaces the value and policy targets of the positions with at
 least M moves played by the truth, enumerated on the device (include/qttt_selfplay_exact.h).
+value_mix=L / td_lambda=L make the value targets of fresh samples out of the searched value of every recorded root instead
+of the game's outcome alone (include/qttt_selfplay_value.h).
 """
 import ctypes
 
@@ -33,7 +35,10 @@ class SelfPlayBatch:
     `length` are zero): states u8[10, qttt_state_bytes(G)], pi f64[10, G, 36], mask u8[10, G, 36], done u8[10, G],
     v f32[10, G], action36 u8[10, G] (the move played from the row, 255 in the terminal row), length u8[G] (rows of
     the game, its terminal row included), winner i8[G] (1 / 0 / -1 = True / False / None) and actions u8[G, 2], the
-    last ply's move."""
+    last ply's move.
+    q f32[10, G], the searched value of every recorded root (include/qttt_selfplay_value.h), is there only when
+    SelfPlay(value_mix= / td_lambda=) or alloc_q() asked for it; it is no part of _ROWS, _FIELDS or flat(), and an
+    augmented batch has no q."""
 
     _ROWS = {"pi": (torch.float64, (36,)), "mask": (torch.uint8, (36,)), "done": (torch.uint8, ()),
              "v": (torch.float32, ()), "action36": (torch.uint8, ())}
@@ -94,6 +99,45 @@ class SelfPlayBatch:
                 _raw_stream(self.device.index))
         _native.check(rc, "qttt_selfplay_exact_targets")
 
+    VALUE_MODES = {"mix": _native.VALUE_MIX, "td": _native.VALUE_TD}
+
+    def alloc_q(self):
+        """Gives the batch its q f32[10, G] row field, zero-filled (once); returns it."""
+        if getattr(self, "q", None) is None:
+            self.q = torch.zeros((ROWS, self.num_games), dtype=torch.float32, device=self.device)
+        return self.q
+
+    @staticmethod
+    def check_lambda(lam, what):
+        if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0.0 <= float(lam) <= 1.0:
+            raise ValueError("%s must be a number in [0, 1]" % what)
+        return float(lam)
+
+    def value_targets(self, mode, lam, rows=None, exact=None):
+        """Rewrites v in place from the searched values q (include/qttt_selfplay_value.h qttt_selfplay_value_targets, one
+        launch, no host synchronisation).  mode "mix": v = (1 - lam) v + lam q on every recorded, non-terminal row,
+        Reanalyser's rule; mode "td": the TD(lam) return of the rest of the game, backwards from the last row, negated from
+        row to row (lam = 1 is the outcome, bit for bit; lam = 0 the one-step target).  rows (u8[G], optional) stands in
+        for `length`, as in exact_targets; exact (u8[10, G], optional: exact_targets' result) marks rows that keep their v
+        and, under "td", restart the recursion from it.  Needs q: a batch recorded with SelfPlay(value_mix= / td_lambda=),
+        or alloc_q() and SelfPlay.record_value."""
+        if mode not in self.VALUE_MODES:
+            raise ValueError('mode must be "mix" or "td"')
+        lam = self.check_lambda(lam, "lam")
+        G, dev = self.num_games, self.device
+        if getattr(self, "q", None) is None:
+            raise ValueError("the batch has no q: record it with SelfPlay(value_mix= / td_lambda=) or alloc_q()")
+        check_tensor(self.q, torch.float32, (ROWS, G), dev, "q")
+        if rows is not None:
+            check_tensor(rows, torch.uint8, (G,), dev, "rows")
+        if exact is not None:
+            check_tensor(exact, torch.uint8, (ROWS, G), dev, "exact")
+        with torch.cuda.device(dev):
+            rc = _native.lib().qttt_selfplay_value_targets(
+                G, self.VALUE_MODES[mode], lam, _ptr(rows), self.length.data_ptr(), self.done.data_ptr(), _ptr(exact),
+                self.q.data_ptr(), self.v.data_ptr(), _raw_stream(dev.index))
+        _native.check(rc, "qttt_selfplay_value_targets")
+
     def flat(self):
         """The reference's batch, game-major and in the order self_play.py:200-216 appends: s f32[n, 18, 10]
         (GameState.to_vector, by encode()), pi f64[n, 36], mask bool[n, 36], v f32[n], done bool[n], with
@@ -138,13 +182,25 @@ class SelfPlay(LibCaller):
     value_targets=(1.0, -1.0): the exact value is the mover's, in [-1, 1], and the reference's (1, 0) is not zero-sum.
     Cost: from M = 7 the launch is cheaper than VecEnv.solve per row and adds under a tenth to a stream
     ply; at M = 6 it is several times dearer than that composition and a stream ply takes about four times as long.
-    With the default None play() and stream() issue the calls they always did, and batch.exact is absent."""
+    With the default None play() and stream() issue the calls they always did, and batch.exact is absent.
+    value_mix=L or td_lambda=L (L in [0, 1]; at most one of the two; with or without a net: W and N exist for MCTS too)
+    makes the value targets out of the search (include/qttt_selfplay_value.h).  Every searched ply then adds
+    one launch BEFORE its record, record_value: the root's searched value sum W / sum N, the mover's, goes to row
+    length[g] of batch.q.  value_mix: v = (1 - L) v + L q on every non-terminal row, Reanalyser's rule for fresh samples.
+    td_lambda: v = the TD(L) return of the rest of the game, a backward pass that alternates the sign from row to row;
+    L = 1 is the outcome, L = 0 the one-step target.  play() runs exact_targets (if set) and after it
+    SelfPlayBatch.value_targets(..., exact=batch.exact), following its last ply: the exact rows keep their value and the
+    rows before them are bootstrapped through it.  stream() runs the two in that order between the harvest and the ring's
+    append, with rows = the harvested lengths.  No host synchronisation on either route.  Both need
+    value_targets=(1.0, -1.0), as Reanalyser's value_mix does.  With both None play() and stream() issue the calls they
+    always did, and batch.q is absent."""
 
     def __init__(self, num_games, n_rollouts=100, num_simulations=10, net=None, alpha=1.0, c_puct=1.0,
                  value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts",
                  root_noise=None, temperature=1.0, sample_plies=0, leaves=1, virtual_loss=1.0,
                  eval_symmetries=None, root_policy="puct", max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None,
-                 exact_targets=None, exact_policy=True, prove=False):
+                 exact_targets=None, exact_policy=True, prove=False, value_mix=None, td_lambda=None):
+        self.value_mode, self.value_lambda = self.check_value_args(value_mix, td_lambda, value_targets)
         self.exact_targets = self.check_exact_targets(exact_targets, value_targets)
         self.exact_policy = bool(exact_policy)
         self.exact_from = TreeSearch.check_exact_from(leaf_eval, net, exact_from)
@@ -219,9 +275,42 @@ class SelfPlay(LibCaller):
                              "than the rest of the batch")
         return m
 
+    @staticmethod
+    def check_value_args(value_mix, td_lambda, value_targets):
+        """The constructor's check of value_mix and td_lambda: (None, None), or ("mix" | "td", lambda)."""
+        if value_mix is None and td_lambda is None:
+            return None, None
+        if value_mix is not None and td_lambda is not None:
+            raise ValueError("at most one of value_mix and td_lambda may be given")
+        what, mode, lam = ("value_mix", "mix", value_mix) if td_lambda is None else ("td_lambda", "td", td_lambda)
+        lam = SelfPlayBatch.check_lambda(lam, what)
+        if tuple(float(x) for x in value_targets) != (1.0, -1.0):
+            raise ValueError("%s needs value_targets=(1.0, -1.0): the searched value is the mover's, in [-1, 1], "
+                             "and the reference's (1, 0) is not zero-sum, so the mixed v would be on two scales" % what)
+        return mode, lam
+
     def new_batch(self):
-        """A zero-filled SelfPlayBatch for num_games games."""
-        return SelfPlayBatch(self.num_games, self.device, self._lib.qttt_state_bytes(self.num_games))
+        """A zero-filled SelfPlayBatch for num_games games; with value_mix or td_lambda it has the q rows."""
+        batch = SelfPlayBatch(self.num_games, self.device, self._lib.qttt_state_bytes(self.num_games))
+        if self.value_mode is not None:
+            batch.alloc_q()
+        return batch
+
+    def record_value(self, tree, ply, batch):
+        """One qttt_selfplay_record_value, BEFORE the ply's record(): the searched value of every root that record is about
+        to write goes to row `ply` of batch.q (ply=None: the stream form, row length[g]); a root without a visit gets the
+        row's v."""
+        G, dev = self.num_games, self.device
+        if tree.num_games != G or tree.device != dev or batch.num_games != G:
+            raise ValueError("tree and batch must hold %d games on %s" % (G, dev))
+        if getattr(batch, "q", None) is None:
+            raise ValueError("the batch has no q: alloc_q() first")
+        check_tensor(batch.q, torch.float32, (ROWS, G), dev, "batch.q")
+        check_tensor(batch.v, torch.float32, (ROWS, G), dev, "batch.v")
+        check_tensor(batch.length, torch.uint8, (G,), dev, "batch.length")
+        self._call("qttt_selfplay_record_value", tree.tree.data_ptr(), G, tree.capacity, -1 if ply is None else int(ply),
+                   batch.length.data_ptr(), batch.q.data_ptr(), batch.v.data_ptr())
+        return batch.q
 
     def record(self, tree, ply, batch, draw_index=None):
         """One qttt_selfplay_record: the roots of `tree` become row `ply` of `batch`; returns batch.actions, the move
@@ -327,12 +416,16 @@ class SelfPlay(LibCaller):
         for ply in range(ROWS):
             if ply < ROWS - 1:                  # at ply 9 every game is over: nine moves fill the board
                 self._search(tree)
+                if self.value_mode is not None:
+                    self.record_value(tree, ply, batch)
             env.step_raw(self.record(tree, ply, batch, draw_index=p + ply if p else None))
             tree.sync(env)
             if self.compact:
                 tree.compact()
         if self.exact_targets is not None:
             batch.exact = batch.exact_targets(self.exact_targets, self.exact_policy)
+        if self.value_mode is not None:
+            batch.value_targets(self.value_mode, self.value_lambda, exact=getattr(batch, "exact", None))
         return batch
 
     # ------------------------------------------------------------------ continuous self-play
@@ -398,13 +491,22 @@ class SelfPlay(LibCaller):
             # behind it, and a restart gives the slot's nodes back, so no slot holds more than this before its search
             tree._bound = 1 + (ROWS - 2) * (2 * R + 1)
         self._search(tree)
+        if self.value_mode is not None:
+            self.record_value(tree, None, batch)
         env.step_raw(self.record(tree, None, batch, draw_index=st["ply"]))
         tree.sync(env)
         if self.compact:
             tree.compact()
         self._stream_harvest(st)
+        exact = None
         if self.exact_targets is not None:          # only the games this ply hands to the ring, once each
-            batch._exact_targets(self.exact_targets, self.exact_policy, st["harvest_len"], None)
+            if self.value_mode is not None:         # the value targets need to know which rows hold the truth
+                exact = st.get("exact")
+                if exact is None:
+                    exact = st["exact"] = torch.empty((ROWS, self.num_games), dtype=torch.uint8, device=self.device)
+            batch._exact_targets(self.exact_targets, self.exact_policy, st["harvest_len"], exact)
+        if self.value_mode is not None:
+            batch.value_targets(self.value_mode, self.value_lambda, rows=st["harvest_len"], exact=exact)
         ring.add(batch, length=st["harvest_len"])
         self._stream_restart(st)
         st["ply"] += 1
