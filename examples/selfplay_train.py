@@ -158,6 +158,12 @@ def main():
                     help="Dirichlet(ALPHA) noise with weight EPS on the roots' priors before every searched move")
     ap.add_argument("--temperature", type=float, default=1.0, help="the sampled moves follow N ** (1 / temperature)")
     ap.add_argument("--sample-plies", type=int, default=0, help="plies whose move is drawn from the visit counts")
+    ap.add_argument("--forced-playouts", type=float, default=None, metavar="K",
+                    help="forced playouts at the PUCT root and pruned policy targets (SelfPlay(forced_playouts=K), "
+                         "include/qttt_tree_forced.h; KataGo uses 2; needs --leaf-eval value): what makes --root-noise "
+                         "work at small --rollouts")
+    ap.add_argument("--no-prune-targets", action="store_true",
+                    help="with --forced-playouts: force only, record the unpruned visit counts (SelfPlay(prune_targets=False))")
     ap.add_argument("--root-policy", choices=("puct", "gumbel"), default="puct",
                     help="gumbel: the Gumbel root, sequential halving over --max-considered actions; pi is then the "
                          "improved policy and the move the best survivor (needs --leaf-eval value; --rollouts of 16-32 do)")
@@ -220,6 +226,8 @@ def main():
         model.load_state_dict(torch.load(args.model, map_location=dev))
     optim = torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-3, amsgrad=True)      # nn.py:27
     net = PolicyValueNet(model, device=dev, dtype=torch.float32 if args.dtype == "f32" else torch.bfloat16)
+    if args.no_prune_targets and args.forced_playouts is None:
+        ap.error("--no-prune-targets needs --forced-playouts")
     if args.exact_value_only and args.exact_targets is None:
         ap.error("--exact-value-only needs --exact-targets")
     zero_sum = args.exact_targets is not None or args.value_mix is not None or args.td_lambda is not None
@@ -231,7 +239,8 @@ def main():
                   eval_symmetries=parse_eval_symmetries(args.eval_symmetries), root_policy=args.root_policy,
                   max_considered=args.max_considered, exact_from=args.exact_from, prove=args.prove,
                   exact_targets=args.exact_targets, exact_policy=not args.exact_value_only,
-                  value_mix=args.value_mix, td_lambda=args.td_lambda)
+                  value_mix=args.value_mix, td_lambda=args.td_lambda, forced_playouts=args.forced_playouts,
+                  prune_targets=None if args.forced_playouts is None else not args.no_prune_targets)
     ring = ReplayBuffer(args.replay, device=dev, seed=args.seed, prioritized=args.prioritized is not None) if args.replay else None
     reanalyser = Reanalyser(sp, ring, args.reanalyse, value_mix=args.reanalyse_value_mix, seed=args.seed) if args.reanalyse else None
     trainer = Trainer(model, device=dev, net=net) if args.device_train else None      # nn.py:27's defaults

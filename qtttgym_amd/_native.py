@@ -244,6 +244,14 @@ SELFPLAY_VALUE_SIGNATURES = {
     "qttt_selfplay_record_value": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
     "qttt_selfplay_value_targets": (_i32, [_i64, _i32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# every symbol include/qttt_tree_forced.h declares (forced playouts at the root and policy target pruning; qttt.h includes it)
+TREE_FORCED_SIGNATURES = {
+    "qttt_tree_select_batch_forced": (_i32, TREE_LEAVES_SIGNATURES["qttt_tree_select_batch"][1][:-1] + [_f64, _vp]),
+    "qttt_tree_root_forced": (_i32, [_vp, _i64, _i64, _f64, _f64, _vp, _vp, _vp]),
+    "qttt_selfplay_record_pruned": (_i32, TREE_EXPLORE_SIGNATURES["qttt_selfplay_record_sampled"][1][:-1] + [_f64, _f64, _vp]),
+    "qttt_selfplay_record_stream_pruned": (_i32, SELFPLAY_STREAM_SIGNATURES["qttt_selfplay_record_stream_sampled"][1][:-1]
+                                           + [_f64, _f64, _vp]),
+}
 
 _lib = None
 
@@ -316,7 +324,7 @@ def lib():
                                   + list(TREE_EXACT_SIGNATURES.items()) + list(SELFPLAY_EXACT_SIGNATURES.items())
                                   + list(TREE_PROVE_SIGNATURES.items()) + list(REPLAY_REANALYSE_SIGNATURES.items())
                                   + list(REPLAY_PRIORITY_SIGNATURES.items()) + list(TRAIN_WEIGHTED_SIGNATURES.items())
-                                  + list(SELFPLAY_VALUE_SIGNATURES.items())):
+                                  + list(SELFPLAY_VALUE_SIGNATURES.items()) + list(TREE_FORCED_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

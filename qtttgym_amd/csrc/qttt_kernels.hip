@@ -56,6 +56,8 @@
 // qttt_tree_leaves_kernels.h (leaf-parallel rounds: K descents per game under virtual loss, and their backup);
 // qttt_tree_explore_kernels.h (root exploration: Dirichlet noise on the roots' priors, the sampled move);
 // qttt_tree_gumbel_kernels.h (the Gumbel root: considered actions, sequential halving, the improved policy);
+// qttt_tree_forced_kernels.h (forced playouts at the root and policy target pruning: the root rule, the pruned record's counts)
+// with qttt_tree_forced_host.h (free of HIP: the argument checks and one action's arithmetic);
 // qttt_replay_kernels.h (the replay ring: the append's scan and move, the sampled minibatch, and reanalysis: the gathered
 // window and the guarded update) with qttt_replay_host.h (host only and free of HIP: the ring's layout, the scan plan, the
 // window and holder arithmetic, the argument checks);
@@ -89,6 +91,7 @@
 #include "qttt_tree_value_kernels.h"
 #include "qttt_tree_leaves_kernels.h"
 #include "qttt_tree_gumbel_kernels.h"
+#include "qttt_tree_forced_kernels.h"
 #include "qttt_replay_kernels.h"
 #include "qttt_train_kernels.h"
 #include "qttt_replay_priority_kernels.h"
@@ -1021,6 +1024,62 @@ int qttt_selfplay_record_gumbel(const void *tree, int64_t games, int64_t capacit
     const SelfPlaySampling<RECORD_GUMBEL> s = {static_cast<const GumbelRec *>(rec), c_visit, c_scale};
     return launch(selfplay_record_kernel<RECORD_GUMBEL>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
                   capacity, ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
+}
+
+// ---------------------------------------------------------------- forced playouts and pruned targets (include/qttt_tree_forced.h)
+int qttt_tree_select_batch_forced(void *tree, int64_t games, int64_t capacity, uint64_t seed, uint32_t rollout_idx0,
+                                  int leaves, int64_t board_offset, double c_puct, double virtual_loss, void *paths,
+                                  void *leaf_state, double forced_k, void *stream) {
+    bool work;
+    const int rc = forced_select_check(tree, games, capacity, rollout_idx0, leaves, board_offset, virtual_loss, paths, leaf_state,
+                                       forced_k, work);
+    if (rc || !work) return rc;
+    const Planes l = planes(leaf_state, games * leaves);
+    return launch(tree_select_batch_forced_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (u64)seed, rollout_idx0, (u32)leaves, (u64)board_offset, c_puct, virtual_loss, static_cast<TreePathRec *>(paths),
+                  l.P, l.Q, forced_k);
+}
+
+int qttt_tree_root_forced(const void *tree, int64_t games, int64_t capacity, double forced_k, double c_puct,
+                          uint8_t *forced, int32_t *n_pruned, void *stream) {
+    bool work;
+    const int rc = forced_root_check(tree, games, capacity, forced_k, c_puct, n_pruned, work);
+    if (rc || !work) return rc;
+    return launch(tree_root_forced_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  forced_k, c_puct, forced, n_pruned);
+}
+
+int qttt_selfplay_record_pruned(const void *tree, int64_t games, int64_t capacity, int ply, uint32_t n_rollouts,
+                                double alpha, double v_first, double v_second, void *states, double *pi, uint8_t *mask,
+                                uint8_t *done, float *v, uint8_t *action36, uint8_t *length, int8_t *winner,
+                                uint8_t *actions, uint64_t seed, int64_t board_offset, double temperature,
+                                int sample_plies, double forced_k, double c_puct, void *stream) {
+    bool work;
+    const ForcedRecordArgs p = {tree, states, pi, mask, done, v, action36, length, winner, actions};
+    const int rc = forced_record_check(p, games, capacity, false, ply, 0u, n_rollouts, alpha, v_first, v_second, board_offset,
+                                       temperature, sample_plies, forced_k, c_puct, work);
+    if (rc || !work) return rc;
+    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    const SelfPlaySampling<RECORD_PRUNED> s = {(u64)seed, (u64)board_offset, temperature, sample_plies, forced_k, c_puct};
+    return launch(selfplay_record_kernel<RECORD_PRUNED>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
+                  capacity, ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
+}
+
+int qttt_selfplay_record_stream_pruned(const void *tree, int64_t games, int64_t capacity, uint32_t n_rollouts, double alpha,
+                                       double v_first, double v_second, void *states, double *pi, uint8_t *mask,
+                                       uint8_t *done, float *v, uint8_t *action36, uint8_t *length, int8_t *winner,
+                                       uint8_t *actions, uint64_t seed, int64_t board_offset, double temperature,
+                                       int sample_plies, uint32_t draw_index, double forced_k, double c_puct, void *stream) {
+    bool work;
+    const ForcedRecordArgs p = {tree, states, pi, mask, done, v, action36, length, winner, actions};
+    const int rc = forced_record_check(p, games, capacity, true, 0, draw_index, n_rollouts, alpha, v_first, v_second, board_offset,
+                                       temperature, sample_plies, forced_k, c_puct, work);
+    if (rc || !work) return rc;
+    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    const SelfPlaySampling<RECORD_PRUNED> s = {(u64)seed, (u64)board_offset, temperature, sample_plies, forced_k, c_puct};
+    // (the stream kernels take the draw index where the lockstep ones take the ply)
+    return launch(selfplay_record_kernel<RECORD_PRUNED, true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
+                  capacity, (int)draw_index, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
 }
 
 // ---------------------------------------------------------------- the replay ring (include/qttt_replay.h)

@@ -10,7 +10,10 @@
 // selfplay_record_kernel<RECORD_SAMPLED> is the sampled record of include/qttt_tree_explore.h: the same kernel with the
 // move of the first plies drawn from the visit counts (explore_sample_move); <RECORD_GUMBEL> is the Gumbel record of
 // include/qttt_tree_gumbel.h: the move and the pi row are gumbel_final's (qttt_tree_gumbel_kernels.h), two more
-// butterflies and one exp per lane; <RECORD_PLAIN> is qttt_selfplay_record's, whose code the mode does not touch.
+// butterflies and one exp per lane; <RECORD_PLAIN> is qttt_selfplay_record's, whose code the mode does not touch;
+// <RECORD_PRUNED> is the pruned record of include/qttt_tree_forced.h: the sampled record whose pi row is made of forced_root's
+// pruned visit counts (qttt_tree_forced_kernels.h), the other three instantiations compiling to what they were without it
+// (profiles/forced/kernel_resources.txt).
 // selfplay_record_kernel<MODE, true> is the stream record of include/qttt_selfplay_stream.h: the same body with the row
 // read per game from length[g]; the lockstep instantiations compile to what they were without it
 // (profiles/stream/record_kernels_before_after.txt).  A root's row is written by selfplay_row_head and, at a terminal
@@ -20,6 +23,7 @@
 #include "qttt_tree_kernels.h"
 #include "qttt_tree_explore_kernels.h"
 #include "qttt_tree_gumbel_kernels.h"
+#include "qttt_tree_forced_kernels.h"
 #include "qttt_selfplay.h"
 
 namespace {
@@ -36,7 +40,7 @@ struct SelfPlayOut {
     uint8_t *actions;                  // [games][2]
 };
 
-constexpr int RECORD_PLAIN = 0, RECORD_SAMPLED = 1, RECORD_GUMBEL = 2;
+constexpr int RECORD_PLAIN = 0, RECORD_SAMPLED = 1, RECORD_GUMBEL = 2, RECORD_PRUNED = 3;
 
 // what the sampled and the Gumbel record take besides: nothing at all in the plain one
 template <int MODE>
@@ -51,6 +55,13 @@ template <>
 struct SelfPlaySampling<RECORD_GUMBEL> {
     const GumbelRec *recs;
     double c_visit, c_scale;
+};
+template <>
+struct SelfPlaySampling<RECORD_PRUNED> {                         // the sampled record's, then the prune's
+    u64 seed, board_offset;
+    double temperature;
+    int sample_plies;
+    double forced_k, c_puct;
 };
 
 // what every recorded root writes first: its packed state, the done byte and the game's new length
@@ -129,11 +140,13 @@ __global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void 
         pi = f.pi;
     } else {
         // self_play.py:208-213: pi[a] = (N / n_rollouts) ** alpha on the legal actions, normalised
-        double x = r.legal ? (double)r.s.N / (double)n_rollouts : 0.0;
+        u32 n_pi = r.s.N;
+        if constexpr (MODE == RECORD_PRUNED) n_pi = forced_root(v, g, r, lane, sampling.forced_k, sampling.c_puct).n_pruned;
+        double x = r.legal ? (double)n_pi / (double)n_rollouts : 0.0;
         if (alpha != 1.0) x = r.legal ? pow(x, alpha) : 0.0;
         const double sum = selfplay_wave_sum(x);
         a = tree_choose(r, lane);
-        if constexpr (MODE == RECORD_SAMPLED) {
+        if constexpr (MODE == RECORD_SAMPLED || MODE == RECORD_PRUNED) {
             if (ply < sampling.sample_plies) {                   // wave-uniform
                 const int drawn = explore_sample_move(r.s.N, lane, sampling.seed, sampling.board_offset + (u64)g, draw,
                                                       sampling.temperature);

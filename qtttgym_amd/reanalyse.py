@@ -30,7 +30,8 @@ class ReanalyseStats:
 
 class Reanalyser(LibCaller):
     """Re-searches n positions of `ring` per run() with the search settings of the SelfPlay `sp` — net, n_rollouts,
-    leaf_eval, leaves, eval_symmetries, root_policy, exact_from, prove, alpha, c_puct, exact_targets / exact_policy; its
+    leaf_eval, leaves, eval_symmetries, root_policy, exact_from, prove, forced_playouts / prune_targets, alpha, c_puct,
+    exact_targets / exact_policy; its
     root_noise and sample_plies are ignored, a reanalysis plays no move — and writes the new policy targets into their
     slots (ReplayBuffer.gather / update).  The policy target is the record kernels' own: the visit-count target, or the
     improved policy under root_policy="gumbel".
@@ -64,8 +65,8 @@ class Reanalyser(LibCaller):
                                  eval_symmetries=sp.eval_symmetries, root_policy=sp.root_policy,
                                  max_considered=sp.max_considered, c_visit=sp.c_visit, c_scale=sp.c_scale,
                                  exact_from=sp.exact_from, exact_targets=sp.exact_targets, exact_policy=sp.exact_policy,
-                                 prove=sp.prove)
-        self.env = VecEnv(self.n, device=self.device)
+                                 prove=sp.prove, forced_playouts=sp.forced_playouts, prune_targets=sp.prune_targets)
+        self.env =VecEnv(self.n, device=self.device)
         self.tree = self.new_tree(self.tree_seed(0))
         self.batch = self.recorder.new_batch()
         self.runs = 0                   # run() calls so far: what the next run's trees are seeded with
@@ -82,7 +83,7 @@ class Reanalyser(LibCaller):
                           net=sp.net, seed=seed, device=self.device, leaf_eval=sp.leaf_eval, leaves=sp.leaves,
                           virtual_loss=sp.virtual_loss, eval_symmetries=sp.eval_symmetries, root_policy=sp.root_policy,
                           max_considered=sp.max_considered, c_visit=sp.c_visit, c_scale=sp.c_scale, exact_from=sp.exact_from,
-                          prove=sp.prove)
+                          prove=sp.prove, forced_playouts=sp.forced_playouts)
 
     def run(self, start=None):
         """One reanalysis of n positions, without a host synchronisation: gather a window (start: ReplayBuffer.gather's) ->

@@ -193,13 +193,21 @@ class SelfPlay(LibCaller):
     rows before them are bootstrapped through it.  stream() runs the two in that order between the harvest and the ring's
     append, with rows = the harvested lengths.  No host synchronisation on either route.  Both need
     value_targets=(1.0, -1.0), as Reanalyser's value_mix does.  With both None play() and stream() issue the calls they
-    always did, and batch.q is absent."""
+    always did, and batch.q is absent.
+    forced_playouts=k (TreeSearch's; value leaves and the PUCT root only) with prune_targets (default: True exactly when
+    forced_playouts is given) are KataGo's pair of remedies for root noise at small budgets (include/qttt_tree_forced.h,
+    DESIGN.md §30).  The trees search with forced playouts; with prune_targets the record is qttt_selfplay_record_pruned
+    (qttt_selfplay_record_stream_pruned in stream()): pi is made of the visits that are left after every action but the most
+    visited one has given back the forced visits PUCT would not have made; the move, v, mask and done are the sampled
+    record's, read from the unpruned counts.  prune_targets=True needs forced_playouts; forced_playouts with
+    prune_targets=False only forces.  With both at their defaults play() and stream() issue the calls they always did."""
 
     def __init__(self, num_games, n_rollouts=100, num_simulations=10, net=None, alpha=1.0, c_puct=1.0,
                  value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts",
                  root_noise=None, temperature=1.0, sample_plies=0, leaves=1, virtual_loss=1.0,
                  eval_symmetries=None, root_policy="puct", max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None,
-                 exact_targets=None, exact_policy=True, prove=False, value_mix=None, td_lambda=None):
+                 exact_targets=None, exact_policy=True, prove=False, value_mix=None, td_lambda=None,
+                 forced_playouts=None, prune_targets=None):
         self.value_mode, self.value_lambda = self.check_value_args(value_mix, td_lambda, value_targets)
         self.exact_targets = self.check_exact_targets(exact_targets, value_targets)
         self.exact_policy = bool(exact_policy)
@@ -209,6 +217,8 @@ class SelfPlay(LibCaller):
         self.root_policy, self.max_considered, self.c_visit, self.c_scale = TreeSearch.check_root_args(
             leaf_eval, net, root_policy, max_considered, c_visit, c_scale)
         self.eval_symmetries = TreeSearch.check_eval_symmetries(leaf_eval, eval_symmetries)
+        self.forced_playouts = TreeSearch.check_forced_playouts(leaf_eval, net, root_policy, forced_playouts)
+        self.prune_targets = self.check_prune_targets(self.forced_playouts, prune_targets)
         self.leaf_eval = leaf_eval
         self.num_games, self.n_rollouts = int(num_games), int(n_rollouts)
         self.num_simulations, self.net = int(num_simulations), net
@@ -253,6 +263,17 @@ class SelfPlay(LibCaller):
         self.env = self.tree = None   # the last play()'s or stream()'s environment (at its positions) and trees
         self._stream = None           # stream()'s games in progress: environment, trees, staging batch, counters
         self.stream_epoch_plies = None    # None: a seed serves as many plies as the draw counters allow (epoch_plies)
+
+    @staticmethod
+    def check_prune_targets(forced_playouts, prune_targets):
+        """The constructor's check of prune_targets: a bool; None stands for "exactly when forced_playouts is given"."""
+        if prune_targets is None:
+            return forced_playouts is not None
+        if not isinstance(prune_targets, bool):
+            raise ValueError("prune_targets must be True or False")
+        if prune_targets and forced_playouts is None:
+            raise ValueError("prune_targets=True needs forced_playouts: it subtracts the visits that forcing added")
+        return prune_targets
 
     @staticmethod
     def check_min_ply(m, what):
@@ -315,7 +336,8 @@ class SelfPlay(LibCaller):
     def record(self, tree, ply, batch, draw_index=None):
         """One qttt_selfplay_record: the roots of `tree` become row `ply` of `batch`; returns batch.actions, the move
         to step with.  With sample_plies > 0 it is qttt_selfplay_record_sampled, drawing with the tree's seed and
-        board_offset.  ply=None is the stream record (include/qttt_selfplay_stream.h): every game's row is its own
+        board_offset.  With prune_targets it is qttt_selfplay_record_pruned: the same move, the pi row pruned with the
+        tree's c_puct.  ply=None is the stream record (include/qttt_selfplay_stream.h): every game's row is its own
         length[g].  draw_index (the sampled move's draw, where it is not the ply: stream() and play(start_ply=p)) goes
         through the stream record too, which writes a lockstep batch's rows exactly as the lockstep entry does."""
         G, dev = self.num_games, self.device
@@ -331,6 +353,8 @@ class SelfPlay(LibCaller):
         per_game = ply is None or (sampled and draw_index is not None)
         if sampled and ply is None and draw_index is None:
             raise ValueError("the sampled stream record needs a draw_index")
+        if self.prune_targets and tree.root_policy == "gumbel":
+            raise ValueError("the pruned record needs a tree searched with the PUCT root")
         args = (tree.tree.data_ptr(), G, tree.capacity) + (() if per_game else (int(ply),)) + (
             self.n_rollouts, self.alpha, self.v_first, self.v_second,
             batch.states.data_ptr(), batch.pi.data_ptr(), batch.mask.data_ptr(), batch.done.data_ptr(),
@@ -341,6 +365,9 @@ class SelfPlay(LibCaller):
             if tree.root_policy != "gumbel" or tree._gumbel is None:
                 raise ValueError("the Gumbel record needs a tree searched with root_policy=\"gumbel\"")
             self._call(entry + "_gumbel", *args, tree._gumbel["rec"].data_ptr(), tree.c_visit, tree.c_scale)
+        elif self.prune_targets:       # the sampled record's arguments (sample_plies = 0: no draw is taken), then the prune's
+            self._call(entry + "_pruned", *args, tree.seed, tree.board_offset, self.temperature, self.sample_plies,
+                       *((int(draw_index or 0),) if per_game else ()), self.forced_playouts, tree.c_puct)
         elif sampled:
             self._call(entry + "_sampled", *args, tree.seed, tree.board_offset, self.temperature, self.sample_plies,
                        *((int(draw_index),) if per_game else ()))
@@ -358,7 +385,7 @@ class SelfPlay(LibCaller):
                           leaf_eval=self.leaf_eval, leaves=self.leaves, virtual_loss=self.virtual_loss,
                           eval_symmetries=self.eval_symmetries, root_policy=self.root_policy,
                           max_considered=self.max_considered, c_visit=self.c_visit, c_scale=self.c_scale,
-                          exact_from=self.exact_from, prove=self.prove)
+                          exact_from=self.exact_from, prove=self.prove, forced_playouts=self.forced_playouts)
         tree.reset(env)
         return env, tree
 

@@ -35,6 +35,12 @@ solved children, with the solver's own formula; a proven node below the root end
 root_stats() then says which root actions are proven and their exact q, and choose(exact=True) plays the solver's move at
 a proven root.
 
+forced_playouts=k (value leaves only, the PUCT root) is KataGo's remedy for noise at small budgets
+(include/qttt_tree_forced.h): at the root a visited action a with n(a)^2 < k P(a) sum(n) is searched before
+the PUCT choice.  Every rollout after the first of a reset() or sync() is then a leaf-parallel round through
+qttt_tree_select_batch_forced, and root_stats() says which actions are forced now and what the pruned policy target would
+keep of the visits.
+
 add_root_noise() is AlphaZero's root exploration (include/qttt_tree_explore.h): Dirichlet noise mixed into
 the priors of every root that has them, one launch.
 """
@@ -59,6 +65,9 @@ class TreeSearch(LibCaller):
     # what the Gumbel root adds to them (qttt_tree_gumbel_root)
     _GUMBEL_ROWS = {"choose": (torch.uint8, ()), "pi": (torch.float64, (36,)), "q_completed": (torch.float64, (36,))}
 
+    # what forced_playouts adds to them (qttt_tree_root_forced)
+    _FORCED_ROWS = {"forced": (torch.uint8, (36,)), "n_pruned": (torch.int32, (36,))}
+
     LEAF_EVALS = ("playouts", "value")
     ROOT_POLICIES = ("puct", "gumbel")
     leaf_eval = "playouts"
@@ -66,10 +75,11 @@ class TreeSearch(LibCaller):
     eval_symmetries = None
     exact_from = None
     prove = False
+    forced_playouts = None
 
     def __init__(self, num_games, capacity, num_simulations=10, c_puct=1.0, net=None, seed=0, board_offset=0,
                  device=None, leaf_eval="playouts", leaves=1, virtual_loss=1.0, eval_symmetries=None, root_policy="puct",
-                 max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None, prove=False):
+                 max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None, prove=False, forced_playouts=None):
         """leaf_eval="playouts": the reference's rollout, num_simulations playouts from the leaf (uniform, or guided by
         `net`).  leaf_eval="value" (needs `net`): the leaf is scored by the value head, seen by the player to move
         there; a terminal leaf by its reward.  num_simulations is then ignored: no playout draw is taken.
@@ -89,7 +99,13 @@ class TreeSearch(LibCaller):
         prove=True (needs exact_from; 9 is allowed: only terminal children prove anything then): every round ends with
         qttt_tree_prove, a fifth launch, which solves the nodes on the round's paths whose children are all terminal or
         solved.  A proven node below the root loses its priors, so descents end on it and it is backed up with its exact
-        value; the root keeps its priors.  False is the search as it always was."""
+        value; the root keeps its priors.  False is the search as it always was.
+        forced_playouts=k (finite, >= 0; needs a net and leaf_eval="value"; not with root_policy="gumbel"): a legal root
+        action a with n(a) > 0 and n(a) * n(a) < (k * P(a)) * sum(n) is forced: the descent takes the forced action of
+        largest score before it looks at the others (n counts the visits in flight).  contemplate() then runs one single
+        rollout where the roots may lack priors and rounds of `leaves` through qttt_tree_select_batch_forced after it, a
+        round of one leaf where leaves == 1.  k = 0 forces nothing.  None is the search as it always was."""
+        self.forced_playouts = self.check_forced_playouts(leaf_eval, net, root_policy, forced_playouts)
         self.exact_from = self.check_exact_from(leaf_eval, net, exact_from)
         self.prove = self.check_prove(self.exact_from, prove)
         self.leaves, self.virtual_loss = self.check_search_args(leaf_eval, net, leaves, virtual_loss)
@@ -193,6 +209,20 @@ class TreeSearch(LibCaller):
         return int(exact_from)
 
     @staticmethod
+    def check_forced_playouts(leaf_eval, net, root_policy, forced_playouts):
+        """The constructors' check of forced_playouts: None, or the factor k as a float."""
+        if forced_playouts is None:
+            return None
+        if isinstance(forced_playouts, bool) or not isinstance(forced_playouts, (int, float)) or \
+                not 0.0 <= float(forced_playouts) < float("inf"):
+            raise ValueError("forced_playouts must be None or a finite number >= 0")
+        if leaf_eval != "value" or net is None:
+            raise ValueError('forced_playouts needs a net and leaf_eval="value": the forced rounds are leaf-parallel rounds')
+        if root_policy == "gumbel":
+            raise ValueError('forced_playouts is a rule of the PUCT root: root_policy="gumbel" replaces that root')
+        return float(forced_playouts)
+
+    @staticmethod
     def check_prove(exact_from, prove):
         """The constructors' check of prove: a bool, True only with exact_from."""
         if not isinstance(prove, bool):
@@ -241,7 +271,8 @@ class TreeSearch(LibCaller):
         rounds of K and one shorter round for what is left.  Without eval_symmetries the calls are what they always were.
         root_policy="gumbel": after that single rollout (the root needs its priors to be descended from) the roots are
         evaluated, the Gumbel state of the move is drawn for the budget n = the rollouts that remain, and the rounds go
-        through the Gumbel select; every contemplate() is one budget of its own."""
+        through the Gumbel select; every contemplate() is one budget of its own.
+        forced_playouts: the same single rollout, then rounds of K (also at K = 1) through the forced select."""
         r = int(rollouts)
         if r < 0:
             raise ValueError("rollouts must be >= 0")
@@ -273,7 +304,7 @@ class TreeSearch(LibCaller):
                 self._gumbel_round(k)
                 self._bound += 2 * k
             return
-        if self.leaves == 1:
+        if self.leaves == 1 and self.forced_playouts is None:
             for _ in range(r):
                 single()
                 self._bound += 2
@@ -333,8 +364,13 @@ class TreeSearch(LibCaller):
             raise ValueError('a leaf-parallel round needs leaf_eval="value"')
         b = self._round_buffers(k)
         G, cap, tree = self.num_games, self.capacity, self.tree.data_ptr()
-        self._call("qttt_tree_select_batch", tree, G, cap, self.seed, self.rollout_idx, k, self.board_offset, self.c_puct,
-                   self.virtual_loss, b["paths"].data_ptr(), b["leaf"].state.data_ptr())
+        args = (tree, G, cap, self.seed, self.rollout_idx, k, self.board_offset, self.c_puct, self.virtual_loss,
+                b["paths"].data_ptr(), b["leaf"].state.data_ptr())
+        # a root that may lack priors (the single rollout after a reset() or sync()) is never asked the rule
+        if self.forced_playouts is None or self._fresh:
+            self._call("qttt_tree_select_batch", *args)
+        else:
+            self._call("qttt_tree_select_batch_forced", *args, self.forced_playouts)
         b["leaf"].evaluate(self.net, out=b["out"], symmetries=self.eval_symmetries)
         self._backup_round(b, k)
         self.rollout_idx += k
@@ -446,7 +482,9 @@ class TreeSearch(LibCaller):
     def root_stats(self):
         """The roots' statistics: N i32[G,36], W / Q / P f64[G,36], Ntot i32[G], choose u8[G], nodes_used i32[G],
         overflow bool[G].  root_policy="gumbel": choose is the Gumbel choice, and pi f64[G,36] (the improved policy) and
-        q_completed f64[G,36] are there too.  prove=True: proven bool[G,36] (the action's children are all terminal or
+        q_completed f64[G,36] are there too.  forced_playouts: forced bool[G,36] (the predicate of
+        include/qttt_tree_forced.h as the roots stand) and n_pruned i32[G,36] (the visits that the pruned policy target
+        keeps), one qttt_tree_root_forced launch.  prove=True: proven bool[G,36] (the action's children are all terminal or
         solved), q_exact f32[G,36] (its exact q, NaN where it is not proven), root_solved bool[G] and root_value_exact
         f32[G] (NaN where the root is not solved), one qttt_tree_root_exact launch."""
         o = out_rows(self._ROOT_ROWS, self.num_games, self.device)
@@ -457,6 +495,12 @@ class TreeSearch(LibCaller):
         if self.root_policy == "gumbel":
             o.update(out_rows(self._GUMBEL_ROWS, self.num_games, self.device))
             self._gumbel_root(o["choose"], o["pi"], o["q_completed"])
+        if self.forced_playouts is not None:
+            f = out_rows(self._FORCED_ROWS, self.num_games, self.device)
+            self._call("qttt_tree_root_forced", self.tree.data_ptr(), self.num_games, self.capacity, self.forced_playouts,
+                       self.c_puct, f["forced"].data_ptr(), f["n_pruned"].data_ptr())
+            f["forced"] = f["forced"].bool()
+            o.update(f)
         return o
 
     def _root(self, N=None, W=None, Q=None, P=None, Ntot=None, choose=None, nodes_used=None, overflow=None):
