@@ -57,7 +57,7 @@
 // qttt_tree_explore_kernels.h (root exploration: Dirichlet noise on the roots' priors, the sampled move);
 // qttt_tree_gumbel_kernels.h (the Gumbel root: considered actions, sequential halving, the improved policy);
 // qttt_tree_forced_kernels.h (forced playouts at the root and policy target pruning: the root rule, the pruned record's counts)
-// with qttt_tree_forced_host.h (free of HIP: the argument checks and one action's arithmetic);
+// with qttt_tree_forced_host.h (free of HIP: the root entry's argument check and one action's arithmetic);
 // qttt_replay_kernels.h (the replay ring: the append's scan and move, the sampled minibatch, and reanalysis: the gathered
 // window and the guarded update) with qttt_replay_host.h (host only and free of HIP: the ring's layout, the scan plan, the
 // window and holder arithmetic, the argument checks);
@@ -73,8 +73,9 @@
 // records walked upwards, a wave per game, integers only, and the roots' exact q);
 // qttt_selfplay_value_kernels.h (search-value targets: the roots' searched value, a wave per game, and the value targets made
 // of it, a lane per game) with qttt_selfplay_value_host.h (free of HIP: the argument checks and one game's row arithmetic).  Host only: qttt_launch.h (launch shape, kernel selection,
-// the one launch form, the argument checks), qttt_mailbox.h (the host half of the single-record mailbox); this file: the
-// step's launch logic + the C ABI.
+// the one launch form), qttt_checks.h (free of HIP: what every argument check is made of), qttt_selfplay_record_host.h (free of
+// HIP: the one check of the self-play records and the one of the leaf-parallel selects), qttt_mailbox.h (the host half of the
+// single-record mailbox); this file: the step's launch logic + the C ABI.
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -222,14 +223,22 @@ bool expand_rows_misaligned(const int8_t *winner, const uint8_t *terminal, const
            misaligned(state_key, 16);
 }
 
-bool tree_size_bad(int64_t games, int64_t capacity) { return games < 0 || capacity < 1 || capacity > QTTT_TREE_MAX_CAPACITY; }
-// the sizes of a leaf-parallel round: K in range, and games * K boards, records and priors rows addressable
-bool tree_leaves_bad(int64_t games, int leaves) {
-    return games < 0 || leaves < 1 || leaves > QTTT_TREE_MAX_LEAVES || games > INT64_MAX / (256 * (int64_t)QTTT_TREE_MAX_LEAVES);
+// THE SelfPlayOut of nine output pointers, typed by the C ABI entry that took them (the augment's inputs are const there)
+SelfPlayOut selfplay_out(const void *states, const void *pi, const void *mask, const void *done, const void *v,
+                         const void *action36, const void *length, const void *winner, const void *actions) {
+    return {(u64 *)states, (double *)pi, (uint8_t *)mask, (uint8_t *)done, (float *)v, (uint8_t *)action36, (uint8_t *)length,
+            (int8_t *)winner, (uint8_t *)actions};
 }
 
-// the scales of sigma (include/qttt_tree_gumbel.h): c_visit finite and >= 0, c_scale finite
-bool gumbel_scale_bad(double c_visit, double c_scale) { return !std::isfinite(c_visit) || c_visit < 0.0 || !std::isfinite(c_scale); }
+// THE launch of the self-play record, after record_check (qttt_selfplay_record_host.h) let the arguments through; the stream
+// kernels take the draw index (0 where the mode draws nothing) where the lockstep ones take the ply
+template <int MODE, bool STREAM>
+int record_launch(const RecordArgs &a, int64_t games, int64_t capacity, int ply_or_draw, uint32_t n_rollouts, double alpha,
+                  double v_first, double v_second, const SelfPlaySampling<MODE> &sampling, void *stream) {
+    const SelfPlayOut o = selfplay_out(a.states, a.pi, a.mask, a.done, a.v, a.action36, a.length, a.winner, a.actions);
+    return launch(selfplay_record_kernel<MODE, STREAM>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, a.tree, games,
+                  capacity, ply_or_draw, n_rollouts, alpha, (float)v_first, (float)v_second, o, sampling);
+}
 
 }  // namespace
 
@@ -768,15 +777,12 @@ int qttt_tree_score(const double *W, const uint32_t *N, const double *prior, con
 int qttt_selfplay_record(const void *tree, int64_t games, int64_t capacity, int ply, uint32_t n_rollouts, double alpha,
                          double v_first, double v_second, void *states, double *pi, uint8_t *mask, uint8_t *done,
                          float *v, uint8_t *action36, uint8_t *length, int8_t *winner, uint8_t *actions, void *stream) {
-    if (tree_size_bad(games, capacity) || ply < 0 || ply >= QTTT_SELFPLAY_ROWS || n_rollouts == 0u || !std::isfinite(alpha) ||
-        !std::isfinite(v_first) || !std::isfinite(v_second) || alpha <= 0.0)
-        return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions)) return QTTT_ERR_NULL;
-    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
-    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
-    return launch(selfplay_record_kernel<RECORD_PLAIN>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
-                  ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, SelfPlaySampling<RECORD_PLAIN>{});
+    const RecordArgs a = {tree, states, pi, mask, done, v, action36, length, winner, actions};
+    bool work;
+    if (const int rc = record_check(RECORD_PLAIN, false, a, games, capacity, ply, 0u, n_rollouts, alpha, v_first, v_second, {}, work);
+        rc || !work)
+        return rc;
+    return record_launch<RECORD_PLAIN, false>(a, games, capacity, ply, n_rollouts, alpha, v_first, v_second, {}, stream);
 }
 
 // ---------------------------------------------------------------- symmetries (include/qttt_symmetry.h)
@@ -819,11 +825,9 @@ int qttt_selfplay_augment(int64_t games, const uint8_t *symmetries, int n_sym, c
     if (misaligned(states, 16) || misaligned(states_out, 16) || misaligned(pi, 8) || misaligned(pi_out, 8) ||
         misaligned(v, 4) || misaligned(v_out, 4))
         return QTTT_ERR_ACTION;
-    const SelfPlayOut in = {static_cast<u64 *>(const_cast<void *>(states)), const_cast<double *>(pi), const_cast<uint8_t *>(mask),
-                            const_cast<uint8_t *>(done), const_cast<float *>(v), const_cast<uint8_t *>(action36),
-                            const_cast<uint8_t *>(length), const_cast<int8_t *>(winner), const_cast<uint8_t *>(actions)};
-    const SelfPlayOut out = {static_cast<u64 *>(states_out), pi_out, mask_out, done_out, v_out, action36_out, length_out,
-                             winner_out, actions_out};
+    const SelfPlayOut in = selfplay_out(states, pi, mask, done, v, action36, length, winner, actions);
+    const SelfPlayOut out = selfplay_out(states_out, pi_out, mask_out, done_out, v_out, action36_out, length_out, winner_out,
+                                         actions_out);
     return launch(selfplay_augment_kernel, ceil_div(games * n_sym, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, games, (u32)n_sym,
                   syms, in, out);
 }
@@ -875,12 +879,9 @@ int64_t qttt_tree_paths_bytes(int64_t games, int leaves) {
 int qttt_tree_select_batch(void *tree, int64_t games, int64_t capacity, uint64_t seed, uint32_t rollout_idx0, int leaves,
                            int64_t board_offset, double c_puct, double virtual_loss, void *paths, void *leaf_state,
                            void *stream) {
-    if (tree_size_bad(games, capacity) || board_offset < 0 || tree_leaves_bad(games, leaves) ||
-        (uint64_t)rollout_idx0 + (uint64_t)leaves > QTTT_TREE_MAX_ROLLOUTS || !std::isfinite(virtual_loss) || virtual_loss < 0.0)
-        return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (any_null(tree, paths, leaf_state)) return QTTT_ERR_NULL;
-    if (misaligned(tree, 16) || misaligned(paths, 16)) return QTTT_ERR_ACTION;
+    bool work;
+    if (const int rc = select_batch_check(SELECT_PUCT, tree, games, capacity, rollout_idx0, leaves, board_offset, virtual_loss, paths,
+                                      leaf_state, {}, work); rc || !work) return rc;
     const Planes l = planes(leaf_state, games * leaves);
     return launch(tree_select_batch_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
                   (u64)seed, rollout_idx0, (u32)leaves, (u64)board_offset, c_puct, virtual_loss, static_cast<TreePathRec *>(paths),
@@ -903,7 +904,7 @@ int qttt_tree_root_noise(void *tree, int64_t games, int64_t capacity, uint64_t s
                          int64_t board_offset, double epsilon, double alpha, double *noise, uint8_t *applied,
                          void *stream) {
     if (tree_size_bad(games, capacity) || board_offset < 0 || noise_idx >= QTTT_TREE_MAX_NOISE || !(epsilon >= 0.0 && epsilon <= 1.0) ||
-        !std::isfinite(alpha) || alpha <= 0.0)
+        !is_finite(alpha) || alpha <= 0.0)
         return QTTT_ERR_SIZE;
     if (games == 0) return 0;
     if (!tree) return QTTT_ERR_NULL;
@@ -917,17 +918,12 @@ int qttt_selfplay_record_sampled(const void *tree, int64_t games, int64_t capaci
                                  uint8_t *done, float *v, uint8_t *action36, uint8_t *length, int8_t *winner,
                                  uint8_t *actions, uint64_t seed, int64_t board_offset, double temperature,
                                  int sample_plies, void *stream) {
-    if (tree_size_bad(games, capacity) || ply < 0 || ply >= QTTT_SELFPLAY_ROWS || n_rollouts == 0u || !std::isfinite(alpha) ||
-        !std::isfinite(v_first) || !std::isfinite(v_second) || alpha <= 0.0 || board_offset < 0 || !std::isfinite(temperature) ||
-        temperature <= 0.0 || sample_plies < 0 || sample_plies > QTTT_SELFPLAY_ROWS)
-        return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions)) return QTTT_ERR_NULL;
-    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
-    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    const RecordArgs a = {tree, states, pi, mask, done, v, action36, length, winner, actions};
+    bool work;
+    if (const int rc = record_check(RECORD_SAMPLED, false, a, games, capacity, ply, 0u, n_rollouts, alpha, v_first, v_second,
+                                {board_offset, temperature, sample_plies}, work); rc || !work) return rc;
     const SelfPlaySampling<RECORD_SAMPLED> s = {(u64)seed, (u64)board_offset, temperature, sample_plies};
-    return launch(selfplay_record_kernel<RECORD_SAMPLED>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
-                  ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
+    return record_launch<RECORD_SAMPLED, false>(a, games, capacity, ply, n_rollouts, alpha, v_first, v_second, s, stream);
 }
 
 // ---------------------------------------------------------------- the Gumbel root (include/qttt_tree_gumbel.h)
@@ -985,14 +981,11 @@ int qttt_tree_select_batch_gumbel(void *tree, int64_t games, int64_t capacity, u
                                   int leaves, int64_t board_offset, double c_puct, double virtual_loss, void *paths,
                                   void *leaf_state, const void *rec, const int32_t *visit_table, int n_sims, int sim_idx0,
                                   double c_visit, double c_scale, void *stream) {
-    if (tree_size_bad(games, capacity) || board_offset < 0 || tree_leaves_bad(games, leaves) ||
-        (uint64_t)rollout_idx0 + (uint64_t)leaves > QTTT_TREE_MAX_ROLLOUTS || !std::isfinite(virtual_loss) || virtual_loss < 0.0 ||
-        n_sims < 1 || n_sims > QTTT_TREE_MAX_ROLLOUTS || sim_idx0 < 0 || (int64_t)sim_idx0 + leaves > n_sims ||
-        gumbel_scale_bad(c_visit, c_scale))
-        return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (any_null(tree, paths, leaf_state, rec, visit_table)) return QTTT_ERR_NULL;
-    if (misaligned(tree, 16) || misaligned(paths, 16) || misaligned(rec, 16) || misaligned(visit_table, 4)) return QTTT_ERR_ACTION;
+    bool work;
+    if (const int rc = select_batch_check(SELECT_GUMBEL, tree, games, capacity, rollout_idx0, leaves, board_offset, virtual_loss, paths,
+                                      leaf_state, {0.0, rec, visit_table, n_sims, sim_idx0, c_visit, c_scale}, work);
+        rc || !work)
+        return rc;
     const Planes l = planes(leaf_state, games * leaves);
     return launch(tree_select_batch_gumbel_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
                   (u64)seed, rollout_idx0, (u32)leaves, (u64)board_offset, c_puct, virtual_loss, static_cast<TreePathRec *>(paths),
@@ -1013,17 +1006,12 @@ int qttt_selfplay_record_gumbel(const void *tree, int64_t games, int64_t capacit
                                 double alpha, double v_first, double v_second, void *states, double *pi, uint8_t *mask,
                                 uint8_t *done, float *v, uint8_t *action36, uint8_t *length, int8_t *winner,
                                 uint8_t *actions, const void *rec, double c_visit, double c_scale, void *stream) {
-    if (tree_size_bad(games, capacity) || ply < 0 || ply >= QTTT_SELFPLAY_ROWS || !std::isfinite(v_first) ||
-        !std::isfinite(v_second) || gumbel_scale_bad(c_visit, c_scale))
-        return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions, rec)) return QTTT_ERR_NULL;
-    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4) || misaligned(rec, 16))
-        return QTTT_ERR_ACTION;
-    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    const RecordArgs a = {tree, states, pi, mask, done, v, action36, length, winner, actions};
+    bool work;
+    if (const int rc = record_check(RECORD_GUMBEL, false, a, games, capacity, ply, 0u, n_rollouts, alpha, v_first, v_second,
+                                {0, 0.0, 0, 0.0, 0.0, rec, c_visit, c_scale}, work); rc || !work) return rc;
     const SelfPlaySampling<RECORD_GUMBEL> s = {static_cast<const GumbelRec *>(rec), c_visit, c_scale};
-    return launch(selfplay_record_kernel<RECORD_GUMBEL>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
-                  capacity, ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
+    return record_launch<RECORD_GUMBEL, false>(a, games, capacity, ply, n_rollouts, alpha, v_first, v_second, s, stream);
 }
 
 // ---------------------------------------------------------------- forced playouts and pruned targets (include/qttt_tree_forced.h)
@@ -1031,9 +1019,8 @@ int qttt_tree_select_batch_forced(void *tree, int64_t games, int64_t capacity, u
                                   int leaves, int64_t board_offset, double c_puct, double virtual_loss, void *paths,
                                   void *leaf_state, double forced_k, void *stream) {
     bool work;
-    const int rc = forced_select_check(tree, games, capacity, rollout_idx0, leaves, board_offset, virtual_loss, paths, leaf_state,
-                                       forced_k, work);
-    if (rc || !work) return rc;
+    if (const int rc = select_batch_check(SELECT_FORCED, tree, games, capacity, rollout_idx0, leaves, board_offset, virtual_loss, paths,
+                                      leaf_state, {forced_k}, work); rc || !work) return rc;
     const Planes l = planes(leaf_state, games * leaves);
     return launch(tree_select_batch_forced_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
                   (u64)seed, rollout_idx0, (u32)leaves, (u64)board_offset, c_puct, virtual_loss, static_cast<TreePathRec *>(paths),
@@ -1054,15 +1041,12 @@ int qttt_selfplay_record_pruned(const void *tree, int64_t games, int64_t capacit
                                 uint8_t *done, float *v, uint8_t *action36, uint8_t *length, int8_t *winner,
                                 uint8_t *actions, uint64_t seed, int64_t board_offset, double temperature,
                                 int sample_plies, double forced_k, double c_puct, void *stream) {
+    const RecordArgs a = {tree, states, pi, mask, done, v, action36, length, winner, actions};
     bool work;
-    const ForcedRecordArgs p = {tree, states, pi, mask, done, v, action36, length, winner, actions};
-    const int rc = forced_record_check(p, games, capacity, false, ply, 0u, n_rollouts, alpha, v_first, v_second, board_offset,
-                                       temperature, sample_plies, forced_k, c_puct, work);
-    if (rc || !work) return rc;
-    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    if (const int rc = record_check(RECORD_PRUNED, false, a, games, capacity, ply, 0u, n_rollouts, alpha, v_first, v_second,
+                                {board_offset, temperature, sample_plies, forced_k, c_puct}, work); rc || !work) return rc;
     const SelfPlaySampling<RECORD_PRUNED> s = {(u64)seed, (u64)board_offset, temperature, sample_plies, forced_k, c_puct};
-    return launch(selfplay_record_kernel<RECORD_PRUNED>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
-                  capacity, ply, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
+    return record_launch<RECORD_PRUNED, false>(a, games, capacity, ply, n_rollouts, alpha, v_first, v_second, s, stream);
 }
 
 int qttt_selfplay_record_stream_pruned(const void *tree, int64_t games, int64_t capacity, uint32_t n_rollouts, double alpha,
@@ -1070,16 +1054,12 @@ int qttt_selfplay_record_stream_pruned(const void *tree, int64_t games, int64_t 
                                        uint8_t *done, float *v, uint8_t *action36, uint8_t *length, int8_t *winner,
                                        uint8_t *actions, uint64_t seed, int64_t board_offset, double temperature,
                                        int sample_plies, uint32_t draw_index, double forced_k, double c_puct, void *stream) {
+    const RecordArgs a = {tree, states, pi, mask, done, v, action36, length, winner, actions};
     bool work;
-    const ForcedRecordArgs p = {tree, states, pi, mask, done, v, action36, length, winner, actions};
-    const int rc = forced_record_check(p, games, capacity, true, 0, draw_index, n_rollouts, alpha, v_first, v_second, board_offset,
-                                       temperature, sample_plies, forced_k, c_puct, work);
-    if (rc || !work) return rc;
-    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    if (const int rc = record_check(RECORD_PRUNED, true, a, games, capacity, 0, draw_index, n_rollouts, alpha, v_first, v_second,
+                                {board_offset, temperature, sample_plies, forced_k, c_puct}, work); rc || !work) return rc;
     const SelfPlaySampling<RECORD_PRUNED> s = {(u64)seed, (u64)board_offset, temperature, sample_plies, forced_k, c_puct};
-    // (the stream kernels take the draw index where the lockstep ones take the ply)
-    return launch(selfplay_record_kernel<RECORD_PRUNED, true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
-                  capacity, (int)draw_index, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
+    return record_launch<RECORD_PRUNED, true>(a, games, capacity, (int)draw_index, n_rollouts, alpha, v_first, v_second, s, stream);
 }
 
 // ---------------------------------------------------------------- the replay ring (include/qttt_replay.h)
@@ -1212,15 +1192,12 @@ int qttt_selfplay_record_stream(const void *tree, int64_t games, int64_t capacit
                                 double v_first, double v_second, void *states, double *pi, uint8_t *mask, uint8_t *done,
                                 float *v, uint8_t *action36, uint8_t *length, int8_t *winner, uint8_t *actions,
                                 void *stream) {
-    if (tree_size_bad(games, capacity) || n_rollouts == 0u || !std::isfinite(alpha) || !std::isfinite(v_first) ||
-        !std::isfinite(v_second) || alpha <= 0.0)
-        return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions)) return QTTT_ERR_NULL;
-    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
-    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
-    return launch(selfplay_record_kernel<RECORD_PLAIN, true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
-                  capacity, 0, n_rollouts, alpha, (float)v_first, (float)v_second, o, SelfPlaySampling<RECORD_PLAIN>{});
+    const RecordArgs a = {tree, states, pi, mask, done, v, action36, length, winner, actions};
+    bool work;
+    if (const int rc = record_check(RECORD_PLAIN, true, a, games, capacity, 0, 0u, n_rollouts, alpha, v_first, v_second, {}, work);
+        rc || !work)
+        return rc;
+    return record_launch<RECORD_PLAIN, true>(a, games, capacity, 0, n_rollouts, alpha, v_first, v_second, {}, stream);
 }
 
 int qttt_selfplay_record_stream_sampled(const void *tree, int64_t games, int64_t capacity, uint32_t n_rollouts, double alpha,
@@ -1228,41 +1205,31 @@ int qttt_selfplay_record_stream_sampled(const void *tree, int64_t games, int64_t
                                         uint8_t *done, float *v, uint8_t *action36, uint8_t *length, int8_t *winner,
                                         uint8_t *actions, uint64_t seed, int64_t board_offset, double temperature,
                                         int sample_plies, uint32_t draw_index, void *stream) {
-    if (tree_size_bad(games, capacity) || n_rollouts == 0u || !std::isfinite(alpha) || !std::isfinite(v_first) ||
-        !std::isfinite(v_second) || alpha <= 0.0 || board_offset < 0 || !std::isfinite(temperature) || temperature <= 0.0 ||
-        sample_plies < 0 || sample_plies > QTTT_SELFPLAY_ROWS || draw_index >= QTTT_SELFPLAY_MAX_MOVE_DRAWS)
-        return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions)) return QTTT_ERR_NULL;
-    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
-    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    const RecordArgs a = {tree, states, pi, mask, done, v, action36, length, winner, actions};
+    bool work;
+    if (const int rc = record_check(RECORD_SAMPLED, true, a, games, capacity, 0, draw_index, n_rollouts, alpha, v_first, v_second,
+                                {board_offset, temperature, sample_plies}, work); rc || !work) return rc;
     const SelfPlaySampling<RECORD_SAMPLED> s = {(u64)seed, (u64)board_offset, temperature, sample_plies};
-    // (the stream kernels take the draw index where the lockstep ones take the ply)
-    return launch(selfplay_record_kernel<RECORD_SAMPLED, true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
-                  capacity, (int)draw_index, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
+    return record_launch<RECORD_SAMPLED, true>(a, games, capacity, (int)draw_index, n_rollouts, alpha, v_first, v_second, s, stream);
 }
 
 int qttt_selfplay_record_stream_gumbel(const void *tree, int64_t games, int64_t capacity, uint32_t n_rollouts, double alpha,
                                        double v_first, double v_second, void *states, double *pi, uint8_t *mask,
                                        uint8_t *done, float *v, uint8_t *action36, uint8_t *length, int8_t *winner,
                                        uint8_t *actions, const void *rec, double c_visit, double c_scale, void *stream) {
-    if (tree_size_bad(games, capacity) || !std::isfinite(v_first) || !std::isfinite(v_second) || gumbel_scale_bad(c_visit, c_scale))
-        return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions, rec)) return QTTT_ERR_NULL;
-    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4) || misaligned(rec, 16))
-        return QTTT_ERR_ACTION;
-    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    const RecordArgs a = {tree, states, pi, mask, done, v, action36, length, winner, actions};
+    bool work;
+    if (const int rc = record_check(RECORD_GUMBEL, true, a, games, capacity, 0, 0u, n_rollouts, alpha, v_first, v_second,
+                                {0, 0.0, 0, 0.0, 0.0, rec, c_visit, c_scale}, work); rc || !work) return rc;
     const SelfPlaySampling<RECORD_GUMBEL> s = {static_cast<const GumbelRec *>(rec), c_visit, c_scale};
-    return launch(selfplay_record_kernel<RECORD_GUMBEL, true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games,
-                  capacity, 0, n_rollouts, alpha, (float)v_first, (float)v_second, o, s);
+    return record_launch<RECORD_GUMBEL, true>(a, games, capacity, 0, n_rollouts, alpha, v_first, v_second, s, stream);
 }
 
 int qttt_selfplay_harvest(const void *tree, int64_t games, int64_t capacity, double v_first, double v_second, void *states,
                           double *pi, uint8_t *mask, uint8_t *done, float *v, uint8_t *action36, uint8_t *length,
                           int8_t *winner, uint8_t *actions, uint8_t *harvest_len, uint8_t *finished, int64_t *games_done,
                           int64_t *tally, void *stream) {
-    if (tree_size_bad(games, capacity) || !std::isfinite(v_first) || !std::isfinite(v_second)) return QTTT_ERR_SIZE;
+    if (tree_size_bad(games, capacity) || !is_finite(v_first) || !is_finite(v_second)) return QTTT_ERR_SIZE;
     if (games == 0) return 0;
     if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions) ||
         any_null(harvest_len, finished, games_done, tally))
@@ -1270,7 +1237,7 @@ int qttt_selfplay_harvest(const void *tree, int64_t games, int64_t capacity, dou
     if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(games_done, 8) || misaligned(tally, 8) ||
         misaligned(v, 4))
         return QTTT_ERR_ACTION;
-    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, winner, actions};
+    const SelfPlayOut o = selfplay_out(states, pi, mask, done, v, action36, length, winner, actions);
     const SelfPlayHarvest hv = {harvest_len, finished, games_done, tally};
     return launch(selfplay_harvest_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
                   (float)v_first, (float)v_second, o, hv);
@@ -1285,7 +1252,7 @@ int qttt_selfplay_restart(void *tree, int64_t games, int64_t capacity, void *sta
     if (misaligned(tree, 16) || misaligned(state, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4))
         return QTTT_ERR_ACTION;
     const Planes p = planes(state, games);
-    const SelfPlayOut o = {static_cast<u64 *>(states), pi, mask, done, v, action36, length, nullptr, nullptr};
+    const SelfPlayOut o = selfplay_out(states, pi, mask, done, v, action36, length, nullptr, nullptr);
     return launch(selfplay_restart_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity, p.P, p.Q,
                   finished, o);
 }

@@ -1,11 +1,12 @@
 // qttt_launch.h — host only: what every C ABI entry of qttt_kernels.hip is written with.  The step's launch-shape
-// table, the compile-time dispatch of runtime flags (with_bools / with_int), the one launch form, and the argument
-// checks in the order include/qttt.h promises.
+// table, the compile-time dispatch of runtime flags (with_bools / with_int), the one launch form, and the observation
+// buffers' check (the predicates of every argument check are qttt_checks.h's).
 #ifndef QTTT_LAUNCH_H
 #define QTTT_LAUNCH_H
 #include <atomic>
 #include <type_traits>
 #include "qttt_step_kernels.h"
+#include "qttt_checks.h"
 
 namespace {
 
@@ -124,13 +125,6 @@ inline int fused_runs(uint64_t seed, uint32_t step_idx0, int32_t n_steps, F &&la
     }
     return 0;
 }
-
-// Argument checks.  Every entry asks in the order include/qttt.h promises: a bad size -> QTTT_ERR_SIZE, an empty batch
-// -> 0, a required pointer missing -> QTTT_ERR_NULL, a pointer the kernel's vector accesses cannot take ->
-// QTTT_ERR_ACTION; only then does anything reach a kernel.
-template <typename... P>
-inline bool any_null(const P *...p) { return (... || !p); }
-inline bool misaligned(const void *p, unsigned bytes) { return ((uintptr_t)p & (bytes - 1u)) != 0; }   // bytes: 2^k; null passes
 
 // The observation buffers (qttt_observe's outputs) of a batch of n boards: all given when n > 0, q_p1 2-byte and q_p2
 // 8-byte aligned (the kernels store whole rows from LDS, 2 / 8 bytes at a time).

@@ -1,10 +1,9 @@
 // qttt_replay_host.h — host only, plain C++ without HIP: the layout of the replay ring, the plan of the append's scan
-// levels and the argument checks of include/qttt_replay.h, in the order that header promises.  Kept apart from the
+// levels and the argument checks of include/qttt_replay.h, in the order that header promises (on qttt_checks.h).  Kept apart from the
 // kernels so that a stand-alone program can exercise this code under the host sanitizers (tools/replay_host_check.cpp).
 #ifndef QTTT_REPLAY_HOST_H
 #define QTTT_REPLAY_HOST_H
-#include <stdint.h>
-#include "qttt.h"
+#include "qttt_checks.h"
 
 #ifdef __HIPCC__
 #define QTTT_REPLAY_HD __host__ __device__
@@ -17,7 +16,6 @@ namespace {
 inline int64_t replay_align64(int64_t bytes) { return (bytes + 63) & ~(int64_t)63; }
 inline bool replay_capacity_bad(int64_t capacity) { return capacity < 1 || capacity > QTTT_REPLAY_MAX_CAPACITY; }
 inline bool replay_games_bad(int64_t games) { return games < 0 || games > QTTT_REPLAY_MAX_GAMES; }
-inline bool replay_misaligned(const void *p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1u)) != 0; }   // null passes
 
 // P, Q, pi, mask, v, done behind the header, each at a 64-byte-aligned offset; bytes = the whole ring
 struct ReplayLayout {
@@ -72,8 +70,8 @@ inline int replay_append_check(const void *replay, int64_t capacity, int64_t gam
     if (replay_capacity_bad(capacity) || replay_games_bad(games)) return QTTT_ERR_SIZE;
     if (games == 0) return 0;
     if (!replay || !states || !pi || !mask || !done || !v || !length || !scratch) return QTTT_ERR_NULL;
-    if (replay_misaligned(replay, 64) || replay_misaligned(states, 16) || replay_misaligned(pi, 8) ||
-        replay_misaligned(scratch, 8) || replay_misaligned(v, 4))
+    if (misaligned(replay, 64) || misaligned(states, 16) || misaligned(pi, 8) ||
+        misaligned(scratch, 8) || misaligned(v, 4))
         return QTTT_ERR_ACTION;
     launch = true;
     return 0;
@@ -87,8 +85,8 @@ inline int replay_sample_check(const void *replay, int64_t capacity, int64_t n, 
     if (replay_capacity_bad(capacity) || n < 0 || n > QTTT_REPLAY_MAX_CAPACITY || draw >= 0x80000000u) return QTTT_ERR_SIZE;
     if (n == 0) return 0;
     if (!replay || !s_out || !pi_out || !mask_out || !v_out || !done_out) return QTTT_ERR_NULL;
-    if (replay_misaligned(replay, 64) || replay_misaligned(s_out, 16) || replay_misaligned(pi_out, 16) ||
-        replay_misaligned(mask_out, 4) || replay_misaligned(v_out, 4) || replay_misaligned(index_out, 4))
+    if (misaligned(replay, 64) || misaligned(s_out, 16) || misaligned(pi_out, 16) ||
+        misaligned(mask_out, 4) || misaligned(v_out, 4) || misaligned(index_out, 4))
         return QTTT_ERR_ACTION;
     launch = true;
     return 0;
@@ -121,8 +119,8 @@ inline int replay_gather_check(const void *replay, int64_t capacity, int64_t n, 
     if (replay_capacity_bad(capacity) || n < 0 || n > QTTT_REPLAY_MAX_CAPACITY || draw >= 0x80000000u) return QTTT_ERR_SIZE;
     if (n == 0) return 0;
     if (!replay || !state_out || !slot_out || !number_out) return QTTT_ERR_NULL;
-    if (replay_misaligned(replay, 64) || replay_misaligned(state_out, 16) || replay_misaligned(number_out, 8) ||
-        replay_misaligned(slot_out, 4) || replay_misaligned(v_out, 4))
+    if (misaligned(replay, 64) || misaligned(state_out, 16) || misaligned(number_out, 8) ||
+        misaligned(slot_out, 4) || misaligned(v_out, 4))
         return QTTT_ERR_ACTION;
     launch = true;
     return 0;
@@ -135,8 +133,8 @@ inline int replay_update_check(const void *replay, int64_t capacity, int64_t n, 
     if (replay_capacity_bad(capacity) || n < 0 || n > QTTT_REPLAY_MAX_CAPACITY) return QTTT_ERR_SIZE;
     if (n == 0) return 0;
     if (!replay || !slot || !number || (!pi && !v)) return QTTT_ERR_NULL;
-    if (replay_misaligned(replay, 64) || replay_misaligned(pi, 8) || replay_misaligned(number, 8) ||
-        replay_misaligned(slot, 4) || replay_misaligned(v, 4))
+    if (misaligned(replay, 64) || misaligned(pi, 8) || misaligned(number, 8) ||
+        misaligned(slot, 4) || misaligned(v, 4))
         return QTTT_ERR_ACTION;
     launch = true;
     return 0;

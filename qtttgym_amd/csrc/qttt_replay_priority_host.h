@@ -4,7 +4,7 @@
 // kernels so that a stand-alone program can exercise this code under the host sanitizers (tools/priority_host_check.cpp).
 #ifndef QTTT_REPLAY_PRIORITY_HOST_H
 #define QTTT_REPLAY_PRIORITY_HOST_H
-#include <stdint.h>
+#include "qttt_checks.h"
 #include "qttt_replay_host.h"
 #include "qttt_replay_priority.h"
 
@@ -89,7 +89,7 @@ inline int64_t priority_first_past(const T *c, int64_t count, uint64_t &t) {
 inline int priority_sync_check(const void *replay, const void *prio, int64_t capacity) {
     if (replay_capacity_bad(capacity)) return QTTT_ERR_SIZE;
     if (!replay || !prio) return QTTT_ERR_NULL;
-    if (replay_misaligned(replay, 64) || replay_misaligned(prio, 64)) return QTTT_ERR_ACTION;
+    if (misaligned(replay, 64) || misaligned(prio, 64)) return QTTT_ERR_ACTION;
     return 0;
 }
 
@@ -100,8 +100,8 @@ inline int priority_update_check(const void *replay, const void *prio, int64_t c
     if (replay_capacity_bad(capacity) || n < 0 || n > QTTT_REPLAY_MAX_CAPACITY) return QTTT_ERR_SIZE;
     if (n == 0) return 0;
     if (!replay || !prio || !slot || !number || !priority) return QTTT_ERR_NULL;
-    if (replay_misaligned(replay, 64) || replay_misaligned(prio, 64) || replay_misaligned(number, 8) ||
-        replay_misaligned(slot, 4) || replay_misaligned(priority, 4))
+    if (misaligned(replay, 64) || misaligned(prio, 64) || misaligned(number, 8) ||
+        misaligned(slot, 4) || misaligned(priority, 4))
         return QTTT_ERR_ACTION;
     launch = true;
     return 0;
@@ -116,10 +116,10 @@ inline int priority_sample_check(const void *replay, const void *prio, int64_t c
     if (replay_capacity_bad(capacity) || n < 0 || n > QTTT_REPLAY_MAX_CAPACITY || draw >= 0x80000000u) return QTTT_ERR_SIZE;
     if (n == 0) return 0;
     if (!replay || !prio || !s_out || !pi_out || !mask_out || !v_out || !done_out) return QTTT_ERR_NULL;
-    if (replay_misaligned(replay, 64) || replay_misaligned(prio, 64) || replay_misaligned(s_out, 16) ||
-        replay_misaligned(pi_out, 16) || replay_misaligned(mask_out, 4) || replay_misaligned(v_out, 4) ||
-        replay_misaligned(index_out, 4) || replay_misaligned(number_out, 8) || replay_misaligned(q_out, 4) ||
-        replay_misaligned(total_out, 8))
+    if (misaligned(replay, 64) || misaligned(prio, 64) || misaligned(s_out, 16) ||
+        misaligned(pi_out, 16) || misaligned(mask_out, 4) || misaligned(v_out, 4) ||
+        misaligned(index_out, 4) || misaligned(number_out, 8) || misaligned(q_out, 4) ||
+        misaligned(total_out, 8))
         return QTTT_ERR_ACTION;
     launch = true;
     return 0;

@@ -25,6 +25,7 @@
 #include "qttt_tree_gumbel_kernels.h"
 #include "qttt_tree_forced_kernels.h"
 #include "qttt_selfplay.h"
+#include "qttt_selfplay_record_host.h"
 
 namespace {
 
@@ -39,8 +40,6 @@ struct SelfPlayOut {
     int8_t *winner;                    // [games]
     uint8_t *actions;                  // [games][2]
 };
-
-constexpr int RECORD_PLAIN = 0, RECORD_SAMPLED = 1, RECORD_GUMBEL = 2, RECORD_PRUNED = 3;
 
 // what the sampled and the Gumbel record take besides: nothing at all in the plain one
 template <int MODE>

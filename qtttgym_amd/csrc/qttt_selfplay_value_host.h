@@ -1,11 +1,10 @@
 // qttt_selfplay_value_host.h — plain C++ without HIP: the argument checks of include/qttt_selfplay_value.h in the order
-// that header promises, and the row arithmetic of qttt_selfplay_value_targets for ONE game, which the kernel
+// that header promises (on qttt_checks.h), and the row arithmetic of qttt_selfplay_value_targets for ONE game, which the kernel
 // (qttt_selfplay_value_kernels.h) runs in a lane and a stand-alone program runs under the host sanitizers
 // (tools/value_host_check.cpp).  Kept apart from the kernels for that program's sake.
 #ifndef QTTT_SELFPLAY_VALUE_HOST_H
 #define QTTT_SELFPLAY_VALUE_HOST_H
-#include <stdint.h>
-#include "qttt.h"
+#include "qttt_checks.h"
 
 #ifdef __HIPCC__
 #define QTTT_VALUE_HD __host__ __device__
@@ -15,17 +14,16 @@
 
 namespace {
 
-inline bool value_misaligned(const void *p, unsigned bytes) { return ((uintptr_t)p & (bytes - 1u)) != 0; }
 inline bool value_lambda_bad(double lambda) { return !(lambda >= 0.0 && lambda <= 1.0); }      // NaN fails both
 
 // `work`: the call has something to launch (games > 0)
 inline int value_record_check(const void *tree, int64_t games, int64_t capacity, int ply, const uint8_t *length, const float *q,
                               const float *v, bool &work) {
     work = false;
-    if (games < 0 || capacity < 1 || capacity > QTTT_TREE_MAX_CAPACITY || ply > QTTT_SELFPLAY_ROWS - 1) return QTTT_ERR_SIZE;
+    if (tree_size_bad(games, capacity) || ply > QTTT_SELFPLAY_ROWS - 1) return QTTT_ERR_SIZE;
     if (games == 0) return 0;
     if (!tree || !length || !q || !v) return QTTT_ERR_NULL;
-    if (value_misaligned(tree, 16) || value_misaligned(q, 4) || value_misaligned(v, 4)) return QTTT_ERR_ACTION;
+    if (misaligned(tree, 16) || misaligned(q, 4) || misaligned(v, 4)) return QTTT_ERR_ACTION;
     work = true;
     return 0;
 }
@@ -36,7 +34,7 @@ inline int value_targets_check(int64_t games, int mode, double lambda, const uin
     if (games < 0 || (mode != QTTT_VALUE_MIX && mode != QTTT_VALUE_TD) || value_lambda_bad(lambda)) return QTTT_ERR_SIZE;
     if (games == 0) return 0;
     if (!length || !done || !q || !v) return QTTT_ERR_NULL;
-    if (value_misaligned(q, 4) || value_misaligned(v, 4)) return QTTT_ERR_ACTION;
+    if (misaligned(q, 4) || misaligned(v, 4)) return QTTT_ERR_ACTION;
     work = true;
     return 0;
 }

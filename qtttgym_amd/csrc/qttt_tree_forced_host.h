@@ -1,11 +1,11 @@
-// qttt_tree_forced_host.h — plain C++ without HIP: the argument checks of include/qttt_tree_forced.h in the order that
-// header promises, and the arithmetic of its rules for ONE action (the forced predicate, min(N, F), the pruned visit count),
+// qttt_tree_forced_host.h — plain C++ without HIP: the factor's and the root entry's argument checks (the forced select's and
+// the pruned records' are qttt_selfplay_record_host.h's), and the arithmetic of include/qttt_tree_forced.h's rules for ONE
+// action (the forced predicate, min(N, F), the pruned visit count),
 // which the kernels (qttt_tree_forced_kernels.h) run in a lane and a stand-alone program runs under the host sanitizers
 // (tools/forced_host_check.cpp).  Kept apart from the kernels for that program's sake.
 #ifndef QTTT_TREE_FORCED_HOST_H
 #define QTTT_TREE_FORCED_HOST_H
-#include <stdint.h>
-#include "qttt.h"
+#include "qttt_checks.h"
 
 #ifdef __HIPCC__
 #define QTTT_FORCED_HD __host__ __device__
@@ -15,61 +15,16 @@
 
 namespace {
 
-inline bool forced_misaligned(const void *p, unsigned bytes) { return ((uintptr_t)p & (bytes - 1u)) != 0; }
-inline bool forced_finite(double x) { return x - x == 0.0; }                            // false for NaN and the infinities
-inline bool forced_k_bad(double k) { return !(forced_finite(k) && k >= 0.0); }
-inline bool forced_tree_size_bad(int64_t games, int64_t capacity) {
-    return games < 0 || capacity < 1 || capacity > QTTT_TREE_MAX_CAPACITY;
-}
+inline bool forced_k_bad(double k) { return !(is_finite(k) && k >= 0.0); }
 
 // `work`: the call has something to launch (games > 0)
-inline int forced_select_check(const void *tree, int64_t games, int64_t capacity, uint32_t rollout_idx0, int leaves,
-                               int64_t board_offset, double virtual_loss, const void *paths, const void *leaf_state,
-                               double forced_k, bool &work) {
-    work = false;
-    if (forced_tree_size_bad(games, capacity) || board_offset < 0 || leaves < 1 || leaves > QTTT_TREE_MAX_LEAVES ||
-        games > INT64_MAX / (256 * (int64_t)QTTT_TREE_MAX_LEAVES) ||
-        (uint64_t)rollout_idx0 + (uint64_t)leaves > QTTT_TREE_MAX_ROLLOUTS || !forced_finite(virtual_loss) || virtual_loss < 0.0 ||
-        forced_k_bad(forced_k))
-        return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (!tree || !paths || !leaf_state) return QTTT_ERR_NULL;
-    if (forced_misaligned(tree, 16) || forced_misaligned(paths, 16)) return QTTT_ERR_ACTION;
-    work = true;
-    return 0;
-}
-
 inline int forced_root_check(const void *tree, int64_t games, int64_t capacity, double forced_k, double c_puct,
                              const int32_t *n_pruned, bool &work) {
     work = false;
-    if (forced_tree_size_bad(games, capacity) || forced_k_bad(forced_k) || !forced_finite(c_puct)) return QTTT_ERR_SIZE;
+    if (tree_size_bad(games, capacity) || forced_k_bad(forced_k) || !is_finite(c_puct)) return QTTT_ERR_SIZE;
     if (games == 0) return 0;
     if (!tree) return QTTT_ERR_NULL;
-    if (forced_misaligned(tree, 16) || forced_misaligned(n_pruned, 4)) return QTTT_ERR_ACTION;
-    work = true;
-    return 0;
-}
-
-// the lockstep record (stream = false: ply in 0..9) and the stream record (stream = true: draw_index below the bound)
-struct ForcedRecordArgs {
-    const void *tree, *states, *pi, *mask, *done, *v, *action36, *length, *winner, *actions;
-};
-inline int forced_record_check(const ForcedRecordArgs &p, int64_t games, int64_t capacity, bool stream, int ply,
-                               uint32_t draw_index, uint32_t n_rollouts, double alpha, double v_first, double v_second,
-                               int64_t board_offset, double temperature, int sample_plies, double forced_k, double c_puct,
-                               bool &work) {
-    work = false;
-    if (forced_tree_size_bad(games, capacity) || (!stream && (ply < 0 || ply >= QTTT_SELFPLAY_ROWS)) ||
-        (stream && draw_index >= QTTT_SELFPLAY_MAX_MOVE_DRAWS) || n_rollouts == 0u || !forced_finite(alpha) || alpha <= 0.0 ||
-        !forced_finite(v_first) || !forced_finite(v_second) || board_offset < 0 || !forced_finite(temperature) ||
-        temperature <= 0.0 || sample_plies < 0 || sample_plies > QTTT_SELFPLAY_ROWS || forced_k_bad(forced_k) ||
-        !forced_finite(c_puct))
-        return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (!p.tree || !p.states || !p.pi || !p.mask || !p.done || !p.v || !p.action36 || !p.length || !p.winner || !p.actions)
-        return QTTT_ERR_NULL;
-    if (forced_misaligned(p.tree, 16) || forced_misaligned(p.states, 16) || forced_misaligned(p.pi, 8) || forced_misaligned(p.v, 4))
-        return QTTT_ERR_ACTION;
+    if (misaligned(tree, 16) || misaligned(n_pruned, 4)) return QTTT_ERR_ACTION;
     work = true;
     return 0;
 }

@@ -57,15 +57,10 @@ class Reanalyser(LibCaller):
                              "and the reference's (1, 0) is not zero-sum, so the mixed v would be on two scales")
         self._open(sp.device)
         self.sp, self.ring = sp, ring
-        R = sp.n_rollouts
         # the recorder: sp's settings for n games, without the exploration a reanalysis has no move for
-        self.recorder = SelfPlay(self.n, n_rollouts=R, num_simulations=sp.num_simulations, net=sp.net, alpha=sp.alpha,
-                                 c_puct=sp.c_puct, value_targets=(sp.v_first, sp.v_second), seed=self.seed, device=sp.device,
-                                 leaf_eval=sp.leaf_eval, leaves=sp.leaves, virtual_loss=sp.virtual_loss,
-                                 eval_symmetries=sp.eval_symmetries, root_policy=sp.root_policy,
-                                 max_considered=sp.max_considered, c_visit=sp.c_visit, c_scale=sp.c_scale,
-                                 exact_from=sp.exact_from, exact_targets=sp.exact_targets, exact_policy=sp.exact_policy,
-                                 prove=sp.prove, forced_playouts=sp.forced_playouts, prune_targets=sp.prune_targets)
+        self.recorder = SelfPlay(self.n, n_rollouts=sp.n_rollouts, alpha=sp.alpha, value_targets=(sp.v_first, sp.v_second),
+                                 seed=self.seed, device=sp.device, exact_targets=sp.exact_targets,
+                                 exact_policy=sp.exact_policy, prune_targets=sp.prune_targets, **sp.search_kwargs())
         self.env =VecEnv(self.n, device=self.device)
         self.tree = self.new_tree(self.tree_seed(0))
         self.batch = self.recorder.new_batch()
@@ -79,11 +74,7 @@ class Reanalyser(LibCaller):
         """A TreeSearch of n games with the SelfPlay's search settings and the nodes of one searched ply: the root, two
         per rollout, one to spare (SelfPlay's 2 * n_rollouts + 1 per ply, and the root)."""
         sp = self.recorder
-        return TreeSearch(self.n, capacity=2 * sp.n_rollouts + 2, num_simulations=sp.num_simulations, c_puct=sp.c_puct,
-                          net=sp.net, seed=seed, device=self.device, leaf_eval=sp.leaf_eval, leaves=sp.leaves,
-                          virtual_loss=sp.virtual_loss, eval_symmetries=sp.eval_symmetries, root_policy=sp.root_policy,
-                          max_considered=sp.max_considered, c_visit=sp.c_visit, c_scale=sp.c_scale, exact_from=sp.exact_from,
-                          prove=sp.prove, forced_playouts=sp.forced_playouts)
+        return TreeSearch(self.n, capacity=2 * sp.n_rollouts + 2, seed=seed, device=self.device, **sp.search_kwargs())
 
     def run(self, start=None):
         """One reanalysis of n positions, without a host synchronisation: gather a window (start: ReplayBuffer.gather's) ->

@@ -333,6 +333,16 @@ class SelfPlay(LibCaller):
                    batch.length.data_ptr(), batch.q.data_ptr(), batch.v.data_ptr())
         return batch.q
 
+    # mode -> (the entry's suffix, what it takes after the outputs); draw: (the draw index,) in the per-game form, else ().
+    # The pruned record takes the sampled record's arguments (sample_plies = 0: no draw is taken), then the prune's.
+    _RECORD_MODES = {
+        "plain": ("", lambda sp, t, draw: ()),
+        "sampled": ("_sampled", lambda sp, t, draw: (t.seed, t.board_offset, sp.temperature, sp.sample_plies) + draw),
+        "pruned": ("_pruned", lambda sp, t, draw: (t.seed, t.board_offset, sp.temperature, sp.sample_plies) + draw
+                   + (sp.forced_playouts, t.c_puct)),
+        "gumbel": ("_gumbel", lambda sp, t, draw: (t._gumbel["rec"].data_ptr(), t.c_visit, t.c_scale)),
+    }
+
     def record(self, tree, ply, batch, draw_index=None):
         """One qttt_selfplay_record: the roots of `tree` become row `ply` of `batch`; returns batch.actions, the move
         to step with.  With sample_plies > 0 it is qttt_selfplay_record_sampled, drawing with the tree's seed and
@@ -355,37 +365,27 @@ class SelfPlay(LibCaller):
             raise ValueError("the sampled stream record needs a draw_index")
         if self.prune_targets and tree.root_policy == "gumbel":
             raise ValueError("the pruned record needs a tree searched with the PUCT root")
-        args = (tree.tree.data_ptr(), G, tree.capacity) + (() if per_game else (int(ply),)) + (
-            self.n_rollouts, self.alpha, self.v_first, self.v_second,
-            batch.states.data_ptr(), batch.pi.data_ptr(), batch.mask.data_ptr(), batch.done.data_ptr(),
-            batch.v.data_ptr(), batch.action36.data_ptr(), batch.length.data_ptr(), batch.winner.data_ptr(),
-            batch.actions.data_ptr())
-        entry = "qttt_selfplay_record_stream" if per_game else "qttt_selfplay_record"
-        if self.root_policy == "gumbel":
-            if tree.root_policy != "gumbel" or tree._gumbel is None:
-                raise ValueError("the Gumbel record needs a tree searched with root_policy=\"gumbel\"")
-            self._call(entry + "_gumbel", *args, tree._gumbel["rec"].data_ptr(), tree.c_visit, tree.c_scale)
-        elif self.prune_targets:       # the sampled record's arguments (sample_plies = 0: no draw is taken), then the prune's
-            self._call(entry + "_pruned", *args, tree.seed, tree.board_offset, self.temperature, self.sample_plies,
-                       *((int(draw_index or 0),) if per_game else ()), self.forced_playouts, tree.c_puct)
-        elif sampled:
-            self._call(entry + "_sampled", *args, tree.seed, tree.board_offset, self.temperature, self.sample_plies,
-                       *((int(draw_index),) if per_game else ()))
-        else:
-            self._call(entry, *args)
+        mode = "gumbel" if self.root_policy == "gumbel" else "pruned" if self.prune_targets else "sampled" if sampled else "plain"
+        if mode == "gumbel" and (tree.root_policy != "gumbel" or tree._gumbel is None):
+            raise ValueError("the Gumbel record needs a tree searched with root_policy=\"gumbel\"")
+        suffix, extra = self._RECORD_MODES[mode]
+        self._call(("qttt_selfplay_record_stream" if per_game else "qttt_selfplay_record") + suffix,
+                   tree.tree.data_ptr(), G, tree.capacity, *(() if per_game else (int(ply),)),
+                   self.n_rollouts, self.alpha, self.v_first, self.v_second, *self._staging(batch, SelfPlayBatch._FIELDS),
+                   *extra(self, tree, (int(draw_index or 0),) if per_game else ()))
         return batch.actions
+
+    def search_kwargs(self):
+        """The search keywords that TreeSearch takes from a SelfPlay: what its trees, and a Reanalyser's, are built with."""
+        return {k: getattr(self, k) for k in (
+            "num_simulations", "c_puct", "net", "leaf_eval", "leaves", "virtual_loss", "eval_symmetries", "root_policy",
+            "max_considered", "c_visit", "c_scale", "exact_from", "prove", "forced_playouts")}
 
     def _new_game_objects(self, s):
         """The environment (seed s) and the trees (seed 2 s + 1) of a play() or a stream, the trees reset at the empty
         boards."""
-        G = self.num_games
-        env = VecEnv(G, device=self.device, seed=s)
-        tree = TreeSearch(G, capacity=self.capacity, num_simulations=self.num_simulations,
-                          c_puct=self.c_puct, net=self.net, seed=2 * s + 1, device=self.device,
-                          leaf_eval=self.leaf_eval, leaves=self.leaves, virtual_loss=self.virtual_loss,
-                          eval_symmetries=self.eval_symmetries, root_policy=self.root_policy,
-                          max_considered=self.max_considered, c_visit=self.c_visit, c_scale=self.c_scale,
-                          exact_from=self.exact_from, prove=self.prove, forced_playouts=self.forced_playouts)
+        env = VecEnv(self.num_games, device=self.device, seed=s)
+        tree = TreeSearch(self.num_games, capacity=self.capacity, seed=2 * s + 1, device=self.device, **self.search_kwargs())
         tree.reset(env)
         return env, tree
 

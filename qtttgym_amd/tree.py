@@ -286,25 +286,8 @@ class TreeSearch(LibCaller):
         # a single rollout: the fused value rollout, or — under eval_symmetries or exact_from — a round of one leaf
         rounds_only = self.eval_symmetries is not None or self.exact_from is not None
         single = (lambda: self._round(1)) if rounds_only else self._rollout
-        if self.root_policy == "gumbel":
-            if r and self._fresh:
-                single()
-                self._bound += 2
-                r -= 1
-                self._fresh = False
-            if r:
-                if self.gumbel_idx >= _native.TREE_MAX_GUMBEL:
-                    raise ValueError("%d Gumbel roots since reset: the bound is %d (draw indices)"
-                                     % (self.gumbel_idx, _native.TREE_MAX_GUMBEL))
-                self._gumbel_begin(r)
-            elif self._gumbel is not None:
-                self._gumbel["n"] = 0     # no budget: no Gumbel state of this root
-            K = self.leaves
-            for k in [K] * (r // K) + [r % K] * (r % K > 0):
-                self._gumbel_round(k)
-                self._bound += 2 * k
-            return
-        if self.leaves == 1 and self.forced_playouts is None:
+        gumbel = self.root_policy == "gumbel"
+        if self.leaves == 1 and self.forced_playouts is None and not gumbel:
             for _ in range(r):
                 single()
                 self._bound += 2
@@ -314,9 +297,16 @@ class TreeSearch(LibCaller):
             self._bound += 2
             r -= 1
             self._fresh = False
-        K = self.leaves
+        if gumbel and r:
+            if self.gumbel_idx >= _native.TREE_MAX_GUMBEL:
+                raise ValueError("%d Gumbel roots since reset: the bound is %d (draw indices)"
+                                 % (self.gumbel_idx, _native.TREE_MAX_GUMBEL))
+            self._gumbel_begin(r)
+        elif gumbel and self._gumbel is not None:
+            self._gumbel["n"] = 0     # no budget: no Gumbel state of this root
+        one_round, K = (self._gumbel_round if gumbel else self._round), self.leaves
         for k in [K] * (r // K) + [r % K] * (r % K > 0):
-            self._round(k)
+            one_round(k)
             self._bound += 2 * k
 
     def _round_buffers(self, k):
@@ -354,23 +344,25 @@ class TreeSearch(LibCaller):
         if self.prove:
             self._call("qttt_tree_prove", tree, G, cap, k, b["paths"].data_ptr(), b["proved"].data_ptr())
 
-    def _round(self, k):
-        """One round of k rollouts (1..TREE_MAX_LEAVES) through the leaf-parallel entries, without contemplate's bounds:
-        k descents per game under virtual loss, one evaluation of the G * k leaves, their backup."""
+    def _round(self, k, g=None):
+        """One round of k rollouts (1..TREE_MAX_LEAVES) through the leaf-parallel entries, without contemplate's bounds: k descents
+        per game under virtual loss, one evaluation of the G * k leaves, their backup.  g: _gumbel_round's buffers, its select."""
         k = int(k)
         if not 1 <= k <= _native.TREE_MAX_LEAVES:
             raise ValueError("a round holds 1..%d leaves" % _native.TREE_MAX_LEAVES)
         if self.leaf_eval != "value":
             raise ValueError('a leaf-parallel round needs leaf_eval="value"')
         b = self._round_buffers(k)
-        G, cap, tree = self.num_games, self.capacity, self.tree.data_ptr()
-        args = (tree, G, cap, self.seed, self.rollout_idx, k, self.board_offset, self.c_puct, self.virtual_loss,
-                b["paths"].data_ptr(), b["leaf"].state.data_ptr())
-        # a root that may lack priors (the single rollout after a reset() or sync()) is never asked the rule
-        if self.forced_playouts is None or self._fresh:
-            self._call("qttt_tree_select_batch", *args)
+        if g is not None:
+            entry, rule = "qttt_tree_select_batch_gumbel", (g["rec"].data_ptr(), g["table"].data_ptr(), g["n"], g["sim"],
+                                                            self.c_visit, self.c_scale)
+        elif self.forced_playouts is None or self._fresh:
+            # a root that may lack priors (the single rollout after a reset() or sync()) is never asked the forced rule
+            entry, rule = "qttt_tree_select_batch", ()
         else:
-            self._call("qttt_tree_select_batch_forced", *args, self.forced_playouts)
+            entry, rule = "qttt_tree_select_batch_forced", (self.forced_playouts,)
+        self._call(entry, self.tree.data_ptr(), self.num_games, self.capacity, self.seed, self.rollout_idx, k,
+                   self.board_offset, self.c_puct, self.virtual_loss, b["paths"].data_ptr(), b["leaf"].state.data_ptr(), *rule)
         b["leaf"].evaluate(self.net, out=b["out"], symmetries=self.eval_symmetries)
         self._backup_round(b, k)
         self.rollout_idx += k
@@ -419,14 +411,7 @@ class TreeSearch(LibCaller):
         k, g = int(k), self._gumbel
         if g is None or not 1 <= k <= _native.TREE_MAX_LEAVES or g["sim"] + k > g["n"]:
             raise ValueError("a Gumbel round holds 1..%d leaves within the budget of the last begin" % _native.TREE_MAX_LEAVES)
-        b = self._round_buffers(k)
-        G, cap, tree = self.num_games, self.capacity, self.tree.data_ptr()
-        self._call("qttt_tree_select_batch_gumbel", tree, G, cap, self.seed, self.rollout_idx, k, self.board_offset,
-                   self.c_puct, self.virtual_loss, b["paths"].data_ptr(), b["leaf"].state.data_ptr(), g["rec"].data_ptr(),
-                   g["table"].data_ptr(), g["n"], g["sim"], self.c_visit, self.c_scale)
-        b["leaf"].evaluate(self.net, out=b["out"], symmetries=self.eval_symmetries)
-        self._backup_round(b, k)
-        self.rollout_idx += k
+        self._round(k, g)
         g["sim"] += k
 
     def _gumbel_root(self, choose=None, pi=None, q_completed=None):
