@@ -66,10 +66,11 @@
 // qttt_replay_priority_kernels.h (prioritised replay: the priority table's sums, the guarded write-back, the proportional draw
 // on the sample kernel's row functions) with qttt_replay_priority_host.h (host only and free of HIP: layout, guard, quantiser);
 // qttt_selfplay_stream_kernels.h (continuous self-play: the harvest of finished games and their restart in place);
-// qttt_solve_kernels.h (the exact endgame solver: the full expectimax tree of a late position, a workgroup per board);
-// qttt_tree_exact_kernels.h (exact leaves in the search trees: a lane per path record, the solver's recursion for the leaves
-// that need it); qttt_selfplay_exact_kernels.h (exact targets for the late rows of a self-play batch: a lane per staging row,
-// the same recursion, every action's value kept for the policy); qttt_tree_prove_kernels.h (proven interior nodes: a round's
+// qttt_solve_kernels.h (the exact endgame solver: the full expectimax tree of a late position, a workgroup per board; and what
+// the kernels that call its recursion on many small boards share: table fill, root classification, the workgroup's list of
+// boards and its item loop); qttt_tree_exact_kernels.h (exact leaves in the search trees: a lane per path record, on that list);
+// qttt_selfplay_exact_kernels.h (exact targets for the late rows of a self-play batch: a lane per staging row, on that list,
+// every action's value kept for the policy); qttt_tree_prove_kernels.h (proven interior nodes: a round's
 // records walked upwards, a wave per game, integers only, and the roots' exact q);
 // qttt_selfplay_value_kernels.h (search-value targets: the roots' searched value, a wave per game, and the value targets made
 // of it, a lane per game) with qttt_selfplay_value_host.h (free of HIP: the argument checks and one game's row arithmetic).  Host only: qttt_launch.h (launch shape, kernel selection,
@@ -238,6 +239,19 @@ int record_launch(const RecordArgs &a, int64_t games, int64_t capacity, int ply_
     const SelfPlayOut o = selfplay_out(a.states, a.pi, a.mask, a.done, a.v, a.action36, a.length, a.winner, a.actions);
     return launch(selfplay_record_kernel<MODE, STREAM>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, a.tree, games,
                   capacity, ply_or_draw, n_rollouts, alpha, (float)v_first, (float)v_second, o, sampling);
+}
+
+// THE backup of a leaf-parallel round: qttt_tree_backup_batch, and with EXACT the one that honours solved nodes
+template <bool EXACT>
+int backup_batch(void *tree, int64_t games, int64_t capacity, int leaves, const void *paths, const float *leaf_value,
+                 const float *leaf_probs, void *stream) {
+    if (tree_size_bad(games, capacity) || tree_leaves_bad(games, leaves)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, paths, leaf_value, leaf_probs)) return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(paths, 16) || misaligned(leaf_value, 4) || misaligned(leaf_probs, 4))
+        return QTTT_ERR_ACTION;
+    return launch(tree_backup_batch_kernel<EXACT>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (u32)leaves, static_cast<const TreePathRec *>(paths), leaf_value, leaf_probs);
 }
 
 }  // namespace
@@ -890,13 +904,7 @@ int qttt_tree_select_batch(void *tree, int64_t games, int64_t capacity, uint64_t
 
 int qttt_tree_backup_batch(void *tree, int64_t games, int64_t capacity, int leaves, const void *paths,
                            const float *leaf_value, const float *leaf_probs, void *stream) {
-    if (tree_size_bad(games, capacity) || tree_leaves_bad(games, leaves)) return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (any_null(tree, paths, leaf_value, leaf_probs)) return QTTT_ERR_NULL;
-    if (misaligned(tree, 16) || misaligned(paths, 16) || misaligned(leaf_value, 4) || misaligned(leaf_probs, 4))
-        return QTTT_ERR_ACTION;
-    return launch(tree_backup_batch_kernel<false>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
-                  (u32)leaves, static_cast<const TreePathRec *>(paths), leaf_value, leaf_probs);
+    return backup_batch<false>(tree, games, capacity, leaves, paths, leaf_value, leaf_probs, stream);
 }
 
 // ---------------------------------------------------------------- root exploration (include/qttt_tree_explore.h)
@@ -1267,13 +1275,9 @@ int qttt_solve(const void *state, int64_t n, int min_ply, float *value, float *q
     if (!value && !q && !best && !nodes && !status) return 0;                // nothing asked for
     const Planes p = planes(const_cast<void *>(state), n);
     const SolveOut o = {value, q, best, nodes, status};
-    // a workgroup per board; a grid holds at most 2^30 of them
-    constexpr int64_t GRID_MAX = (int64_t)1 << 30;
-    for (int64_t i0 = 0; i0 < n; i0 += GRID_MAX)
-        if (const int rc = launch(solve_kernel, n - i0 < GRID_MAX ? n - i0 : GRID_MAX, SOLVE_BLOCK, stream, (const u64 *)p.P,
-                                  (const u64 *)p.Q, i0, min_ply, o))
-            return rc;
-    return 0;
+    return chunked_launch(n, [&](int64_t i0, int64_t grid) {           // a workgroup per board
+        return launch(solve_kernel, grid, SOLVE_BLOCK, stream, (const u64 *)p.P, (const u64 *)p.Q, i0, min_ply, o);
+    });
 }
 
 // ---------------------------------------------------------------- exact leaves in the search trees (include/qttt_tree_exact.h)
@@ -1288,26 +1292,16 @@ int qttt_tree_solve_leaves(void *tree, int64_t games, int64_t capacity, int leav
         return QTTT_ERR_ACTION;
     const int64_t rows = games * leaves;
     const Planes l = planes(const_cast<void *>(leaf_state), rows);
-    // a lane per record; a grid holds at most 2^30 workgroups
-    constexpr int64_t GRID_MAX = (int64_t)1 << 30;
-    const int64_t blocks = ceil_div(rows, EXACT_RECORDS);
-    for (int64_t b0 = 0; b0 < blocks; b0 += GRID_MAX)
-        if (const int rc = launch(tree_solve_leaves_kernel, blocks - b0 < GRID_MAX ? blocks - b0 : GRID_MAX, EXACT_BLOCK, stream,
-                                  tree, games, capacity, (u32)leaves, static_cast<const TreePathRec *>(paths), (const u64 *)l.P,
-                                  (const u64 *)l.Q, b0 * EXACT_RECORDS, rows, min_ply, leaf_value, leaf_exact))
-            return rc;
-    return 0;
+    return chunked_launch(ceil_div(rows, SOLVE_LIST_RECORDS), [&](int64_t b0, int64_t grid) {     // a lane per record
+        return launch(tree_solve_leaves_kernel, grid, SOLVE_BLOCK, stream, tree, games, capacity, (u32)leaves,
+                      static_cast<const TreePathRec *>(paths), (const u64 *)l.P, (const u64 *)l.Q, b0 * SOLVE_LIST_RECORDS, rows,
+                      min_ply, leaf_value, leaf_exact);
+    });
 }
 
 int qttt_tree_backup_batch_exact(void *tree, int64_t games, int64_t capacity, int leaves, const void *paths,
                                  const float *leaf_value, const float *leaf_probs, void *stream) {
-    if (tree_size_bad(games, capacity) || tree_leaves_bad(games, leaves)) return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (any_null(tree, paths, leaf_value, leaf_probs)) return QTTT_ERR_NULL;
-    if (misaligned(tree, 16) || misaligned(paths, 16) || misaligned(leaf_value, 4) || misaligned(leaf_probs, 4))
-        return QTTT_ERR_ACTION;
-    return launch(tree_backup_batch_kernel<true>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
-                  (u32)leaves, static_cast<const TreePathRec *>(paths), leaf_value, leaf_probs);
+    return backup_batch<true>(tree, games, capacity, leaves, paths, leaf_value, leaf_probs, stream);
 }
 
 // ---------------------------------------------------------------- proven interior nodes (include/qttt_tree_prove.h)
@@ -1341,14 +1335,10 @@ int qttt_selfplay_exact_targets(const void *states, int64_t games, int min_ply, 
     if (any_null(states, length, done, mask) || any_null(pi, v)) return QTTT_ERR_NULL;
     if (misaligned(states, 16) || misaligned(pi, 8) || misaligned(v, 4)) return QTTT_ERR_ACTION;
     const ExactTargets o = {static_cast<const u64 *>(states), rows, length, done, pi, v, exact};
-    // a lane per record; a grid holds at most 2^30 workgroups
-    constexpr int64_t GRID_MAX = (int64_t)1 << 30;
-    const int64_t blocks = ceil_div((int64_t)QTTT_SELFPLAY_ROWS * games, TARGETS_RECORDS);
-    for (int64_t b0 = 0; b0 < blocks; b0 += GRID_MAX)
-        if (const int rc = launch(selfplay_exact_targets_kernel, blocks - b0 < GRID_MAX ? blocks - b0 : GRID_MAX, TARGETS_BLOCK,
-                                  stream, o, games, b0 * TARGETS_RECORDS, min_ply, policy))
-            return rc;
-    return 0;
+    const int64_t blocks = ceil_div((int64_t)QTTT_SELFPLAY_ROWS * games, SOLVE_LIST_RECORDS);
+    return chunked_launch(blocks, [&](int64_t b0, int64_t grid) {                                 // a lane per record
+        return launch(selfplay_exact_targets_kernel, grid, SOLVE_BLOCK, stream, o, games, b0 * SOLVE_LIST_RECORDS, min_ply, policy);
+    });
 }
 
 // ---------------------------------------------------------------- reanalysis of the replay ring (include/qttt_replay_reanalyse.h)

@@ -1,5 +1,5 @@
 // qttt_launch.h — host only: what every C ABI entry of qttt_kernels.hip is written with.  The step's launch-shape
-// table, the compile-time dispatch of runtime flags (with_bools / with_int), the one launch form, and the observation
+// table, the compile-time dispatch of runtime flags (with_bools / with_int), the one launch form and its chunked loop, and the observation
 // buffers' check (the predicates of every argument check are qttt_checks.h's).
 #ifndef QTTT_LAUNCH_H
 #define QTTT_LAUNCH_H
@@ -109,6 +109,14 @@ inline int launch(void (*kernel)(P...), int64_t groups, int block, void *stream,
     hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3((unsigned)block), 0, (hipStream_t)stream, args...);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
+}
+// `blocks` workgroups in grids of at most 2^30: launch_chunk(first block, grid) per chunk, in order, up to the first failure.
+template <typename F>
+inline int chunked_launch(int64_t blocks, F &&launch_chunk) {
+    constexpr int64_t GRID_MAX = (int64_t)1 << 30;
+    for (int64_t b0 = 0; b0 < blocks; b0 += GRID_MAX)
+        if (const int rc = launch_chunk(b0, blocks - b0 < GRID_MAX ? blocks - b0 : GRID_MAX)) return rc;
+    return 0;
 }
 
 // Runs of at most CAP plies from step_idx0 on, one launch each (the plies' launch keys travel as a kernel argument, KEYS:

@@ -6,6 +6,8 @@
 // collapse are exact integer operations and no order of evaluation can change a bit.  Nothing is pruned.
 // The rules are the shared ones: expand_pair and pair_action (qttt_search_core.h), update_winner_from_step /
 // lite_update_winner and the legal-mask table (qttt_board_forms.h), leaf_turn_signed and reward_of_winner.
+// Shared with tree_solve_leaves_kernel and selfplay_exact_targets_kernel, which call the recursion on many small boards:
+// SolveList, the workgroup's list of boards with its table fill, its roots' classification and its item loop.
 #ifndef QTTT_SOLVE_KERNELS_H
 #define QTTT_SOLVE_KERNELS_H
 #include "qttt_solve.h"
@@ -76,6 +78,94 @@ __device__ __forceinline__ int solve_position(u64 P, u64 Q, u64 legal, const Sol
     return best;
 }
 
+// ---------------------------------------------------------------- many small boards: a list per workgroup
+// The kernels that solve the records of a batch (a round's leaves, a self-play batch's rows) have another workload than
+// solve_kernel: most records need nothing, and a board that does need enumeration has under 5 * 10^4 positions at six
+// moves played and at most 2 000 from seven on, where solve_kernel's boards have up to 10^7.  So:
+// Mapping.  ONE LANE PER RECORD, 64 records per SOLVE_BLOCK-thread workgroup (its first wavefront classifies, all four
+// solve); the grid is ceil(records / 64), known on the host.  64 and not 256 records: a round of 4 096 games * 8 leaves is
+// then 512 workgroups, two per CU, where 128 would leave half the device idle while each ran several boards' items in turn.
+//   1. classify (the kernel's own): a record that needs no enumeration is finished by its lane, at the cost of that lane's
+//      loads and stores; a lane whose board needs it appends the board to the list (an integer LDS atomic hands out the slot).
+//   2. one barrier; a workgroup whose list is empty returns.  The others fill the tables, once.
+//   3. root() of every listed board, then the work item is (listed board, action), 36 per board, taken from an LDS counter
+//      by all 256 lanes; an item is solve_action<SOLVE_LIST_DEPTH> — the recursion above, called, not restated — with the
+//      board in registers, and its 16 Q goes to the kernel's callable: an integer, so there is no floating-point atomic and
+//      no order of evaluation can change a bit.  One level of items, not solve_kernel's two: below a root action of a
+//      six-move board lie at most a few thousand positions, a fraction of a solve_kernel item, and 36 items per board
+//      already spread one board over more than half a wave.
+//   4. write back (the kernel's own): the lane that listed a board writes its row.
+// Every loop is bounded (64 * 36 items, the recursion's depth a constant); no scratch; no wait on another workgroup.
+constexpr int SOLVE_LIST_RECORDS = 64;                           // records per workgroup: one per lane of its first wavefront
+constexpr u32 SOLVE_LIST_ITEMS = (u32)SOLVE_LIST_RECORDS * 36u;  // (listed board, action)
+// a listed board has SOLVE_LIST_MIN_PLY moves played or more (each kernel asserts its header's), its children one more
+constexpr int SOLVE_LIST_MIN_PLY = 6;
+constexpr int SOLVE_LIST_DEPTH = 9 - SOLVE_LIST_MIN_PLY - 1;
+static_assert(SOLVE_LIST_DEPTH >= 0 && SOLVE_LIST_DEPTH <= SOLVE_ITEM_DEPTH, "the recursion is no deeper than solve_kernel's");
+
+// The root of a listed board: its winner and its legal mask, the mask 0 for a leaf of the solver (a terminal position, or
+// one without a legal action: its value is solve_leaf_value(winner, P)).
+struct SolveRoot {
+    int winner;
+    u64 legal;
+};
+
+// Holds its tables too: ONE __shared__ variable per kernel, aligned(16) for the line table, and no LDS padding inside.
+struct SolveList {
+    uint8_t lut[LINE_LUT_BYTES];
+    u64 ltbl[512];
+    uint16_t act[36];
+    u64 boardP[SOLVE_LIST_RECORDS], boardQ[SOLVE_LIST_RECORDS], boardLegal[SOLVE_LIST_RECORDS];
+    u32 n_boards, next_item;
+
+    // empty, for every lane after the barrier
+    __device__ __forceinline__ void open() {
+        if (threadIdx.x == 0u) n_boards = next_item = 0u;
+        __syncthreads();
+    }
+    // the three tables, by all SOLVE_BLOCK lanes; ends with the workgroup barrier
+    __device__ __forceinline__ SolveTables fill_tables() {
+        fill_legal_lut<SOLVE_BLOCK>(ltbl);
+        if (threadIdx.x < 36u) act[threadIdx.x] = (uint16_t)pair_action<false>(threadIdx.x);
+        fill_line_lut<SOLVE_BLOCK>(lut);
+        return {lut, ltbl, act};
+    }
+    // by a classifying lane, once at most: the board's slot, < SOLVE_LIST_RECORDS
+    __device__ __forceinline__ int append(u64 P, u64 Q) {
+        const int slot = (int)atomicAdd(&n_boards, 1u);
+        boardP[slot] = P;
+        boardQ[slot] = Q;
+        return slot;
+    }
+    // by the lane b < n_boards, before items(): the listed board's legal mask into the list, none for a leaf of the solver
+    __device__ __forceinline__ SolveRoot root(u32 b, const SolveTables &t) {
+        int winner, terminal;
+        lite_update_winner(lite_unpack(boardP[b]), t.lut, winner, terminal);
+        const u64 legal = t.legal[classical_with_autofill(boardP[b])];
+        boardLegal[b] = terminal ? 0ull : legal;
+        return {winner, terminal ? 0ull : legal};
+    }
+    // by all lanes, between two workgroup barriers: f(b, a, 16 Q) for every action a of every listed board b, once each;
+    // SOLVE_NO_Q for an action that is not legal or has no child
+    template <typename F>
+    __device__ __forceinline__ void items(const SolveTables &t, F &&f) {
+        __syncthreads();
+        const u32 count = n_boards * 36u;
+        for (u32 it = 0; it < SOLVE_LIST_ITEMS; ++it) {
+            const u32 k = atomicAdd(&next_item, 1u);
+            if (k >= count) break;
+            const u32 b = k / 36u, a = k - b * 36u;
+            int qv = SOLVE_NO_Q;
+            if ((boardLegal[b] >> a) & 1ull) {
+                u32 nodes = 0u;
+                qv = solve_action<SOLVE_LIST_DEPTH>(boardP[b], boardQ[b], a, t, nodes);
+            }
+            f(b, a, qv);
+        }
+        __syncthreads();
+    }
+};
+
 struct SolveOut {
     float *value;               // [n]
     float *q;                   // [n, 36]
@@ -86,7 +176,7 @@ struct SolveOut {
 
 __device__ __forceinline__ float solve_to_float(int v16) { return (float)v16 * (1.0f / (float)SOLVE_ONE); }
 
-// Board i0 + blockIdx.x of the planes pP / pQ.
+// Board i0 + blockIdx.x of the planes pP / pQ.  Its table fill and root classification are spelled out here on purpose.
 __global__ __launch_bounds__(SOLVE_BLOCK) void solve_kernel(const u64 *pP, const u64 *pQ, int64_t i0, int min_ply, SolveOut out) {
     __shared__ __attribute__((aligned(16))) uint8_t lut[LINE_LUT_BYTES];
     __shared__ u64 ltbl[512];

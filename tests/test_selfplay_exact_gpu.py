@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import selfplay_exact_model as M  # noqa: E402
 import test_selfplay_stream_gpu as S  # noqa: E402  (Watch, arrays, assert_ring: the stream tests' own drivers)
 import tree_harness as H  # noqa: E402
-from qtttgym_amd import ReplayBuffer, SelfPlay, Trainer, VecEnv, _native  # noqa: E402
+from qtttgym_amd import ReplayBuffer, SelfPlay, Trainer, _native  # noqa: E402
 from qtttgym_amd.selfplay import SelfPlayBatch  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -230,15 +230,46 @@ def test_fixture_batch_guard_bytes_nullable_exact_and_idempotence(m):
     assert not np.signbit(v[v == 0]).any()                       # never -0.0
 
 
+def test_a_full_list_and_a_one_board_list_in_one_launch():
+    """A hand-built staging batch of 65 games whose row 0 holds 65 distinct boards of tests/golden/solve_positions.npz
+    with six or more moves played and a root that is no leaf; length 1, nothing done.  Record r = t * 65 + g, so records
+    0..63 are one workgroup whose list is full (64 boards, 2 304 items) and record 64 opens a workgroup that lists one
+    board.  Every row of row 0 holds the solver's value and the uniform policy over its argmax set, bit for bit."""
+    G, m = 65, 6
+    with np.load(os.path.join(M.GOLDEN, "solve_positions.npz")) as z:
+        pick = np.flatnonzero((z["played"] >= m) & (z["best"] != 255))[:G]
+        arrays = {k: z[k][pick] for k in M.ARRAYS}
+    assert len(pick) == G
+    env = H.env_from_arrays(arrays)
+    planes = env.state.cpu().numpy().view(np.uint64).reshape(2, -1)[:, :G]
+    assert len({(int(p), int(q)) for p, q in planes.T}) == G      # 65 distinct boards
+    res = env.solve(min_ply=m)
+    assert res.solved.all() and (res.nodes > 1).all()
+    batch = SelfPlayBatch(G, torch.device(DEV), _native.lib().qttt_state_bytes(G))
+    batch.states[0].copy_(env.state)
+    batch.length.fill_(1)
+    rng = np.random.default_rng(11)
+    raws = {}
+    raws["pi"], batch.pi = _guarded((ROWS, G, 36), torch.float64, rng.random((ROWS, G, 36)))
+    raws["v"], batch.v = _guarded((ROWS, G), torch.float32, rng.choice(np.array([-1.0, 0.0, 1.0, 0.3125], np.float32), (ROWS, G)))
+    raws["exact"], exact = _guarded((ROWS, G), torch.uint8)
+    before = {f: getattr(batch, f).clone() for f in ("states", "mask", "done", "length")}
+    pi0, v0 = batch.pi.clone(), batch.v.clone()
+    batch._exact_targets(m, True, None, exact)
+    for raw in raws.values():
+        assert (raw[:GUARD] == SENTINEL).all() and (raw[-GUARD:] == SENTINEL).all()
+    for f, t in before.items():
+        assert torch.equal(getattr(batch, f), t), f
+    assert (exact[0] == 1).all() and not exact[1:].any()
+    assert torch.equal(batch.v[0].view(torch.int32), res.value.view(torch.int32))
+    best = res.q == res.value[:, None]
+    k = best.sum(1, keepdim=True).double()
+    assert (k >= 1).all() and torch.equal(batch.pi[0], torch.where(best, 1.0 / k, torch.zeros_like(k)))
+    assert torch.equal(batch.v[1:].view(torch.int32), v0[1:].view(torch.int32))
+    assert torch.equal(batch.pi[1:].view(torch.int64), pi0[1:].view(torch.int64))
+
+
 # ---------------------------------------------------------------- the stream
-def _env_of_planes(P, Q):
-    n = len(P)
-    stride = (n + 63) & ~63
-    planes = np.zeros((2, stride), dtype=np.uint64)
-    planes[0, :n], planes[1, :n] = P, Q
-    return VecEnv.from_state(torch.from_numpy(planes.view(np.uint8).reshape(-1).copy()).to(DEV), n)
-
-
 @pytest.mark.parametrize("G", [3, 65])
 def test_the_stream_hands_the_ring_the_model_s_rows(G):
     plies, m = 12, 7
@@ -252,7 +283,7 @@ def test_the_stream_hands_the_ring_the_model_s_rows(G):
         assert np.array_equal(fin, fin2) and np.array_equal(hl, hl2)
         pi, v = a["pi"], a["v"]
         if fin.any():
-            boards = [H.export(_env_of_planes(a["states"][t, 0], a["states"][t, 1])) for t in range(ROWS)]
+            boards = [H.export(H.env_of_planes(a["states"][t, 0], a["states"][t, 1])) for t in range(ROWS)]
             pi, v, exact = M.relabel(boards, hl, a["done"], a["mask"], a["pi"].view(np.float64), a["v"].view(np.float32), m, True)
             assert not exact[:, fin == 0].any()                  # a game in progress: nothing relabelled in staging
             relabelled += int(exact.sum())

@@ -3,7 +3,6 @@ trees, solved flags and leaf rows against tests/exact_leaves_model.py's float64 
 VecEnv.solve; W / N at the root against the solver's q (the test that fails without the feature); unchanged bytes where
 nothing is eligible; sync, compact and further search; guard bytes and nullable outputs; self-play and one Gumbel case.
 tests/test_tree_exact_cpu.py asserts, without a GPU, that every search compared here solves nodes."""
-import copy
 import functools
 import os
 
@@ -13,90 +12,23 @@ import torch
 
 import exact_leaves_model as E
 import gumbel_model as GM
-import nn_reference64 as R
 import selfplay_model
+import tree_harness as H
 import tree_layout
 import tree_model
-from tree_harness import DEV, SENTINEL, TAIL, env_from_arrays, export
+from tree_harness import DEV, GUARD, env_from_arrays, export
+from tree_harness import bits32 as _bits, check_exact_tree as _check, env_of_planes as _env_of_planes, exact_net as _net
+from tree_harness import exact_rounds as _rounds, games_view as _view, prefix as _prefix
 
-from qtttgym_amd import PolicyValueNet, SelfPlay, TreeSearch, VecEnv, _native
+from qtttgym_amd import SelfPlay
 from qtttgym_amd.actions import action36_to_pairs
 
 pytestmark = pytest.mark.gpu
-NETS = {"zero": R.zero_state_dict, "greedy": R.greedy_state_dict, "counting": R.counting_state_dict,
-        "sharp": R.sharp_counting_state_dict}
+NETS = H.exact_nets()
 SOLVED, SHIFT, MASK = E.NODE_SOLVED, E.NODE_VALUE_SHIFT, E.NODE_VALUE_MASK
-GUARD = 0xA5
-
-
-@functools.lru_cache(maxsize=None)
-def _net(name):
-    sd = NETS[name]() if name in NETS else R.golden_state_dict(R.load_golden())
-    return PolicyValueNet(sd, device=DEV, dtype=torch.float32)
-
-
-def _evaluate_probs(leaves):
-    env = env_from_arrays({"board": leaves.board, "moves": leaves.moves, "n_moves": leaves.n_moves, "qmask": leaves.qmask,
-                           "n_q": leaves.n_q})
-    return env.evaluate(_net("counting"), rows=("probs",))["probs"].cpu().numpy()
-
-
-@functools.lru_cache(maxsize=None)
-def _model(net, K, M, capacity):
-    return E.searched(NETS[net](), K, M, capacity, probs_of=_evaluate_probs if net == "counting" else None)
-
-
-@functools.lru_cache(maxsize=None)
-def _stages(net, K, M):
-    return E.searched(NETS[net](), K, M, E.CAPACITY, stages=True)
-
-
-def _view(m, G):
-    v = copy.copy(m)
-    v.games = m.games[:G]
-    return v
-
-
-def _prefix(arrays, G):
-    return {k: np.asarray(v)[:G] for k, v in arrays.items()}
-
-
-def _search(arrays, capacity, net, **kw):
-    env = env_from_arrays(arrays)
-    G = env.num_envs
-    t = TreeSearch(G, capacity=capacity, net=net, seed=E.SEED, board_offset=E.OFFSET, device=DEV, leaf_eval="value", **kw)
-    t.tree = torch.full((tree_layout.tree_bytes(G, capacity) + TAIL,), SENTINEL, dtype=torch.uint8, device=DEV)
-    t.reset(env)
-    return t, env
-
-
-def _rounds(t, r):
-    """TreeSearch.contemplate's schedule under exact_from, without the host's node bound (the pool that overflows)."""
-    if r and t._fresh:
-        t._round(1)
-        r -= 1
-        t._fresh = False
-    K = t.leaves
-    for k in [K] * (r // K) + [r % K] * (r % K > 0):
-        t._round(k)
-
-
-def _check(t, m, compacted=False):
-    """The whole tree buffer against the model: the solved bit and the value bits of every live node against the model's
-    solved nodes, then — those bits taken out of a copy — every other byte by tests/tree_layout.py's comparison."""
-    G, cap = t.num_games, t.capacity
-    buf = t.tree.cpu().numpy().copy()
-    games, nodes, _, _ = tree_layout.decode(buf, G, cap)
-    want = np.zeros((G, cap), dtype=np.uint32)
-    for g, flags in enumerate(m.solved_flags()):
-        for i, f in flags.items():
-            want[g, i] = f
-    live = np.arange(cap)[None, :] < games["used"][:, None]
-    got = nodes["flags"] & np.uint32(SOLVED | MASK)
-    assert np.array_equal(got[live], want[live]), np.argwhere((got != want) & live)[:8].tolist()
-    assert np.array_equal(t.solved_count().cpu().numpy(), m.solved_counts())
-    nodes["flags"][live] &= ~np.uint32(SOLVED | MASK)
-    return tree_layout.assert_tree_equals_model(buf, G, cap, m, SENTINEL, DEV, compacted=compacted)
+_model = functools.partial(H.exact_model, E)
+_stages = functools.partial(H.exact_stages, E)
+_search = functools.partial(H.exact_search, E)
 
 
 # ---------------------------------------------------------------- whole trees under the exact networks
@@ -118,10 +50,6 @@ def test_whole_trees_match_the_model_bit_for_bit(case, G):
 
 
 # ---------------------------------------------------------------- the golden network: rounds in lockstep
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 @pytest.mark.parametrize("K,M", [(1, 7), (4, 6), (8, 7)])
 def test_rounds_in_lockstep_with_the_model_fed_by_evaluate(K, M):
     """Per round the model backs up the device's own evaluate rows; the device's leaf_value / leaf_exact rows after
@@ -156,17 +84,55 @@ def test_rounds_in_lockstep_with_the_model_fed_by_evaluate(K, M):
     assert exact_rows > 0 and m.met["reused"] > 0 and (shared > 0 or K == 1) and m.in_flight() == 0
 
 
+# ---------------------------------------------------------------- a workgroup whose list of boards is full
+def _fresh_rows(m):
+    """Per game and record of the model's round in flight: the leaf is eligible and not yet solved."""
+    return np.array([[bool(m.eligible(st, rec)) and rec["leaf"] not in st["solved"] for rec in m.round[g]]
+                     for g, st in enumerate(m._games)])
+
+
+def _model_at(arrays, K, M):
+    m = E.ExactLeavesModel(1, seed=E.SEED, board_offset=E.OFFSET, capacity=E.CAPACITY, net=NETS["sharp"](), leaves=K, exact_from=M)
+    m.reset(E.boards_of(arrays))
+    return m
+
+
+def test_a_round_whose_aligned_blocks_of_64_records_are_all_fresh_eligible_leaves():
+    """qttt_tree_solve_leaves with full lists: 33 games * 4 leaves, so records 0..63 and 64..127 are two workgroups of
+    64 and records 128..131 a third.  The roots are the fixture's five-move boards, chosen with the model alone: game g
+    takes the first board, cycling from g, whose four leaves of the second round the model finds eligible and unsolved
+    (a game's descents depend on its position and its index only).  After the one-leaf round that gives the roots their
+    priors, every record of the round of four is then a six-move child that needs enumeration."""
+    K, M, G = 4, 6, 33
+    z = E.fixture()
+    five = np.flatnonzero(z["played"] == 5)
+    ok = np.zeros((len(five), G), dtype=bool)
+    for i, p in enumerate(five):
+        m = _model_at({k: z[k][np.full(G, p)] for k in E.ARRAYS}, K, M)
+        m.round_of(1)
+        m.select_batch(K, m.virtual_loss)
+        ok[i] = _fresh_rows(m).all(1)
+    assert ok.any(0).all()
+    pick = [five[next((g + i) % len(five) for i in range(len(five)) if ok[(g + i) % len(five), g])] for g in range(G)]
+    arrays = {k: z[k][np.array(pick)] for k in E.ARRAYS}
+    m = _model_at(arrays, K, M)
+    t, _ = _search(arrays, E.CAPACITY, _net("sharp"), leaves=K, exact_from=M)
+    m.round_of(1)
+    t._round(1)
+    assert int(t.solved_count().sum()) == 0
+    leaves = m.select_batch(K, m.virtual_loss)
+    assert _fresh_rows(m).all()                                   # the model alone: both blocks of 64 are full
+    distinct = np.array([len({rec["leaf"] for rec in m.round[g]}) for g in range(G)])
+    m.backup_batch(m.playouts(leaves), m.priors(leaves))
+    t._round(K)
+    exact = t._rounds[K]["exact"].cpu().numpy()
+    assert exact.shape == (G * K,) and (exact[:128] == 1).all() and np.array_equal(exact, m.last_rows[1])
+    assert np.array_equal(t.solved_count().cpu().numpy(), distinct) and (distinct >= 1).all()   # from 0: none was solved before
+    assert np.array_equal(_bits(t._rounds[K]["out"]["value"].cpu().numpy()), _bits(m.last_rows[0]))
+    _check(t, m)
+
+
 # ---------------------------------------------------------------- solved nodes against the solver
-def _env_of_planes(P, Q):
-    n = len(P)
-    stride = (n + 63) & ~63
-    planes = np.zeros((2, stride), dtype=np.uint64)
-    planes[0, :n], planes[1, :n] = P, Q
-    state = torch.from_numpy(planes.view(np.uint8).reshape(-1).copy()).to(DEV)
-    assert state.numel() == int(_native.lib().qttt_state_bytes(n))
-    return VecEnv.from_state(state, n)
-
-
 @pytest.mark.parametrize("K,M", [(8, 6), (4, 7), (1, 8)])
 def test_every_solved_node_holds_the_solver_s_value_and_is_a_leaf(K, M):
     G = E.G_MAX

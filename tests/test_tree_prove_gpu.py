@@ -4,7 +4,6 @@ float64 model; every solved node against VecEnv.solve; q_exact, root_value_exact
 solver's q, value and best of the roots (the test that pins the rule); unchanged bytes and launches without the keyword;
 sync onto a proven child, compact and further search; guard bytes, nullable outputs and idempotence; one Gumbel search
 and one self-play.  tests/test_tree_prove_cpu.py asserts, without a GPU, what each search compared here proves."""
-import copy
 import functools
 
 import numpy as np
@@ -13,101 +12,25 @@ import torch
 
 import exact_leaves_model as E
 import gumbel_model as GM
-import nn_reference64 as R
 import prove_model as PM
 import selfplay_model
+import tree_harness as H
 import tree_layout
 import tree_model
-from tree_harness import DEV, SENTINEL, TAIL, env_from_arrays, export
+from tree_harness import DEV, GUARD, SENTINEL, TAIL, export
+from tree_harness import bits32 as _bits, env_of_planes as _env_of_planes, exact_net as _net
+from tree_harness import exact_rounds as _rounds, games_view as _view, prefix as _prefix
 
-from qtttgym_amd import PolicyValueNet, SelfPlay, TreeSearch, VecEnv, _native
+from qtttgym_amd import SelfPlay
 from qtttgym_amd.actions import action36_to_pairs
 
 pytestmark = pytest.mark.gpu
-NETS = {"zero": R.zero_state_dict, "greedy": R.greedy_state_dict, "counting": R.counting_state_dict,
-        "sharp": R.sharp_counting_state_dict}
+NETS = H.exact_nets()
 SOLVED, SHIFT, MASK = E.NODE_SOLVED, E.NODE_VALUE_SHIFT, E.NODE_VALUE_MASK
-GUARD = 0xA5
-
-
-@functools.lru_cache(maxsize=None)
-def _net(name):
-    sd = NETS[name]() if name in NETS else R.golden_state_dict(R.load_golden())
-    return PolicyValueNet(sd, device=DEV, dtype=torch.float32)
-
-
-def _evaluate_probs(leaves):
-    env = env_from_arrays({"board": leaves.board, "moves": leaves.moves, "n_moves": leaves.n_moves, "qmask": leaves.qmask,
-                           "n_q": leaves.n_q})
-    return env.evaluate(_net("counting"), rows=("probs",))["probs"].cpu().numpy()
-
-
-@functools.lru_cache(maxsize=None)
-def _model(net, K, M, capacity):
-    return PM.searched(NETS[net](), K, M, capacity, probs_of=_evaluate_probs if net == "counting" else None)
-
-
-@functools.lru_cache(maxsize=None)
-def _stages(net, K, M):
-    return PM.searched(NETS[net](), K, M, PM.CAPACITY, stages=True)
-
-
-def _view(m, G):
-    v = copy.copy(m)
-    v.games = m.games[:G]
-    return v
-
-
-def _prefix(arrays, G):
-    return {k: np.asarray(v)[:G] for k, v in arrays.items()}
-
-
-def _search(arrays, capacity, net, **kw):
-    env = env_from_arrays(arrays)
-    G = env.num_envs
-    t = TreeSearch(G, capacity=capacity, net=net, seed=PM.SEED, board_offset=PM.OFFSET, device=DEV, leaf_eval="value", **kw)
-    t.tree = torch.full((tree_layout.tree_bytes(G, capacity) + TAIL,), SENTINEL, dtype=torch.uint8, device=DEV)
-    t.reset(env)
-    return t, env
-
-
-def _rounds(t, r):
-    """TreeSearch.contemplate's schedule under exact_from, without the host's node bound (the pool that overflows)."""
-    for k in PM.schedule(r, t.leaves, t._fresh):
-        t._round(k)
-        t._fresh = False
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _check(t, m, compacted=False):
-    """The whole tree buffer against the model: the solved bit and the value bits of every live node against the model's
-    solved nodes (proven ones included); the priors row that a proven node keeps under its cleared flag against the row
-    the model kept; then — those bits taken out of a copy and those rows painted over — every other byte by
-    tests/tree_layout.py's comparison (which expects no has-priors flag on a proven node below the root)."""
-    G, cap = t.num_games, t.capacity
-    buf = t.tree.cpu().numpy().copy()
-    games, nodes, priors, _ = tree_layout.decode(buf, G, cap)
-    want = np.zeros((G, cap), dtype=np.uint32)
-    for g, flags in enumerate(m.solved_flags()):
-        for i, f in flags.items():
-            want[g, i] = f
-    live = np.arange(cap)[None, :] < games["used"][:, None]
-    got = nodes["flags"] & np.uint32(SOLVED | MASK)
-    assert np.array_equal(got[live], want[live]), np.argwhere((got != want) & live)[:8].tolist()
-    assert np.array_equal(t.solved_count().cpu().numpy(), m.solved_counts())
-    kept = 0
-    if not compacted:
-        for g, st in enumerate(m.games):
-            for x, row in st["kept"].items():
-                assert np.array_equal(_bits(priors[g, x]), _bits(row)), ("kept priors row", g, x)
-                priors[g, x].view(np.uint8)[:] = SENTINEL
-                kept += 1
-    nodes["flags"][live] &= ~np.uint32(SOLVED | MASK)
-    tree_layout.assert_tree_equals_model(buf, G, cap, m, SENTINEL, DEV, compacted=compacted)
-    return kept
+_model = functools.partial(H.exact_model, PM)
+_stages = functools.partial(H.exact_stages, PM)
+_search = functools.partial(H.exact_search, PM)
+_check = functools.partial(H.check_exact_tree, kept_rows=True)      # and the priors rows that proven nodes keep
 
 
 # ---------------------------------------------------------------- whole trees under the exact networks
@@ -189,16 +112,6 @@ def test_rounds_in_lockstep_with_the_model_fed_by_evaluate(K, M):
 
 
 # ---------------------------------------------------------------- solved nodes and the roots against the solver
-def _env_of_planes(P, Q):
-    n = len(P)
-    stride = (n + 63) & ~63
-    planes = np.zeros((2, stride), dtype=np.uint64)
-    planes[0, :n], planes[1, :n] = P, Q
-    state = torch.from_numpy(planes.view(np.uint8).reshape(-1).copy()).to(DEV)
-    assert state.numel() == int(_native.lib().qttt_state_bytes(n))
-    return VecEnv.from_state(state, n)
-
-
 @pytest.mark.parametrize("K,M", [(4, 8), (8, 7), (1, 8)])
 def test_every_solved_node_holds_the_solver_s_value_of_its_own_state(K, M):
     G = PM.G_MAX

@@ -1,7 +1,12 @@
 """The drivers the search and self-play GPU tests share (tests/test_tree_gpu.py, test_tree_whole_gpu.py,
 test_tree_compact_gpu.py, test_selfplay_gpu.py): positions as import arrays, a TreeSearch over a sentinel-filled buffer
 beside its float64 model (tests/tree_model.py), one rollout and one move of the two in lockstep, and the comparison of
-the roots' statistics.  The whole-tree comparison is tests/tree_layout.py's.  A plain helper module."""
+the roots' statistics.  The whole-tree comparison is tests/tree_layout.py's.  Last, the driver of the exact-leaves and
+prove tests (tests/test_tree_exact_gpu.py, test_tree_prove_gpu.py; env_of_planes also test_selfplay_exact_gpu.py), by
+the model module: tests/exact_leaves_model.py or tests/prove_model.py.  A plain helper module."""
+import copy
+import functools
+
 import numpy as np
 import torch
 
@@ -108,3 +113,117 @@ def move(t, m, env, act, bits):
     env.step_raw(action36_to_pairs(torch.as_tensor(act, device=DEV)).contiguous(), torch.as_tensor(bits, device=DEV))
     t.sync(env)
     m.sync(boards(export(env)))
+
+
+# ---------------------------------------------------------------- exact leaves and proven nodes: one driver, two models
+GUARD = 0xA5
+
+
+def exact_nets():
+    import nn_reference64 as R
+    return {"zero": R.zero_state_dict, "greedy": R.greedy_state_dict, "counting": R.counting_state_dict,
+            "sharp": R.sharp_counting_state_dict}
+
+
+@functools.lru_cache(maxsize=None)
+def exact_net(name):
+    """The f32 network of an exact state dict by name; any other name: the golden network."""
+    import nn_reference64 as R
+    from qtttgym_amd import PolicyValueNet
+    nets = exact_nets()
+    sd = nets[name]() if name in nets else R.golden_state_dict(R.load_golden())
+    return PolicyValueNet(sd, device=DEV, dtype=torch.float32)
+
+
+def _evaluate_probs(leaves):
+    env = env_from_arrays({"board": leaves.board, "moves": leaves.moves, "n_moves": leaves.n_moves, "qmask": leaves.qmask,
+                           "n_q": leaves.n_q})
+    return env.evaluate(exact_net("counting"), rows=("probs",))["probs"].cpu().numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def exact_model(MM, net, K, M, capacity):
+    """MM.searched's model (MM: exact_leaves_model or prove_model), computed once and left alone."""
+    return MM.searched(exact_nets()[net](), K, M, capacity, probs_of=_evaluate_probs if net == "counting" else None)
+
+
+@functools.lru_cache(maxsize=None)
+def exact_stages(MM, net, K, M):
+    return MM.searched(exact_nets()[net](), K, M, MM.CAPACITY, stages=True)
+
+
+def games_view(m, G):
+    v = copy.copy(m)
+    v.games = m.games[:G]
+    return v
+
+
+def prefix(arrays, G):
+    return {k: np.asarray(v)[:G] for k, v in arrays.items()}
+
+
+def bits32(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def exact_search(MM, arrays, capacity, net, **kw):
+    """(t, env): a value-leaf TreeSearch with MM's seed and offset over a sentinel-filled buffer, at `arrays`."""
+    from qtttgym_amd import TreeSearch
+    env = env_from_arrays(arrays)
+    G = env.num_envs
+    t = TreeSearch(G, capacity=capacity, net=net, seed=MM.SEED, board_offset=MM.OFFSET, device=DEV, leaf_eval="value", **kw)
+    t.tree = torch.full((tree_layout.tree_bytes(G, capacity) + TAIL,), SENTINEL, dtype=torch.uint8, device=DEV)
+    t.reset(env)
+    return t, env
+
+
+def exact_rounds(t, r):
+    """TreeSearch.contemplate's schedule under exact_from (tests/prove_model.py's schedule: one leaf while the tree is
+    fresh, rounds of K, the rest), without the host's node bound (the pool that overflows)."""
+    import prove_model
+    for k in prove_model.schedule(r, t.leaves, t._fresh):
+        t._round(k)
+        t._fresh = False
+
+
+def check_exact_tree(t, m, compacted=False, kept_rows=False):
+    """The whole tree buffer against the model: the solved bit and the value bits of every live node against the model's
+    solved nodes (proven ones included); with kept_rows the priors row that a proven node keeps under its cleared flag
+    against the row the model kept; then — those bits taken out of a copy and those rows painted over — every other byte
+    by tests/tree_layout.py's comparison (which expects no has-priors flag on a proven node below the root).  Returns
+    the number of kept rows compared."""
+    import exact_leaves_model as E
+    solved_bits = np.uint32(E.NODE_SOLVED | E.NODE_VALUE_MASK)
+    G, cap = t.num_games, t.capacity
+    buf = t.tree.cpu().numpy().copy()
+    games, nodes, priors, _ = tree_layout.decode(buf, G, cap)
+    want = np.zeros((G, cap), dtype=np.uint32)
+    for g, flags in enumerate(m.solved_flags()):
+        for i, f in flags.items():
+            want[g, i] = f
+    live = np.arange(cap)[None, :] < games["used"][:, None]
+    got = nodes["flags"] & solved_bits
+    assert np.array_equal(got[live], want[live]), np.argwhere((got != want) & live)[:8].tolist()
+    assert np.array_equal(t.solved_count().cpu().numpy(), m.solved_counts())
+    kept = 0
+    if kept_rows and not compacted:
+        for g, st in enumerate(m.games):
+            for x, row in st["kept"].items():
+                assert np.array_equal(bits32(priors[g, x]), bits32(row)), ("kept priors row", g, x)
+                priors[g, x].view(np.uint8)[:] = SENTINEL
+                kept += 1
+    nodes["flags"][live] &= ~solved_bits
+    tree_layout.assert_tree_equals_model(buf, G, cap, m, SENTINEL, DEV, compacted=compacted)
+    return kept
+
+
+def env_of_planes(P, Q):
+    """A VecEnv over the state planes P, Q (u64 arrays of one length)."""
+    from qtttgym_amd import VecEnv, _native
+    n = len(P)
+    stride = (n + 63) & ~63
+    planes = np.zeros((2, stride), dtype=np.uint64)
+    planes[0, :n], planes[1, :n] = P, Q
+    state = torch.from_numpy(planes.view(np.uint8).reshape(-1).copy()).to(DEV)
+    assert state.numel() == int(_native.lib().qttt_state_bytes(n))
+    return VecEnv.from_state(state, n)
