@@ -164,6 +164,10 @@ def main():
                          "work at small --rollouts")
     ap.add_argument("--no-prune-targets", action="store_true",
                     help="with --forced-playouts: force only, record the unpruned visit counts (SelfPlay(prune_targets=False))")
+    ap.add_argument("--playout-cap", default=None, metavar="P,N",
+                    help="playout cap randomisation (SelfPlay(playout_cap=(P, N)), include/qttt_selfplay_cap.h; KataGo uses "
+                         "0.25 and a fifth of --rollouts; needs --leaf-eval value): a fraction P of the plies gets the full "
+                         "search and is recorded, the others N rollouts without noise and no sample")
     ap.add_argument("--root-policy", choices=("puct", "gumbel"), default="puct",
                     help="gumbel: the Gumbel root, sequential halving over --max-considered actions; pi is then the "
                          "improved policy and the move the best survivor (needs --leaf-eval value; --rollouts of 16-32 do)")
@@ -240,7 +244,9 @@ def main():
                   max_considered=args.max_considered, exact_from=args.exact_from, prove=args.prove,
                   exact_targets=args.exact_targets, exact_policy=not args.exact_value_only,
                   value_mix=args.value_mix, td_lambda=args.td_lambda, forced_playouts=args.forced_playouts,
-                  prune_targets=None if args.forced_playouts is None else not args.no_prune_targets)
+                  prune_targets=None if args.forced_playouts is None else not args.no_prune_targets,
+                  playout_cap=None if args.playout_cap is None else (float(args.playout_cap.split(",")[0]),
+                                                                     int(args.playout_cap.split(",")[1])))
     ring = ReplayBuffer(args.replay, device=dev, seed=args.seed, prioritized=args.prioritized is not None) if args.replay else None
     reanalyser = Reanalyser(sp, ring, args.reanalyse, value_mix=args.reanalyse_value_mix, seed=args.seed) if args.reanalyse else None
     trainer = Trainer(model, device=dev, net=net) if args.device_train else None      # nn.py:27's defaults

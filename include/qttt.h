@@ -364,4 +364,6 @@ uint64_t qttt_hash(uint64_t seed, uint64_t board_id, uint32_t step_idx);
 #include "qttt_train_weighted.h"
 #include "qttt_selfplay_value.h"
 #include "qttt_tree_forced.h"
+#include "qttt_tree_subset.h"
+#include "qttt_selfplay_cap.h"
 #endif

@@ -3,6 +3,7 @@ the one way into libqttt_hip.so, the one tensor check and the allocate-or-check 
 (_native.py stays free of torch; this module is where the two meet.)"""
 import math
 
+import numpy as np
 import torch
 
 from . import _native
@@ -98,3 +99,40 @@ def out_rows(spec, n, dev, out=None, keys=None, required=(), strict=False, numel
         elif strict:
             raise ValueError("out[%r] is not a row of this call (%s)" % (k, ", ".join(spec)))
     return out
+
+
+# ---------------------------------------------------------------- the counter hash on the host (include/qttt.h qttt_hash)
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(x):
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def _lowbias32(x):
+    with np.errstate(over="ignore"):
+        x = (x ^ (x >> np.uint32(16))) * np.uint32(0x7FEB352D)
+        x = (x ^ (x >> np.uint32(15))) * np.uint32(0x846CA68B)
+        return x ^ (x >> np.uint32(16))
+
+
+def counter_hash(seed, board_id0, n, idx):
+    """qttt_hash(seed, board_id0 + i, idx) for i = 0..n-1 as u64[n] (numpy): the library's counter hash restated for whole
+    batches, for the draws that the host makes itself (SelfPlay's playout cap) so that it knows them without a read-back."""
+    key = _splitmix64((int(seed) & _M64) ^ (((int(idx) & 0xFFFFFFFF) * 0xD1B54A32D192ED03) & _M64))
+    ids = np.arange(n, dtype=np.uint64) + np.uint64(int(board_id0))
+    with np.errstate(over="ignore"):
+        fold = ids.astype(np.uint32) ^ ((ids >> np.uint64(32)).astype(np.uint32) * np.uint32(0x9E3779B9))    # hi = 0: lo
+    h1 = _lowbias32(fold ^ np.uint32(key & 0xFFFFFFFF))
+    h2 = _lowbias32(h1 ^ np.uint32(key >> 32))
+    return (h2.astype(np.uint64) << np.uint64(32)) | h1.astype(np.uint64)
+
+
+def cap_full_mask(seed, board_offset, n, ply_index, p):
+    """include/qttt_selfplay_cap.h's draw: u8[n] (numpy), 1 where ply number `ply_index` of game g is searched in full:
+    (double)(qttt_hash(seed, board_offset + g, QTTT_SELFPLAY_CAP_BASE + ply_index) >> 11) * 2^-53 < p."""
+    h = counter_hash(seed, board_offset, n, _native.SELFPLAY_CAP_BASE + int(ply_index))
+    return ((h >> np.uint64(11)).astype(np.float64) * 2.0 ** -53 < float(p)).astype(np.uint8)

@@ -252,6 +252,21 @@ TREE_FORCED_SIGNATURES = {
     "qttt_selfplay_record_stream_pruned": (_i32, SELFPLAY_STREAM_SIGNATURES["qttt_selfplay_record_stream_sampled"][1][:-1]
                                            + [_f64, _f64, _vp]),
 }
+# every symbol include/qttt_tree_subset.h declares (rounds and root noise for a listed subset of the games; qttt.h includes it)
+_i32p = ctypes.c_void_p                 # const int32_t *ids: a device address
+TREE_SUBSET_SIGNATURES = {
+    "qttt_tree_select_batch_subset": (_i32, [_vp, _i64, _i64, _u64, _u32, _i32, _i64, _f64, _f64, _f64, _i32p, _i64, _vp, _vp,
+                                             _vp]),
+    "qttt_tree_backup_batch_subset": (_i32, [_vp, _i64, _i64, _i32, _i32p, _i64, _vp, _vp, _vp, _vp]),
+    "qttt_tree_root_noise_subset": (_i32, [_vp, _i64, _i64, _u64, _u32, _i64, _f64, _f64, _i32p, _i64, _vp, _vp, _vp]),
+}
+# every symbol include/qttt_selfplay_cap.h declares (the record and harvest of playout cap randomisation; qttt.h includes it)
+SELFPLAY_CAP_BASE = 0xA0000000
+SELFPLAY_MAX_CAP_DRAWS = 1 << 28
+SELFPLAY_CAP_SIGNATURES = {
+    "qttt_selfplay_record_capped": (_i32, TREE_FORCED_SIGNATURES["qttt_selfplay_record_stream_pruned"][1][:-1] + [_vp, _vp]),
+    "qttt_selfplay_harvest_capped": SELFPLAY_STREAM_SIGNATURES["qttt_selfplay_harvest"],
+}
 
 _lib = None
 
@@ -324,7 +339,8 @@ def lib():
                                   + list(TREE_EXACT_SIGNATURES.items()) + list(SELFPLAY_EXACT_SIGNATURES.items())
                                   + list(TREE_PROVE_SIGNATURES.items()) + list(REPLAY_REANALYSE_SIGNATURES.items())
                                   + list(REPLAY_PRIORITY_SIGNATURES.items()) + list(TRAIN_WEIGHTED_SIGNATURES.items())
-                                  + list(SELFPLAY_VALUE_SIGNATURES.items()) + list(TREE_FORCED_SIGNATURES.items())):
+                                  + list(SELFPLAY_VALUE_SIGNATURES.items()) + list(TREE_FORCED_SIGNATURES.items())
+                                  + list(TREE_SUBSET_SIGNATURES.items()) + list(SELFPLAY_CAP_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -73,7 +73,10 @@
 // every action's value kept for the policy); qttt_tree_prove_kernels.h (proven interior nodes: a round's
 // records walked upwards, a wave per game, integers only, and the roots' exact q);
 // qttt_selfplay_value_kernels.h (search-value targets: the roots' searched value, a wave per game, and the value targets made
-// of it, a lane per game) with qttt_selfplay_value_host.h (free of HIP: the argument checks and one game's row arithmetic).  Host only: qttt_launch.h (launch shape, kernel selection,
+// of it, a lane per game) with qttt_selfplay_value_host.h (free of HIP: the argument checks and one game's row arithmetic);
+// qttt_tree_subset_kernels.h (rounds and root noise for a listed subset of the games, a wave per listed game, on the full
+// launches' own device functions) with qttt_tree_subset_host.h (free of HIP: the argument checks); qttt_selfplay_cap_kernels.h
+// (the record and harvest of playout cap randomisation: the stream record's and the harvest's bodies).  Host only: qttt_launch.h (launch shape, kernel selection,
 // the one launch form), qttt_checks.h (free of HIP: what every argument check is made of), qttt_selfplay_record_host.h (free of
 // HIP: the one check of the self-play records and the one of the leaf-parallel selects), qttt_mailbox.h (the host half of the
 // single-record mailbox); this file: the step's launch logic + the C ABI.
@@ -103,6 +106,8 @@
 #include "qttt_selfplay_exact_kernels.h"
 #include "qttt_tree_prove_kernels.h"
 #include "qttt_selfplay_value_kernels.h"
+#include "qttt_tree_subset_kernels.h"
+#include "qttt_selfplay_cap_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -239,6 +244,22 @@ int record_launch(const RecordArgs &a, int64_t games, int64_t capacity, int ply_
     const SelfPlayOut o = selfplay_out(a.states, a.pi, a.mask, a.done, a.v, a.action36, a.length, a.winner, a.actions);
     return launch(selfplay_record_kernel<MODE, STREAM>, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, a.tree, games,
                   capacity, ply_or_draw, n_rollouts, alpha, (float)v_first, (float)v_second, o, sampling);
+}
+
+// THE check of the two harvests (include/qttt_selfplay_stream.h, qttt_selfplay_cap.h); `work`: there is something to launch
+int harvest_check(const void *tree, int64_t games, int64_t capacity, double v_first, double v_second, const SelfPlayOut &o,
+                  const SelfPlayHarvest &hv, bool &work) {
+    work = false;
+    if (tree_size_bad(games, capacity) || !is_finite(v_first) || !is_finite(v_second)) return QTTT_ERR_SIZE;
+    if (games == 0) return 0;
+    if (any_null(tree, o.states, o.pi, o.mask, o.done, o.v, o.action36, o.length, o.winner, o.actions) ||
+        any_null(hv.harvest_len, hv.finished, hv.games_done, hv.tally))
+        return QTTT_ERR_NULL;
+    if (misaligned(tree, 16) || misaligned(o.states, 16) || misaligned(o.pi, 8) || misaligned(hv.games_done, 8) ||
+        misaligned(hv.tally, 8) || misaligned(o.v, 4))
+        return QTTT_ERR_ACTION;
+    work = true;
+    return 0;
 }
 
 // THE backup of a leaf-parallel round: qttt_tree_backup_batch, and with EXACT the one that honours solved nodes
@@ -1070,6 +1091,83 @@ int qttt_selfplay_record_stream_pruned(const void *tree, int64_t games, int64_t 
     return record_launch<RECORD_PRUNED, true>(a, games, capacity, (int)draw_index, n_rollouts, alpha, v_first, v_second, s, stream);
 }
 
+// ---------------------------------------------------------------- rounds and noise for a listed subset (include/qttt_tree_subset.h)
+int qttt_tree_select_batch_subset(void *tree, int64_t games, int64_t capacity, uint64_t seed, uint32_t rollout_idx0,
+                                  int leaves, int64_t board_offset, double c_puct, double virtual_loss, double forced_k,
+                                  const int32_t *ids, int64_t n_ids, void *paths, void *leaf_state, void *stream) {
+    bool work;
+    if (const int rc = subset_select_check(tree, games, capacity, rollout_idx0, leaves, board_offset, virtual_loss, forced_k, ids,
+                                           n_ids, paths, leaf_state, work); rc || !work) return rc;
+    const Planes l = planes(leaf_state, n_ids * leaves);
+    const auto go = [&](auto kernel) {
+        return launch(kernel, ceil_div(n_ids, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity, (u64)seed,
+                      rollout_idx0, (u32)leaves, (u64)board_offset, c_puct, virtual_loss, forced_k, ids, n_ids,
+                      static_cast<TreePathRec *>(paths), l.P, l.Q);
+    };
+    return forced_k >= 0.0 ? go(tree_select_batch_subset_kernel<true>) : go(tree_select_batch_subset_kernel<false>);
+}
+
+int qttt_tree_backup_batch_subset(void *tree, int64_t games, int64_t capacity, int leaves, const int32_t *ids,
+                                  int64_t n_ids, const void *paths, const float *leaf_value, const float *leaf_probs,
+                                  void *stream) {
+    bool work;
+    if (const int rc = subset_backup_check(tree, games, capacity, leaves, ids, n_ids, paths, leaf_value, leaf_probs, work);
+        rc || !work)
+        return rc;
+    return launch(tree_backup_batch_subset_kernel, ceil_div(n_ids, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (u32)leaves, ids, n_ids, static_cast<const TreePathRec *>(paths), leaf_value, leaf_probs);
+}
+
+int qttt_tree_root_noise_subset(void *tree, int64_t games, int64_t capacity, uint64_t seed, uint32_t noise_idx,
+                                int64_t board_offset, double epsilon, double alpha, const int32_t *ids, int64_t n_ids,
+                                double *noise, uint8_t *applied, void *stream) {
+    bool work;
+    if (const int rc = subset_noise_check(tree, games, capacity, noise_idx, board_offset, epsilon, alpha, ids, n_ids, noise, work);
+        rc || !work)
+        return rc;
+    return launch(tree_root_noise_subset_kernel, ceil_div(n_ids, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (u64)seed, noise_idx, (u64)board_offset, epsilon, alpha, ids, n_ids, noise, applied);
+}
+
+// ---------------------------------------------------------------- the capped record and harvest (include/qttt_selfplay_cap.h)
+int qttt_selfplay_record_capped(const void *tree, int64_t games, int64_t capacity, uint32_t n_rollouts, double alpha,
+                                double v_first, double v_second, void *states, double *pi, uint8_t *mask, uint8_t *done,
+                                float *v, uint8_t *action36, uint8_t *length, int8_t *winner, uint8_t *actions,
+                                uint64_t seed, int64_t board_offset, double temperature, int sample_plies,
+                                uint32_t draw_index, double forced_k, double c_puct, const uint8_t *full, void *stream) {
+    const RecordArgs a = {tree, states, pi, mask, done, v, action36, length, winner, actions};
+    const bool pruned = forced_k >= 0.0;
+    bool work;
+    if (!is_finite(forced_k)) return QTTT_ERR_SIZE;
+    if (const int rc = record_check(pruned ? RECORD_PRUNED : RECORD_SAMPLED, true, a, games, capacity, 0, draw_index, n_rollouts,
+                                    alpha, v_first, v_second,
+                                    {board_offset, temperature, sample_plies, forced_k, c_puct, nullptr, 0.0, 0.0, true, full}, work);
+        rc || !work)
+        return rc;
+    const SelfPlayOut o = selfplay_out(a.states, a.pi, a.mask, a.done, a.v, a.action36, a.length, a.winner, a.actions);
+    const int64_t grid = ceil_div(games, TREE_GAMES_PER_BLOCK);
+    if (pruned) {
+        const SelfPlaySampling<RECORD_PRUNED> s = {(u64)seed, (u64)board_offset, temperature, sample_plies, forced_k, c_puct};
+        return launch(selfplay_record_capped_kernel<RECORD_PRUNED>, grid, TREE_BLOCK, stream, tree, games, capacity, (int)draw_index,
+                      n_rollouts, alpha, (float)v_first, (float)v_second, o, s, full);
+    }
+    const SelfPlaySampling<RECORD_SAMPLED> s = {(u64)seed, (u64)board_offset, temperature, sample_plies};
+    return launch(selfplay_record_capped_kernel<RECORD_SAMPLED>, grid, TREE_BLOCK, stream, tree, games, capacity, (int)draw_index,
+                  n_rollouts, alpha, (float)v_first, (float)v_second, o, s, full);
+}
+
+int qttt_selfplay_harvest_capped(const void *tree, int64_t games, int64_t capacity, double v_first, double v_second,
+                                 void *states, double *pi, uint8_t *mask, uint8_t *done, float *v, uint8_t *action36,
+                                 uint8_t *length, int8_t *winner, uint8_t *actions, uint8_t *harvest_len, uint8_t *finished,
+                                 int64_t *games_done, int64_t *tally, void *stream) {
+    const SelfPlayOut o = selfplay_out(states, pi, mask, done, v, action36, length, winner, actions);
+    const SelfPlayHarvest hv = {harvest_len, finished, games_done, tally};
+    bool work;
+    if (const int rc = harvest_check(tree, games, capacity, v_first, v_second, o, hv, work); rc || !work) return rc;
+    return launch(selfplay_harvest_capped_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
+                  (float)v_first, (float)v_second, o, hv);
+}
+
 // ---------------------------------------------------------------- the replay ring (include/qttt_replay.h)
 int64_t qttt_replay_bytes(int64_t capacity) {
     return replay_capacity_bad(capacity) ? (int64_t)QTTT_ERR_SIZE : replay_layout(capacity).bytes;
@@ -1237,16 +1335,10 @@ int qttt_selfplay_harvest(const void *tree, int64_t games, int64_t capacity, dou
                           double *pi, uint8_t *mask, uint8_t *done, float *v, uint8_t *action36, uint8_t *length,
                           int8_t *winner, uint8_t *actions, uint8_t *harvest_len, uint8_t *finished, int64_t *games_done,
                           int64_t *tally, void *stream) {
-    if (tree_size_bad(games, capacity) || !is_finite(v_first) || !is_finite(v_second)) return QTTT_ERR_SIZE;
-    if (games == 0) return 0;
-    if (any_null(tree, states, pi, mask, done, v, action36, length, winner, actions) ||
-        any_null(harvest_len, finished, games_done, tally))
-        return QTTT_ERR_NULL;
-    if (misaligned(tree, 16) || misaligned(states, 16) || misaligned(pi, 8) || misaligned(games_done, 8) || misaligned(tally, 8) ||
-        misaligned(v, 4))
-        return QTTT_ERR_ACTION;
     const SelfPlayOut o = selfplay_out(states, pi, mask, done, v, action36, length, winner, actions);
     const SelfPlayHarvest hv = {harvest_len, finished, games_done, tally};
+    bool work;
+    if (const int rc = harvest_check(tree, games, capacity, v_first, v_second, o, hv, work); rc || !work) return rc;
     return launch(selfplay_harvest_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
                   (float)v_first, (float)v_second, o, hv);
 }

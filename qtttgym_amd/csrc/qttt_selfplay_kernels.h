@@ -76,7 +76,10 @@ __device__ __forceinline__ void selfplay_row_head(const SelfPlayOut &o, int64_t 
     }
 }
 
-// the rest of a terminal root's row (self_play.py:203-206) and the v of the whole game (:195-216)
+// the rest of a terminal root's row (self_play.py:203-206) and the v of the whole game (:195-216).  BY_STATE
+// (include/qttt_selfplay_cap.h: batches in which not every ply is a row): row r is signed by the side to move in row r's
+// recorded state, the first player's rows get v0; where every ply is a row that is the row's parity, the default's bits.
+template <bool BY_STATE = false>
 __device__ __forceinline__ void selfplay_terminal_row(const SelfPlayOut &o, int64_t games, int64_t row, int64_t g, int ply,
                                                       const TreeNodeHdr &h, float v_first, float v_second, u32 lane) {
     uint8_t *act = o.actions + 2 * g;
@@ -87,7 +90,12 @@ __device__ __forceinline__ void selfplay_terminal_row(const SelfPlayOut &o, int6
     const int w = (int)((h.flags >> 8) & 3u) - 1;                // 1 / 0 / -1 = True / False / None
     const float v0 = w > 0 ? v_first : (w == 0 ? v_second : 0.0f);
     if ((int)lane <= ply) {
-        const float x = (lane & 1u) ? -v0 : v0;
+        u32 odd = lane & 1u;
+        if constexpr (BY_STATE) {                                // this row's state is h's, written by lane 0 just now
+            const u64 P = (int)lane == ply ? h.P : o.states[(int64_t)lane * 2 * plane_stride(games) + g];
+            odd = ((u32)(P >> 32) >> P1_N_SHIFT) & 1u;           // the moves played (no autofill move among them)
+        }
+        const float x = odd ? -v0 : v0;
         o.v[(int64_t)lane * games + g] = x == 0.0f ? 0.0f : x;            // a zero is +0.0
     }
     if (lane == 0u) {
@@ -97,16 +105,16 @@ __device__ __forceinline__ void selfplay_terminal_row(const SelfPlayOut &o, int6
     }
 }
 
-// STREAM: `ply` is the index of the sampled move's draw and the row is the game's own ply, length[g]; a game whose
-// terminal row is recorded (or whose ten rows are full) is not live
-template <int MODE, bool STREAM = false>
-__global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void *tree, int64_t games, int64_t capacity,
-                                                                     int ply, u32 n_rollouts, double alpha, float v_first,
-                                                                     float v_second, SelfPlayOut o,
-                                                                     SelfPlaySampling<MODE> sampling) {
-    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
-    const u32 lane = threadIdx.x & 63u;
-    if (g >= games) return;
+// One game's record (the wave's), the body of selfplay_record_kernel and of the capped record
+// (qttt_selfplay_cap_kernels.h).  STREAM: `ply` is the index of the sampled move's draw and the row is the game's own ply,
+// length[g]; a game whose terminal row is recorded (or whose ten rows are full) is not live.  CAPPED
+// (include/qttt_selfplay_cap.h, STREAM only): a live game with full[g] == 0 whose root is not terminal writes its move to
+// actions[g] and nothing else, and the finished game's v is signed by the rows' states; full is not read otherwise.
+template <int MODE, bool STREAM, bool CAPPED>
+__device__ __forceinline__ void selfplay_record_game(const void *tree, int64_t games, int64_t capacity, int ply, u32 n_rollouts,
+                                                     double alpha, float v_first, float v_second, const SelfPlayOut &o,
+                                                     const SelfPlaySampling<MODE> &sampling, const uint8_t *full, int64_t g,
+                                                     u32 lane) {
     uint8_t *act = o.actions + 2 * g;
     const int draw = ply;
     if constexpr (STREAM) {
@@ -126,9 +134,11 @@ __global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void 
     const TreeRootLane r = tree_root_lane(v, g, lane);
     const int64_t stride = plane_stride(games), row = (int64_t)ply * games + g;
     const bool terminal = (r.h.flags & TN_TERMINAL) != 0u;
-    selfplay_row_head(o, stride, row, g, ply, r.h, terminal, lane);
+    bool fast = false;                                           // wave-uniform
+    if constexpr (CAPPED) fast = !terminal && full[g] == 0;
+    if (!fast) selfplay_row_head(o, stride, row, g, ply, r.h, terminal, lane);
     if (terminal) {
-        selfplay_terminal_row(o, games, row, g, ply, r.h, v_first, v_second, lane);
+        selfplay_terminal_row<CAPPED>(o, games, row, g, ply, r.h, v_first, v_second, lane);
         return;
     }
     int a;
@@ -154,15 +164,27 @@ __global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void 
         }
         pi = r.legal ? x / sum : 0.0;
     }
-    if (lane < 36u) {
+    if (lane < 36u && !fast) {
         o.pi[row * 36 + lane] = pi;
         o.mask[row * 36 + lane] = r.legal ? 1 : 0;
     }
     if (lane == 0u) {
         const u32 pr = a < 0 ? 0xFFFFu : pair_action<false>(a < 0 ? 0 : a);      // lo | hi << 8
-        o.action36[row] = a < 0 ? (uint8_t)255 : (uint8_t)a;
+        if (!fast) o.action36[row] = a < 0 ? (uint8_t)255 : (uint8_t)a;
         act[0] = (uint8_t)pr; act[1] = (uint8_t)(pr >> 8);
     }
+}
+
+template <int MODE, bool STREAM = false>
+__global__ __launch_bounds__(TREE_BLOCK) void selfplay_record_kernel(const void *tree, int64_t games, int64_t capacity,
+                                                                     int ply, u32 n_rollouts, double alpha, float v_first,
+                                                                     float v_second, SelfPlayOut o,
+                                                                     SelfPlaySampling<MODE> sampling) {
+    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
+    const u32 lane = threadIdx.x & 63u;
+    if (g >= games) return;
+    selfplay_record_game<MODE, STREAM, false>(tree, games, capacity, ply, n_rollouts, alpha, v_first, v_second, o, sampling,
+                                              nullptr, g, lane);
 }
 
 }  // namespace

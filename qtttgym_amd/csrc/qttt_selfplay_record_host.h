@@ -27,6 +27,8 @@ struct RecordExtra {
     double forced_k, c_puct;           // the pruned record
     const void *rec;                   // the Gumbel record: rec (required, 16-byte aligned) and the scales
     double c_visit, c_scale;
+    bool capped;                       // the capped record (include/qttt_selfplay_cap.h): full is required
+    const void *full;
 };
 
 // The lockstep record (stream = false) tests ply in 0..9; the stream record has no ply, and tests draw_index below its bound
@@ -44,7 +46,8 @@ inline int record_check(int mode, bool stream, const RecordArgs &p, int64_t game
         (mode == RECORD_PRUNED && (forced_k_bad(x.forced_k) || !is_finite(x.c_puct))) || (gumbel && gumbel_scale_bad(x.c_visit, x.c_scale)))
         return QTTT_ERR_SIZE;
     if (games == 0) return 0;
-    if (any_null(p.tree, p.states, p.pi, p.mask, p.done, p.v, p.action36, p.length, p.winner, p.actions) || (gumbel && !x.rec))
+    if (any_null(p.tree, p.states, p.pi, p.mask, p.done, p.v, p.action36, p.length, p.winner, p.actions) || (gumbel && !x.rec) ||
+        (x.capped && !x.full))
         return QTTT_ERR_NULL;
     if (misaligned(p.tree, 16) || misaligned(p.states, 16) || misaligned(p.pi, 8) || misaligned(p.v, 4) ||
         (gumbel && misaligned(x.rec, 16)))

@@ -24,12 +24,12 @@ struct SelfPlayHarvest {
     int64_t *tally;                    // [games][QTTT_SELFPLAY_TALLIES]  first wins, second wins, no winner, rows; cumulative
 };
 
-__global__ __launch_bounds__(TREE_BLOCK) void selfplay_harvest_kernel(const void *tree, int64_t games, int64_t capacity,
-                                                                      float v_first, float v_second, SelfPlayOut o,
-                                                                      SelfPlayHarvest hv) {
-    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
-    const u32 lane = threadIdx.x & 63u;
-    if (g >= games) return;
+// one slot's harvest (the wave's), the body of selfplay_harvest_kernel and of the capped harvest
+// (qttt_selfplay_cap_kernels.h), whose BY_STATE signs the finished game's v by the rows' states
+template <bool BY_STATE>
+__device__ __forceinline__ void selfplay_harvest_game(const void *tree, int64_t games, int64_t capacity, float v_first,
+                                                      float v_second, const SelfPlayOut &o, const SelfPlayHarvest &hv, int64_t g,
+                                                      u32 lane) {
     const TreeView v = tree_view(const_cast<void *>(tree), games, capacity);
     const TreeNodeHdr h = *v.hdr(g, v.games[g].root);
     const int ply = (int)o.length[g];
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(TREE_BLOCK) void selfplay_harvest_kernel(const void
     }
     const int64_t row = (int64_t)ply * games + g;
     selfplay_row_head(o, plane_stride(games), row, g, ply, h, true, lane);
-    selfplay_terminal_row(o, games, row, g, ply, h, v_first, v_second, lane);
+    selfplay_terminal_row<BY_STATE>(o, games, row, g, ply, h, v_first, v_second, lane);
     if (lane == 0u) {
         const int w = (int)((h.flags >> 8) & 3u) - 1;            // 1 / 0 / -1 = True / False / None
         hv.harvest_len[g] = (uint8_t)(ply + 1);
@@ -50,6 +50,15 @@ __global__ __launch_bounds__(TREE_BLOCK) void selfplay_harvest_kernel(const void
         t[w > 0 ? 0 : (w == 0 ? 1 : 2)] += 1;
         t[3] += ply + 1;
     }
+}
+
+__global__ __launch_bounds__(TREE_BLOCK) void selfplay_harvest_kernel(const void *tree, int64_t games, int64_t capacity,
+                                                                      float v_first, float v_second, SelfPlayOut o,
+                                                                      SelfPlayHarvest hv) {
+    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
+    const u32 lane = threadIdx.x & 63u;
+    if (g >= games) return;
+    selfplay_harvest_game<false>(tree, games, capacity, v_first, v_second, o, hv, g, lane);
 }
 
 __global__ __launch_bounds__(TREE_BLOCK) void selfplay_restart_kernel(void *tree, int64_t games, int64_t capacity, u64 *pP,

@@ -24,14 +24,12 @@ __device__ __forceinline__ u64 explore_hash(u64 seed, u32 id, u32 idx) {
 __device__ __forceinline__ double explore_u53(u64 h) { return ((double)(h >> 11) + 0.5) * 0x1p-53; }
 __device__ __forceinline__ double explore_u32(u32 w) { return ((double)w + 0.5) * 0x1p-32; }
 
-__global__ __launch_bounds__(TREE_BLOCK) void tree_root_noise_kernel(void *tree, int64_t games, int64_t capacity, u64 seed,
-                                                                     u32 noise_idx, u64 board_offset, double epsilon,
-                                                                     double alpha, double *noise, uint8_t *applied) {
+// the noise of one game's root (the wave's): the body of tree_root_noise_kernel, and of the subset form
+// (qttt_tree_subset_kernels.h), whose wave w takes game ids[w]; the outputs' rows are the game's either way
+__device__ __forceinline__ void tree_root_noise_game(const TreeView &v, int64_t g, u32 lane, u64 seed, u32 noise_idx,
+                                                     u64 board_offset, double epsilon, double alpha, double *noise,
+                                                     uint8_t *applied) {
 #pragma clang fp contract(off)
-    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
-    const u32 lane = threadIdx.x & 63u;
-    if (g >= games) return;
-    const TreeView v = tree_view(tree, games, capacity);
     const int32_t root = v.games[g].root;
     const TreeNodeHdr h = *v.hdr(g, root);
     const bool legal = lane < 36u && ((h.legal >> lane) & 1ull);
@@ -66,6 +64,15 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_root_noise_kernel(void *tree,
     }
     if (noise && lane < 36u) noise[g * 36 + lane] = n;
     if (applied && lane == 0u) applied[g] = noised ? 1 : 0;
+}
+
+__global__ __launch_bounds__(TREE_BLOCK) void tree_root_noise_kernel(void *tree, int64_t games, int64_t capacity, u64 seed,
+                                                                     u32 noise_idx, u64 board_offset, double epsilon,
+                                                                     double alpha, double *noise, uint8_t *applied) {
+    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
+    const u32 lane = threadIdx.x & 63u;
+    if (g >= games) return;
+    tree_root_noise_game(tree_view(tree, games, capacity), g, lane, seed, noise_idx, board_offset, epsilon, alpha, noise, applied);
 }
 
 // The sampled record's move (include/qttt_tree_explore.h): lane a holds action a of a live root that is not terminal,

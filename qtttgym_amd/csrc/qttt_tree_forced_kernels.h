@@ -62,7 +62,7 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_select_batch_forced_kernel(vo
     if (g >= games) return;
     const TreeView v = tree_view(tree, games, capacity);
     const float *row = v.prior(g, v.games[g].root);              // select never moves the root
-    tree_select_batch_game(v, g, lane, lut, seed, rollout_idx0, leaves, board_offset, c_puct, vloss, paths, leafP, leafQ,
+    tree_select_batch_game(v, g, g * (int64_t)leaves, lane, lut, seed, rollout_idx0, leaves, board_offset, c_puct, vloss, paths, leafP, leafQ,
                            [&](u32) { return ForcedRootRule{row, forced_k, c_puct, vloss}; });
 }
 

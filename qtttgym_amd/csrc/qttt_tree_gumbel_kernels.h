@@ -177,7 +177,7 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_select_batch_gumbel_kernel(vo
     const GumbelLane l = gumbel_lane(recs + g, lane);
     // row m_eff <= 36 of i32[37, n_sims], entries sim_idx0 + j < n_sims (the host's check)
     const int32_t *row = visit_table + (int64_t)l.m_eff * n_sims + sim_idx0;
-    tree_select_batch_game(tree_view(tree, games, capacity), g, lane, lut, seed, rollout_idx0, leaves, board_offset, c_puct,
+    tree_select_batch_game(tree_view(tree, games, capacity), g, g * (int64_t)leaves, lane, lut, seed, rollout_idx0, leaves, board_offset, c_puct,
                            vloss, paths, leafP, leafQ,
                            [&](u32 j) { return GumbelRootRule{l, (u32)row[j], c_visit, c_scale}; });
 }

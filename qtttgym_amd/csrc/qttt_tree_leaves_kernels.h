@@ -52,10 +52,12 @@ __device__ __forceinline__ double tree_score_in_flight(double W, u32 Nword, doub
 }
 
 // The K descents of one game (the wave's), the body of tree_select_batch_kernel and of the Gumbel select
-// (qttt_tree_gumbel_kernels.h): root_of(j) = the root rule of descent j, TreePuctRoot for the plain round.
+// (qttt_tree_gumbel_kernels.h): root_of(j) = the root rule of descent j, TreePuctRoot for the plain round.  row0 = the
+// game's first row of paths and leaves: g * leaves in a round of all games, w * leaves for wave w of a subset round
+// (qttt_tree_subset_kernels.h).
 template <typename RootOf>
-__device__ __forceinline__ void tree_select_batch_game(const TreeView &v, int64_t g, u32 lane, const uint8_t *lut, u64 seed,
-                                                       u32 rollout_idx0, u32 leaves, u64 board_offset, double c_puct,
+__device__ __forceinline__ void tree_select_batch_game(const TreeView &v, int64_t g, int64_t row0, u32 lane, const uint8_t *lut,
+                                                       u64 seed, u32 rollout_idx0, u32 leaves, u64 board_offset, double c_puct,
                                                        double vloss, TreePathRec *paths, u64 *leafP, u64 *leafQ,
                                                        RootOf &&root_of) {
     TreeGame *gh = &v.games[g];
@@ -73,7 +75,7 @@ __device__ __forceinline__ void tree_select_batch_game(const TreeView &v, int64_
         const u32 over = d.overflow ? TG_OVERFLOW : 0u;
         overflow |= over;
         // one in-flight visit on every edge of the path: lane d owns edge d, and the edges lie in different nodes
-        TreePathRec *rec = paths + (g * (int64_t)leaves + j);
+        TreePathRec *rec = paths + (row0 + j);
         if ((int32_t)lane < d.depth) {
             TreeSlot *slot = &v.slots(g, d.edge_node)[d.edge_action];
             TreeNodeHdr *nh = v.hdr(g, d.edge_node);
@@ -86,8 +88,8 @@ __device__ __forceinline__ void tree_select_batch_game(const TreeView &v, int64_
             rec->leaf = d.leaf;
             rec->depth = (uint8_t)d.depth;
             rec->flags = (uint8_t)(over | tree_leaf_flags(d.h.flags));
-            leafP[g * (int64_t)leaves + j] = d.h.P;
-            leafQ[g * (int64_t)leaves + j] = d.h.Q;
+            leafP[row0 + j] = d.h.P;
+            leafQ[row0 + j] = d.h.Q;
         }
     }
     if (lane == 0u) {                                            // the recorded path as tree_compact_kernel leaves it
@@ -107,8 +109,8 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_select_batch_kernel(void *tre
     const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
     const u32 lane = threadIdx.x & 63u;
     if (g >= games) return;
-    tree_select_batch_game(tree_view(tree, games, capacity), g, lane, lut, seed, rollout_idx0, leaves, board_offset, c_puct,
-                           vloss, paths, leafP, leafQ, [](u32) { return TreePuctRoot(); });
+    tree_select_batch_game(tree_view(tree, games, capacity), g, g * (int64_t)leaves, lane, lut, seed, rollout_idx0, leaves,
+                           board_offset, c_puct, vloss, paths, leafP, leafQ, [](u32) { return TreePuctRoot(); });
 }
 
 // record j + 1 is fetched while record j is backed up: the records are not written here, so their loads need no order
@@ -128,18 +130,15 @@ __device__ __forceinline__ TreePathLane tree_path_lane(const TreePathRec *paths,
     return p;
 }
 
+// The backup of one game's K records (the wave's), rows row0 .. row0 + K - 1 of paths, leaf_value and leaf_probs: the body
+// of tree_backup_batch_kernel, and of the subset round's backup (qttt_tree_subset_kernels.h), where row0 is not g * K.
 // EXACT: qttt_tree_backup_batch_exact (include/qttt_tree_exact.h): a record of depth >= 1 that ends on a solved leaf is
 // backed up with the node's stored value and the leaf gets no priors; EXACT = false is qttt_tree_backup_batch.
 template <bool EXACT>
-__global__ __launch_bounds__(TREE_BLOCK) void tree_backup_batch_kernel(void *tree, int64_t games, int64_t capacity, u32 leaves,
-                                                                       const TreePathRec *paths, const float *leaf_value,
-                                                                       const float *leaf_probs) {
+__device__ __forceinline__ void tree_backup_batch_game(const TreeView &v, int64_t g, int64_t row0, u32 lane, int64_t capacity,
+                                                       u32 leaves, const TreePathRec *paths, const float *leaf_value,
+                                                       const float *leaf_probs) {
 #pragma clang fp contract(off)
-    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
-    const u32 lane = threadIdx.x & 63u;
-    if (g >= games) return;
-    const TreeView v = tree_view(tree, games, capacity);
-    const int64_t row0 = g * (int64_t)leaves;
     TreePathLane next = tree_path_lane(paths, leaf_value, row0, lane);
     for (u32 j = 0; j < leaves; ++j) {
         const TreePathLane p = next;
@@ -165,6 +164,17 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_backup_batch_kernel(void *tre
         if (!solved) tree_leaf_priors(v, g, p.leaf, lf, lane, true, [&](u32 a) { return leaf_probs[(row0 + j) * 36 + a]; });
         tree_wave_sync();                                        // the next record may pass the same edges and leaf
     }
+}
+
+template <bool EXACT>
+__global__ __launch_bounds__(TREE_BLOCK) void tree_backup_batch_kernel(void *tree, int64_t games, int64_t capacity, u32 leaves,
+                                                                       const TreePathRec *paths, const float *leaf_value,
+                                                                       const float *leaf_probs) {
+    const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
+    const u32 lane = threadIdx.x & 63u;
+    if (g >= games) return;
+    tree_backup_batch_game<EXACT>(tree_view(tree, games, capacity), g, g * (int64_t)leaves, lane, capacity, leaves, paths,
+                                  leaf_value, leaf_probs);
 }
 
 }  // namespace

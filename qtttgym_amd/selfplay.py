@@ -16,13 +16,16 @@ to a ReplayBuffer and restarts in place.  exact_targets=M replaces the value and
 least M moves played by the truth, enumerated on the device (include/qttt_selfplay_exact.h).
 value_mix=L / td_lambda=L make the value targets of fresh samples out of the searched value of every recorded root instead
 of the game's outcome alone (include/qttt_selfplay_value.h).
+playout_cap=(p, n_fast) is KataGo's playout cap randomisation (include/qttt_selfplay_cap.h): a random
+fraction p of the plies gets the full search and becomes a sample, the others are searched with n_fast rollouts, without
+noise, and are played but not recorded.
 """
 import ctypes
 
 import torch
 
 from . import _native
-from ._host import LibCaller, _ptr, _raw_stream, check_net, check_tensor, resolve_device
+from ._host import LibCaller, _ptr, _raw_stream, cap_full_mask, check_net, check_tensor, resolve_device
 from .symmetry import check_symmetries
 from .tree import TreeSearch
 from .vec_env import VecEnv
@@ -200,14 +203,32 @@ class SelfPlay(LibCaller):
     (qttt_selfplay_record_stream_pruned in stream()): pi is made of the visits that are left after every action but the most
     visited one has given back the forced visits PUCT would not have made; the move, v, mask and done are the sampled
     record's, read from the unpruned counts.  prune_targets=True needs forced_playouts; forced_playouts with
-    prune_targets=False only forces.  With both at their defaults play() and stream() issue the calls they always did."""
+    prune_targets=False only forces.  With both at their defaults play() and stream() issue the calls they always did.
+    playout_cap=(p, n_fast), p in (0, 1], 1 <= n_fast <= n_rollouts (a net and value leaves only), is playout cap
+    randomisation (include/qttt_selfplay_cap.h).  One capped ply: the host draws full[g] for every game with
+    the counter hash of (the trees' seed, board_offset + g, the ply's index) — no read-back, so it knows both groups — and
+    uploads the mask and the two id lists; one plain rollout runs in all games; root_noise goes to the full group only; the
+    fast group runs n_fast - 1 more rollouts with the plain root rule and the full group n_rollouts - 1, forced if
+    forced_playouts is set, both through TreeSearch.contemplate(games=), so a round's network launch has (games in the
+    group) * leaves rows; the trees' rollout index advances by n_rollouts.  The record is qttt_selfplay_record_capped: a
+    full game's row is what it would have been, a fast game's move is played and nothing is recorded, so batch.length
+    counts rows, not plies, and a game whose plies were all fast yields its terminal row alone; v is signed by the side to
+    move of each recorded state.  stream() harvests with qttt_selfplay_harvest_capped.  play() uses the same record; it
+    cannot know which games are over without a read-back, so a finished game stays in the group its draw names and costs
+    that group's rows (its root is terminal: every descent ends there and nothing changes).  value_mix, exact_targets,
+    root_noise, forced_playouts, prune_targets, sample_plies and compact compose; root_policy="gumbel", exact_from and
+    prove are refused (their kernels index their records by game), and so is td_lambda: TD(lambda) chains consecutive
+    plies, and the rows are no longer consecutive.  playout_cap=(1.0, n) records every ply: the batch of playout_cap=None.
+    With the default None every call, buffer and launch sequence is what it was."""
 
     def __init__(self, num_games, n_rollouts=100, num_simulations=10, net=None, alpha=1.0, c_puct=1.0,
                  value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts",
                  root_noise=None, temperature=1.0, sample_plies=0, leaves=1, virtual_loss=1.0,
                  eval_symmetries=None, root_policy="puct", max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None,
                  exact_targets=None, exact_policy=True, prove=False, value_mix=None, td_lambda=None,
-                 forced_playouts=None, prune_targets=None):
+                 forced_playouts=None, prune_targets=None, playout_cap=None):
+        self.playout_cap = self.check_playout_cap(playout_cap, n_rollouts, leaf_eval, net, root_policy, exact_from, prove,
+                                                  td_lambda)
         self.value_mode, self.value_lambda = self.check_value_args(value_mix, td_lambda, value_targets)
         self.exact_targets = self.check_exact_targets(exact_targets, value_targets)
         self.exact_policy = bool(exact_policy)
@@ -263,6 +284,29 @@ class SelfPlay(LibCaller):
         self.env = self.tree = None   # the last play()'s or stream()'s environment (at its positions) and trees
         self._stream = None           # stream()'s games in progress: environment, trees, staging batch, counters
         self.stream_epoch_plies = None    # None: a seed serves as many plies as the draw counters allow (epoch_plies)
+
+    @staticmethod
+    def check_playout_cap(playout_cap, n_rollouts, leaf_eval, net, root_policy, exact_from, prove, td_lambda):
+        """The constructor's check of playout_cap: None, or (p, n_fast) as (float, int)."""
+        if playout_cap is None:
+            return None
+        try:
+            p, n_fast = playout_cap
+        except (TypeError, ValueError):
+            raise ValueError("playout_cap must be None or (p, n_fast)") from None
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < float(p) <= 1.0:
+            raise ValueError("playout_cap: p must be a number in (0, 1]")
+        if isinstance(n_fast, bool) or not isinstance(n_fast, int) or not 1 <= n_fast <= int(n_rollouts):
+            raise ValueError("playout_cap: n_fast must be an integer in 1..n_rollouts")
+        if leaf_eval != "value" or net is None:
+            raise ValueError('playout_cap needs a net and leaf_eval="value": the two groups are searched in subset rounds')
+        if root_policy == "gumbel" or exact_from is not None or prove:
+            raise ValueError('playout_cap is not available with root_policy="gumbel", exact_from or prove: their kernels '
+                             "index their records by game, not by a subset's dense rows")
+        if td_lambda is not None:
+            raise ValueError("playout_cap is not available with td_lambda: TD(lambda) chains consecutive plies, and the "
+                             "recorded rows are no longer consecutive")
+        return float(p), int(n_fast)
 
     @staticmethod
     def check_prune_targets(forced_playouts, prune_targets):
@@ -400,6 +444,39 @@ class SelfPlay(LibCaller):
             tree.add_root_noise(*self.root_noise)
             tree.contemplate(R - 1)
 
+    def _search_capped(self, tree, ply_index):
+        """The search of one capped ply (playout_cap): returns full u8[G] on the device, the record's mask.  The draw is
+        the host's (include/qttt_selfplay_cap.h), addressed by (the trees' seed, board_offset + g, ply_index); the mask and
+        the two id lists are uploaded from pinned memory and nothing waits for the device."""
+        (p, n_fast), R, G = self.playout_cap, self.n_rollouts, self.num_games
+        full = torch.from_numpy(cap_full_mask(tree.seed, tree.board_offset, G, ply_index, p))
+        mask = full.pin_memory().to(self.device, non_blocking=True)
+        group_full, group_fast = tree.subset(full), tree.subset(1 - full)
+        idx0, bound0 = tree.rollout_idx, tree._bound
+        tree.contemplate(1)
+        if self.root_noise is not None:
+            tree.add_root_noise(*self.root_noise, games=group_full)
+        # a game is in one group: both groups take the rollout indices after the first, and no game more than R - 1 of them
+        for group, n, forced in ((group_fast, n_fast - 1, False), (group_full, R - 1, None)):
+            tree.rollout_idx, tree._bound = idx0 + 1, bound0 + 2
+            tree.contemplate(n, games=group, forced=forced)
+        tree.rollout_idx, tree._bound = idx0 + R, bound0 + 2 * R
+        return mask
+
+    def record_capped(self, tree, batch, full, draw_index=0):
+        """One qttt_selfplay_record_capped (include/qttt_selfplay_cap.h): record(tree, None, batch, draw_index) for the live
+        games with full[g] != 0 or a terminal root; a fast game's move goes to batch.actions and nothing else is written.
+        full u8[G] on the device.  The pi row is the pruned one with prune_targets, else the plain one."""
+        G, dev = self.num_games, self.device
+        if tree.num_games != G or tree.device != dev or batch.num_games != G:
+            raise ValueError("tree and batch must hold %d games on %s" % (G, dev))
+        check_tensor(full, torch.uint8, (G,), dev, "full")
+        self._call("qttt_selfplay_record_capped", tree.tree.data_ptr(), G, tree.capacity, self.n_rollouts, self.alpha,
+                   self.v_first, self.v_second, *self._staging(batch, SelfPlayBatch._FIELDS), tree.seed, tree.board_offset,
+                   self.temperature, self.sample_plies, int(draw_index),
+                   self.forced_playouts if self.prune_targets else -1.0, tree.c_puct, full.data_ptr())
+        return batch.actions
+
     def epoch_plies(self, tree):
         """Searched plies that one seed serves before one of the draw counters would pass its limit: the environment's
         step index (u32), the trees' rollout index (R per ply), the noise and Gumbel indices and the sampled move's
@@ -408,6 +485,8 @@ class SelfPlay(LibCaller):
         limits = [1 << 32, tree.max_rollouts // self.n_rollouts, _native.SELFPLAY_MAX_MOVE_DRAWS]
         if self.root_noise is not None:
             limits.append(_native.TREE_MAX_NOISE)
+        if self.playout_cap is not None:
+            limits.append(_native.SELFPLAY_MAX_CAP_DRAWS)
         if self.root_policy == "gumbel":
             limits.append(_native.TREE_MAX_GUMBEL)
         n = min(limits)
@@ -441,6 +520,16 @@ class SelfPlay(LibCaller):
             self._set_counters(env, tree, p)
         batch = self.new_batch()
         for ply in range(ROWS):
+            if self.playout_cap is not None:    # the capped ply: rows are per game, a game that is over is not live
+                if ply < ROWS - 1:
+                    full = self._search_capped(tree, p + ply)
+                    if self.value_mode is not None:
+                        self.record_value(tree, None, batch)
+                env.step_raw(self.record_capped(tree, batch, full, draw_index=p + ply))
+                tree.sync(env)
+                if self.compact:
+                    tree.compact()
+                continue
             if ply < ROWS - 1:                  # at ply 9 every game is over: nine moves fill the board
                 self._search(tree)
                 if self.value_mode is not None:
@@ -517,10 +606,16 @@ class SelfPlay(LibCaller):
             # what the host cannot know without a read-back, it knows from the game: a live root has at most eight moves
             # behind it, and a restart gives the slot's nodes back, so no slot holds more than this before its search
             tree._bound = 1 + (ROWS - 2) * (2 * R + 1)
-        self._search(tree)
-        if self.value_mode is not None:
-            self.record_value(tree, None, batch)
-        env.step_raw(self.record(tree, None, batch, draw_index=st["ply"]))
+        if self.playout_cap is not None:
+            full = self._search_capped(tree, st["ply"])
+            if self.value_mode is not None:
+                self.record_value(tree, None, batch)
+            env.step_raw(self.record_capped(tree, batch, full, draw_index=st["ply"]))
+        else:
+            self._search(tree)
+            if self.value_mode is not None:
+                self.record_value(tree, None, batch)
+            env.step_raw(self.record(tree, None, batch, draw_index=st["ply"]))
         tree.sync(env)
         if self.compact:
             tree.compact()
@@ -544,7 +639,7 @@ class SelfPlay(LibCaller):
 
     def _stream_harvest(self, st):
         tree = st["tree"]
-        self._call("qttt_selfplay_harvest", tree.tree.data_ptr(), self.num_games, tree.capacity, self.v_first, self.v_second,
+        self._call("qttt_selfplay_harvest" if self.playout_cap is None else "qttt_selfplay_harvest_capped", tree.tree.data_ptr(), self.num_games, tree.capacity, self.v_first, self.v_second,
                    *self._staging(st["batch"], SelfPlayBatch._FIELDS), st["harvest_len"].data_ptr(),
                    st["finished"].data_ptr(), st["games_done"].data_ptr(), st["tally"].data_ptr())
 

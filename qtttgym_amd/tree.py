@@ -41,6 +41,10 @@ the PUCT choice.  Every rollout after the first of a reset() or sync() is then a
 qttt_tree_select_batch_forced, and root_stats() says which actions are forced now and what the pruned policy target would
 keep of the visits.
 
+contemplate(n, games=...) and add_root_noise(..., games=...) search and noise a listed subset of the games
+(include/qttt_tree_subset.h): the listed games' leaves are packed densely, so a round's network launch has
+n_ids * K rows and the other games cost nothing and keep every byte.  It is what SelfPlay(playout_cap=) is made of.
+
 add_root_noise() is AlphaZero's root exploration (include/qttt_tree_explore.h): Dirichlet noise mixed into
 the priors of every root that has them, one launch.
 """
@@ -151,6 +155,7 @@ class TreeSearch(LibCaller):
         self.gumbel_idx = 0           # Gumbel begins since the last reset: what addresses their draws
         self._gumbel = None           # the Gumbel root's buffers, allocated by its first begin
         self._tables = {}             # n -> the visit table i32[37, n] of a budget of n simulations, on the device
+        self._subset_rounds = {}      # (n_ids, k) -> a subset round's dense buffers: views of the full round's storage
 
     # ------------------------------------------------------------------ helpers
     @staticmethod
@@ -261,18 +266,114 @@ class TreeSearch(LibCaller):
         not touched.  What a search that never resets (SelfPlay.stream) does before a counter would pass its bound."""
         self.seed = int(seed)
         envs = [self.leaf] + [b["leaf"] for b in self._rounds.values()] + ([self._gumbel["root"]] if self._gumbel else [])
+        envs += [b["leaf"] for b in self._subset_rounds.values()]
         for env in envs:
             env.seed = self.seed
         self.rollout_idx = self.noise_idx = self.gumbel_idx = 0
 
-    def contemplate(self, rollouts):
+    SUBSET_CACHE = 64                 # (n_ids, k) buffer sets kept before the cache is emptied (they are views: a few tensors each)
+
+    def subset(self, games):
+        """What `games=` of contemplate() and add_root_noise() is turned into: (ids, n) with ids i32[n] on this device,
+        ascending and distinct.  games: a bool or u8 mask [G] on the host (a tensor, numpy array or sequence: the list is
+        made on the host and uploaded from pinned memory, nothing waits for the device) or on this device (torch.nonzero:
+        one host synchronisation), or an i32 tensor of ids, ascending, distinct and in range — the caller's word is taken
+        for that on the device, checked on the host — whose length is its shape's.  A result of this method passes through."""
+        G, dev = self.num_games, self.device
+        if isinstance(games, tuple) and len(games) == 2 and torch.is_tensor(games[0]):
+            ids, n = games
+            check_tensor(ids, torch.int32, (int(n),), dev, "games ids")
+            return ids, int(n)
+        t = games if torch.is_tensor(games) else torch.as_tensor(games)
+        upload = lambda ids: (ids.contiguous().pin_memory().to(dev, non_blocking=True) if ids.numel()      # noqa: E731
+                              else torch.empty(0, dtype=torch.int32, device=dev))
+        if t.dtype == torch.int32:
+            if t.dim() != 1 or t.numel() > G:
+                raise ValueError("an id list must be a 1-d int32 tensor of at most %d entries" % G)
+            if t.device.type == "cpu":
+                if t.numel() and (int(t.min()) < 0 or int(t.max()) >= G or bool((t[1:] <= t[:-1]).any())):
+                    raise ValueError("ids must be ascending, distinct and in 0..%d" % (G - 1))
+                return upload(t), t.numel()
+            return check_tensor(t, torch.int32, (t.numel(),), dev, "games ids"), t.numel()
+        if t.dtype not in (torch.bool, torch.uint8) or tuple(t.shape) != (G,):
+            raise ValueError("games must be a bool or uint8 mask of shape (%d,) or an int32 id tensor" % G)
+        if t.device.type == "cpu":
+            ids = torch.nonzero(t, as_tuple=True)[0].to(torch.int32)
+            return upload(ids), ids.numel()
+        if t.device != dev:
+            raise ValueError("a device mask must be on %s" % (dev,))
+        ids = torch.nonzero(t, as_tuple=True)[0].to(torch.int32)
+        return ids, ids.numel()
+
+    def _check_subset_search(self):
+        if self.root_policy == "gumbel" or self.exact_from is not None or self.prove:
+            raise ValueError('a subset search (games=...) is not available with root_policy="gumbel", exact_from or prove: '
+                             "their kernels index their records by game, not by the subset's dense rows")
+        if self.leaf_eval != "value":
+            raise ValueError('a subset search (games=...) needs leaf_eval="value": its rounds are leaf-parallel rounds')
+
+    def _subset_buffers(self, n, k):
+        """The dense buffers of a subset round of n listed games and k leaves each: the n * k leaves as a VecEnv, the path
+        records and the network's rows, all views of the first n * k rows of the full round's storage for k (the two
+        kinds of round never overlap on a stream)."""
+        b = self._subset_rounds.get((n, k))
+        if b is None:
+            full, rows = self._round_buffers(k), n * k
+            if len(self._subset_rounds) >= self.SUBSET_CACHE:
+                self._subset_rounds.clear()
+            nbytes = int(self._lib.qttt_tree_paths_bytes(n, k))
+            state = full["leaf"].state[:int(self._lib.qttt_state_bytes(rows))]
+            b = self._subset_rounds[(n, k)] = {
+                "leaf": VecEnv.from_state(state, rows, seed=self.seed, board_offset=self.board_offset),
+                "paths": full["paths"][:max(nbytes, 16)],
+                "out": {key: t[:rows] for key, t in full["out"].items()}}
+        return b
+
+    def _subset_round(self, k, ids, n, forced_k):
+        """One round of k rollouts in the n listed games through the subset entries, without contemplate's bounds: the
+        select (forced_k < 0: the plain PUCT root), one evaluation of the n * k leaves, their backup."""
+        k = int(k)
+        if not 1 <= k <= _native.TREE_MAX_LEAVES:
+            raise ValueError("a round holds 1..%d leaves" % _native.TREE_MAX_LEAVES)
+        if n:
+            b = self._subset_buffers(n, k)
+            G, cap, tree = self.num_games, self.capacity, self.tree.data_ptr()
+            self._call("qttt_tree_select_batch_subset", tree, G, cap, self.seed, self.rollout_idx, k, self.board_offset,
+                       self.c_puct, self.virtual_loss, forced_k, ids.data_ptr(), n, b["paths"].data_ptr(),
+                       b["leaf"].state.data_ptr())
+            b["leaf"].evaluate(self.net, out=b["out"], symmetries=self.eval_symmetries)
+            self._call("qttt_tree_backup_batch_subset", tree, G, cap, k, ids.data_ptr(), n, b["paths"].data_ptr(),
+                       b["out"]["value"].data_ptr(), b["out"]["probs"].data_ptr())
+        self.rollout_idx += k
+
+    def _contemplate_subset(self, r, games, forced):
+        self._check_subset_search()
+        ids, n = self.subset(games)
+        forced_k = -1.0 if (self.forced_playouts is None or forced is False) else self.forced_playouts
+        K = self.leaves
+        if r and self._fresh:         # a listed root may lack priors: one plain descent first; the others stay fresh
+            self._subset_round(1, ids, n, -1.0)
+            self._bound += 2
+            r -= 1
+        for k in [K] * (r // K) + [r % K] * (r % K > 0):
+            self._subset_round(k, ids, n, forced_k)
+            self._bound += 2 * k
+
+    def contemplate(self, rollouts, games=None, forced=None):
         """`rollouts` x MCTS._rollout (mcts.py:166-176) in every game.  With leaves = K > 1 they are taken K at a time:
         after a reset() or sync() one single rollout first (K descents would all end on a root without priors), then
         rounds of K and one shorter round for what is left.  Without eval_symmetries the calls are what they always were.
         root_policy="gumbel": after that single rollout (the root needs its priors to be descended from) the roots are
         evaluated, the Gumbel state of the move is drawn for the budget n = the rollouts that remain, and the rounds go
         through the Gumbel select; every contemplate() is one budget of its own.
-        forced_playouts: the same single rollout, then rounds of K (also at K = 1) through the forced select."""
+        forced_playouts: the same single rollout, then rounds of K (also at K = 1) through the forced select.
+        games (see subset()): only the listed games are searched, by the same rules and with the same draws — the collapse
+        bits are addressed by the game and by rollout_idx, which advances by `rollouts` as for a full call, so draw indices
+        stay a function of the schedule alone — through qttt_tree_select_batch_subset / qttt_tree_backup_batch_subset
+        (include/qttt_tree_subset.h): rounds of K (also at K = 1), the network launch of n_ids * K rows, the other games
+        untouched.  Not with root_policy="gumbel", exact_from or prove.  An empty list launches nothing.
+        forced=False searches with the plain PUCT root although the tree has forced_playouts (subset rounds only; None:
+        the tree's rule).  games=None and forced=None issue the calls they always did."""
         r = int(rollouts)
         if r < 0:
             raise ValueError("rollouts must be >= 0")
@@ -283,6 +384,10 @@ class TreeSearch(LibCaller):
         if self._bound + 2 * r > self.capacity:
             raise ValueError("%d rollouts could use %d nodes, more than capacity %d"
                              % (r, self._bound + 2 * r, self.capacity))
+        if games is not None:
+            return self._contemplate_subset(r, games, forced)
+        if forced is not None:
+            raise ValueError("forced= goes with games=: a search of all games takes the tree's own root rule")
         # a single rollout: the fused value rollout, or — under eval_symmetries or exact_from — a round of one leaf
         rounds_only = self.eval_symmetries is not None or self.exact_from is not None
         single = (lambda: self._round(1)) if rounds_only else self._rollout
@@ -440,12 +545,15 @@ class TreeSearch(LibCaller):
                        self._out["probs"].data_ptr())
         self.rollout_idx = k + 1
 
-    def add_root_noise(self, epsilon=0.25, alpha=0.3, noise=None, applied=None):
+    def add_root_noise(self, epsilon=0.25, alpha=0.3, noise=None, applied=None, games=None):
         """P <- (1 - epsilon) P + epsilon Dirichlet(alpha) at every root that has priors, is not terminal and has a
         legal action (qttt_tree_root_noise); a root that has no priors yet is left alone, so run one rollout first.
         The draws are addressed by (seed, board_offset + g, noise_idx), and noise_idx counts these calls since reset():
         a call never repeats an earlier one's noise, and a second call on the same root mixes again.  noise f64[G, 36]
-        and applied u8[G], both optional, receive the normalised noise and whether the game was noised."""
+        and applied u8[G], both optional, receive the normalised noise and whether the game was noised.
+        games (see subset()): only the listed games are noised (qttt_tree_root_noise_subset), each with exactly the noise
+        that the full call would give it; the other games keep every byte, and their rows of noise and applied keep what
+        they held.  The call counts as one noise call either way."""
         eps, alpha = float(epsilon), float(alpha)
         if not 0.0 <= eps <= 1.0:
             raise ValueError("epsilon must be in [0, 1]")
@@ -460,8 +568,14 @@ class TreeSearch(LibCaller):
             check_tensor(noise, torch.float64, (G, 36), dev, "noise")
         if applied is not None:
             check_tensor(applied, torch.uint8, (G,), dev, "applied")
-        self._call("qttt_tree_root_noise", self.tree.data_ptr(), G, self.capacity, self.seed, self.noise_idx,
-                   self.board_offset, eps, alpha, _ptr(noise), _ptr(applied))
+        if games is None:
+            self._call("qttt_tree_root_noise", self.tree.data_ptr(), G, self.capacity, self.seed, self.noise_idx,
+                       self.board_offset, eps, alpha, _ptr(noise), _ptr(applied))
+        else:
+            ids, n = self.subset(games)
+            if n:
+                self._call("qttt_tree_root_noise_subset", self.tree.data_ptr(), G, self.capacity, self.seed, self.noise_idx,
+                           self.board_offset, eps, alpha, ids.data_ptr(), n, _ptr(noise), _ptr(applied))
         self.noise_idx += 1
 
     def root_stats(self):
