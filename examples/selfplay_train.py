@@ -168,6 +168,9 @@ def main():
                     help="playout cap randomisation (SelfPlay(playout_cap=(P, N)), include/qttt_selfplay_cap.h; KataGo uses "
                          "0.25 and a fifth of --rollouts; needs --leaf-eval value): a fraction P of the plies gets the full "
                          "search and is recorded, the others N rollouts without noise and no sample")
+    ap.add_argument("--resident", action="store_true",
+                    help="the resident search (SelfPlay(resident=True), include/qttt_tree_resident.h; needs --leaf-eval value): "
+                         "every round of a ply inside one fused launch, the same games bit for bit")
     ap.add_argument("--root-policy", choices=("puct", "gumbel"), default="puct",
                     help="gumbel: the Gumbel root, sequential halving over --max-considered actions; pi is then the "
                          "improved policy and the move the best survivor (needs --leaf-eval value; --rollouts of 16-32 do)")
@@ -246,7 +249,8 @@ def main():
                   value_mix=args.value_mix, td_lambda=args.td_lambda, forced_playouts=args.forced_playouts,
                   prune_targets=None if args.forced_playouts is None else not args.no_prune_targets,
                   playout_cap=None if args.playout_cap is None else (float(args.playout_cap.split(",")[0]),
-                                                                     int(args.playout_cap.split(",")[1])))
+                                                                     int(args.playout_cap.split(",")[1])),
+                  resident=args.resident)
     ring = ReplayBuffer(args.replay, device=dev, seed=args.seed, prioritized=args.prioritized is not None) if args.replay else None
     reanalyser = Reanalyser(sp, ring, args.reanalyse, value_mix=args.reanalyse_value_mix, seed=args.seed) if args.reanalyse else None
     trainer = Trainer(model, device=dev, net=net) if args.device_train else None      # nn.py:27's defaults

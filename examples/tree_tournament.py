@@ -55,13 +55,14 @@ VALUE_KINDS = ("azv", "azg")           # the players that score a leaf by the va
 
 
 def play(players, G, sims, net, seed, carry=None, leaves=(1, 1), eval_symmetries=None, max_considered=16, exact_from=None,
-         prove=False, forced_playouts=None):
+         prove=False, forced_playouts=None, resident=False):
     """One half: players[0] moves first; leaves[i] = the leaves per round of players[i] when it is an azv player, and
     eval_symmetries what the azv players average the network over.  Returns winner i8[G] (1 = the first mover, 0 = the second, -1 = none).
     carry: None = the trees never compact; else they compact after every sync and hold 2 * R + carry nodes (carry < 0:
     2 * R + 2 of them).  exact_from: the azv and azg players solve leaves with that many moves played exactly; prove: they
     prove interior nodes as well (the played move stays the search's own choice).  forced_playouts: the azv players search
-    with forced playouts at the root (TreeSearch(forced_playouts=k))."""
+    with forced playouts at the root (TreeSearch(forced_playouts=k)); resident: the azv players that use neither exact leaves
+    nor symmetry-averaged ones run their rounds inside the fused launch (TreeSearch(resident=True))."""
     env = VecEnv(G, seed=seed)
     trees = []
     for i, (kind, R) in enumerate(players):
@@ -76,7 +77,8 @@ def play(players, G, sims, net, seed, carry=None, leaves=(1, 1), eval_symmetries
                        leaves=leaves[i] if value else 1, eval_symmetries=eval_symmetries if value else None,
                        root_policy="gumbel" if kind == "azg" else "puct", max_considered=max_considered,
                        exact_from=exact_from if value else None, prove=prove and value and exact_from is not None,
-                       forced_playouts=forced_playouts if kind == "azv" else None)
+                       forced_playouts=forced_playouts if kind == "azv" else None,
+                       resident=resident and kind == "azv" and exact_from is None and eval_symmetries is None)
         t.reset(env)
         trees.append(t)
     finished = torch.zeros(G, dtype=torch.bool, device=env.device)
@@ -132,6 +134,9 @@ def main():
     ap.add_argument("--forced-playouts", type=float, default=None, metavar="K",
                     help="the azv players force root actions with n * n < K * P * sum(n) (TreeSearch(forced_playouts=K), "
                          "include/qttt_tree_forced.h)")
+    ap.add_argument("--resident", action="store_true",
+                    help="the azv players search with the resident search (TreeSearch(resident=True), "
+                         "include/qttt_tree_resident.h): the same games, one fused launch for a move's rounds")
     args = ap.parse_args()
     if args.prove and args.exact_from is None:
         raise SystemExit("--prove needs --exact-from")
@@ -154,9 +159,9 @@ def main():
             raise SystemExit("--carry must be >= 0")
         carry = args.carry if args.carry is not None else -1
     w_a = play((p1, p2), half, args.sims, net, args.seed, carry, (k1, k2), syms, args.max_considered,
-               args.exact_from, args.prove, args.forced_playouts)                                           # player 1 moves first
+               args.exact_from, args.prove, args.forced_playouts, args.resident)                                        # player 1 moves first
     w_b = play((p2, p1), half, args.sims, net, args.seed + 1, carry, (k2, k1), syms, args.max_considered,
-               args.exact_from, args.prove, args.forced_playouts)                                           # player 2 moves first
+               args.exact_from, args.prove, args.forced_playouts, args.resident)                                        # player 2 moves first
     wins = int((w_a == 1).sum()) + int((w_b == 0).sum())
     losses = int((w_a == 0).sum()) + int((w_b == 1).sum())
     draws = int((w_a == -1).sum()) + int((w_b == -1).sum())

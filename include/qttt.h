@@ -366,4 +366,5 @@ uint64_t qttt_hash(uint64_t seed, uint64_t board_id, uint32_t step_idx);
 #include "qttt_tree_forced.h"
 #include "qttt_tree_subset.h"
 #include "qttt_selfplay_cap.h"
+#include "qttt_tree_resident.h"
 #endif

@@ -267,6 +267,13 @@ SELFPLAY_CAP_SIGNATURES = {
     "qttt_selfplay_record_capped": (_i32, TREE_FORCED_SIGNATURES["qttt_selfplay_record_stream_pruned"][1][:-1] + [_vp, _vp]),
     "qttt_selfplay_harvest_capped": SELFPLAY_STREAM_SIGNATURES["qttt_selfplay_harvest"],
 }
+# every symbol include/qttt_tree_resident.h declares (the resident search: every round of a move in one launch; qttt.h
+# includes it)
+TREE_RESIDENT_SIGNATURES = {
+    "qttt_tree_search_resident": (_i32, [_vp, _i64, _i64, _u64, _u32, _i32, _u32, _i64, _f64, _f64, _f64, _vp, _i32, _vp]),
+    "qttt_tree_resident_games_per_group": (_i32, [_i32, _i32]),
+    "qttt_tree_resident_plan": (_i32, [_i32, _u32, _vp, _i32]),
+}
 
 _lib = None
 
@@ -340,7 +347,8 @@ def lib():
                                   + list(TREE_PROVE_SIGNATURES.items()) + list(REPLAY_REANALYSE_SIGNATURES.items())
                                   + list(REPLAY_PRIORITY_SIGNATURES.items()) + list(TRAIN_WEIGHTED_SIGNATURES.items())
                                   + list(SELFPLAY_VALUE_SIGNATURES.items()) + list(TREE_FORCED_SIGNATURES.items())
-                                  + list(TREE_SUBSET_SIGNATURES.items()) + list(SELFPLAY_CAP_SIGNATURES.items())):
+                                  + list(TREE_SUBSET_SIGNATURES.items()) + list(SELFPLAY_CAP_SIGNATURES.items())
+                                  + list(TREE_RESIDENT_SIGNATURES.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -76,7 +76,10 @@
 // of it, a lane per game) with qttt_selfplay_value_host.h (free of HIP: the argument checks and one game's row arithmetic);
 // qttt_tree_subset_kernels.h (rounds and root noise for a listed subset of the games, a wave per listed game, on the full
 // launches' own device functions) with qttt_tree_subset_host.h (free of HIP: the argument checks); qttt_selfplay_cap_kernels.h
-// (the record and harvest of playout cap randomisation: the stream record's and the harvest's bodies).  Host only: qttt_launch.h (launch shape, kernel selection,
+// (the record and harvest of playout cap randomisation: the stream record's and the harvest's bodies);
+// qttt_tree_resident_kernels.h (the resident search: every round of a move in one launch, a workgroup per tile of games, on the
+// select's, the network's and the backup's own device functions) with qttt_tree_resident_host.h (free of HIP: the tile, the
+// round plan, the argument check).  Host only: qttt_launch.h (launch shape, kernel selection,
 // the one launch form), qttt_checks.h (free of HIP: what every argument check is made of), qttt_selfplay_record_host.h (free of
 // HIP: the one check of the self-play records and the one of the leaf-parallel selects), qttt_mailbox.h (the host half of the
 // single-record mailbox); this file: the step's launch logic + the C ABI.
@@ -108,6 +111,7 @@
 #include "qttt_selfplay_value_kernels.h"
 #include "qttt_tree_subset_kernels.h"
 #include "qttt_selfplay_cap_kernels.h"
+#include "qttt_tree_resident_kernels.h"
 #include "qttt_launch.h"
 #include "qttt_mailbox.h"
 
@@ -1166,6 +1170,29 @@ int qttt_selfplay_harvest_capped(const void *tree, int64_t games, int64_t capaci
     if (const int rc = harvest_check(tree, games, capacity, v_first, v_second, o, hv, work); rc || !work) return rc;
     return launch(selfplay_harvest_capped_kernel, ceil_div(games, TREE_GAMES_PER_BLOCK), TREE_BLOCK, stream, tree, games, capacity,
                   (float)v_first, (float)v_second, o, hv);
+}
+
+// ---------------------------------------------------------------- the resident search (include/qttt_tree_resident.h)
+int qttt_tree_search_resident(void *tree, int64_t games, int64_t capacity, uint64_t seed, uint32_t rollout_idx0, int leaves,
+                              uint32_t rollouts, int64_t board_offset, double c_puct, double virtual_loss, double forced_k,
+                              const void *weights, int precision, void *stream) {
+    bool work;
+    if (const int rc = resident_search_check(tree, games, capacity, rollout_idx0, leaves, rollouts, board_offset, virtual_loss,
+                                             forced_k, weights, precision, work); rc || !work) return rc;
+    const int64_t grid = ceil_div(games, (int64_t)resident_games_per_group(leaves, precision));
+    return with_int<QTTT_NN_F32, QTTT_NN_BF16>(precision, [&](auto P) {
+        const auto go = [&](auto kernel) {
+            return launch(kernel, grid, QTTT_NN_BLOCK, stream, tree, games, capacity, (u64)seed, rollout_idx0, (u32)leaves,
+                          rollouts, (u64)board_offset, c_puct, virtual_loss, forced_k, weights);
+        };
+        return forced_k >= 0.0 ? go(tree_search_resident_kernel<P, true>) : go(tree_search_resident_kernel<P, false>);
+    });
+}
+
+int qttt_tree_resident_games_per_group(int leaves, int precision) { return resident_games_per_group(leaves, precision); }
+
+int qttt_tree_resident_plan(int leaves, uint32_t rollouts, int32_t *rounds_out, int cap) {
+    return resident_plan(leaves, rollouts, rounds_out, cap);
 }
 
 // ---------------------------------------------------------------- the replay ring (include/qttt_replay.h)

@@ -119,30 +119,39 @@ struct TreePathLane {
     u32 depth, action;
     float value;
 };
-__device__ __forceinline__ TreePathLane tree_path_lane(const TreePathRec *paths, const float *leaf_value, int64_t row, u32 lane) {
+template <typename ValueOf>
+__device__ __forceinline__ TreePathLane tree_path_lane(const TreePathRec *paths, ValueOf &&value_of, int64_t row, u32 lane) {
     const TreePathRec *rec = paths + row;
     TreePathLane p;
     p.leaf = rec->leaf;
     p.depth = rec->depth;
     p.node = lane < (u32)QTTT_TREE_MAX_DEPTH ? rec->node[lane] : 0;
     p.action = lane < (u32)QTTT_TREE_MAX_DEPTH ? rec->action[lane] : 0u;
-    p.value = leaf_value[row];
+    p.value = value_of(row);
     return p;
 }
 
-// The backup of one game's K records (the wave's), rows row0 .. row0 + K - 1 of paths, leaf_value and leaf_probs: the body
-// of tree_backup_batch_kernel, and of the subset round's backup (qttt_tree_subset_kernels.h), where row0 is not g * K.
+// The backup of one game's K records (the wave's), rows row0 .. row0 + K - 1 of paths, of the values and of the priors: the
+// body of tree_backup_batch_kernel, of the subset round's backup (qttt_tree_subset_kernels.h), where row0 is not g * K, and
+// of the resident search (qttt_tree_resident_kernels.h), where the records and the network's rows are in LDS.
+// value_of(row) = the network's value of a row, prob_of(row, a) = its prior of action a: TreeLeafRows for the two arrays of
+// the C ABI.
 // EXACT: qttt_tree_backup_batch_exact (include/qttt_tree_exact.h): a record of depth >= 1 that ends on a solved leaf is
 // backed up with the node's stored value and the leaf gets no priors; EXACT = false is qttt_tree_backup_batch.
-template <bool EXACT>
+struct TreeLeafRows {                  // leaf_value f32[rows], leaf_probs f32[rows, 36]
+    const float *leaf_value, *leaf_probs;
+    __device__ __forceinline__ float operator()(int64_t row) const { return leaf_value[row]; }
+    __device__ __forceinline__ float operator()(int64_t row, u32 a) const { return leaf_probs[row * 36 + a]; }
+};
+template <bool EXACT, typename ValueOf, typename ProbOf>
 __device__ __forceinline__ void tree_backup_batch_game(const TreeView &v, int64_t g, int64_t row0, u32 lane, int64_t capacity,
-                                                       u32 leaves, const TreePathRec *paths, const float *leaf_value,
-                                                       const float *leaf_probs) {
+                                                       u32 leaves, const TreePathRec *paths, ValueOf &&value_of,
+                                                       ProbOf &&prob_of) {
 #pragma clang fp contract(off)
-    TreePathLane next = tree_path_lane(paths, leaf_value, row0, lane);
+    TreePathLane next = tree_path_lane(paths, value_of, row0, lane);
     for (u32 j = 0; j < leaves; ++j) {
         const TreePathLane p = next;
-        if (j + 1u < leaves) next = tree_path_lane(paths, leaf_value, row0 + j + 1u, lane);
+        if (j + 1u < leaves) next = tree_path_lane(paths, value_of, row0 + j + 1u, lane);
         // a record that does not lie in the pool is skipped (wave-uniform: every lane sees every lane's entry)
         const bool edge = lane < p.depth;
         const bool bad_edge = edge && (p.node < 0 || (int64_t)p.node >= capacity || p.action >= 36u);
@@ -161,7 +170,7 @@ __device__ __forceinline__ void tree_backup_batch_game(const TreeView &v, int64_
             slot->N = slot->N + 1u - TREE_FLIGHT_ONE;
             nh->Ntot = nh->Ntot + 1u - TREE_FLIGHT_ONE;
         }
-        if (!solved) tree_leaf_priors(v, g, p.leaf, lf, lane, true, [&](u32 a) { return leaf_probs[(row0 + j) * 36 + a]; });
+        if (!solved) tree_leaf_priors(v, g, p.leaf, lf, lane, true, [&](u32 a) { return prob_of(row0 + j, a); });
         tree_wave_sync();                                        // the next record may pass the same edges and leaf
     }
 }
@@ -173,8 +182,9 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_backup_batch_kernel(void *tre
     const int64_t g = (int64_t)blockIdx.x * TREE_GAMES_PER_BLOCK + threadIdx.x / 64;
     const u32 lane = threadIdx.x & 63u;
     if (g >= games) return;
+    const TreeLeafRows rows = {leaf_value, leaf_probs};
     tree_backup_batch_game<EXACT>(tree_view(tree, games, capacity), g, g * (int64_t)leaves, lane, capacity, leaves, paths,
-                                  leaf_value, leaf_probs);
+                                  rows, rows);
 }
 
 }  // namespace

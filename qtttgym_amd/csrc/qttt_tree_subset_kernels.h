@@ -68,8 +68,9 @@ __global__ __launch_bounds__(TREE_BLOCK) void tree_backup_batch_subset_kernel(vo
     const SubsetWave s = subset_wave(ids, n_ids, games);
     const u32 lane = threadIdx.x & 63u;
     if (s.g < 0) return;
+    const TreeLeafRows rows = {leaf_value, leaf_probs};
     tree_backup_batch_game<false>(tree_view(tree, games, capacity), s.g, s.w * (int64_t)leaves, lane, capacity, leaves, paths,
-                                  leaf_value, leaf_probs);
+                                  rows, rows);
 }
 
 __global__ __launch_bounds__(TREE_BLOCK) void tree_root_noise_subset_kernel(void *tree, int64_t games, int64_t capacity,

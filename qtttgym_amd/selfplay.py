@@ -219,14 +219,25 @@ class SelfPlay(LibCaller):
     root_noise, forced_playouts, prune_targets, sample_plies and compact compose; root_policy="gumbel", exact_from and
     prove are refused (their kernels index their records by game), and so is td_lambda: TD(lambda) chains consecutive
     plies, and the rows are no longer consecutive.  playout_cap=(1.0, n) records every ply: the batch of playout_cap=None.
-    With the default None every call, buffer and launch sequence is what it was."""
+    With the default None every call, buffer and launch sequence is what it was.
+    resident=True with rounds_per_launch (TreeSearch's; a net, value leaves and the PUCT root only) searches every ply of
+    play() and stream() with the resident search (include/qttt_tree_resident.h): the rounds of a ply run
+    inside launches of qttt_tree_search_resident and every tensor of the batch, the ring and the statistics is what it was.
+    root_noise, sample_plies, forced_playouts, prune_targets, compact, value_mix, td_lambda and exact_targets compose;
+    playout_cap (subset rounds), root_policy="gumbel", exact_from, prove and eval_symmetries are refused, here and in a
+    Reanalyser made of such a SelfPlay.  With the default False every call, buffer and launch is what it was."""
 
     def __init__(self, num_games, n_rollouts=100, num_simulations=10, net=None, alpha=1.0, c_puct=1.0,
                  value_targets=(1.0, 0.0), seed=0, compact=False, carry=None, device=None, leaf_eval="playouts",
                  root_noise=None, temperature=1.0, sample_plies=0, leaves=1, virtual_loss=1.0,
                  eval_symmetries=None, root_policy="puct", max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None,
                  exact_targets=None, exact_policy=True, prove=False, value_mix=None, td_lambda=None,
-                 forced_playouts=None, prune_targets=None, playout_cap=None):
+                 forced_playouts=None, prune_targets=None, playout_cap=None, resident=False, rounds_per_launch=64):
+        self.resident, self.rounds_per_launch = TreeSearch.check_resident(
+            resident, rounds_per_launch, leaf_eval, net, root_policy, exact_from, prove, eval_symmetries)
+        if self.resident and playout_cap is not None:
+            raise ValueError("resident=True with playout_cap: the cap's two groups are searched in subset rounds, "
+                             "which the fused launch does not run")
         self.playout_cap = self.check_playout_cap(playout_cap, n_rollouts, leaf_eval, net, root_policy, exact_from, prove,
                                                   td_lambda)
         self.value_mode, self.value_lambda = self.check_value_args(value_mix, td_lambda, value_targets)
@@ -423,7 +434,8 @@ class SelfPlay(LibCaller):
         """The search keywords that TreeSearch takes from a SelfPlay: what its trees, and a Reanalyser's, are built with."""
         return {k: getattr(self, k) for k in (
             "num_simulations", "c_puct", "net", "leaf_eval", "leaves", "virtual_loss", "eval_symmetries", "root_policy",
-            "max_considered", "c_visit", "c_scale", "exact_from", "prove", "forced_playouts")}
+            "max_considered", "c_visit", "c_scale", "exact_from", "prove", "forced_playouts", "resident",
+            "rounds_per_launch")}
 
     def _new_game_objects(self, s):
         """The environment (seed s) and the trees (seed 2 s + 1) of a play() or a stream, the trees reset at the empty

@@ -45,6 +45,11 @@ contemplate(n, games=...) and add_root_noise(..., games=...) search and noise a 
 (include/qttt_tree_subset.h): the listed games' leaves are packed densely, so a round's network launch has
 n_ids * K rows and the other games cost nothing and keep every byte.  It is what SelfPlay(playout_cap=) is made of.
 
+resident=True (value leaves, the PUCT root) is the resident search (include/qttt_tree_resident.h): after the
+single rollout that follows a reset() or sync(), contemplate() runs its rounds — the same rounds, the same draws, the same
+bytes — inside launches of qttt_tree_search_resident, at most rounds_per_launch rounds each, instead of three launches a
+round.
+
 add_root_noise() is AlphaZero's root exploration (include/qttt_tree_explore.h): Dirichlet noise mixed into
 the priors of every root that has them, one launch.
 """
@@ -80,10 +85,13 @@ class TreeSearch(LibCaller):
     exact_from = None
     prove = False
     forced_playouts = None
+    resident = False
+    rounds_per_launch = 64
 
     def __init__(self, num_games, capacity, num_simulations=10, c_puct=1.0, net=None, seed=0, board_offset=0,
                  device=None, leaf_eval="playouts", leaves=1, virtual_loss=1.0, eval_symmetries=None, root_policy="puct",
-                 max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None, prove=False, forced_playouts=None):
+                 max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None, prove=False, forced_playouts=None,
+                 resident=False, rounds_per_launch=64):
         """leaf_eval="playouts": the reference's rollout, num_simulations playouts from the leaf (uniform, or guided by
         `net`).  leaf_eval="value" (needs `net`): the leaf is scored by the value head, seen by the player to move
         there; a terminal leaf by its reward.  num_simulations is then ignored: no playout draw is taken.
@@ -108,7 +116,15 @@ class TreeSearch(LibCaller):
         action a with n(a) > 0 and n(a) * n(a) < (k * P(a)) * sum(n) is forced: the descent takes the forced action of
         largest score before it looks at the others (n counts the visits in flight).  contemplate() then runs one single
         rollout where the roots may lack priors and rounds of `leaves` through qttt_tree_select_batch_forced after it, a
-        round of one leaf where leaves == 1.  k = 0 forces nothing.  None is the search as it always was."""
+        round of one leaf where leaves == 1.  k = 0 forces nothing.  None is the search as it always was.
+        resident=True (needs a net and leaf_eval="value"; not with root_policy="gumbel", exact_from, prove or
+        eval_symmetries): contemplate() runs the single rollout after a reset() or sync() as always and every round after
+        it inside qttt_tree_search_resident, one launch per rounds_per_launch (>= 1) rounds; rounds of `leaves` also at
+        leaves == 1.  rounds_per_launch bounds one launch's duration on a shared device and does not change a byte.
+        forced_playouts, add_root_noise(), compact(), choose(), root_stats() and sync() compose; contemplate(games=...)
+        does not.  False is the search as it always was, every call, buffer and launch."""
+        self.resident, self.rounds_per_launch = self.check_resident(
+            resident, rounds_per_launch, leaf_eval, net, root_policy, exact_from, prove, eval_symmetries)
         self.forced_playouts = self.check_forced_playouts(leaf_eval, net, root_policy, forced_playouts)
         self.exact_from = self.check_exact_from(leaf_eval, net, exact_from)
         self.prove = self.check_prove(self.exact_from, prove)
@@ -226,6 +242,26 @@ class TreeSearch(LibCaller):
         if root_policy == "gumbel":
             raise ValueError('forced_playouts is a rule of the PUCT root: root_policy="gumbel" replaces that root')
         return float(forced_playouts)
+
+    @staticmethod
+    def check_resident(resident, rounds_per_launch, leaf_eval, net, root_policy, exact_from, prove, eval_symmetries):
+        """The constructors' check of resident and rounds_per_launch; returns (resident, rounds_per_launch).  Every pair
+        that the fused launch cannot run is refused by name."""
+        if not isinstance(resident, bool):
+            raise ValueError("resident must be True or False")
+        if isinstance(rounds_per_launch, bool) or not isinstance(rounds_per_launch, int) or rounds_per_launch < 1:
+            raise ValueError("rounds_per_launch must be an integer >= 1")
+        if not resident:
+            return False, rounds_per_launch
+        if leaf_eval != "value" or net is None:
+            raise ValueError('resident=True with leaf_eval="playouts" (or without a net): the fused launch evaluates the '
+                             'leaves with the value head, it plays no playouts')
+        for name, on in (('root_policy="gumbel"', root_policy == "gumbel"), ("exact_from", exact_from is not None),
+                         ("prove", bool(prove)), ("eval_symmetries", eval_symmetries is not None)):
+            if on:
+                raise ValueError("resident=True with %s: the fused launch runs the PUCT (or forced) select, one plain "
+                                 "evaluation and the plain backup, nothing between them" % name)
+        return True, rounds_per_launch
 
     @staticmethod
     def check_prove(exact_from, prove):
@@ -373,7 +409,10 @@ class TreeSearch(LibCaller):
         (include/qttt_tree_subset.h): rounds of K (also at K = 1), the network launch of n_ids * K rows, the other games
         untouched.  Not with root_policy="gumbel", exact_from or prove.  An empty list launches nothing.
         forced=False searches with the plain PUCT root although the tree has forced_playouts (subset rounds only; None:
-        the tree's rule).  games=None and forced=None issue the calls they always did."""
+        the tree's rule).  games=None and forced=None issue the calls they always did.
+        resident=True: the same single rollout while the tree is fresh, then the rounds inside
+        ceil(rounds / rounds_per_launch) launches of qttt_tree_search_resident; rollout_idx and the node bound advance as
+        for the launches they replace.  Not with games=."""
         r = int(rollouts)
         if r < 0:
             raise ValueError("rollouts must be >= 0")
@@ -385,6 +424,9 @@ class TreeSearch(LibCaller):
             raise ValueError("%d rollouts could use %d nodes, more than capacity %d"
                              % (r, self._bound + 2 * r, self.capacity))
         if games is not None:
+            if self.resident:
+                raise ValueError("resident=True with contemplate(games=...): the fused launch tiles all the games, "
+                                 "a subset search needs the subset rounds")
             return self._contemplate_subset(r, games, forced)
         if forced is not None:
             raise ValueError("forced= goes with games=: a search of all games takes the tree's own root rule")
@@ -392,6 +434,15 @@ class TreeSearch(LibCaller):
         rounds_only = self.eval_symmetries is not None or self.exact_from is not None
         single = (lambda: self._round(1)) if rounds_only else self._rollout
         gumbel = self.root_policy == "gumbel"
+        if self.resident:
+            if r and self._fresh:
+                self._rollout()
+                self._bound += 2
+                r -= 1
+                self._fresh = False
+            self._resident_rounds(r)
+            self._bound += 2 * r
+            return
         if self.leaves == 1 and self.forced_playouts is None and not gumbel:
             for _ in range(r):
                 single()
@@ -413,6 +464,20 @@ class TreeSearch(LibCaller):
         for k in [K] * (r // K) + [r % K] * (r % K > 0):
             one_round(k)
             self._bound += 2 * k
+
+    def _resident_rounds(self, r):
+        """r rollouts in rounds of `leaves` (and one shorter round for what is left) inside qttt_tree_search_resident,
+        without contemplate's bounds: one launch per rounds_per_launch rounds, cut at round boundaries, so the rounds and
+        their draw indices are those of one launch of r."""
+        per_launch = self.rounds_per_launch * self.leaves
+        forced_k = -1.0 if self.forced_playouts is None else self.forced_playouts
+        while r > 0:
+            n = min(r, per_launch)
+            self._call("qttt_tree_search_resident", self.tree.data_ptr(), self.num_games, self.capacity, self.seed,
+                       self.rollout_idx, self.leaves, n, self.board_offset, self.c_puct, self.virtual_loss, forced_k,
+                       self.net.blob.data_ptr(), self.net.precision)
+            self.rollout_idx += n
+            r -= n
 
     def _round_buffers(self, k):
         """The buffers of a round of k leaves per game: the G * k leaves as a VecEnv, the path records, and the rows that
