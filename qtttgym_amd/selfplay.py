@@ -19,6 +19,8 @@ of the game's outcome alone (include/qttt_selfplay_value.h).
 playout_cap=(p, n_fast) is KataGo's playout cap randomisation (include/qttt_selfplay_cap.h): a random
 fraction p of the plies gets the full search and becomes a sample, the others are searched with n_fast rollouts, without
 noise, and are played but not recorded.
+play() and stream() run one ply through one method, SelfPlay._ply: the search (capped or not), record_value, the record, the
+step, the sync and the compaction.
 """
 import ctypes
 
@@ -209,7 +211,7 @@ class SelfPlay(LibCaller):
     the counter hash of (the trees' seed, board_offset + g, the ply's index) — no read-back, so it knows both groups — and
     uploads the mask and the two id lists; one plain rollout runs in all games; root_noise goes to the full group only; the
     fast group runs n_fast - 1 more rollouts with the plain root rule and the full group n_rollouts - 1, forced if
-    forced_playouts is set, both through TreeSearch.contemplate(games=), so a round's network launch has (games in the
+    forced_playouts is set, both in one TreeSearch.contemplate_groups(), so a round's network launch has (games in the
     group) * leaves rows; the trees' rollout index advances by n_rollouts.  The record is qttt_selfplay_record_capped: a
     full game's row is what it would have been, a fast game's move is played and nothing is recorded, so batch.length
     counts rows, not plies, and a game whose plies were all fast yields its terminal row alone; v is signed by the side to
@@ -233,25 +235,18 @@ class SelfPlay(LibCaller):
                  eval_symmetries=None, root_policy="puct", max_considered=16, c_visit=50.0, c_scale=1.0, exact_from=None,
                  exact_targets=None, exact_policy=True, prove=False, value_mix=None, td_lambda=None,
                  forced_playouts=None, prune_targets=None, playout_cap=None, resident=False, rounds_per_launch=64):
-        self.resident, self.rounds_per_launch = TreeSearch.check_resident(
-            resident, rounds_per_launch, leaf_eval, net, root_policy, exact_from, prove, eval_symmetries)
+        self.playout_cap = self.check_playout_cap(playout_cap, n_rollouts, leaf_eval, net, root_policy, exact_from, prove,
+                                                  td_lambda)
+        vars(self).update(TreeSearch.check_search(leaf_eval, net, leaves, virtual_loss, eval_symmetries, root_policy,
+                                                  max_considered, c_visit, c_scale, exact_from, prove, forced_playouts,
+                                                  resident, rounds_per_launch))
         if self.resident and playout_cap is not None:
             raise ValueError("resident=True with playout_cap: the cap's two groups are searched in subset rounds, "
                              "which the fused launch does not run")
-        self.playout_cap = self.check_playout_cap(playout_cap, n_rollouts, leaf_eval, net, root_policy, exact_from, prove,
-                                                  td_lambda)
         self.value_mode, self.value_lambda = self.check_value_args(value_mix, td_lambda, value_targets)
         self.exact_targets = self.check_exact_targets(exact_targets, value_targets)
         self.exact_policy = bool(exact_policy)
-        self.exact_from = TreeSearch.check_exact_from(leaf_eval, net, exact_from)
-        self.prove = TreeSearch.check_prove(self.exact_from, prove)
-        self.leaves, self.virtual_loss = TreeSearch.check_search_args(leaf_eval, net, leaves, virtual_loss)
-        self.root_policy, self.max_considered, self.c_visit, self.c_scale = TreeSearch.check_root_args(
-            leaf_eval, net, root_policy, max_considered, c_visit, c_scale)
-        self.eval_symmetries = TreeSearch.check_eval_symmetries(leaf_eval, eval_symmetries)
-        self.forced_playouts = TreeSearch.check_forced_playouts(leaf_eval, net, root_policy, forced_playouts)
         self.prune_targets = self.check_prune_targets(self.forced_playouts, prune_targets)
-        self.leaf_eval = leaf_eval
         self.num_games, self.n_rollouts = int(num_games), int(n_rollouts)
         self.num_simulations, self.net = int(num_simulations), net
         self.alpha, self.c_puct, self.seed, self.compact = float(alpha), float(c_puct), int(seed), bool(compact)
@@ -294,6 +289,7 @@ class SelfPlay(LibCaller):
         self.plays = 0                # play() calls so far: the default seed of the next
         self.env = self.tree = None   # the last play()'s or stream()'s environment (at its positions) and trees
         self._stream = None           # stream()'s games in progress: environment, trees, staging batch, counters
+        self._cap_full = None         # the last capped search's mask full u8[G], on the device
         self.stream_epoch_plies = None    # None: a seed serves as many plies as the draw counters allow (epoch_plies)
 
     @staticmethod
@@ -311,7 +307,7 @@ class SelfPlay(LibCaller):
             raise ValueError("playout_cap: n_fast must be an integer in 1..n_rollouts")
         if leaf_eval != "value" or net is None:
             raise ValueError('playout_cap needs a net and leaf_eval="value": the two groups are searched in subset rounds')
-        if root_policy == "gumbel" or exact_from is not None or prove:
+        if TreeSearch.subset_refused(root_policy, exact_from, prove):
             raise ValueError('playout_cap is not available with root_policy="gumbel", exact_from or prove: their kernels '
                              "index their records by game, not by a subset's dense rows")
         if td_lambda is not None:
@@ -432,10 +428,7 @@ class SelfPlay(LibCaller):
 
     def search_kwargs(self):
         """The search keywords that TreeSearch takes from a SelfPlay: what its trees, and a Reanalyser's, are built with."""
-        return {k: getattr(self, k) for k in (
-            "num_simulations", "c_puct", "net", "leaf_eval", "leaves", "virtual_loss", "eval_symmetries", "root_policy",
-            "max_considered", "c_visit", "c_scale", "exact_from", "prove", "forced_playouts", "resident",
-            "rounds_per_launch")}
+        return {k: getattr(self, k) for k in TreeSearch.SEARCH_KEYS}
 
     def _new_game_objects(self, s):
         """The environment (seed s) and the trees (seed 2 s + 1) of a play() or a stream, the trees reset at the empty
@@ -464,15 +457,11 @@ class SelfPlay(LibCaller):
         full = torch.from_numpy(cap_full_mask(tree.seed, tree.board_offset, G, ply_index, p))
         mask = full.pin_memory().to(self.device, non_blocking=True)
         group_full, group_fast = tree.subset(full), tree.subset(1 - full)
-        idx0, bound0 = tree.rollout_idx, tree._bound
         tree.contemplate(1)
         if self.root_noise is not None:
             tree.add_root_noise(*self.root_noise, games=group_full)
         # a game is in one group: both groups take the rollout indices after the first, and no game more than R - 1 of them
-        for group, n, forced in ((group_fast, n_fast - 1, False), (group_full, R - 1, None)):
-            tree.rollout_idx, tree._bound = idx0 + 1, bound0 + 2
-            tree.contemplate(n, games=group, forced=forced)
-        tree.rollout_idx, tree._bound = idx0 + R, bound0 + 2 * R
+        tree.contemplate_groups(R - 1, [(group_fast, n_fast - 1, False), (group_full, R - 1, None)])
         return mask
 
     def record_capped(self, tree, batch, full, draw_index=0):
@@ -512,6 +501,30 @@ class SelfPlay(LibCaller):
         tree.noise_idx = p if self.root_noise is not None else 0
         tree.gumbel_idx = p if self.root_policy == "gumbel" else 0
 
+    def _ply(self, env, tree, batch, row, index, search=True):
+        """One ply, play()'s and stream()'s: the search (capped or not; none where search is False), record_value, the record,
+        the step, the sync and the compaction.  row: the batch row, or None for the record at every game's own length[g]
+        (stream(), and every capped ply: a capped batch's rows are per game).  index: the ply's number since the seed's
+        first, which addresses the cap's draw and the sampled move's."""
+        capped = self.playout_cap is not None
+        if capped:
+            row = None
+        if search:
+            if capped:
+                self._cap_full = self._search_capped(tree, index)
+            else:
+                self._search(tree)
+            if self.value_mode is not None:
+                self.record_value(tree, row, batch)
+        if capped:      # an unsearched ply (play()'s last: every root is terminal and recorded as such) reads no bit of the mask
+            actions = self.record_capped(tree, batch, self._cap_full, draw_index=index)
+        else:
+            actions = self.record(tree, row, batch, draw_index=None if row == index else index)
+        env.step_raw(actions)
+        tree.sync(env)
+        if self.compact:
+            tree.compact()
+
     def play(self, seed=None, start_ply=0):
         """play_game (self_play.py:43-76) of num_games games from the empty board and their samples
         (self_play.py:193-216) as a SelfPlayBatch.  seed=None: self.seed + the number of earlier play() calls.  The
@@ -531,25 +544,8 @@ class SelfPlay(LibCaller):
                 raise ValueError("start_ply %d passes the draw counters' limit of %d plies" % (p, self.epoch_plies(tree)))
             self._set_counters(env, tree, p)
         batch = self.new_batch()
-        for ply in range(ROWS):
-            if self.playout_cap is not None:    # the capped ply: rows are per game, a game that is over is not live
-                if ply < ROWS - 1:
-                    full = self._search_capped(tree, p + ply)
-                    if self.value_mode is not None:
-                        self.record_value(tree, None, batch)
-                env.step_raw(self.record_capped(tree, batch, full, draw_index=p + ply))
-                tree.sync(env)
-                if self.compact:
-                    tree.compact()
-                continue
-            if ply < ROWS - 1:                  # at ply 9 every game is over: nine moves fill the board
-                self._search(tree)
-                if self.value_mode is not None:
-                    self.record_value(tree, ply, batch)
-            env.step_raw(self.record(tree, ply, batch, draw_index=p + ply if p else None))
-            tree.sync(env)
-            if self.compact:
-                tree.compact()
+        for ply in range(ROWS):                 # at ply 9 every game is over: nine moves fill the board
+            self._ply(env, tree, batch, ply, p + ply, search=ply < ROWS - 1)
         if self.exact_targets is not None:
             batch.exact = batch.exact_targets(self.exact_targets, self.exact_policy)
         if self.value_mode is not None:
@@ -618,19 +614,7 @@ class SelfPlay(LibCaller):
             # what the host cannot know without a read-back, it knows from the game: a live root has at most eight moves
             # behind it, and a restart gives the slot's nodes back, so no slot holds more than this before its search
             tree._bound = 1 + (ROWS - 2) * (2 * R + 1)
-        if self.playout_cap is not None:
-            full = self._search_capped(tree, st["ply"])
-            if self.value_mode is not None:
-                self.record_value(tree, None, batch)
-            env.step_raw(self.record_capped(tree, batch, full, draw_index=st["ply"]))
-        else:
-            self._search(tree)
-            if self.value_mode is not None:
-                self.record_value(tree, None, batch)
-            env.step_raw(self.record(tree, None, batch, draw_index=st["ply"]))
-        tree.sync(env)
-        if self.compact:
-            tree.compact()
+        self._ply(env, tree, batch, None, st["ply"])
         self._stream_harvest(st)
         exact = None
         if self.exact_targets is not None:          # only the games this ply hands to the ring, once each

@@ -43,7 +43,12 @@ keep of the visits.
 
 contemplate(n, games=...) and add_root_noise(..., games=...) search and noise a listed subset of the games
 (include/qttt_tree_subset.h): the listed games' leaves are packed densely, so a round's network launch has
-n_ids * K rows and the other games cost nothing and keep every byte.  It is what SelfPlay(playout_cap=) is made of.
+n_ids * K rows and the other games cost nothing and keep every byte.  contemplate_groups(n, groups) searches several disjoint
+subsets from the same rollout index, each with a budget and a root rule of its own: what SelfPlay(playout_cap=) is made of.
+
+Every one of these searches follows one plan, search_plan(): one single rollout while the roots are fresh, then rounds of
+`leaves`, then one shorter round.  _round() is the one round — select, one evaluation, backup — of the plain, forced, Gumbel
+and subset forms, and contemplate() the one place where the node bound advances.
 
 resident=True (value leaves, the PUCT root) is the resident search (include/qttt_tree_resident.h): after the
 single rollout that follows a reset() or sync(), contemplate() runs its rounds — the same rounds, the same draws, the same
@@ -59,6 +64,21 @@ from . import _native
 from ._host import LibCaller, _ptr, check_net, check_tensor, out_rows, out_tensor, resolve_device
 from .symmetry import check_eval_symmetries
 from .vec_env import VecEnv
+
+
+def search_plan(rollouts, leaves, fresh, rounds=True):
+    """The plan of a search of `rollouts` rollouts, every path's of TreeSearch.contemplate: (singles, sizes).  A search in
+    rounds (rounds=True) takes one single rollout while the roots are fresh — no contemplate since the last reset() or
+    sync(): K descents would all end on a root without priors — then rounds of K = leaves and one shorter round for what
+    is left.  A search without rounds (leaves == 1 at the plain PUCT root, outside the resident search) is `rollouts`
+    singles.  What a single is — _rollout, or a round of one leaf — is the caller's; it counts one rollout and two nodes
+    either way, so singles + sum(sizes) == rollouts and the node bound advances by 2 * rollouts."""
+    r, K = int(rollouts), int(leaves)
+    if not rounds:
+        return r, []
+    singles = 1 if r and fresh else 0
+    r -= singles
+    return singles, [K] * (r // K) + [r % K] * (r % K > 0)
 
 
 class TreeSearch(LibCaller):
@@ -123,16 +143,8 @@ class TreeSearch(LibCaller):
         leaves == 1.  rounds_per_launch bounds one launch's duration on a shared device and does not change a byte.
         forced_playouts, add_root_noise(), compact(), choose(), root_stats() and sync() compose; contemplate(games=...)
         does not.  False is the search as it always was, every call, buffer and launch."""
-        self.resident, self.rounds_per_launch = self.check_resident(
-            resident, rounds_per_launch, leaf_eval, net, root_policy, exact_from, prove, eval_symmetries)
-        self.forced_playouts = self.check_forced_playouts(leaf_eval, net, root_policy, forced_playouts)
-        self.exact_from = self.check_exact_from(leaf_eval, net, exact_from)
-        self.prove = self.check_prove(self.exact_from, prove)
-        self.leaves, self.virtual_loss = self.check_search_args(leaf_eval, net, leaves, virtual_loss)
-        self.root_policy, self.max_considered, self.c_visit, self.c_scale = self.check_root_args(
-            leaf_eval, net, root_policy, max_considered, c_visit, c_scale)
-        self.eval_symmetries = self.check_eval_symmetries(leaf_eval, eval_symmetries)
-        self.leaf_eval = leaf_eval
+        vars(self).update(self.check_search(leaf_eval, net, leaves, virtual_loss, eval_symmetries, root_policy, max_considered,
+                                            c_visit, c_scale, exact_from, prove, forced_playouts, resident, rounds_per_launch))
         self.num_games, self.capacity = int(num_games), int(capacity)
         self.num_simulations, self.c_puct = int(num_simulations), float(c_puct)
         self.net, self.seed, self.board_offset = net, int(seed), int(board_offset)
@@ -272,6 +284,36 @@ class TreeSearch(LibCaller):
             raise ValueError("prove=True needs exact_from: the plain backup would hand a proven node its priors back")
         return prove
 
+    # what a SelfPlay hands to its trees, and a Reanalyser to its own: SelfPlay.search_kwargs()
+    SEARCH_KEYS = ("num_simulations", "c_puct", "net", "leaf_eval", "leaves", "virtual_loss", "eval_symmetries", "root_policy",
+                   "max_considered", "c_visit", "c_scale", "exact_from", "prove", "forced_playouts", "resident",
+                   "rounds_per_launch")
+
+    @staticmethod
+    def check_search(leaf_eval, net, leaves, virtual_loss, eval_symmetries, root_policy, max_considered, c_visit, c_scale,
+                     exact_from, prove, forced_playouts, resident, rounds_per_launch):
+        """The search keywords' checks, every check_* above, for the constructors of TreeSearch and SelfPlay alike, before
+        anything is opened; returns name -> normalised value for every SEARCH_KEYS name but num_simulations, c_puct and net.
+        The order is one: resident, forced_playouts, exact_from, prove, the search's form, the root's rule, eval_symmetries.
+        An input with several bad keywords is refused for the first of them in that order, by either constructor."""
+        T, o = TreeSearch, {"leaf_eval": leaf_eval}
+        o["resident"], o["rounds_per_launch"] = T.check_resident(resident, rounds_per_launch, leaf_eval, net, root_policy,
+                                                                 exact_from, prove, eval_symmetries)
+        o["forced_playouts"] = T.check_forced_playouts(leaf_eval, net, root_policy, forced_playouts)
+        o["exact_from"] = T.check_exact_from(leaf_eval, net, exact_from)
+        o["prove"] = T.check_prove(o["exact_from"], prove)
+        o["leaves"], o["virtual_loss"] = T.check_search_args(leaf_eval, net, leaves, virtual_loss)
+        o["root_policy"], o["max_considered"], o["c_visit"], o["c_scale"] = T.check_root_args(
+            leaf_eval, net, root_policy, max_considered, c_visit, c_scale)
+        o["eval_symmetries"] = T.check_eval_symmetries(leaf_eval, eval_symmetries)
+        return o
+
+    @staticmethod
+    def subset_refused(root_policy, exact_from, prove):
+        """Whether a search with these keywords cannot search a subset of its games (contemplate(games=),
+        SelfPlay(playout_cap=)): the Gumbel, exact and prove kernels index their records by game."""
+        return root_policy == "gumbel" or exact_from is not None or bool(prove)
+
     def _need_reset(self):
         if self._bound is None:
             raise RuntimeError("reset() first")
@@ -342,7 +384,7 @@ class TreeSearch(LibCaller):
         return ids, ids.numel()
 
     def _check_subset_search(self):
-        if self.root_policy == "gumbel" or self.exact_from is not None or self.prove:
+        if self.subset_refused(self.root_policy, self.exact_from, self.prove):
             raise ValueError('a subset search (games=...) is not available with root_policy="gumbel", exact_from or prove: '
                              "their kernels index their records by game, not by the subset's dense rows")
         if self.leaf_eval != "value":
@@ -365,55 +407,46 @@ class TreeSearch(LibCaller):
                 "out": {key: t[:rows] for key, t in full["out"].items()}}
         return b
 
-    def _subset_round(self, k, ids, n, forced_k):
-        """One round of k rollouts in the n listed games through the subset entries, without contemplate's bounds: the
-        select (forced_k < 0: the plain PUCT root), one evaluation of the n * k leaves, their backup."""
-        k = int(k)
-        if not 1 <= k <= _native.TREE_MAX_LEAVES:
-            raise ValueError("a round holds 1..%d leaves" % _native.TREE_MAX_LEAVES)
-        if n:
-            b = self._subset_buffers(n, k)
-            G, cap, tree = self.num_games, self.capacity, self.tree.data_ptr()
-            self._call("qttt_tree_select_batch_subset", tree, G, cap, self.seed, self.rollout_idx, k, self.board_offset,
-                       self.c_puct, self.virtual_loss, forced_k, ids.data_ptr(), n, b["paths"].data_ptr(),
-                       b["leaf"].state.data_ptr())
-            b["leaf"].evaluate(self.net, out=b["out"], symmetries=self.eval_symmetries)
-            self._call("qttt_tree_backup_batch_subset", tree, G, cap, k, ids.data_ptr(), n, b["paths"].data_ptr(),
-                       b["out"]["value"].data_ptr(), b["out"]["probs"].data_ptr())
-        self.rollout_idx += k
-
-    def _contemplate_subset(self, r, games, forced):
-        self._check_subset_search()
-        ids, n = self.subset(games)
-        forced_k = -1.0 if (self.forced_playouts is None or forced is False) else self.forced_playouts
-        K = self.leaves
-        if r and self._fresh:         # a listed root may lack priors: one plain descent first; the others stay fresh
-            self._subset_round(1, ids, n, -1.0)
-            self._bound += 2
-            r -= 1
-        for k in [K] * (r // K) + [r % K] * (r % K > 0):
-            self._subset_round(k, ids, n, forced_k)
-            self._bound += 2 * k
-
     def contemplate(self, rollouts, games=None, forced=None):
-        """`rollouts` x MCTS._rollout (mcts.py:166-176) in every game.  With leaves = K > 1 they are taken K at a time:
-        after a reset() or sync() one single rollout first (K descents would all end on a root without priors), then
-        rounds of K and one shorter round for what is left.  Without eval_symmetries the calls are what they always were.
-        root_policy="gumbel": after that single rollout (the root needs its priors to be descended from) the roots are
-        evaluated, the Gumbel state of the move is drawn for the budget n = the rollouts that remain, and the rounds go
-        through the Gumbel select; every contemplate() is one budget of its own.
-        forced_playouts: the same single rollout, then rounds of K (also at K = 1) through the forced select.
-        games (see subset()): only the listed games are searched, by the same rules and with the same draws — the collapse
-        bits are addressed by the game and by rollout_idx, which advances by `rollouts` as for a full call, so draw indices
-        stay a function of the schedule alone — through qttt_tree_select_batch_subset / qttt_tree_backup_batch_subset
-        (include/qttt_tree_subset.h): rounds of K (also at K = 1), the network launch of n_ids * K rows, the other games
-        untouched.  Not with root_policy="gumbel", exact_from or prove.  An empty list launches nothing.
-        forced=False searches with the plain PUCT root although the tree has forced_playouts (subset rounds only; None:
-        the tree's rule).  games=None and forced=None issue the calls they always did.
-        resident=True: the same single rollout while the tree is fresh, then the rounds inside
-        ceil(rounds / rounds_per_launch) launches of qttt_tree_search_resident; rollout_idx and the node bound advance as
-        for the launches they replace.  Not with games=."""
-        r = int(rollouts)
+        """`rollouts` x MCTS._rollout (mcts.py:166-176) in every game, by the one plan of search_plan(): after a reset() or
+        sync() one single rollout first (K descents would all end on a root without priors), then rounds of K = leaves and
+        one shorter round for what is left.  What a single and a round are is the search's form:
+        leaves == 1 at the plain PUCT root: no rounds, every rollout a single; the calls are what they always were.
+        eval_symmetries or exact_from: a single is a round of one leaf.
+        root_policy="gumbel": after the single (the root needs its priors to be descended from) the roots are evaluated, the
+        Gumbel state of the move is drawn for the budget n = the rollouts that remain, and the rounds go through the Gumbel
+        select; every contemplate() is one budget of its own.
+        forced_playouts: the rounds (also at K = 1) go through the forced select.
+        resident=True: the rounds run inside ceil(rounds / rounds_per_launch) launches of qttt_tree_search_resident;
+        rollout_idx and the node bound advance as for the launches they replace.  Not with games=.
+        games (see subset()): contemplate_groups(rollouts, [(games, rollouts, forced)]).  forced= goes with games=."""
+        if games is not None:
+            return self.contemplate_groups(rollouts, [(games, rollouts, forced)])
+        if forced is not None:
+            raise ValueError("forced= goes with games=: a search of all games takes the tree's own root rule")
+        self._contemplate(rollouts, [(None, rollouts, None)])
+
+    def contemplate_groups(self, rollouts, groups):
+        """groups = [(games, n, forced), ...]: every group's listed games (see subset()) are searched for n <= rollouts
+        rollouts, by the same plan and with the same draws as a search of all games — the collapse bits are addressed by the
+        game and by rollout_idx, and every group starts at the rollout_idx of the call — through
+        qttt_tree_select_batch_subset / qttt_tree_backup_batch_subset (include/qttt_tree_subset.h): a single is a round of one
+        with the plain root, the rounds are rounds of K (also at K = 1), the network launch has n_ids * K rows, and the other
+        games keep every byte.  rollout_idx and the node bound then advance by `rollouts`, once, so draw indices stay a
+        function of the schedule alone.  forced=False searches a group with the plain PUCT root although the tree has
+        forced_playouts (None: the tree's rule).  An empty list launches nothing.  Every bound is checked before the first
+        launch.  The groups' games must be disjoint: a game listed twice would be searched twice with the same draws.  That
+        is the caller's word; nothing checks it on the device.  Not with root_policy="gumbel", exact_from, prove or resident."""
+        if self.resident:
+            raise ValueError("resident=True with contemplate(games=...): the fused launch tiles all the games, "
+                             "a subset search needs the subset rounds")
+        self._check_subset_search()
+        self._contemplate(rollouts, [(self.subset(games), n, forced) for games, n, forced in groups])
+
+    def _contemplate(self, rollouts, groups):
+        """The bounds of `rollouts` rollouts, then every group's search (ids = subset()'s pair, None: all games) from the same
+        rollout_idx, then the one place where rollout_idx and the node bound move on."""
+        r, budgets = int(rollouts), [int(n) for _, n, _ in groups]
         if r < 0:
             raise ValueError("rollouts must be >= 0")
         self._need_reset()
@@ -423,47 +456,46 @@ class TreeSearch(LibCaller):
         if self._bound + 2 * r > self.capacity:
             raise ValueError("%d rollouts could use %d nodes, more than capacity %d"
                              % (r, self._bound + 2 * r, self.capacity))
-        if games is not None:
-            if self.resident:
-                raise ValueError("resident=True with contemplate(games=...): the fused launch tiles all the games, "
-                                 "a subset search needs the subset rounds")
-            return self._contemplate_subset(r, games, forced)
-        if forced is not None:
-            raise ValueError("forced= goes with games=: a search of all games takes the tree's own root rule")
-        # a single rollout: the fused value rollout, or — under eval_symmetries or exact_from — a round of one leaf
-        rounds_only = self.eval_symmetries is not None or self.exact_from is not None
-        single = (lambda: self._round(1)) if rounds_only else self._rollout
-        gumbel = self.root_policy == "gumbel"
-        if self.resident:
-            if r and self._fresh:
+        if not all(0 <= n <= r for n in budgets):
+            raise ValueError("a group's rollouts must be in 0..%d, the rollouts of the call" % r)
+        if self.root_policy == "gumbel" and r > (1 if self._fresh else 0) and self.gumbel_idx >= _native.TREE_MAX_GUMBEL:
+            raise ValueError("%d Gumbel roots since reset: the bound is %d (draw indices)"
+                             % (self.gumbel_idx, _native.TREE_MAX_GUMBEL))
+        idx0 = self.rollout_idx
+        for (ids, _, forced), n in zip(groups, budgets):
+            self.rollout_idx = idx0
+            self._search(n, ids, forced)
+        self.rollout_idx = idx0 + r
+        self._bound += 2 * r
+
+    def _search(self, r, ids=None, forced=None):
+        """r rollouts by search_plan(), without contemplate's bounds and without the node bound: in all games, or (ids =
+        subset()'s pair) in the listed ones, which leave _fresh alone: the games not listed stay fresh."""
+        gumbel, K = self.root_policy == "gumbel", self.leaves
+        rounds = K > 1 or self.forced_playouts is not None or gumbel or self.resident or ids is not None
+        singles, sizes = search_plan(r, K, self._fresh, rounds)
+        for _ in range(singles):
+            if ids is not None:         # a listed root may lack priors: one plain descent
+                self._round(1, ids=ids, forced=False)
+            elif self.eval_symmetries is not None or self.exact_from is not None:
+                self._round(1)          # no fused value rollout under these: a round of one leaf
+            else:
                 self._rollout()
-                self._bound += 2
-                r -= 1
-                self._fresh = False
-            self._resident_rounds(r)
-            self._bound += 2 * r
+        if ids is not None:
+            fk = self.forced_playouts if forced is not False and self.forced_playouts is not None else False
+            for k in sizes:
+                self._round(k, ids=ids, forced=fk)
             return
-        if self.leaves == 1 and self.forced_playouts is None and not gumbel:
-            for _ in range(r):
-                single()
-                self._bound += 2
-            return
-        if r and self._fresh:
-            single()
-            self._bound += 2
-            r -= 1
+        if rounds and singles:
             self._fresh = False
-        if gumbel and r:
-            if self.gumbel_idx >= _native.TREE_MAX_GUMBEL:
-                raise ValueError("%d Gumbel roots since reset: the bound is %d (draw indices)"
-                                 % (self.gumbel_idx, _native.TREE_MAX_GUMBEL))
-            self._gumbel_begin(r)
+        if self.resident:
+            return self._resident_rounds(r - singles)
+        if gumbel and sizes:
+            self._gumbel_begin(r - singles)
         elif gumbel and self._gumbel is not None:
             self._gumbel["n"] = 0     # no budget: no Gumbel state of this root
-        one_round, K = (self._gumbel_round if gumbel else self._round), self.leaves
-        for k in [K] * (r // K) + [r % K] * (r % K > 0):
-            one_round(k)
-            self._bound += 2 * k
+        for k in sizes:
+            (self._gumbel_round if gumbel else self._round)(k)
 
     def _resident_rounds(self, r):
         """r rollouts in rounds of `leaves` (and one shorter round for what is left) inside qttt_tree_search_resident,
@@ -498,43 +530,57 @@ class TreeSearch(LibCaller):
                 b["proved"] = torch.zeros(self.num_games, dtype=torch.int32, device=dev)
         return b
 
-    def _backup_round(self, b, k):
+    def _backup_round(self, b, k, ids=()):
         """The backup of a round of k leaves whose leaves were just evaluated into b["out"]; with exact_from the eligible
         leaves are solved first (their rows of b["out"]["value"] become exact, b["exact"] says which) and the backup is
         the one that honours solved nodes; with prove the round's paths are then walked upwards (b["proved"] counts the
-        nodes of every game that this round proved)."""
+        nodes of every game that this round proved).  ids: a subset round's (ids, n) as pointer and count, its backup."""
         G, cap, tree = self.num_games, self.capacity, self.tree.data_ptr()
         value, probs = b["out"]["value"].data_ptr(), b["out"]["probs"].data_ptr()
-        if self.exact_from is None:
+        if ids:
+            self._call("qttt_tree_backup_batch_subset", tree, G, cap, k, *ids, b["paths"].data_ptr(), value, probs)
+        elif self.exact_from is None:
             self._call("qttt_tree_backup_batch", tree, G, cap, k, b["paths"].data_ptr(), value, probs)
-            return
-        self._call("qttt_tree_solve_leaves", tree, G, cap, k, b["paths"].data_ptr(), b["leaf"].state.data_ptr(),
-                   self.exact_from, value, b["exact"].data_ptr())
-        self._call("qttt_tree_backup_batch_exact", tree, G, cap, k, b["paths"].data_ptr(), value, probs)
-        if self.prove:
-            self._call("qttt_tree_prove", tree, G, cap, k, b["paths"].data_ptr(), b["proved"].data_ptr())
+        else:
+            self._call("qttt_tree_solve_leaves", tree, G, cap, k, b["paths"].data_ptr(), b["leaf"].state.data_ptr(),
+                       self.exact_from, value, b["exact"].data_ptr())
+            self._call("qttt_tree_backup_batch_exact", tree, G, cap, k, b["paths"].data_ptr(), value, probs)
+            if self.prove:
+                self._call("qttt_tree_prove", tree, G, cap, k, b["paths"].data_ptr(), b["proved"].data_ptr())
 
-    def _round(self, k, g=None):
-        """One round of k rollouts (1..TREE_MAX_LEAVES) through the leaf-parallel entries, without contemplate's bounds: k descents
-        per game under virtual loss, one evaluation of the G * k leaves, their backup.  g: _gumbel_round's buffers, its select."""
+    # a round's form -> (its select's entry, whether the form's own arguments stand before the paths and the leaves or after)
+    _ROUND_FORMS = {"plain": ("qttt_tree_select_batch", False), "forced": ("qttt_tree_select_batch_forced", False),
+                    "gumbel": ("qttt_tree_select_batch_gumbel", False), "subset": ("qttt_tree_select_batch_subset", True)}
+
+    def _round(self, k, g=None, ids=None, forced=None):
+        """One round of k rollouts (1..TREE_MAX_LEAVES) through the leaf-parallel entries, without contemplate's bounds: k
+        descents per game under virtual loss, one evaluation of the leaves, their backup.  g: _gumbel_round's buffers, its
+        select.  ids: subset()'s (ids, n), the round of the n listed games through the subset entries on n * k dense rows; no
+        games, no launch.  forced: the root's rule; None is the tree's (forced_playouts, but never at a root that may lack
+        priors: the single rollout after a reset() or sync()), False or a negative number the plain PUCT root, a number
+        >= 0 that factor."""
         k = int(k)
         if not 1 <= k <= _native.TREE_MAX_LEAVES:
             raise ValueError("a round holds 1..%d leaves" % _native.TREE_MAX_LEAVES)
         if self.leaf_eval != "value":
             raise ValueError('a leaf-parallel round needs leaf_eval="value"')
-        b = self._round_buffers(k)
+        if forced is None:
+            forced = False if self._fresh else self.forced_playouts
+        fk = -1.0 if forced is None or forced is False else float(forced)
         if g is not None:
-            entry, rule = "qttt_tree_select_batch_gumbel", (g["rec"].data_ptr(), g["table"].data_ptr(), g["n"], g["sim"],
-                                                            self.c_visit, self.c_scale)
-        elif self.forced_playouts is None or self._fresh:
-            # a root that may lack priors (the single rollout after a reset() or sync()) is never asked the forced rule
-            entry, rule = "qttt_tree_select_batch", ()
+            form, own = "gumbel", (g["rec"].data_ptr(), g["table"].data_ptr(), g["n"], g["sim"], self.c_visit, self.c_scale)
+        elif ids is not None:
+            form, own = "subset", (fk, ids[0].data_ptr(), ids[1])
         else:
-            entry, rule = "qttt_tree_select_batch_forced", (self.forced_playouts,)
-        self._call(entry, self.tree.data_ptr(), self.num_games, self.capacity, self.seed, self.rollout_idx, k,
-                   self.board_offset, self.c_puct, self.virtual_loss, b["paths"].data_ptr(), b["leaf"].state.data_ptr(), *rule)
-        b["leaf"].evaluate(self.net, out=b["out"], symmetries=self.eval_symmetries)
-        self._backup_round(b, k)
+            form, own = ("forced", (fk,)) if fk >= 0 else ("plain", ())
+        if ids is None or ids[1]:
+            b = self._round_buffers(k) if ids is None else self._subset_buffers(ids[1], k)
+            entry, own_first = self._ROUND_FORMS[form]
+            buffers = (b["paths"].data_ptr(), b["leaf"].state.data_ptr())
+            self._call(entry, self.tree.data_ptr(), self.num_games, self.capacity, self.seed, self.rollout_idx, k,
+                       self.board_offset, self.c_puct, self.virtual_loss, *(own + buffers if own_first else buffers + own))
+            b["leaf"].evaluate(self.net, out=b["out"], symmetries=self.eval_symmetries)
+            self._backup_round(b, k, own[1:] if ids is not None else ())
         self.rollout_idx += k
 
     def _gumbel_buffers(self):

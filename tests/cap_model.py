@@ -89,20 +89,20 @@ class CapModel:
                                          **dict(sp.search_kwargs(), **over))
         self.fast_tree, self.full_tree = make(forced_playouts=None), make()
 
-    def _group_copy(self, t, idx0, bound0):
+    def _group_copy(self, t):
+        """A whole copy of the trees as they stand after the first rollout, their counters included."""
         src = self.tree
         t.tree.copy_(src.tree)
-        t.rollout_idx, t._bound, t._fresh, t.noise_idx = idx0 + 1, bound0 + 2, False, src.noise_idx
+        t.rollout_idx, t._bound, t._fresh, t.noise_idx = src.rollout_idx, src._bound, src._fresh, src.noise_idx
         return t
 
     def search(self, ply_index):
         sp, t, G = self.sp, self.tree, self.G
         full = full_mask(t.seed, t.board_offset, G, ply_index, self.p)
-        idx0, bound0 = t.rollout_idx, t._bound
         t.contemplate(1)
-        fast_t = self._group_copy(self.fast_tree, idx0, bound0)
+        fast_t = self._group_copy(self.fast_tree)
         fast_t.contemplate(self.n_fast - 1)
-        full_t = self._group_copy(self.full_tree, idx0, bound0)
+        full_t = self._group_copy(self.full_tree)
         if sp.root_noise is not None:
             full_t.add_root_noise(*sp.root_noise)
             t.noise_idx += 1
@@ -110,7 +110,7 @@ class CapModel:
         m = torch.as_tensor(full.astype(bool), device=sp.device)
         copy_games(t.tree, full_t.tree, m, G, t.capacity)
         copy_games(t.tree, fast_t.tree, ~m, G, t.capacity)
-        t.rollout_idx, t._bound, t._fresh = idx0 + sp.n_rollouts, bound0 + 2 * sp.n_rollouts, False
+        t.rollout_idx, t._bound, t._fresh = full_t.rollout_idx, full_t._bound, full_t._fresh   # the copy that ran them all
         return m
 
     def _resign(self, games):

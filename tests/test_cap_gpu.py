@@ -59,7 +59,7 @@ def _subset_round(t, k, ids, forced_k):
     full["paths"].zero_()
     full["leaf"].state.zero_()
     n = len(ids)
-    t._subset_round(k, _ids(ids), n, float(forced_k))
+    t._round(k, ids=(_ids(ids), n), forced=float(forced_k))
     if not n:
         return None
     b = t._subset_rounds[(n, k)]
